@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — OCM tiles/s of the ViT attention-map hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]        (N > 1: starts its own N ranks, one per GPU)
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]   (N > 1: starts its own N ranks, one per GPU)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -12,6 +12,10 @@ A step = one such forward over one resident batch on every rank (weak scaling: t
 sweep are independent) followed by the all-gather of the per-tile CLS-row maps
 (RCCL, overlapped with the next step's compute). Inputs and weights are in HBM before the timed
 region. Rank 0 prints ONE JSON line.
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step returned (the `attn` and `rows` arrays of
+the forward, and with N > 1 the all-gathered `rows_gathered`) as DIR/<name>.npy in float32, at most DUMP_BYTES in all
+(dump_arrays). Inputs and weights are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import ctypes as C
@@ -19,16 +23,19 @@ import json
 import os
 import sys
 import time
+import zlib
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
+import numpy as np  # noqa: E402
 import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
 
 PEAK_BF16_DENSE_TFLOPS = 2500.0  # MI355X_MICROARCH.md: ~2.5 PF dense bf16 MFMA
 PEAK_FP32_MFMA_TFLOPS = 157.3    # same guide: f32-input MFMA = 1/16 of the bf16 rate
+DUMP_BYTES = 64 * 10 ** 6        # --dump-outputs: at most this many bytes in all
 
 
 def flops_per_tile(D, L, p, S, in_chans=3):
@@ -99,6 +106,25 @@ def cpu_baseline(arch_dims, patch, size, batch, seconds_budget=20.0):
             "sample": f"{iters} batches of {batch} tiles ({size}x{size}, get_last_selfattention, fp32 torch-CPU "
                       f"oracle, {cores} threads) after 1 warm-up; b1_value = {it1} single-tile calls (the reference's "
                       f"callers run B = 1)"}
+
+
+def dump_arrays(arrays, budget=DUMP_BYTES, seed=0):
+    """name -> tensor (any device) of what the timed path returned -> name -> float32 numpy array to save.
+    Whole arrays when all of them fit in `budget` bytes (the default workload: the (1,64,6,197,197) maps are 59.6 MB);
+    otherwise a fixed, seeded sample of the flat positions of every array, sorted, gathered on the tensor's device: `name`
+    holds the sampled values (1-D) and `name_index` their flat positions (float64, exact below 2^53)."""
+    total = sum(t.numel() * 4 for t in arrays.values())
+    if total <= budget:
+        return {k: t.detach().float().cpu().numpy() for k, t in arrays.items()}
+    res = {}
+    for k, t in arrays.items():
+        n = t.numel()
+        keep = max(1, int(n * budget // (3 * total)))  # a kept element costs 4 + 8 bytes (value + position)
+        rng = np.random.default_rng([seed, zlib.crc32(k.encode())])
+        idx = np.unique(rng.integers(0, n, size=keep, dtype=np.int64))
+        res[k] = t.detach().reshape(-1)[torch.from_numpy(idx).to(t.device)].float().cpu().numpy()
+        res[k + "_index"] = idx.astype(np.float64)
+    return res
 
 
 def spread(values):
@@ -216,7 +242,11 @@ def main():
     ap.add_argument("--no-slab", action="store_true", help="skip the sharded 4096^2 slab sweep (BASELINE configs[3]) extra")
     ap.add_argument("--slab-size", type=int, default=4096)
     ap.add_argument("--breakdown", action="store_true", help="print a per-kernel-class table to stderr")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned to DIR/<name>.npy (float32, at most 64 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` started directly: become the launcher. Nothing in this process has touched HIP yet
@@ -316,6 +346,11 @@ def main():
         dist.all_gather(tall, tall[rank].clone())
     rank_ms = [float(t.item()) / args.steps * 1e3 for t in tall]  # ms per step as each rank saw it
     dt = max(float(t.item()) for t in tall)                       # the contract: MAX over ranks
+    # what the last timed step returned, taken before anything else runs (the forward returns fresh tensors, and after
+    # sync() the last all-gather has landed in `gathered`)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_arrays({**out, **({"rows_gathered": gathered} if world > 1 else {})})
 
     # per-class breakdown (separate, untimed pass: events around every launch)
     breakdown = None
@@ -473,6 +508,12 @@ def main():
         line["slab_sweep"] = slab
     if not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline((D, L, H), p, S, B)
+    if dumped is not None:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, arr in dumped.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), arr)
+        line["dumped_outputs"] = {"dir": args.dump_outputs,
+                                  "arrays": {name: list(arr.shape) for name, arr in dumped.items()}}
     print(json.dumps(line))
 
 

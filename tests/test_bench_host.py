@@ -91,6 +91,46 @@ def test_flop_bookkeeping_matches_survey():
     assert abs(cf["qkv_gemm"] / 1e9 - 11.155) < 1e-2 and abs(cf["proj_gemm"] / 1e9 - 3.718) < 1e-2
 
 
+def test_dump_arrays_whole_within_budget():
+    """--dump-outputs: arrays that fit are written whole, as float32, in the shapes the caller received."""
+    import numpy as np
+    import torch
+    arrays = {"attn": torch.rand(1, 2, 3, 5, 5), "rows": torch.rand(2, 3, 1, 4, dtype=torch.float64)}
+    got = bench.dump_arrays(arrays, budget=10 ** 6)
+    assert sorted(got) == ["attn", "rows"]
+    for k, t in arrays.items():
+        assert got[k].dtype == np.float32 and got[k].shape == tuple(t.shape)
+        assert np.array_equal(got[k], t.float().numpy())
+    # the default workload's maps + CLS rows (B = 64, 6 heads, N = 197) are dumped whole
+    assert (64 * 6 * 197 * 197 + 64 * 6 * 196) * 4 <= bench.DUMP_BYTES
+
+
+def test_dump_arrays_samples_over_budget_deterministically():
+    """Over the budget: the same seeded positions in every run, values + float64 positions within the budget in all."""
+    import numpy as np
+    import torch
+    arrays = {"attn": torch.randn(4, 6, 50, 50), "rows": torch.randn(4, 6, 1, 49)}
+    budget = 20_000
+    a = bench.dump_arrays(arrays, budget=budget)
+    b = bench.dump_arrays({k: v.clone() for k, v in arrays.items()}, budget=budget)
+    assert sorted(a) == ["attn", "attn_index", "rows", "rows_index"]
+    assert sum(v.nbytes for v in a.values()) <= budget
+    for k, t in arrays.items():
+        assert np.array_equal(a[k + "_index"], b[k + "_index"]) and np.array_equal(a[k], b[k])
+        idx = a[k + "_index"]
+        assert a[k].dtype == np.float32 and idx.dtype == np.float64 and a[k].shape == idx.shape and idx.size > 0
+        assert np.all(np.diff(idx) > 0) and idx[0] >= 0 and idx[-1] < t.numel()
+        assert np.array_equal(a[k], t.reshape(-1).numpy()[idx.astype(np.int64)])
+
+
+@pytest.mark.parametrize("flags", [["--steps", "0"], ["--warmup", "-1"]])
+def test_main_refuses_no_timed_steps_or_negative_warmup(monkeypatch, flags):
+    monkeypatch.setattr(sys, "argv", ["bench.py"] + flags)
+    with pytest.raises(SystemExit) as e:
+        bench.main()
+    assert e.value.code == 2
+
+
 def test_spread_is_min_median_max():
     assert bench.spread([3.0]) == [3.0, 3.0, 3.0]
     assert bench.spread([2.0, 1.0]) == [1.0, 1.5, 2.0]

@@ -25,14 +25,17 @@ def test_oracle_matches_reference_golden(name):
         feat, attns, qkvs = O.get_intermediate_feat(sd, cfg, x, n)
         a = attns[-1]
         # the saturated set is ill-conditioned: another summation order of the same fp32 arithmetic (other core count /
-        # BLAS blocking) moves it by up to ~5e-4 (fp32 vs float64: tools/precision_study.py)
+        # BLAS blocking) moves it by up to ~5e-4 (fp32 vs float64: tools/precision_study.py). That holds for the last block's
+        # qkv too, not only for the maps: MKL's AVX2 kernels instead of the AVX-512 ones the fixture was written with move
+        # it (|q|, |k|, |v| up to 18) by 4.6e-4 (the block's output by 8e-5, inside the common bound)
         atol = 2e-3 if name in SATURATED else TOL
+        atol_qkv = 2e-3 if name in SATURATED else 10 * TOL
         np.testing.assert_allclose(a[:, :, 0, 1:].numpy(), gold[pfx + "cls_rows"], rtol=0, atol=atol)
         np.testing.assert_allclose(a[:, :, a.shape[-1] // 2, :].numpy(), gold[pfx + "mid_rows"], rtol=0, atol=atol)
         assert np.array_equal(a[:, :, 0, 1:].mean(1).argmax(-1).numpy(), gold[pfx + "argmax"])  # indices: exact
         np.testing.assert_allclose(feat[-1][:, :4, :16].numpy(), gold[pfx + "feat_head"], rtol=0, atol=10 * TOL)
         assert abs(float(feat[-1].double().abs().sum()) / float(gold[pfx + "feat_abssum"]) - 1) < 1e-5
-        np.testing.assert_allclose(qkvs[-1][:, :, :, :3, :8].numpy(), gold[pfx + "qkv_head"], rtol=0, atol=10 * TOL)
+        np.testing.assert_allclose(qkvs[-1][:, :, :, :3, :8].numpy(), gold[pfx + "qkv_head"], rtol=0, atol=atol_qkv)
         tokens = O.prepare_tokens(sd, cfg, x)
         np.testing.assert_allclose(tokens[:, :3, :16].numpy(), gold[pfx + "tokens_head"], rtol=0, atol=TOL)
         assert abs(float(tokens.double().abs().sum()) / float(gold[pfx + "tokens_abssum"]) - 1) < 1e-6

@@ -8,7 +8,7 @@ Thread 0 of every workgroup stamps the shader clock at the phase boundaries of g
 workgroups of the last launch are printed for the ViT-S/16 B=64 shapes. (Counters of different XCDs are not
 synchronised: only differences inside a workgroup mean anything.)"""
 import ctypes as C, os, sys
-ROOT = "/root/repo" if os.path.isdir("/root/repo") else os.getcwd()
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import numpy as np, torch
 os.environ["OCM_VIT_LIB"] = os.path.join(ROOT, "exp_libs", "stamps.so")

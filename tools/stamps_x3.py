@@ -2,7 +2,7 @@
 """Phase stamps of the split-bf16 GEMM variants (development tool, GPU box; needs `make -C .../csrc stamps`).
     python tools/stamps_x3.py [variant ...]"""
 import ctypes as C, os, sys
-ROOT = "/root/repo" if os.path.isdir("/root/repo") else os.getcwd()
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import numpy as np, torch
 os.environ["OCM_VIT_LIB"] = os.path.join(ROOT, "exp_libs", "stamps.so")

@@ -266,7 +266,8 @@ int ocm_op_attention_rows(int32_t precision, const void *q, const void *k, const
  * embed_dim 384, 3 heads) — in every precision (split-bf16 since round 3, fp32 and single bf16 since round 4). q / k are then
  * [B*H][n_pad][128] and vt [B*H][128][n_pad] in the operand type, ctx [B][N][H*128]. Any other width returns OCM_EINVAL (an
  * engine handle runs such heads on its generic fp32 attention kernel) — except that ocm_op_qkv_proj_hd with q = k = vt = NULL
- * fills only qkv_f32, for any head_dim that is a multiple of 8 (the input of ocm_op_attention_generic). */
+ * fills only qkv_f32, for any head_dim that is a multiple of 8 (the input of ocm_op_attention_generic). D = heads * head_dim must
+ * be a multiple of 64 in every precision (the projection's 64-wide column tiles cover q | k | v exactly). */
 int ocm_op_qkv_proj_hd(int32_t precision, const void *a, const void *w, const float *bias, void *q, void *k, void *vt,
                        float *qkv_f32, int32_t batch, int32_t n_tokens, int32_t heads, int32_t head_dim, void *stream);
 int ocm_op_attention_hd(int32_t precision, const void *q, const void *k, const void *vt, void *ctx, float *lse2,
@@ -274,7 +275,8 @@ int ocm_op_attention_hd(int32_t precision, const void *q, const void *k, const v
 int ocm_op_attention_probs_hd(int32_t precision, const void *q, const void *k, const float *lse2, float *attn,
                               int32_t batch, int32_t n_tokens, int32_t heads, int32_t head_dim, float scale, void *stream);
 
-/* Attention for heads of ANY width (head_dim a multiple of 4, up to 512; at most 8192 tokens) on the fp32 tensor
+/* Attention for heads of ANY width (head_dim a multiple of 4, up to 512; at most 8192 tokens; heads * head_dim a multiple of 32
+ * for a split-bf16 ctx) on the fp32 tensor
  * qkv_f32 [3][B][H][N][head_dim] that ocm_op_qkv_proj_hd writes: plain fp32 FMAs, one wavefront per query row — what an engine
  * handle runs for head widths the MFMA kernels are not built for, and what the free-standing Attention module
  * (dino/vision_transformer.py:66-90 accepts any dim / num_heads) calls for them. ctx (optional): [B][N][H*head_dim] in the

@@ -11,6 +11,7 @@ import pytest
 import torch
 
 from oracle import vit_oracle as O
+from tests.memcheck import assert_same_bits
 import vit_ocm_wmsegmentation_amd.dino.vision_transformer as vits
 from vit_ocm_wmsegmentation_amd import synth
 from vit_ocm_wmsegmentation_amd.sw_processing import SlidingWindowAttention, sliding_window_origins
@@ -45,7 +46,7 @@ def test_config2_batch64_sampled_images(dev, variant):
     assert float((one[0] - attn[31]).abs().max()) <= (2e-4 if variant == "peaked" else 2e-6)
     # intermediate features / qkv of the last block through get_intermediate_feat at the same batch
     feat, attns, qkvs = model.get_intermediate_feat(x.to(dev), n=1)
-    assert torch.equal(attns[0], attn)
+    assert_same_bits(attns[0], attn, "get_intermediate_feat attns[0] vs get_last_selfattention", ("image", "head", "row", "col"))
     ofeat, _, oqkv = O.get_intermediate_feat(sd, cfg, x[pick], 1)
     scale = float(ofeat[0].abs().max())
     assert float((feat[0][pick].cpu() - ofeat[0]).abs().max()) / scale < (2e-3 if variant == "peaked" else 2e-4)

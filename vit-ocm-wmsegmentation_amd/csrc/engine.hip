@@ -819,6 +819,10 @@ static int op_qkv_proj(int32_t precision, const void *a, const void *w, const fl
     const bool copies = q || k || vt;
     if (!a || !w || !bias || (copies && (!q || !k || !vt)) || (!copies && !qkv_f32)) return fail(OCM_EINVAL, "null argument");
     if (batch <= 0 || n_tokens <= 0 || heads <= 0 || head_dim <= 0 || head_dim % 8) return fail(OCM_EINVAL, "bad shape");
+    // D = heads * head_dim is the contraction length and a third of the output width; the projection's column tiles are
+    // 64 wide and cover 3 * D only when D is a multiple of 64 (with D = 96 the last head's v columns were never computed)
+    if ((heads * head_dim) % 64)
+        return fail(OCM_EINVAL, "heads * head_dim = %d must be a multiple of 64", heads * head_dim);
     if (copies && head_dim != 64 && head_dim != 128)
         return fail(OCM_EINVAL, "head_dim %d: operand copies exist for 64- and 128-wide heads", head_dim);
     HIP_TRY(launch_qkv(pc, a, w, bias, q, k, vt, qkv_f32, batch, n_tokens, ocm_n_pad_for(pc, n_tokens), heads, head_dim, true,

@@ -126,8 +126,11 @@ class Attention(nn.Module):
         lib, pc = _lib.load(), _module_prec(self)
         B, N, Cd = x.shape
         H = self.num_heads
-        if Cd % H or (Cd // H) % 8:
-            raise ValueError(f"dim {Cd} / num_heads {H}: the HIP kernels need a head width that is a multiple of 8")
+        # the C limits of the operators this path calls (ocm_op_qkv_proj_hd, ocm_op_attention_generic, ocm_op_linear), the
+        # same in every precision: a head width that is a multiple of 8 up to 512, a dim that is a multiple of 64
+        if Cd % H or (Cd // H) % 8 or Cd // H > 512 or Cd % 64:
+            raise ValueError(f"dim {Cd} / num_heads {H}: the HIP kernels need a head width that is a multiple of 8 (at most 512) "
+                             "and a dim that is a multiple of 64")
         hd = Cd // H
         # 64- and 128-wide heads (model.py:93-103) run the MFMA attention kernels in every precision; any other width (the
         # reference accepts every dim / num_heads, :66-90) the generic fp32 kernel on the fp32 qkv tensor

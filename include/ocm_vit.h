@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define OCM_ABI_VERSION 9
+#define OCM_ABI_VERSION 10
 
 enum {
     OCM_OK = 0,
@@ -385,6 +385,42 @@ int ocm_op_pixel_shuffle(const float *lin, float *out, int32_t batch, int32_t hp
  * matching weight is the (O, C, 3, 3) kernel permuted to (O, 3, 3, C). */
 int ocm_op_im2col3x3(int32_t precision, const float *in, void *out, int32_t batch, int32_t h, int32_t w,
                      int32_t channels, int32_t relu, void *stream);
+
+/* ---- training of the LinearProbing decoders on a frozen encoder (model.py:142-174; kernels_train.hip) ----
+ * Token-major rows m = (image, y, x), M = B*hp*wp. Every reduction runs in a fixed order decided by the shapes alone (no
+ * atomics): the same inputs give the same bits on every run. Statistics, sums and accumulators are fp32. Workspaces are
+ * caller-allocated device memory of at least the queried size; their contents on entry do not matter. */
+
+/* Weight (and bias) gradient of a token-major linear map Y = X W^T + b: dw[N][K] = sum_m dy[m][n] x[m][k] and, when db is
+ * not NULL, db[N] = sum_m dy[m][n]. dy fp32 [M][N], x fp32 [M][K], row-major; the products run on the MFMA in `precision`
+ * (the operands are rounded to bf16 / split pairs on the way into LDS; fp32 keeps exact products), fp32 accumulate. M is
+ * split across workgroups and the partial slabs are added in slice order. N % 32 == 0, K % 32 == 0, any M >= 1.
+ * For the decoders: conv1 (N = 4 s^2, K = 9 D, x = im2col of the patch tokens), conv2 (N = s^2, K = 9 * 4 s^2), the 1x1
+ * head (N = s^2 * c_out, K = D, x = the normed patch tokens). */
+size_t ocm_weight_grad_workspace_bytes(int32_t M, int32_t N, int32_t K);
+int ocm_op_weight_grad(int32_t precision, const float *dy, const float *x, float *dw, float *db, int32_t M, int32_t N,
+                       int32_t K, void *workspace, size_t workspace_bytes, void *stream);
+
+/* Workspace of the per-channel reductions below for `rows` x `channels`. */
+size_t ocm_channel_reduce_workspace_bytes(int64_t rows, int32_t channels);
+/* BatchNorm2d batch statistics of a token-major fp32 [rows][channels] tensor: mean and the BIASED variance, two passes
+ * (the second sums (x - mean)^2: no cancellation when a channel's mean is large against its spread). */
+int ocm_op_batch_stats(const float *x, float *mean, float *var, int64_t rows, int32_t channels, void *workspace,
+                       size_t workspace_bytes, void *stream);
+/* ocm_op_im2col3x3 of z = max(y * scale[c] + shift[c], 0) (BatchNorm with scale = gamma * invstd, shift = beta - mean *
+ * scale, then the ReLU): conv2's operand in the training-mode forward, in the operand type of `precision`. */
+int ocm_op_bn_relu_im2col3x3(int32_t precision, const float *y, const float *scale, const float *shift, void *out,
+                             int32_t batch, int32_t h, int32_t w, int32_t channels, void *stream);
+/* Backward of z = ReLU(BatchNorm(y)) with batch statistics, all [rows][channels] fp32, channels % 4 == 0:
+ *   u = dz * [y * scale + shift > 0],  xhat = (y - mean) * invstd
+ *   dbeta = sum_m u,  dgamma = sum_m u * xhat,  dy = scale * (u - dbeta / rows - xhat * dgamma / rows). */
+int ocm_op_bn_relu_backward(const float *dz, const float *y, const float *mean, const float *invstd, const float *scale,
+                            const float *shift, float *dy, float *dgamma, float *dbeta, int64_t rows, int32_t channels,
+                            void *workspace, size_t workspace_bytes, void *stream);
+/* Inverse of ocm_op_pixel_shuffle: grad_lin[b*hp*wp + y*wp + x][c*s*s + i*s + j] = grad_out[b][c][y*s+i][x*s+j] (a gather,
+ * bit exact). */
+int ocm_op_pixel_shuffle_backward(const float *grad_out, float *grad_lin, int32_t batch, int32_t hp, int32_t wp,
+                                  int32_t c_out, int32_t s, void *stream);
 
 /* ---- sliding-window index math (host, integer; sw_processing.py:151-163) ---- */
 /* Number of windows per axis: len(range(0, size - 2*stride, stride)). */

@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # OCM_VIT_LIB lets kernel experiments A/B two builds of the same ABI; the default is the in-tree build.
 LIB_PATH = os.environ.get("OCM_VIT_LIB") or os.path.join(_HERE, "libocm_vit.so")
 
-OCM_ABI_VERSION = 9
+OCM_ABI_VERSION = 10
 OCM_OK, OCM_EINVAL, OCM_ESTATE, OCM_EHIP, OCM_ENOMEM, OCM_ENAME = 0, 1, 2, 3, 4, 5
 
 OCM_PREC_BF16 = 0
@@ -175,6 +175,13 @@ SIGNATURES = {
     "ocm_vit_set_option": (C.c_int, [C.c_void_p, _i32, _i32]),
     "ocm_prof_begin": (C.c_int, [C.c_uint32, _i32]),
     "ocm_prof_end": (C.c_int, [C.POINTER(C.c_double), C.POINTER(_i64)]),
+    "ocm_weight_grad_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "ocm_op_weight_grad": (C.c_int, [_i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _sz, _vp]),
+    "ocm_channel_reduce_workspace_bytes": (_sz, [_i64, _i32]),
+    "ocm_op_batch_stats": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _vp, _sz, _vp]),
+    "ocm_op_bn_relu_im2col3x3": (C.c_int, [_i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
+    "ocm_op_bn_relu_backward": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _sz, _vp]),
+    "ocm_op_pixel_shuffle_backward": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "ocm_sw_count": (_i32, [_i32, _i32]),
     "ocm_sw_origins": (_i32, [_i32, _i32, _i32, C.POINTER(_i32), _i32]),
     "ocm_sw_shard": (_i32, [_i32, _i32, _i32, C.POINTER(_i32), C.POINTER(_i32)]),

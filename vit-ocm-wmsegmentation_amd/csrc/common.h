@@ -105,6 +105,22 @@ __device__ __forceinline__ f32x4_t mfma16x3(bf16x8 ah, bf16x8 al, bf16x8 bh, bf1
     c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bl, c, 0, 0, 0);
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bh, c, 0, 0, 0);
 }
+// Eight consecutive rows of one column of a row-major 16-bit LDS tile as an MFMA fragment: two ds_read_b64_tr_b16 (gfx950),
+// the second four rows (256 bytes at 64-byte rows) further down. `p` is this lane's address for the first block.
+__device__ __forceinline__ bf16x8 tr_read8(const char *p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    typedef short s16x4 __attribute__((ext_vector_type(4)));
+    typedef __attribute__((address_space(3))) s16x4 *lds_s16x4;
+    const s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)p);
+    const s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(p + 4 * 64));
+    typedef short s16x8 __attribute__((ext_vector_type(8)));
+    const s16x8 v = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
+    return __builtin_bit_cast(bf16x8, v);
+#else
+    return bf16x8{};
+#endif
+}
+
 // Accumulator layouts of a 32 x 32 output tile held as f32x16 per lane. ACCL 0: one 32x32x16 accumulator (register -> row
 // acc_row32, lane & 31 -> column). ACCL 1: four 16x16x32 accumulators, sub-tile q = 2 * (row half) + (column half) in
 // registers 4q .. 4q+3. rpos = coordinate along the register-indexed axis, cpos = along the lane-indexed axis.

@@ -558,9 +558,12 @@ hipError_t launch_pixel_shuffle(const float *lin, float *out, int batch, int hp,
 // in: token-major fp32 [B][h*w][C]; out: operand rows [B*h*w][9*C] with K index (ky*3 + kx)*C + c, zero outside the
 // image, optional ReLU on the way (the nn.ReLU between the two convolutions). One thread = 8 consecutive channels
 // of one (token, tap); C % 32 == 0 keeps every 8-channel run inside one split-pair group.
-template <int OUT>  // 0 fp32, 1 bf16, 2 split pairs
+// AFFINE (the training decoder's BatchNorm with batch statistics, kernels_train.hip): max(fma(x, scale[c], shift[c]), 0)
+// instead of the plain ReLU — the zero padding outside the image stays zero, as the convolution pads the ReLU's output.
+template <int OUT, bool AFFINE = false>  // OUT: 0 fp32, 1 bf16, 2 split pairs
 __global__ __launch_bounds__(256) void im2col3x3_kernel(const float *__restrict__ in, char *__restrict__ out, int B, int h,
-                                                        int w, int C, int relu) {
+                                                        int w, int C, int relu, const float *__restrict__ scale = nullptr,
+                                                        const float *__restrict__ shift = nullptr) {
     const int c8 = C >> 3;
     const size_t total = (size_t)B * h * w * 9 * c8;
     const int esz = OUT == 1 ? 2 : 4;
@@ -578,7 +581,15 @@ __global__ __launch_bounds__(256) void im2col3x3_kernel(const float *__restrict_
             const float *src = in + (((size_t)b * h + yy) * w + xx) * C + cc * 8;
             v0 = *(const f32x4 *)src;
             v1 = *(const f32x4 *)(src + 4);
-            if (relu) {
+            if (AFFINE) {
+                const f32x4 g0 = *(const f32x4 *)(scale + cc * 8), g1 = *(const f32x4 *)(scale + cc * 8 + 4);
+                const f32x4 h0 = *(const f32x4 *)(shift + cc * 8), h1 = *(const f32x4 *)(shift + cc * 8 + 4);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    v0[e] = fmaxf(fmaf(v0[e], g0[e], h0[e]), 0.f);
+                    v1[e] = fmaxf(fmaf(v1[e], g1[e], h1[e]), 0.f);
+                }
+            } else if (relu) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     v0[e] = fmaxf(v0[e], 0.f);
@@ -615,5 +626,21 @@ hipError_t launch_im2col3x3(int prec, const float *in, void *out, int batch, int
         im2col3x3_kernel<0><<<grid, block, 0, s>>>(in, (char *)out, batch, h, w, C, relu);
     else
         im2col3x3_kernel<2><<<grid, block, 0, s>>>(in, (char *)out, batch, h, w, C, relu);
+    return hipGetLastError();
+}
+
+hipError_t launch_bn_relu_im2col3x3(int prec, const float *in, const float *scale, const float *shift, void *out, int batch,
+                                    int h, int w, int C, hipStream_t s) {
+    if (C % 32 || batch <= 0 || h <= 0 || w <= 0) return hipErrorInvalidValue;
+    const size_t total = (size_t)batch * h * w * 9 * (C >> 3);
+    size_t blocks = (total + 255) / 256;
+    if (blocks > 8192) blocks = 8192;
+    const dim3 grid((unsigned)blocks), block(256);
+    if (prec == 0)
+        im2col3x3_kernel<1, true><<<grid, block, 0, s>>>(in, (char *)out, batch, h, w, C, 1, scale, shift);
+    else if (prec == 1)
+        im2col3x3_kernel<0, true><<<grid, block, 0, s>>>(in, (char *)out, batch, h, w, C, 1, scale, shift);
+    else
+        im2col3x3_kernel<2, true><<<grid, block, 0, s>>>(in, (char *)out, batch, h, w, C, 1, scale, shift);
     return hipGetLastError();
 }

@@ -373,22 +373,6 @@ __device__ __forceinline__ int win_region(const WinGeom &g, int ws, int wy, int 
     return ry * 3 + rx;
 }
 
-// Eight consecutive rows of one column of a row-major 16-bit LDS tile as an MFMA fragment: two ds_read_b64_tr_b16 (gfx950),
-// the second four rows (256 bytes at 64-byte rows) further down. `p` is this lane's address for the first block.
-__device__ __forceinline__ bf16x8 tr_read8(const char *p) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    typedef short s16x4 __attribute__((ext_vector_type(4)));
-    typedef __attribute__((address_space(3))) s16x4 *lds_s16x4;
-    const s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)p);
-    const s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(p + 4 * 64));
-    typedef short s16x8 __attribute__((ext_vector_type(8)));
-    const s16x8 v = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-    return __builtin_bit_cast(bf16x8, v);
-#else
-    return bf16x8{};
-#endif
-}
-
 // bf16 / MFMA: one wavefront per (b, window, head), head_dim 32, ws*ws <= 64 positions.
 // S^T = K.Q^T with the K rows in pi order (common.h): registers hold keys, the lane holds the query, so the
 // row max / sum are in-register reductions plus one lane <-> lane+32 exchange and the exponentiated tile is

@@ -1,0 +1,412 @@
+// kernels_train.hip — the backward pass of LinearProbing's decoders (model.py:142-174) on a frozen encoder, and the
+// BatchNorm batch statistics its training-mode forward needs:
+//   wgrad_kernel / wgrad_reduce_kernel   dW[N][K] = sum_m dY[m][N] X[m][K] on MFMA, M split across workgroups, slabs summed
+//                                        in slice order (no atomics: the same bits on every run)
+//   chan_reduce_kernel / chan_finish     per-channel sums of a token-major [rows][C] fp32 tensor in a fixed order: bias
+//                                        gradients, batch mean and (two-pass) variance, the ReLU + BatchNorm backward sums
+//   bn_relu_bwd_kernel                   dy = g (u - mean(u) - xhat mean(u xhat)), u = dz [y g + h > 0]
+//   pixel_shuffle_bwd_kernel             gather (B, c, H, W) -> (B*hp*wp, s*s*c), the exact inverse of pixel_shuffle_kernel
+// The forward's BatchNorm-affine + ReLU operand writer is the AFFINE variant of im2col3x3_kernel (kernels_misc.hip).
+#include "host_common.h"
+#include "launch.h"
+
+#define fail ocm_fail
+
+namespace {
+
+// ---- weight gradient ---------------------------------------------------------------------------------------------------
+// One workgroup (4 waves, 2 x 2) owns a TN x 128 tile of dW and one slice of the M rows. Per stage it stages 32 rows of
+// dY (32 x TN) and X (32 x 128) from HBM (fp32, row-major: both operands are strided along the contraction axis) into
+// LDS in the operand type:
+//   E 0 / 2 (bf16 / split pairs): [column block of 32][32 rows][32 columns] 16-bit images with 64-byte rows (hi and lo
+//           images for split pairs); an MFMA fragment (eight consecutive rows of one column) is two ds_read_b64_tr_b16
+//           (tr_read8, common.h), for A = dY^T as for B = X;
+//   E 1 (fp32): plain [32 rows][columns] fp32 rows, one element per lane and k step of v_mfma_f32_32x32x2_f32.
+// The next stage's global loads are issued before the current stage's MFMAs. Rows past the slice end and columns past
+// N / K load as zeros (pad, don't mask: every lane takes part in the transposed reads).
+constexpr int WG_TK = 128, WG_BM = 32;
+
+template <int E, int TN>
+struct WgradLds {
+    static constexpr int ybytes = E == 1 ? WG_BM * TN * 4 : TN * 64;      // one image of dY (per half for split pairs)
+    static constexpr int xbytes = E == 1 ? WG_BM * WG_TK * 4 : WG_TK * 64;
+    static constexpr int halves = E == 2 ? 2 : 1;
+    static constexpr int bytes = halves * (ybytes + xbytes);
+};
+
+template <int E, int COLS>
+__device__ __forceinline__ void wgrad_stage_store(char *img, int imgbytes, int row, int col, const f32x4 &v) {
+    if (E == 1) {
+        *(f32x4 *)(img + (row * COLS + col) * 4) = v;
+    } else {
+        const int off = (col >> 5) * (WG_BM * 64) + row * 64 + (col & 31) * 2;
+        bf16x4 hi, lo;
+        if (E == 2) {
+            split4(v, hi, lo);
+            *(bf16x4 *)(img + imgbytes + off) = lo;
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) hi[e] = (bf16)v[e];
+        }
+        *(bf16x4 *)(img + off) = hi;
+    }
+}
+
+template <int E, int TN>
+__global__ __launch_bounds__(256) void wgrad_kernel(const float *__restrict__ dy, const float *__restrict__ x,
+                                                    float *__restrict__ out, int M, int N, int K, int rows_per_slice,
+                                                    size_t slab_elems) {
+    using L = WgradLds<E, TN>;
+    __shared__ __attribute__((aligned(16))) char smem[L::bytes];
+    char *Ys = smem, *Xs = smem + L::halves * L::ybytes;
+    constexpr int NI = TN / 64;                 // 32-row output sub-tiles per wave along N
+    constexpr int YV = WG_BM * TN / 4 / 256;    // f32x4 loads per thread per stage
+    constexpr int XV = WG_BM * WG_TK / 4 / 256;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wn = wave >> 1, wk = wave & 1, r = lane & 31, h = lane >> 5;
+    const int k0 = blockIdx.x * WG_TK, n0 = blockIdx.y * TN;
+    const int m_begin = blockIdx.z * rows_per_slice, m_end = min(M, m_begin + rows_per_slice);
+    out += (size_t)blockIdx.z * slab_elems;
+
+    f32x4 yv[YV], xv[XV];
+    auto load = [&](int m0) {
+#pragma unroll
+        for (int i = 0; i < YV; ++i) {
+            const int v = tid + 256 * i, row = v / (TN / 4), col = (v % (TN / 4)) * 4;
+            const int m = m0 + row, n = n0 + col;
+            yv[i] = (m < m_end && n < N) ? *(const f32x4 *)(dy + (size_t)m * N + n) : f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+#pragma unroll
+        for (int i = 0; i < XV; ++i) {
+            const int v = tid + 256 * i, row = v / (WG_TK / 4), col = (v % (WG_TK / 4)) * 4;
+            const int m = m0 + row, k = k0 + col;
+            xv[i] = (m < m_end && k < K) ? *(const f32x4 *)(x + (size_t)m * K + k) : f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+    };
+
+    f32x16 acc[NI][2];
+#pragma unroll
+    for (int i = 0; i < NI; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+
+    // lane address of the transposed read inside one [32 rows][32 columns] block (the Swin V^T read: lane 4q + p of a
+    // 16-lane group addresses row q, columns 4p .. 4p+3 of its half of the block)
+    const int tr_lane = (8 * h + ((lane >> 2) & 3)) * 64 + (16 * ((lane >> 4) & 1) + 4 * (lane & 3)) * 2;
+
+    if (m_begin < m_end) load(m_begin);
+    for (int m0 = m_begin; m0 < m_end; m0 += WG_BM) {
+        __syncthreads();  // the previous stage's reads are done
+#pragma unroll
+        for (int i = 0; i < YV; ++i) {
+            const int v = tid + 256 * i;
+            wgrad_stage_store<E, TN>(Ys, L::ybytes, v / (TN / 4), (v % (TN / 4)) * 4, yv[i]);
+        }
+#pragma unroll
+        for (int i = 0; i < XV; ++i) {
+            const int v = tid + 256 * i;
+            wgrad_stage_store<E, WG_TK>(Xs, L::xbytes, v / (WG_TK / 4), (v % (WG_TK / 4)) * 4, xv[i]);
+        }
+        __syncthreads();
+        if (m0 + WG_BM < m_end) load(m0 + WG_BM);  // in flight during the MFMAs below
+        if (E == 1) {
+            const float *Yf = (const float *)Ys, *Xf = (const float *)Xs;
+#pragma unroll 4
+            for (int t = 0; t < WG_BM / 2; ++t) {
+                const int row = 2 * t + h;
+                float a[NI], b[2];
+#pragma unroll
+                for (int i = 0; i < NI; ++i) a[i] = Yf[row * TN + wn * (TN / 2) + 32 * i + r];
+#pragma unroll
+                for (int j = 0; j < 2; ++j) b[j] = Xf[row * WG_TK + wk * 64 + 32 * j + r];
+#pragma unroll
+                for (int i = 0; i < NI; ++i)
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) acc[i][j] = mfma32f(a[i], b[j], acc[i][j]);
+            }
+        } else {
+#pragma unroll
+            for (int s = 0; s < WG_BM / 16; ++s) {
+                bf16x8 ah[NI], al[NI], bh[2], bl[2];
+#pragma unroll
+                for (int i = 0; i < NI; ++i) {
+                    const char *p = Ys + ((wn * (TN / 2) + 32 * i) >> 5) * (WG_BM * 64) + 16 * s * 64 + tr_lane;
+                    ah[i] = tr_read8(p);
+                    if (E == 2) al[i] = tr_read8(p + L::ybytes);
+                }
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    const char *p = Xs + ((wk * 64 + 32 * j) >> 5) * (WG_BM * 64) + 16 * s * 64 + tr_lane;
+                    bh[j] = tr_read8(p);
+                    if (E == 2) bl[j] = tr_read8(p + L::xbytes);
+                }
+#pragma unroll
+                for (int i = 0; i < NI; ++i)
+#pragma unroll
+                    for (int j = 0; j < 2; ++j)
+                        acc[i][j] = E == 2 ? mfma32x3(ah[i], al[i], bh[j], bl[j], acc[i][j]) : mfma32(ah[i], bh[j], acc[i][j]);
+            }
+        }
+    }
+    // N and K are multiples of 32: a 32 x 32 sub-tile is wholly inside dW or wholly outside
+#pragma unroll
+    for (int i = 0; i < NI; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int nb = n0 + wn * (TN / 2) + 32 * i, kb = k0 + wk * 64 + 32 * j;
+            if (nb >= N || kb >= K) continue;
+#pragma unroll
+            for (int e = 0; e < 16; ++e) out[(size_t)(nb + acc_row32(e, h)) * K + kb + r] = acc[i][j][e];
+        }
+}
+
+// dW = slab 0 + slab 1 + ... in slice order
+__global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float *__restrict__ slabs, int slices, size_t n4,
+                                                           float *__restrict__ dw) {
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
+        f32x4 s = ((const f32x4 *)slabs)[i];
+        for (int z = 1; z < slices; ++z) s += ((const f32x4 *)slabs)[(size_t)z * n4 + i];
+        ((f32x4 *)dw)[i] = s;
+    }
+}
+
+struct WgradPlan {
+    int tn, slices, rows_per_slice;
+};
+
+// Shape-only decomposition (so that a given shape always sums in the same order): enough (tile, slice) workgroups to give
+// the 256 CUs about four each, at least 256 rows per slice, at most 32 slices.
+WgradPlan wgrad_plan(int M, int N, int K) {
+    WgradPlan p;
+    p.tn = N % 128 == 0 ? 128 : 64;
+    const long tiles = (long)((N + p.tn - 1) / p.tn) * ((K + WG_TK - 1) / WG_TK);
+    long s = (1024 + tiles - 1) / tiles;
+    s = std::min<long>(s, (M + 255) / 256);
+    s = std::max<long>(1, std::min<long>(s, 32));
+    const int per = (int)(((M + s - 1) / s + WG_BM - 1) / WG_BM) * WG_BM;
+    p.rows_per_slice = per;
+    p.slices = (M + per - 1) / per;
+    return p;
+}
+
+// ---- per-channel reductions ---------------------------------------------------------------------------------------------
+// Rows are cut into R chunks (a function of the row count alone); a workgroup sums 64 channels of one chunk (4 row groups of
+// 64 threads, rows strided by 4, combined in LDS in group order) and writes partial[k][chunk][c]; chan_finish_kernel adds
+// the R partials of a channel in chunk order. Fixed order everywhere: the same bits on every run.
+//   MODE 0: sum x                           MODE 1: sum (x - mean)^2  (the second pass of the variance)
+//   MODE 2: sum u and sum u * xhat with u = dz [fma(y, g, h) > 0], xhat = (y - mean) * invstd
+int chan_chunks(int64_t rows) { return (int)std::min<int64_t>((rows + 255) / 256, 128); }
+
+template <int MODE>
+__global__ __launch_bounds__(256) void chan_reduce_kernel(const float *__restrict__ a, const float *__restrict__ y,
+                                                          const float *__restrict__ mean, const float *__restrict__ invstd,
+                                                          const float *__restrict__ scale, const float *__restrict__ shift,
+                                                          float *__restrict__ part, int64_t rows, int C, int64_t chunk) {
+    __shared__ float red[2][4][64];
+    const int tc = threadIdx.x & 63, rg = threadIdx.x >> 6;
+    const int c = blockIdx.x * 64 + tc, R = gridDim.y;
+    const int64_t r0 = (int64_t)blockIdx.y * chunk, r1 = std::min<int64_t>(rows, r0 + chunk);
+    float s0 = 0.f, s1 = 0.f;
+    if (c < C) {
+        const float mu = MODE ? mean[c] : 0.f;
+        const float is = MODE == 2 ? invstd[c] : 0.f, g = MODE == 2 ? scale[c] : 0.f, hh = MODE == 2 ? shift[c] : 0.f;
+        for (int64_t m = r0 + rg; m < r1; m += 4) {
+            const float v = a[m * C + c];
+            if (MODE == 0) {
+                s0 += v;
+            } else if (MODE == 1) {
+                const float d = v - mu;
+                s0 = fmaf(d, d, s0);
+            } else {
+                const float yv = y[m * C + c];
+                const float u = fmaf(yv, g, hh) > 0.f ? v : 0.f;
+                s0 += u;
+                s1 = fmaf(u, (yv - mu) * is, s1);
+            }
+        }
+    }
+    red[0][rg][tc] = s0;
+    red[1][rg][tc] = s1;
+    __syncthreads();
+    if (rg == 0 && c < C) {
+        part[(size_t)blockIdx.y * C + c] = ((red[0][0][tc] + red[0][1][tc]) + red[0][2][tc]) + red[0][3][tc];
+        if (MODE == 2)
+            part[((size_t)R + blockIdx.y) * C + c] = ((red[1][0][tc] + red[1][1][tc]) + red[1][2][tc]) + red[1][3][tc];
+    }
+}
+
+// out0[c] = sum_r part[0][r][c] (divided by `div` when div > 0), out1 likewise from part[1] when out1 != null
+__global__ __launch_bounds__(256) void chan_finish_kernel(const float *__restrict__ part, int R, int C, float div,
+                                                          float *__restrict__ out0, float *__restrict__ out1) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= C) return;
+    float s0 = 0.f, s1 = 0.f;
+    for (int r = 0; r < R; ++r) s0 += part[(size_t)r * C + c];
+    out0[c] = div > 0.f ? s0 / div : s0;
+    if (out1) {
+        for (int r = 0; r < R; ++r) s1 += part[((size_t)R + r) * C + c];
+        out1[c] = div > 0.f ? s1 / div : s1;
+    }
+}
+
+template <int MODE>
+hipError_t launch_chan_reduce(const float *a, const float *y, const float *mean, const float *invstd, const float *scale,
+                              const float *shift, float *part, float *out0, float *out1, float div, int64_t rows, int C,
+                              hipStream_t s) {
+    const int R = chan_chunks(rows);
+    const int64_t chunk = (rows + R - 1) / R;
+    chan_reduce_kernel<MODE><<<dim3((C + 63) / 64, R), dim3(256), 0, s>>>(a, y, mean, invstd, scale, shift, part, rows, C,
+                                                                           chunk);
+    chan_finish_kernel<<<dim3((C + 255) / 256), dim3(256), 0, s>>>(part, R, C, div, out0, out1);
+    return hipGetLastError();
+}
+
+// ---- ReLU + BatchNorm backward, elementwise part ----
+__global__ __launch_bounds__(256) void bn_relu_bwd_kernel(const float *__restrict__ dz, const float *__restrict__ y,
+                                                          const float *__restrict__ mean, const float *__restrict__ invstd,
+                                                          const float *__restrict__ scale, const float *__restrict__ shift,
+                                                          const float *__restrict__ dbeta, const float *__restrict__ dgamma,
+                                                          float *__restrict__ dy, size_t n4, int C, float inv_rows) {
+    const int c4 = C >> 2;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
+        const int c = (int)(i % c4) * 4;
+        const f32x4 d = ((const f32x4 *)dz)[i], yv = ((const f32x4 *)y)[i];
+        f32x4 o;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float g = scale[c + e];
+            const float u = fmaf(yv[e], g, shift[c + e]) > 0.f ? d[e] : 0.f;
+            const float xh = (yv[e] - mean[c + e]) * invstd[c + e];
+            o[e] = g * (u - dbeta[c + e] * inv_rows - xh * (dgamma[c + e] * inv_rows));
+        }
+        ((f32x4 *)dy)[i] = o;
+    }
+}
+
+// ---- PixelShuffle backward: one thread per element of the token-major gradient (coalesced stores) ----
+__global__ __launch_bounds__(256) void pixel_shuffle_bwd_kernel(const float *__restrict__ gout, float *__restrict__ lin,
+                                                                int hp, int wp, int c_out, int sh, size_t total) {
+    const int O = c_out * sh * sh, Hs = hp * sh, Ws = wp * sh;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+        const int o = (int)(i % O);
+        const size_t row = i / O;
+        const int x = (int)(row % wp);
+        const size_t r2 = row / wp;
+        const int y = (int)(r2 % hp), b = (int)(r2 / hp);
+        const int jj = o % sh, ii = (o / sh) % sh, c = o / (sh * sh);
+        lin[i] = gout[(((size_t)b * c_out + c) * Hs + y * sh + ii) * Ws + x * sh + jj];
+    }
+}
+
+size_t grid_of(size_t work, size_t cap) { return std::max<size_t>(1, std::min<size_t>((work + 255) / 256, cap)); }
+
+int prec_ok(int32_t precision) {
+    if (precision != OCM_PREC_BF16 && precision != OCM_PREC_FP32 && precision != OCM_PREC_BF16X3)
+        return fail(OCM_EINVAL, "bad precision %d", precision);
+    return OCM_OK;
+}
+
+}  // namespace
+
+// ---- C ABI (include/ocm_vit.h, "decoder training") -----------------------------------------------------------------------
+extern "C" size_t ocm_channel_reduce_workspace_bytes(int64_t rows, int32_t channels) {
+    if (rows <= 0 || channels <= 0) return 0;
+    return (size_t)2 * chan_chunks(rows) * channels * sizeof(float);
+}
+
+extern "C" size_t ocm_weight_grad_workspace_bytes(int32_t M, int32_t N, int32_t K) {
+    if (M <= 0 || N <= 0 || K <= 0) return 0;
+    const WgradPlan p = wgrad_plan(M, N, K);
+    const size_t slabs = p.slices > 1 ? (size_t)p.slices * N * K * sizeof(float) : 0;
+    return std::max(slabs, ocm_channel_reduce_workspace_bytes(M, N));
+}
+
+extern "C" int ocm_op_weight_grad(int32_t precision, const float *dy, const float *x, float *dw, float *db, int32_t M,
+                                  int32_t N, int32_t K, void *workspace, size_t workspace_bytes, void *stream) {
+    if (int rc = prec_ok(precision)) return rc;
+    if (!dy || !x || !dw) return fail(OCM_EINVAL, "null argument");
+    if (M <= 0 || N <= 0 || K <= 0 || N % 32 || K % 32)
+        return fail(OCM_EINVAL, "bad shape M=%d N=%d K=%d (N %% 32, K %% 32)", M, N, K);
+    const size_t need = ocm_weight_grad_workspace_bytes(M, N, K);
+    if (need && (!workspace || workspace_bytes < need))
+        return fail(OCM_ENOMEM, "weight_grad workspace: %zu bytes given, %zu needed", workspace_bytes, need);
+    const hipStream_t s = (hipStream_t)stream;
+    const WgradPlan p = wgrad_plan(M, N, K);
+    float *target = p.slices > 1 ? (float *)workspace : dw;
+    const dim3 grid((K + WG_TK - 1) / WG_TK, (N + p.tn - 1) / p.tn, p.slices), block(256);
+    const size_t slab = (size_t)N * K;
+#define WGRAD(E, TN) wgrad_kernel<E, TN><<<grid, block, 0, s>>>(dy, x, target, M, N, K, p.rows_per_slice, slab)
+    if (p.tn == 128) {
+        if (precision == OCM_PREC_BF16) WGRAD(0, 128); else if (precision == OCM_PREC_FP32) WGRAD(1, 128); else WGRAD(2, 128);
+    } else {
+        if (precision == OCM_PREC_BF16) WGRAD(0, 64); else if (precision == OCM_PREC_FP32) WGRAD(1, 64); else WGRAD(2, 64);
+    }
+#undef WGRAD
+    HIP_TRY(hipGetLastError());
+    if (p.slices > 1) {
+        wgrad_reduce_kernel<<<dim3((unsigned)grid_of(slab / 4, 4096)), dim3(256), 0, s>>>((const float *)workspace, p.slices,
+                                                                                          slab / 4, dw);
+        HIP_TRY(hipGetLastError());
+    }
+    // the bias gradient reuses the workspace once the slabs are consumed (stream order)
+    if (db) HIP_TRY(launch_chan_reduce<0>(dy, nullptr, nullptr, nullptr, nullptr, nullptr, (float *)workspace, db, nullptr,
+                                          0.f, M, N, s));
+    return OCM_OK;
+}
+
+extern "C" int ocm_op_batch_stats(const float *x, float *mean, float *var, int64_t rows, int32_t channels, void *workspace,
+                                  size_t workspace_bytes, void *stream) {
+    if (!x || !mean || !var) return fail(OCM_EINVAL, "null argument");
+    if (rows <= 0 || channels <= 0) return fail(OCM_EINVAL, "bad shape rows=%lld channels=%d", (long long)rows, channels);
+    const size_t need = ocm_channel_reduce_workspace_bytes(rows, channels);
+    if (!workspace || workspace_bytes < need)
+        return fail(OCM_ENOMEM, "batch_stats workspace: %zu bytes given, %zu needed", workspace_bytes, need);
+    const hipStream_t s = (hipStream_t)stream;
+    float *part = (float *)workspace;
+    HIP_TRY(launch_chan_reduce<0>(x, nullptr, nullptr, nullptr, nullptr, nullptr, part, mean, nullptr, (float)rows, rows,
+                                  channels, s));
+    HIP_TRY(launch_chan_reduce<1>(x, nullptr, mean, nullptr, nullptr, nullptr, part, var, nullptr, (float)rows, rows, channels,
+                                  s));
+    return OCM_OK;
+}
+
+extern "C" int ocm_op_bn_relu_im2col3x3(int32_t precision, const float *y, const float *scale, const float *shift, void *out,
+                                        int32_t batch, int32_t h, int32_t w, int32_t channels, void *stream) {
+    if (int rc = prec_ok(precision)) return rc;
+    if (!y || !scale || !shift || !out) return fail(OCM_EINVAL, "null argument");
+    if (batch <= 0 || h <= 0 || w <= 0 || channels <= 0 || channels % 32)
+        return fail(OCM_EINVAL, "bad shape batch=%d h=%d w=%d channels=%d (channels %% 32)", batch, h, w, channels);
+    HIP_TRY(launch_bn_relu_im2col3x3(precision, y, scale, shift, out, batch, h, w, channels, (hipStream_t)stream));
+    return OCM_OK;
+}
+
+extern "C" int ocm_op_bn_relu_backward(const float *dz, const float *y, const float *mean, const float *invstd,
+                                       const float *scale, const float *shift, float *dy, float *dgamma, float *dbeta,
+                                       int64_t rows, int32_t channels, void *workspace, size_t workspace_bytes, void *stream) {
+    if (!dz || !y || !mean || !invstd || !scale || !shift || !dy || !dgamma || !dbeta) return fail(OCM_EINVAL, "null argument");
+    if (rows <= 0 || channels <= 0 || channels % 4)
+        return fail(OCM_EINVAL, "bad shape rows=%lld channels=%d (channels %% 4)", (long long)rows, channels);
+    const size_t need = ocm_channel_reduce_workspace_bytes(rows, channels);
+    if (!workspace || workspace_bytes < need)
+        return fail(OCM_ENOMEM, "bn_relu_backward workspace: %zu bytes given, %zu needed", workspace_bytes, need);
+    const hipStream_t s = (hipStream_t)stream;
+    HIP_TRY(launch_chan_reduce<2>(dz, y, mean, invstd, scale, shift, (float *)workspace, dbeta, dgamma, 0.f, rows, channels, s));
+    const size_t n4 = (size_t)rows * channels / 4;
+    bn_relu_bwd_kernel<<<dim3((unsigned)grid_of(n4, 8192)), dim3(256), 0, s>>>(dz, y, mean, invstd, scale, shift, dbeta, dgamma,
+                                                                              dy, n4, channels, 1.0f / (float)rows);
+    HIP_TRY(hipGetLastError());
+    return OCM_OK;
+}
+
+extern "C" int ocm_op_pixel_shuffle_backward(const float *grad_out, float *grad_lin, int32_t batch, int32_t hp, int32_t wp,
+                                             int32_t c_out, int32_t sh, void *stream) {
+    if (!grad_out || !grad_lin) return fail(OCM_EINVAL, "null argument");
+    if (batch <= 0 || hp <= 0 || wp <= 0 || c_out <= 0 || sh <= 0) return fail(OCM_EINVAL, "bad shape");
+    const size_t total = (size_t)batch * hp * wp * c_out * sh * sh;
+    pixel_shuffle_bwd_kernel<<<dim3((unsigned)grid_of(total, 8192)), dim3(256), 0, (hipStream_t)stream>>>(
+        grad_out, grad_lin, hp, wp, c_out, sh, total);
+    HIP_TRY(hipGetLastError());
+    return OCM_OK;
+}

@@ -16,6 +16,9 @@ hipError_t launch_fold_split(const float *src, void *dst, int D, int C, int pp, 
 hipError_t launch_fold_cast_bf16(const float *src, bf16 *dst, int D, int C, int pp, hipStream_t s);
 hipError_t launch_fold_f32(const float *src, float *dst, int D, int C, int pp, hipStream_t s);
 hipError_t launch_im2col3x3(int prec, const float *in, void *out, int batch, int h, int w, int C, int relu, hipStream_t s);
+// the same gather with the training decoder's BatchNorm + ReLU applied on the way: max(fma(x, scale[c], shift[c]), 0)
+hipError_t launch_bn_relu_im2col3x3(int prec, const float *in, const float *scale, const float *shift, void *out, int batch,
+                                    int h, int w, int C, hipStream_t s);
 hipError_t launch_cls_rows(const float *cls, const float *pos, float *x, int batch, int n_tokens, int dim,
                            hipStream_t s);
 // ---- LayerNorm folded into its consumer GEMM (split-bf16 forward) ----

@@ -8,9 +8,11 @@
 
 Same constructor arguments, attributes and state_dict keys. The encoders run in one engine call (the mask
 blend is fused into the patch-embedding epilogue, the (B,C,H,W) permute is a device transpose); the 1x1-conv
-decoders run token-major as one MFMA GEMM + a pixel-shuffle kernel. Inference only: parameters are read,
-never differentiated. The reference initialises mask_token with timm's trunc_normal_; here the package's
-own trunc_normal_ (dino/utils.py) with the same bounds is used.
+decoders run token-major as one MFMA GEMM + a pixel-shuffle kernel. The encoders are inference only. LinearProbing
+also trains: in training mode with a frozen encoder (no encoder parameter requires grad: finetune.py's linear
+probing) its decoder runs with batch statistics and differentiates through HIP kernels (_DecoderTrain). The
+reference initialises mask_token with timm's trunc_normal_; here the package's own trunc_normal_ (dino/utils.py)
+with the same bounds is used.
 """
 import os
 from functools import partial
@@ -175,7 +177,9 @@ class LinearProbing(nn.Module):
         second convolution's operand, PixelShuffle by the scatter kernel."""
         conv1, bn, _, conv2, _ = self.two_layer_decoder
         if bn.training:
-            raise NotImplementedError("the HIP decoder evaluates BatchNorm with its running statistics: call .eval()")
+            raise NotImplementedError("training mode runs on the HIP path only with a frozen encoder (linear probing: set "
+                                      "requires_grad=False on every encoder parameter); the ViT backward is not "
+                                      "implemented. For inference call .eval()")
         enc, dev, lib = self.encoder, tokens.device, _lib.load()
         prec = _lib.PRECISIONS[enc._precision]
         B, N, D = tokens.shape
@@ -212,14 +216,238 @@ class LinearProbing(nn.Module):
                                                 self.encoder_stride, _stream()))
         return out
 
-    @torch.no_grad()
+    def _encoder_frozen(self):
+        return not any(p.requires_grad for p in self.encoder.parameters())
+
     def forward(self, x):
         _require_hip(x, "input")
-        tokens = self.encoder._encode(x, tokens=True)
-        if self.layer_num == 2:
-            return self._two_layer(tokens)
-        return _conv1x1_pixel_shuffle(self.encoder, tokens, self.one_layer_decoder[0], self.encoder_stride,
-                                      self._dec_cache)
+        if self.training and self._encoder_frozen():
+            with torch.no_grad():
+                tokens = self.encoder._encode(x, tokens=True)
+            return _train_forward(self, tokens)
+        with torch.no_grad():
+            tokens = self.encoder._encode(x, tokens=True)
+            if self.layer_num == 2:
+                return self._two_layer(tokens)
+            return _conv1x1_pixel_shuffle(self.encoder, tokens, self.one_layer_decoder[0], self.encoder_stride,
+                                          self._dec_cache)
+
+
+# ---- training-mode decoders on a frozen encoder (finetune.py --finetune False): forward with batch statistics and
+# backward through kernels_train.hip. Token-major rows m = (image, y, x), M = B*hp*wp; s = stride, mid = 4 s^2. ----
+_OPERAND_DTYPE = {_lib.OCM_PREC_BF16: torch.bfloat16, _lib.OCM_PREC_FP32: torch.float32, _lib.OCM_PREC_BF16X3: torch.int32}
+
+
+def flip_conv3x3(w):
+    """(O, C, 3, 3) kernel -> (C, 9*O) weight of the data gradient as a token-major 3x3 convolution: row c, column
+    (ky*3 + kx)*O + o holds w[o][c][2-ky][2-kx]. im2col3x3(dY) @ flip_conv3x3(w)^T equals conv2d_input(dY, w) with padding
+    1 (the transposed convolution is the convolution with the flipped, channel-transposed kernel)."""
+    return w.flip(2, 3).permute(1, 2, 3, 0).reshape(w.shape[1], -1)
+
+
+def _ws(nbytes, dev):
+    return torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
+
+
+def _weight_grad(prec, dy, x, want_bias):
+    """dW = dy^T x (and db = column sums of dy) on the weight-gradient kernel; dy (M, N), x (M, K) fp32."""
+    lib, (M, N), K = _lib.load(), dy.shape, x.shape[1]
+    dw = torch.empty((N, K), dtype=torch.float32, device=dy.device)
+    db = torch.empty((N,), dtype=torch.float32, device=dy.device) if want_bias else None
+    nbytes = lib.ocm_weight_grad_workspace_bytes(M, N, K)
+    ws = _ws(nbytes, dy.device)
+    _lib.check(lib.ocm_op_weight_grad(prec, _p(dy), _p(x), _p(dw), _p(db), M, N, K, _p(ws), nbytes, _stream()))
+    return dw, db
+
+
+def _pixel_shuffle_backward(g, M, s, hp, wp):
+    g = g.detach().to(torch.float32).contiguous()
+    B, c_out = g.shape[0], g.shape[1]
+    lin = torch.empty((M, c_out * s * s), dtype=torch.float32, device=g.device)
+    _lib.check(_lib.load().ocm_op_pixel_shuffle_backward(_p(g), _p(lin), B, hp, wp, c_out, s, _stream()))
+    return lin
+
+
+def _cached_operand(cache, name, w, prec, make):
+    """Operand copy of a weight, rebuilt when the parameter is replaced or updated in place (data_ptr, _version)."""
+    key = (w.data_ptr(), w._version, prec)
+    hit = cache.get(name)
+    if hit is None or hit[0] != key:
+        hit = (key, make())
+        cache[name] = hit
+    return hit[1]
+
+
+class _DecoderTrain(torch.autograd.Function):
+    """One training-mode decoder call: forward(patches, *params) -> (B, c_out, hp*s, wp*s); backward -> parameter gradients
+    only (the patch tokens come from the frozen encoder and get none). `meta` carries the module, its precision and, for the
+    caller, the batch statistics of the forward (the running-statistics update happens outside the graph)."""
+
+    @staticmethod
+    def forward(ctx, meta, patches, *params):
+        lp, prec, dev = meta["module"], meta["prec"], patches.device
+        lib, s = _lib.load(), lp.encoder_stride
+        B, P, D = patches.shape
+        hp = wp = int(P ** 0.5)
+        M = B * P
+        f32 = dict(device=dev, dtype=torch.float32)
+        cache = lp._dec_cache.setdefault("train", {})
+        out = torch.empty((B, 1 if lp.layer_num == 2 else lp.one_layer_decoder[0].out_channels // (s * s), hp * s, wp * s),
+                          **f32)
+        ctx.meta, ctx.shape = meta, (B, hp, wp, D, M)
+        x2d = patches.reshape(M, D)
+        if lp.layer_num != 2:
+            conv = lp.one_layer_decoder[0]
+            O = conv.out_channels
+            w = _cached_operand(cache, "w_head", conv.weight, prec,
+                                lambda: to_operand(conv.weight.detach().reshape(O, D).to(**f32), prec))
+            b = conv.bias.detach().to(**f32).contiguous() if conv.bias is not None else torch.zeros(O, **f32)
+            lin = torch.empty((M, O), **f32)
+            _lib.check(lib.ocm_op_linear(prec, _p(to_operand(x2d, prec)), _p(w), _p(b), None, _p(lin), M, O, D,
+                                         _lib.OCM_EPI_BIAS_F32, _stream()))
+            _lib.check(lib.ocm_op_pixel_shuffle(_p(lin), _p(out), B, hp, wp, O // (s * s), s, _stream()))
+            ctx.save_for_backward(x2d)
+            return out
+        conv1, bn, _, conv2, _ = lp.two_layer_decoder
+        mid, oc = conv1.out_channels, conv2.out_channels
+        w1 = _cached_operand(cache, "w1", conv1.weight, prec,
+                             lambda: to_operand(conv1.weight.detach().to(**f32).permute(0, 2, 3, 1).reshape(mid, -1), prec))
+        w2 = _cached_operand(cache, "w2", conv2.weight, prec,
+                             lambda: to_operand(conv2.weight.detach().to(**f32).permute(0, 2, 3, 1).reshape(oc, -1), prec))
+        b1 = conv1.bias.detach().to(**f32).contiguous() if conv1.bias is not None else torch.zeros(mid, **f32)
+        b2 = conv2.bias.detach().to(**f32).contiguous() if conv2.bias is not None else torch.zeros(oc, **f32)
+        esz_t = _OPERAND_DTYPE[prec]
+        a1 = torch.empty((M, 9 * D), dtype=esz_t, device=dev)
+        _lib.check(lib.ocm_op_im2col3x3(prec, _p(patches), _p(a1), B, hp, wp, D, 0, _stream()))
+        y1 = torch.empty((M, mid), **f32)
+        _lib.check(lib.ocm_op_linear(prec, _p(a1), _p(w1), _p(b1), None, _p(y1), M, mid, 9 * D, _lib.OCM_EPI_BIAS_F32,
+                                     _stream()))
+        del a1
+        mean, var = torch.empty(mid, **f32), torch.empty(mid, **f32)
+        nbytes = lib.ocm_channel_reduce_workspace_bytes(M, mid)
+        ws = _ws(nbytes, dev)
+        _lib.check(lib.ocm_op_batch_stats(_p(y1), _p(mean), _p(var), M, mid, _p(ws), nbytes, _stream()))
+        # per-channel affine of the normalisation (mid-length vectors): z = relu(y1 * g + h)
+        invstd = torch.rsqrt(var + bn.eps)
+        gamma = bn.weight.detach().to(**f32) if bn.weight is not None else torch.ones(mid, **f32)
+        beta = bn.bias.detach().to(**f32) if bn.bias is not None else torch.zeros(mid, **f32)
+        g = (gamma * invstd).contiguous()
+        h = (beta - mean * g).contiguous()
+        a2 = torch.empty((M, 9 * mid), dtype=esz_t, device=dev)
+        _lib.check(lib.ocm_op_bn_relu_im2col3x3(prec, _p(y1), _p(g), _p(h), _p(a2), B, hp, wp, mid, _stream()))
+        y2 = torch.empty((M, oc), **f32)
+        _lib.check(lib.ocm_op_linear(prec, _p(a2), _p(w2), _p(b2), None, _p(y2), M, oc, 9 * mid, _lib.OCM_EPI_BIAS_F32,
+                                     _stream()))
+        _lib.check(lib.ocm_op_pixel_shuffle(_p(y2), _p(out), B, hp, wp, oc // (s * s), s, _stream()))
+        meta["mean"], meta["var"] = mean, var
+        ctx.save_for_backward(patches, y1, mean, invstd, g, h)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        meta = ctx.meta
+        lp, prec = meta["module"], meta["prec"]
+        B, hp, wp, D, M = ctx.shape
+        s, lib = lp.encoder_stride, _lib.load()
+        need = ctx.needs_input_grad[2:]
+        dev = grad_out.device
+
+        def put(t, like):  # the gradient on the parameter's own device and dtype
+            return None if t is None else t.reshape(like.shape).to(device=like.device, dtype=like.dtype)
+
+        if lp.layer_num != 2:
+            (x2d,) = ctx.saved_tensors
+            conv = lp.one_layer_decoder[0]
+            with torch.cuda.device(dev):
+                dlin = _pixel_shuffle_backward(grad_out, M, s, hp, wp)
+                dw, db = _weight_grad(prec, dlin, x2d, need[1])
+            grads = [put(dw, conv.weight) if need[0] else None, put(db, conv.bias) if need[1] else None]
+            return (None, None, *grads)
+        patches, y1, mean, invstd, g, h = ctx.saved_tensors
+        conv1, bn, _, conv2, _ = lp.two_layer_decoder
+        mid, oc = conv1.out_channels, conv2.out_channels
+        f32 = dict(device=dev, dtype=torch.float32)
+        grads = [None] * 6
+        with torch.cuda.device(dev):
+            dy2 = _pixel_shuffle_backward(grad_out, M, s, hp, wp)  # (M, oc)
+            if need[4] or need[5]:
+                a2 = torch.empty((M, 9 * mid), **f32)  # conv2's operand again, in fp32
+                _lib.check(lib.ocm_op_bn_relu_im2col3x3(_lib.OCM_PREC_FP32, _p(y1), _p(g), _p(h), _p(a2), B, hp, wp, mid,
+                                                        _stream()))
+                dw2, db2 = _weight_grad(prec, dy2, a2, need[5])
+                del a2
+                grads[4] = put(dw2.reshape(oc, 3, 3, mid).permute(0, 3, 1, 2), conv2.weight) if need[4] else None
+                grads[5] = put(db2, conv2.bias) if need[5] else None
+            if any(need[:4]):
+                # conv2's data gradient: a 3x3 pad-1 convolution of dY2 with the flipped, channel-transposed kernel
+                cache = lp._dec_cache.setdefault("train", {})
+                w2f = _cached_operand(cache, "w2_flip", conv2.weight, prec,
+                                      lambda: to_operand(flip_conv3x3(conv2.weight.detach().to(**f32)).contiguous(), prec))
+                d2 = torch.empty((M, 9 * oc), dtype=_OPERAND_DTYPE[prec], device=dev)
+                _lib.check(lib.ocm_op_im2col3x3(prec, _p(dy2), _p(d2), B, hp, wp, oc, 0, _stream()))
+                dz = torch.empty((M, mid), **f32)
+                zero = cache.get("zero_mid")
+                if zero is None or zero.numel() != mid or zero.device != dev:
+                    zero = cache["zero_mid"] = torch.zeros(mid, **f32)
+                _lib.check(lib.ocm_op_linear(prec, _p(d2), _p(w2f), _p(zero), None, _p(dz), M, mid, 9 * oc,
+                                             _lib.OCM_EPI_BIAS_F32, _stream()))
+                del d2
+                dy1, dgam, dbet = torch.empty((M, mid), **f32), torch.empty(mid, **f32), torch.empty(mid, **f32)
+                nbytes = lib.ocm_channel_reduce_workspace_bytes(M, mid)
+                ws = _ws(nbytes, dev)
+                _lib.check(lib.ocm_op_bn_relu_backward(_p(dz), _p(y1), _p(mean), _p(invstd), _p(g), _p(h), _p(dy1), _p(dgam),
+                                                       _p(dbet), M, mid, _p(ws), nbytes, _stream()))
+                del dz
+                grads[2] = put(dgam, bn.weight) if need[2] else None
+                grads[3] = put(dbet, bn.bias) if need[3] else None
+                if need[0] or need[1]:
+                    a1 = torch.empty((M, 9 * D), **f32)  # im2col of the patch tokens again, in fp32
+                    _lib.check(lib.ocm_op_im2col3x3(_lib.OCM_PREC_FP32, _p(patches), _p(a1), B, hp, wp, D, 0, _stream()))
+                    dw1, db1 = _weight_grad(prec, dy1, a1, need[1])
+                    del a1
+                    grads[0] = put(dw1.reshape(mid, 3, 3, D).permute(0, 3, 1, 2), conv1.weight) if need[0] else None
+                    grads[1] = put(db1, conv1.bias) if need[1] else None
+        return (None, None, *grads)
+
+
+def _train_forward(lp, tokens):
+    """LinearProbing.forward in training mode on a frozen encoder: the decoder with batch statistics (layer_num 2), the
+    running statistics updated as nn.BatchNorm2d updates them, and a graph into the decoder's parameters when grad mode is
+    on. The normed tokens (B, N, D) come from the encoder without a graph."""
+    B, N, D = tokens.shape
+    patches = tokens[:, 1:].contiguous()
+    prec = _lib.PRECISIONS[lp.encoder._precision]
+    meta = {"module": lp, "prec": prec}
+    if lp.layer_num == 2:
+        conv1, bn, _, conv2, _ = lp.two_layer_decoder
+        if not bn.training:
+            raise NotImplementedError("the training-mode decoder normalises with batch statistics: BatchNorm2d in eval "
+                                      "mode inside a training LinearProbing is not supported on the HIP path")
+        if B * (N - 1) < 2:
+            raise ValueError(f"Expected more than 1 value per channel when training, got input size "
+                             f"{[B, conv1.out_channels, 1, 1]}")
+        params = (conv1.weight, conv1.bias, bn.weight, bn.bias, conv2.weight, conv2.bias)
+    else:
+        conv = lp.one_layer_decoder[0]
+        params = (conv.weight, conv.bias)
+    with torch.cuda.device(tokens.device):
+        out = _DecoderTrain.apply(meta, patches, *params)
+        if lp.layer_num == 2 and bn.track_running_stats and bn.running_mean is not None:
+            _update_running_stats(bn, meta["mean"], meta["var"], B * (N - 1))
+    return out
+
+
+@torch.no_grad()
+def _update_running_stats(bn, mean, var, n):
+    """nn.BatchNorm2d's update in training mode, in place on the buffers themselves (their _version moves, so the eval
+    path's cache of the folded weights sees it): momentum, or the cumulative average when momentum is None; the
+    unbiased variance goes into running_var."""
+    bn.num_batches_tracked.add_(1)
+    f = (1.0 / float(bn.num_batches_tracked)) if bn.momentum is None else bn.momentum
+    rm, rv = bn.running_mean, bn.running_var
+    unbiased = var * (n / (n - 1))
+    rm.mul_(1.0 - f).add_(mean.to(device=rm.device, dtype=rm.dtype), alpha=f)
+    rv.mul_(1.0 - f).add_(unbiased.to(device=rv.device, dtype=rv.dtype), alpha=f)
 
 
 def build_model(args):

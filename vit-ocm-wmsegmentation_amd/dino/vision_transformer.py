@@ -295,8 +295,8 @@ class VisionTransformer(nn.Module):
                            softmax (attention max 1.0000) fp32 arithmetic itself is 5e-4 from float64 and this
                            mode 2-5e-3.
           "bf16"           single bf16 MFMA operands — the fastest path; within 1e-3 on well-conditioned weights
-                           (init / full / sharp sets) but NOT on peaked, trained-like attention (4-8e-2 there):
-                           rounding operands to 8 mantissa bits is amplified layer by layer
+                           (init / full / sharp sets) but NOT on peaked, trained-like attention (5e-2 on ViT-S/16,
+                           0.2 on ViT-B/16 384²): rounding operands to 8 mantissa bits is amplified layer by layer
           "fp32"           fp32 operands on v_mfma_f32_32x32x2_f32 (exact fp32 products, 1/16 the matrix
                            rate): maps at fp32 round-off level"""
         if precision not in _lib.PRECISIONS:

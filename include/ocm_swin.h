@@ -100,6 +100,13 @@ int ocm_op_swin_window_attention(int32_t precision, const void *qkv, int32_t ld,
                                  const float *rel_table, float *scratch, int32_t batch, int32_t height, int32_t width,
                                  int32_t window, int32_t shift, int32_t heads, void *stream);
 
+/* The LayerNorm of SwinPatchMerging (modeling_swin.py:309-326, before the reduction): x (batch, height, width, channels) fp32;
+ * y (batch * ceil(height / 2) * ceil(width / 2), ldy) operand rows in the precision's element format (fp32, bf16 or split pairs)
+ * = LayerNorm(x0 | x1 | x2 | x3; gamma, beta, 1e-5) of the 2 x 2 neighbourhood, an odd side padded with zeros, columns
+ * [4 * channels, ldy) zero. channels a multiple of 32 up to 512; ldy >= 4 * channels, a multiple of 64 (bf16) or 32. */
+int ocm_op_swin_merge_ln(int32_t precision, const float *x, const float *gamma, const float *beta, void *y, int32_t batch,
+                         int32_t height, int32_t width, int32_t channels, int32_t ldy, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

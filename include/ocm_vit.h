@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define OCM_ABI_VERSION 10
+#define OCM_ABI_VERSION 11
 
 enum {
     OCM_OK = 0,

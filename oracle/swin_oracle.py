@@ -4,8 +4,9 @@ The reference's Allen_data_Backbone/train.py:70-85 builds `SwinForImageClassific
 from the `transformers` package (an un-vendored, un-pinned dependency of the reference). transformers 5.15.0 is
 installed in the build container, so this functional fp32 torch-CPU restatement of
 transformers/models/swin/modeling_swin.py (line numbers of 5.15.0 cited per function) is PINNED against that
-package by oracle/make_golden_swin.py (max |diff| recorded in tests/golden/swin_*.npz). Nothing in the product
-imports this file.
+package by oracle/make_golden_swin.py (max |diff| recorded in tests/golden/swin_*.npz). It runs in the dtype of its
+inputs: float32 as transformers does, or float64 (weights and pixels both) as the reference of
+tests/test_swin_geometry_gpu.py. Nothing in the product imports this file.
 """
 
 import torch
@@ -40,14 +41,14 @@ def window_reverse(w, ws, H, W):
     return w.transpose(2, 3).contiguous().view(-1, H, W, C)
 
 
-def shift_mask(H, W, ws, shift):
-    """SwinLayer.get_attn_mask, modeling_swin.py:584-607 -> (nW, ws*ws, ws*ws) or None."""
+def shift_mask(H, W, ws, shift, dtype=torch.float32):
+    """SwinLayer.get_attn_mask, modeling_swin.py:584-607 -> (nW, ws*ws, ws*ws) or None (entries 0 / -100 in `dtype`)."""
     if shift <= 0:
         return None
     h, w = torch.arange(H), torch.arange(W)
     hr = (h >= H - ws).long() + (h >= H - shift).long()
     wr = (w >= W - ws).long() + (w >= W - shift).long()
-    img = (hr[None, :, None, None] * 3 + wr[None, None, :, None]).to(torch.float32)
+    img = (hr[None, :, None, None] * 3 + wr[None, None, :, None]).to(dtype)
     mw = window_partition(img, ws).view(-1, ws * ws)
     m = mw.unsqueeze(1) - mw.unsqueeze(2)
     return m.masked_fill(m != 0, -100.0).masked_fill(m == 0, 0.0)
@@ -77,7 +78,7 @@ def swin_layer(sd, pre, x, H, W, heads, ws_cfg, shift_cfg, eps):
     v = F.linear(win, sd[a + "v_proj.weight"], sd[a + "v_proj.bias"]).view(-1, ws * ws, heads, d).transpose(1, 2)
     table = sd[a + "relative_position_bias.relative_position_bias_table"]
     bias = table[relative_position_index(ws).view(-1)].view(ws * ws, ws * ws, -1).permute(2, 0, 1).contiguous().unsqueeze(0)
-    mask = shift_mask(Hp, Wp, ws, shift)  # get_attn_mask(height_pad, width_pad)
+    mask = shift_mask(Hp, Wp, ws, shift, x.dtype)  # get_attn_mask(height_pad, width_pad)
     if mask is not None:
         nW = mask.shape[0]
         m = mask.unsqueeze(1).unsqueeze(0).expand(win.shape[0] // nW, -1, -1, -1, -1).reshape(-1, 1, ws * ws, ws * ws)
@@ -85,7 +86,7 @@ def swin_layer(sd, pre, x, H, W, heads, ws_cfg, shift_cfg, eps):
     else:
         comb = bias
     s = torch.matmul(q, k.transpose(2, 3)) * (d ** -0.5) + comb
-    p = F.softmax(s, dim=-1, dtype=torch.float32)
+    p = F.softmax(s, dim=-1, dtype=s.dtype)  # float32 for float32 input (transformers), float64 for the float64 oracle
     o = torch.matmul(p, v).transpose(1, 2).contiguous().reshape(-1, ws * ws, C)
     o = F.linear(o, sd[a + "o_proj.weight"], sd[a + "o_proj.bias"])
     o = window_reverse(o.view(-1, ws, ws, C), ws, Hp, Wp)

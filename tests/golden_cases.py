@@ -78,3 +78,51 @@ SWIN_CASES = {
     # a column of zeros in the patch merging)
     "pad120": dict(batch=2, seed=23, qk_gain=6.0, cfg=dict(image_size=120, depths=(2, 2, 2), num_heads=(3, 6, 12))),
 }
+
+
+# Swin geometries off the Swin-T defaults (oracle/make_golden_swin.py writes tests/golden/swin_geom_<name>.npz;
+# tests/test_swin_geometry_gpu.py runs them in every precision against the float64 oracle). Each entry reaches dispatch
+# branches of libocm_vit.so's Swin engine that SWIN_CASES (window 7, embed_dim 96, mlp_ratio 4, eps 1e-5) never takes.
+# "bf16" names the single-bf16 mode, whose GEMM K step of 64 pads K = 32 / 96 rows; split-bf16 and fp32 step by 32.
+# Counts (batch x windows x heads) per stage are given where they leave partial workgroups (4 wavefronts in the bf16
+# window attention, 3 in the split-bf16 one, 2 / 4 windows in the fused attention halves).
+SWIN_GEOMETRIES = {
+    # embed <1, 2>; grids 14 -> 7 padded to 15 / 10 for windows of 5 (shifted windows in stage 0); layernorm_after + fc1 +
+    # GELU fused at C = 128, N = 256 (hidden != 4C, so no fused MLP); odd depth 3 (the last layer unshifted); generic pool
+    # head at C = 128; config eps 1e-3 against the fixed 1e-5 of embedding / merging; window x head counts 54 and 48
+    "A": dict(batch=3, seed=61, qk_gain=4.0, cfg=dict(image_size=56, embed_dim=64, num_channels=1, depths=(3, 1),
+                                                      num_heads=(2, 4), window_size=5, mlp_ratio=2.0, layer_norm_eps=1e-3,
+                                                      num_labels=7)),
+    # embed <3, 1>; bf16: K padding of C = 32 (Kc 64: the ctx memset) and of M = 96 (Km 128: the hid memset); patch merging
+    # LayerNorm widths 128 and 256; stage 2 grid 4 = window (no shift): fused attention half <4, 0, 8> on 3 windows (one
+    # partial workgroup of 4) and layernorm_after + fc1 + GELU at C = 128, N = 384; one label
+    "B": dict(batch=3, seed=62, qk_gain=5.0, cfg=dict(image_size=64, embed_dim=32, num_channels=3, depths=(2, 2, 1),
+                                                      num_heads=(1, 2, 4), window_size=4, mlp_ratio=3.0, layer_norm_eps=1e-5,
+                                                      num_labels=1)),
+    # one stage (the pool head right after stage 0, no merging); embed <1, 3>; fused attention half <3, 0, 4> (o_proj fused)
+    # at ws 6; layernorm_after + fc1 + GELU at C = 96, N = 96; bf16: Km != M (96 -> 128); eps 1e-6
+    "C": dict(batch=3, seed=63, qk_gain=6.0, cfg=dict(image_size=48, embed_dim=96, num_channels=1, depths=(3,), num_heads=(3,),
+                                                      window_size=6, mlp_ratio=1.0, layer_norm_eps=1e-6, num_labels=3)),
+    # embed <3, 4>; grids 10 -> 5 padded to 12 / 6 for windows of 3 (shift 1 at both); pool head vec<1> (C = 256)
+    "D": dict(batch=3, seed=64, qk_gain=4.0, cfg=dict(image_size=40, embed_dim=128, num_channels=3, depths=(2, 2),
+                                                      num_heads=(4, 8), window_size=3, mlp_ratio=4.0, layer_norm_eps=1e-5,
+                                                      num_labels=3)),
+    # embed <3, 2>; windows of 2 in four stages (the last grid = window); fused MLP and fused attention half <4, 0, 8> at
+    # C = 128; pool head vec<2> (C = 512)
+    "E": dict(batch=3, seed=65, qk_gain=5.0, cfg=dict(image_size=64, embed_dim=64, num_channels=3, depths=(2, 2, 2, 2),
+                                                      num_heads=(2, 4, 8, 16), window_size=2, mlp_ratio=4.0,
+                                                      layer_norm_eps=1e-5, num_labels=4)),
+    # embed <1, 4>; 32 heads in the last stage; pool head vec<4> (C = 1024) with 1000 labels (far more than its 8
+    # wavefronts); batch 1: window x head counts 256, 128, 64, 32
+    "F": dict(batch=1, seed=66, qk_gain=6.0, cfg=dict(image_size=64, embed_dim=128, num_channels=1, depths=(1, 1, 3, 1),
+                                                      num_heads=(4, 8, 16, 32), window_size=2, mlp_ratio=4.0,
+                                                      layer_norm_eps=1e-5, num_labels=1000)),
+    # embed <1, 1>; odd grid 15 padded to 21 for windows of 7, merged (one zero row / column) to 8, padded to 14; generic
+    # pool head at C = 64; batch 1: window x head counts 9 and 8
+    "G": dict(batch=1, seed=67, qk_gain=4.0, cfg=dict(image_size=60, embed_dim=32, num_channels=1, depths=(2, 2), num_heads=(1, 2),
+                                                      window_size=7, mlp_ratio=4.0, layer_norm_eps=1e-5, num_labels=2)),
+    # grids 24 -> 12, multiples of the window 6 (no padding): fused attention halves <3, 0, 4, true> and <6, 0, 8, false>,
+    # fused MLP at C = 96, layernorm_after + fc1 + GELU at C = 192
+    "H": dict(batch=3, seed=68, qk_gain=5.0, cfg=dict(image_size=96, embed_dim=96, num_channels=3, depths=(1, 2), num_heads=(3, 6),
+                                                      window_size=6, mlp_ratio=4.0, layer_norm_eps=1e-5, num_labels=5)),
+}

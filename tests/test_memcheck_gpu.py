@@ -427,13 +427,20 @@ def test_block_entry_points(lib, dev, B, pattern):
 # d. Swin
 # ---------------------------------------------------------------------------------------------------------------------
 def _swin(image_size, precision):
-    from tests.golden_cases import SWIN_CASES
+    """Swin-T at 224^2, the padded 120^2 miniature, or (a str) a SWIN_GEOMETRIES entry."""
+    from tests.golden_cases import SWIN_CASES, SWIN_GEOMETRIES
     from vit_ocm_wmsegmentation_amd import swin as SW
-    extra = SWIN_CASES["pad120"]["cfg"] if image_size == 120 else {}  # three stages: grids 30 / 15 / 8
-    cfg = dict(synth.SWIN_TINY, **extra)
-    sd = synth.synth_swin_state_dict(cfg, seed=21, qk_gain=6.0)
-    model = SW.SwinForImageClassification(SW.SwinConfig(image_size=cfg["image_size"], depths=cfg["depths"],
-                                                        num_heads=cfg["num_heads"], num_labels=cfg["num_labels"]))
+    if isinstance(image_size, str):
+        g = SWIN_GEOMETRIES[image_size]
+        cfg = dict(synth.SWIN_TINY, **g["cfg"])
+        sd = synth.synth_swin_state_dict(cfg, seed=g["seed"], qk_gain=g["qk_gain"])
+    else:
+        extra = SWIN_CASES["pad120"]["cfg"] if image_size == 120 else {}  # three stages: grids 30 / 15 / 8
+        cfg = dict(synth.SWIN_TINY, **extra)
+        sd = synth.synth_swin_state_dict(cfg, seed=21, qk_gain=6.0)
+    model = SW.SwinForImageClassification(SW.SwinConfig(**{k: cfg[k] for k in (
+        "image_size", "num_channels", "embed_dim", "depths", "num_heads", "window_size", "mlp_ratio", "layer_norm_eps",
+        "num_labels")}))
     model.load_state_dict(sd, strict=True)
     model = model.cuda().eval().set_precision(precision)
     return model, model._get_engine(torch.device("cuda", 0))
@@ -441,18 +448,21 @@ def _swin(image_size, precision):
 
 @pytest.mark.parametrize("pattern", POISON)
 @pytest.mark.parametrize("image_size,precision,fuse", [(224, "bf16x3", 1), (224, "bf16x3", 0), (224, "bf16", 1),
-                                                       (224, "fp32", 1), (120, "bf16x3", 1), (120, "fp32", 0)])
+                                                       (224, "fp32", 1), (120, "bf16x3", 1), (120, "fp32", 0),
+                                                       ("B", "bf16", 1), ("B", "fp32", 1), ("C", "bf16", 1), ("C", "fp32", 1)])
 def test_swin_forward_poisoned_workspace(lib, dev, image_size, precision, fuse, pattern):
     """224^2 B = 2 in every precision, the fused split-bf16 MLP / attention halves (OPT_FUSE_MLP 1) and the unfused
-    launches (0), and the padded 120^2 geometry (grids 30 / 15 / 8: zero rows, odd-grid merging)."""
+    launches (0), and the padded 120^2 geometry (grids 30 / 15 / 8: zero rows, odd-grid merging). SWIN_GEOMETRIES B and C at
+    B = 3: the first geometries whose bf16 operands are K-padded (C = 32 -> 64, hidden 96 -> 128), so the engine's ctx / hid
+    memsets and the zero columns of the LayerNorm rows carry the padding, whatever the workspace held before."""
     model, eng = _swin(image_size, precision)
     h = eng["h"]
-    B = 2
     c = model.config
+    B = 2 if isinstance(image_size, int) else 3
     side = c.image_size // c.patch_size
     for _ in range(c.num_layers - 1):
         side = (side + 1) // 2
-    x = synth.synth_tiles(B, image_size, seed=71).cuda()
+    x = synth.synth_tiles(B, c.image_size, seed=71, channels=c.num_channels).cuda()
     nbytes = lib.ocm_swin_workspace_bytes(h, B)
     L.check(lib.ocm_swin_set_option(h, L.OCM_SWIN_OPT_FUSE_MLP, fuse))
     try:

@@ -154,7 +154,8 @@ __device__ __forceinline__ void store4<sp32>(sp32 *row, int c, const f32x4 &v) {
     *(bf16x4 *)(p + 64) = lo;
 }
 
-// LPR lanes per row (32: two rows per wavefront for dim <= 128; 64 otherwise), V float4 chunks per lane.
+// LPR lanes per row (32: two rows per wavefront for dim <= 128; 64 otherwise), V float4 chunks per lane. The widest row is the
+// patch merging of embed_dim 128 into a fourth stage: 4 x 512 = 2048 = 64 lanes x 8 chunks.
 template <class E, bool MERGE, int LPR, int V>
 __global__ __launch_bounds__(256) void swin_ln_kernel(const float *__restrict__ x, const float *__restrict__ g,
                                                       const float *__restrict__ be, E *__restrict__ y, size_t rows,
@@ -236,7 +237,7 @@ static hipError_t launch_swin_ln_e(const float *x, const float *g, const float *
         swin_ln_kernel<E, MERGE, lpr, v><<<grid, block, 0, s>>>(x, g, be, y, rows, dim, ldy, eps, Hin, Win);        \
         return hipGetLastError();                                                                                   \
     }
-    OCM_LN_CASE(32, 1) OCM_LN_CASE(64, 1) OCM_LN_CASE(64, 2) OCM_LN_CASE(64, 3) OCM_LN_CASE(64, 6)
+    OCM_LN_CASE(32, 1) OCM_LN_CASE(64, 1) OCM_LN_CASE(64, 2) OCM_LN_CASE(64, 3) OCM_LN_CASE(64, 6) OCM_LN_CASE(64, 8)
 #undef OCM_LN_CASE
     return hipErrorInvalidValue;
 }

@@ -516,6 +516,21 @@ extern "C" int ocm_op_swin_attn_block(int32_t precision, float *x, const float *
     return OCM_OK;
 }
 
+extern "C" int ocm_op_swin_merge_ln(int32_t precision, const float *x, const float *gamma, const float *beta, void *y,
+                                   int32_t batch, int32_t height, int32_t width, int32_t channels, int32_t ldy, void *stream) {
+    if (!x || !gamma || !beta || !y) return fail(OCM_EINVAL, "null argument");
+    const int pc = precision == OCM_PREC_FP32 ? 1 : precision == OCM_PREC_BF16X3 ? 2 : precision == OCM_PREC_BF16 ? 0 : -1;
+    if (pc < 0) return fail(OCM_EINVAL, "bad precision");
+    if (batch <= 0 || height <= 0 || width <= 0 || channels <= 0 || channels % 32 || channels > 512 || ldy < 4 * channels ||
+        ldy % (pc ? 32 : 64))
+        return fail(OCM_EINVAL, "bad patch-merging geometry (batch %d, %d x %d, %d channels, ldy %d)", batch, height, width,
+                    channels, ldy);
+    const int64_t T4 = (int64_t)batch * ((height + 1) / 2) * ((width + 1) / 2);
+    if ((int64_t)batch * height * width > 0x7fffffffLL) return fail(OCM_EINVAL, "too many tokens");
+    HIP_TRY(launch_swin_ln(pc, x, gamma, beta, y, (size_t)T4, 4 * channels, ldy, 1e-5f, true, height, width, (hipStream_t)stream));
+    return OCM_OK;
+}
+
 extern "C" int ocm_op_swin_window_attention(int32_t precision, const void *qkv, int32_t ld, void *ctx, int32_t ldc,
                                             const float *rel_table, float *scratch, int32_t batch, int32_t height,
                                             int32_t width, int32_t window, int32_t shift, int32_t heads, void *stream) {

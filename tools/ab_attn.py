@@ -1,13 +1,13 @@
 #!/usr/bin/env python3
 """Development: the split-bf16 attention kernel variants against each other, stand-alone (GPU box, development library).
 
-    OCM_VIT_LIB=exp_libs/libocm_vit_dev.so python tools/ab_attn.py [--variants 0,3]
+    OCM_VIT_LIB=exp_libs/libocm_vit_dev.so python tools/ab_attn.py [--knob 7] [--variants 0,2]
 
-For every shape: bit-identity of context rows and log-sum-exp between knob 6 = 0 (the shipped dispatch: attn_fwd_x3_pp_kernel,
-software-pipelined blocks, for N <= 1024; attn_fwd_x3_dma_kernel on eight waves above that) and the other variants (3 = the
-round-3 loop attn_fwd_x3_dma_kernel on four waves; 1 = the register-staged kernel, whose 64-key tiles take the deferred-maximum
-decisions at other points and therefore agrees to rounding only), NaN-poisoned padding; then alternating
-timings with hipEvents (median of rounds). In-forward numbers: tools/ab_bench.sh "6=0" "6=3".
+For every shape: bit-identity of context rows and log-sum-exp between knob value 0 (the shipped dispatch:
+attn_fwd_x3_pp_kernel, software-pipelined blocks, for N <= 1024; attn_fwd_x3_dma_kernel on eight waves above that) and the
+other values of the knob (knob 7 = 2: attn_fwd_x3_dma_kernel on eight waves at every length; knob 6 = 4: the pipelined kernel
+where the wave-split kernel ships), NaN-poisoned padding; then alternating timings with hipEvents (median of rounds).
+In-forward numbers: tools/ab_bench.sh "7=0" "7=2".
 """
 import argparse
 import ctypes as C
@@ -27,7 +27,8 @@ X3 = _lib.OCM_PREC_BF16X3
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--variants", default="0,3")
+    ap.add_argument("--knob", type=int, default=7)
+    ap.add_argument("--variants", default="0,2")
     ap.add_argument("--rounds", type=int, default=7)
     a = ap.parse_args()
     variants = [int(v) for v in a.variants.split(",")]
@@ -37,7 +38,7 @@ def main():
     st = lambda: C.c_void_p(torch.cuda.current_stream().cuda_stream)  # noqa: E731
 
     def knob(v):
-        assert raw.ocm_debug_knob(6, v) == 0
+        assert raw.ocm_debug_knob(a.knob, v) == 0
 
     def operands(B, N, H, sharp, seed=60):
         g = torch.Generator().manual_seed(seed)

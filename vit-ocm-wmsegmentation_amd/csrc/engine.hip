@@ -397,6 +397,36 @@ static int check_ws(const ocm_vit *h, int batch, int n, void *ws, size_t ws_byte
     return OCM_OK;
 }
 
+// y = attn(xn) of Block.forward up to the context rows in w.ctx: attn.qkv (weight qkv_w, bias qkv_b or null, norm1 folded in
+// through `ln` when it carries statistics), the attention, and the probabilities / selected rows the caller asked for.
+// attn_only (the block ends after its probabilities): no context rows.
+static int run_attention(const ocm_vit *h, const Workspace &w, int batch, int n, bool attn_only, float *out_attn, float *out_qkv,
+                         const int32_t *query_rows, int n_rows, float *out_rows, const char *qkv_w, const float *qkv_b,
+                         const LnFold &ln, hipStream_t s) {
+    const int H = h->H, np = ocm_n_pad_for(h->prec, n), pc = h->prec;
+    const float scale = h->cfg.qk_scale;
+    // a block that stops after its probabilities (get_last_selfattention) and returns no qkv never reads V
+    const bool want_v = !(attn_only && !out_qkv);
+    if (!h->mfma_heads()) {  // generic heads: fp32 qkv tensor -> fp32 FMA attention
+        float *qkv = out_qkv ? out_qkv : w.qkv32;
+        { PROF(OCM_K_QKV, s); HIP_TRY(launch_qkv(pc, w.xn, qkv_w, qkv_b, nullptr, nullptr, nullptr, qkv, batch, n, np, H, h->hd, want_v, s, ln)); }
+        { PROF(OCM_K_ATTN, s); HIP_TRY(launch_attention_generic(pc, qkv, attn_only ? nullptr : w.ctx, out_attn, query_rows, n_rows, out_rows, batch, n, H, h->hd, scale, s)); }
+        return OCM_OK;
+    }
+    void *vt_dst = want_v ? w.vt : nullptr;
+    { PROF(OCM_K_QKV, s); HIP_TRY(launch_qkv(pc, w.xn, qkv_w, qkv_b, w.q, w.k, vt_dst, out_qkv, batch, n, np, H, h->hd, want_v, s, ln)); }
+    // selected query rows: a slice of the probabilities when those are materialised for this block anyway,
+    // else their own fp32 dot-product kernel (never the (H,N,N) matrix)
+    if (out_rows && !out_attn) { PROF(OCM_K_PROBS, s); HIP_TRY(launch_attention_rows(pc, w.q, w.k, query_rows, n_rows, out_rows, batch, n, np, H, scale, s, h->hd)); }
+    if (attn_only && !out_attn) return OCM_OK;
+    { PROF(OCM_K_ATTN, s); HIP_TRY(launch_attention(pc, w.q, w.k, w.vt, attn_only ? nullptr : w.ctx, out_attn ? w.lse : nullptr, batch, n, np, H, scale, s, h->hd, w.kpart, w.kpart_bytes)); }
+    if (out_attn) {
+        { PROF(OCM_K_PROBS, s); HIP_TRY(launch_attention_probs(pc, w.q, w.k, w.lse, out_attn, batch, n, np, H, scale, s, h->hd)); }
+        if (out_rows) { PROF(OCM_K_PROBS, s); HIP_TRY(launch_rows_from_probs(out_attn, query_rows, n_rows, out_rows, batch, n, H, s)); }
+    }
+    return OCM_OK;
+}
+
 // Block.forward (:106-114). x is updated in place unless attn_only.
 // `xn_ready`: w.xn already holds norm1(x) (written by the previous block's fused fc2 epilogue). `next_g` / `next_b`: the
 // LayerNorm that consumes this block's output next (the next block's norm1) — when given and the embedding width has a
@@ -406,8 +436,8 @@ static int run_block(const ocm_vit *h, int i, const Workspace &w, float *x, int 
                      hipStream_t s, bool xn_ready = false, const float *next_g = nullptr, const float *next_b = nullptr,
                      bool *xn_out = nullptr) {
     const BlockP &bp = h->blk[i];
-    const int D = h->D, H = h->H, T = batch * n, np = ocm_n_pad_for(h->prec, n);
-    const float eps = h->cfg.ln_eps, scale = h->cfg.qk_scale;
+    const int D = h->D, T = batch * n;
+    const float eps = h->cfg.ln_eps;
     const int pc = h->prec, lnk = ln_kind_of_prec(pc);
     // The fused GEMM + LayerNorm kernel owns full rows (64 x D tiles, D / 128 times the W bytes per workgroup and step):
     // it pays once there are enough row tiles to occupy the chip (measured: +2 % at T = 12 608; at T = 197, four
@@ -421,33 +451,10 @@ static int run_block(const ocm_vit *h, int i, const Workspace &w, float *x, int 
     if (xn_out) *xn_out = false;
     // y = attn(norm1(x))
     if (!xn_ready) { PROF(OCM_K_LN, s); HIP_TRY(launch_layernorm(x, h->ptr<float>(bp.ln1_g), h->ptr<float>(bp.ln1_b), w.xn, lnk, T, D, eps, s)); }
-    // a block that stops after its probabilities (get_last_selfattention) and returns no qkv never reads V
-    const bool want_v = !(attn_only && !out_qkv);
-    if (!h->mfma_heads()) {  // generic heads: fp32 qkv tensor -> fp32 FMA attention
-        float *qkv = out_qkv ? out_qkv : w.qkv32;
-        { PROF(OCM_K_QKV, s); HIP_TRY(launch_qkv(pc, w.xn, h->ptr<char>(bp.qkv_w), h->ptr<float>(bp.qkv_b), nullptr, nullptr, nullptr, qkv, batch, n, np, H, h->hd, want_v, s)); }
-        { PROF(OCM_K_ATTN, s); HIP_TRY(launch_attention_generic(pc, qkv, attn_only ? nullptr : w.ctx, out_attn, query_rows, n_rows, out_rows, batch, n, H, h->hd, scale, s)); }
-        if (attn_only) return OCM_OK;
-    } else {
-    void *vt_dst = want_v ? w.vt : nullptr;
-    { PROF(OCM_K_QKV, s); HIP_TRY(launch_qkv(pc, w.xn, h->ptr<char>(bp.qkv_w), h->ptr<float>(bp.qkv_b), w.q, w.k, vt_dst, out_qkv, batch, n, np, H, h->hd, want_v, s)); }
-    // selected query rows: a slice of the probabilities when those are materialised for this block anyway,
-    // else their own fp32 dot-product kernel (never the (H,N,N) matrix)
-    if (out_rows && !out_attn) { PROF(OCM_K_PROBS, s); HIP_TRY(launch_attention_rows(pc, w.q, w.k, query_rows, n_rows, out_rows, batch, n, np, H, scale, s, h->hd)); }
-    if (attn_only) {
-        if (out_attn) {
-            { PROF(OCM_K_ATTN, s); HIP_TRY(launch_attention(pc, w.q, w.k, w.vt, nullptr, w.lse, batch, n, np, H, scale, s, h->hd, w.kpart, w.kpart_bytes)); }
-            { PROF(OCM_K_PROBS, s); HIP_TRY(launch_attention_probs(pc, w.q, w.k, w.lse, out_attn, batch, n, np, H, scale, s, h->hd)); }
-            if (out_rows) { PROF(OCM_K_PROBS, s); HIP_TRY(launch_rows_from_probs(out_attn, query_rows, n_rows, out_rows, batch, n, H, s)); }
-        }
-        return OCM_OK;
-    }
-    { PROF(OCM_K_ATTN, s); HIP_TRY(launch_attention(pc, w.q, w.k, w.vt, w.ctx, out_attn ? w.lse : nullptr, batch, n, np, H, scale, s, h->hd, w.kpart, w.kpart_bytes)); }
-    if (out_attn) {
-        { PROF(OCM_K_PROBS, s); HIP_TRY(launch_attention_probs(pc, w.q, w.k, w.lse, out_attn, batch, n, np, H, scale, s, h->hd)); }
-        if (out_rows) { PROF(OCM_K_PROBS, s); HIP_TRY(launch_rows_from_probs(out_attn, query_rows, n_rows, out_rows, batch, n, H, s)); }
-    }
-    }
+    if (int rc = run_attention(h, w, batch, n, attn_only, out_attn, out_qkv, query_rows, n_rows, out_rows, h->ptr<char>(bp.qkv_w),
+                               h->ptr<float>(bp.qkv_b), LnFold(), s))
+        return rc;
+    if (attn_only) return OCM_OK;
     // x = x + proj(ctx); xn = norm2(x) — one kernel when the workgroup can own full rows
     if (fuse_ln) {
         PROF(OCM_K_PROJ, s);
@@ -483,38 +490,17 @@ static int run_block_folded(const ocm_vit *h, int i, const Workspace &w, float *
                             float *out_attn, float *out_qkv, const int32_t *query_rows, int n_rows, float *out_rows,
                             hipStream_t s) {
     const BlockP &bp = h->blk[i];
-    const int D = h->D, H = h->H, T = batch * n, np = ocm_n_pad_for(h->prec, n), pc = h->prec;
-    const float scale = h->cfg.qk_scale;
+    const int D = h->D, T = batch * n, pc = h->prec;
     // sites 2i (block input) and 2i+2 (block output) use half 0 of the statistics buffer, site 2i+1 (after attn.proj) half 1
     float *st_in = w.stats, *st_mid = w.stats + (size_t)T * (D / 64) * 2, *st_out = w.stats;
     LnFold ln1, ln2;
     ln1.stats = st_in, ln1.c = h->ptr<float>(bp.qkv_c), ln1.d = h->ptr<float>(bp.qkv_d), ln1.inv_dim = 1.0f / D, ln1.eps = h->cfg.ln_eps;
     ln2.stats = st_mid, ln2.c = h->ptr<float>(bp.fc1_c), ln2.d = h->ptr<float>(bp.fc1_d), ln2.inv_dim = 1.0f / D, ln2.eps = h->cfg.ln_eps;
     ln1.nslot = ln2.nslot = D / 64;
-    const bool want_v = !(attn_only && !out_qkv);
-    if (!h->mfma_heads()) {
-        float *qkv = out_qkv ? out_qkv : w.qkv32;
-        { PROF(OCM_K_QKV, s); HIP_TRY(launch_qkv(pc, w.xn, h->ptr<char>(bp.qkv_wf), nullptr, nullptr, nullptr, nullptr, qkv, batch, n, np, H, h->hd, want_v, s, ln1)); }
-        { PROF(OCM_K_ATTN, s); HIP_TRY(launch_attention_generic(pc, qkv, attn_only ? nullptr : w.ctx, out_attn, query_rows, n_rows, out_rows, batch, n, H, h->hd, scale, s)); }
-        if (attn_only) return OCM_OK;
-    } else {
-        void *vt_dst = want_v ? w.vt : nullptr;
-        { PROF(OCM_K_QKV, s); HIP_TRY(launch_qkv(pc, w.xn, h->ptr<char>(bp.qkv_wf), nullptr, w.q, w.k, vt_dst, out_qkv, batch, n, np, H, h->hd, want_v, s, ln1)); }
-        if (out_rows && !out_attn) { PROF(OCM_K_PROBS, s); HIP_TRY(launch_attention_rows(pc, w.q, w.k, query_rows, n_rows, out_rows, batch, n, np, H, scale, s, h->hd)); }
-        if (attn_only) {
-            if (out_attn) {
-                { PROF(OCM_K_ATTN, s); HIP_TRY(launch_attention(pc, w.q, w.k, w.vt, nullptr, w.lse, batch, n, np, H, scale, s, h->hd, w.kpart, w.kpart_bytes)); }
-                { PROF(OCM_K_PROBS, s); HIP_TRY(launch_attention_probs(pc, w.q, w.k, w.lse, out_attn, batch, n, np, H, scale, s, h->hd)); }
-                if (out_rows) { PROF(OCM_K_PROBS, s); HIP_TRY(launch_rows_from_probs(out_attn, query_rows, n_rows, out_rows, batch, n, H, s)); }
-            }
-            return OCM_OK;
-        }
-        { PROF(OCM_K_ATTN, s); HIP_TRY(launch_attention(pc, w.q, w.k, w.vt, w.ctx, out_attn ? w.lse : nullptr, batch, n, np, H, scale, s, h->hd, w.kpart, w.kpart_bytes)); }
-        if (out_attn) {
-            { PROF(OCM_K_PROBS, s); HIP_TRY(launch_attention_probs(pc, w.q, w.k, w.lse, out_attn, batch, n, np, H, scale, s, h->hd)); }
-            if (out_rows) { PROF(OCM_K_PROBS, s); HIP_TRY(launch_rows_from_probs(out_attn, query_rows, n_rows, out_rows, batch, n, H, s)); }
-        }
-    }
+    if (int rc = run_attention(h, w, batch, n, attn_only, out_attn, out_qkv, query_rows, n_rows, out_rows, h->ptr<char>(bp.qkv_wf),
+                               nullptr, ln1, s))
+        return rc;
+    if (attn_only) return OCM_OK;
     StatsOut so_mid, so_out;
     so_mid.xs = w.xn, so_mid.stats = st_mid;
     so_out.xs = w.xn, so_out.stats = st_out;

@@ -48,19 +48,6 @@ typedef GemmCfg<64, 64, 2, 2> Cfg64x64;
 // exposed prologue of a lone workgroup does (measured: ViT-S/8 slab fc1 +7 % slower, ViT-B GEMMs 13 % faster).
 typedef GemmCfg<256, 256, 2, 4> Cfg256x256;
 
-// hipFuncAttributeMaxDynamicSharedMemorySize is a per-device property of a kernel: remember per kernel template
-// instantiation (one static mask each) on which devices it has been set.
-static inline hipError_t ensure_lds_optin(const void *kern, int bytes, unsigned long long &done_mask) {
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    const unsigned long long bit = 1ull << (dev & 63);
-    if (done_mask & bit) return hipSuccess;  // benign race: setting twice is idempotent
-    e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (e == hipSuccess) done_mask |= bit;
-    return e;
-}
-
 static inline bool big_tiles_pay(int M, int N, int K) {
     return K >= 768 && N % 256 == 0 && (long)((M + 255) / 256) * (N / 256) >= 512;
 }
@@ -348,8 +335,8 @@ static hipError_t launch_gemm_ks(const ALoad &al, const E *w, int64_t ldw, int M
                                  hipStream_t s) {
     auto kern = gemm_kernel<Cfg, E, SWAP, KSTEPS, ALoad, Epi>;
     constexpr int LDS = Cfg::LDS_BYTES + (Epi::ROWTAB ? (Cfg::BM + Cfg::BN) * 8 : 0);  // + the epilogue's row / column tables
-    static unsigned long long optin = 0;
-    if (hipError_t e = ensure_lds_optin((const void *)kern, LDS, optin); e != hipSuccess) return e;
+    static OptinMask optin;
+    if (hipError_t e = lds_optin((const void *)kern, LDS, optin); e != hipSuccess) return e;
     const int tiles = ((M + Cfg::BM - 1) / Cfg::BM) * ((N + Cfg::BN - 1) / Cfg::BN);
     kern<<<dim3(tiles), dim3(Cfg::NT), LDS, s>>>(al, w, ldw, M, N, K, epi);
     return hipGetLastError();
@@ -383,8 +370,8 @@ static hipError_t launch_gemm_dma_ks(const E *a, int64_t lda, const E *w, int64_
     static_assert(LDS <= 160 * 1024, "LDS ring exceeds the CU");
     const int tiles = ((M + Cfg::BM - 1) / Cfg::BM) * ((N + Cfg::BN - 1) / Cfg::BN);
     auto kern = gemm_dma_kernel<Cfg, E, false, KSTEPS, NSTAGE, Epi>;
-    static unsigned long long optin = 0;
-    if (hipError_t e = ensure_lds_optin((const void *)kern, LDS, optin); e != hipSuccess) return e;
+    static OptinMask optin;
+    if (hipError_t e = lds_optin((const void *)kern, LDS, optin); e != hipSuccess) return e;
     kern<<<dim3(tiles), dim3(Cfg::NT), LDS, s>>>(a, lda, w, ldw, M, N, K, epi);
     return hipGetLastError();
 }
@@ -561,8 +548,8 @@ static hipError_t launch_linear_splitk(const E *a, const E *w, const float *bias
     constexpr int NSTAGE = 4, KS = 12;  // K / OCM_SPLITK = 384 elements = 12 steps (ViT-S mlp.fc2); other depths: no split
     constexpr int LDS = NSTAGE * (Cfg::BM + Cfg::BN) * 128;
     auto kern = gemm_dma_splitk_kernel<Cfg, E, KS, NSTAGE>;
-    static unsigned long long optin = 0;
-    if (hipError_t e = ensure_lds_optin((const void *)kern, LDS, optin); e != hipSuccess) return e;
+    static OptinMask optin;
+    if (hipError_t e = lds_optin((const void *)kern, LDS, optin); e != hipSuccess) return e;
     const int tiles = ((M + Cfg::BM - 1) / Cfg::BM) * (N / Cfg::BN);
     kern<<<dim3(tiles, OCM_SPLITK), dim3(Cfg::NT), LDS, s>>>(a, K, w, K, M, N, K / OCM_SPLITK, so.part);
     if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
@@ -986,8 +973,8 @@ static hipError_t launch_qkv_dma_ks(const E *a, const E *w, int M, int D, const 
                                     hipStream_t s) {
     auto kern = qkv_dma_kernel<Cfg, E, KSTEPS, NSTAGE>;
     constexpr int LDS = NSTAGE * (Cfg::BM + Cfg::BN) * 128 + (Cfg::BM + Cfg::BN) * 8;  // + the epilogues' row / column tables
-    static unsigned long long optin = 0;
-    if (hipError_t e = ensure_lds_optin((const void *)kern, LDS, optin); e != hipSuccess) return e;
+    static OptinMask optin;
+    if (hipError_t e = lds_optin((const void *)kern, LDS, optin); e != hipSuccess) return e;
     const int tiles = ((M + Cfg::BM - 1) / Cfg::BM) * ((ev.want_v ? 3 : 2) * D / Cfg::BN);
     kern<<<dim3(tiles), dim3(Cfg::NT), LDS, s>>>(a, w, M, D, eqk, ev);
     return hipGetLastError();
@@ -1009,8 +996,8 @@ static hipError_t launch_qkv_ks(const RowLoader<E> &al, const E *w, int M, int D
                                 const EpiVt<E> &ev, hipStream_t s) {
     auto kern = qkv_kernel<Cfg, E, KSTEPS>;
     constexpr int LDS = Cfg::LDS_BYTES + (Cfg::BM + Cfg::BN) * 8;  // + the epilogues' row / column tables
-    static unsigned long long optin = 0;
-    if (hipError_t e = ensure_lds_optin((const void *)kern, LDS, optin); e != hipSuccess) return e;
+    static OptinMask optin;
+    if (hipError_t e = lds_optin((const void *)kern, LDS, optin); e != hipSuccess) return e;
     const int tiles = ((M + Cfg::BM - 1) / Cfg::BM) * ((ev.want_v ? 3 : 2) * D / Cfg::BN);
     kern<<<dim3(tiles), dim3(Cfg::NT), LDS, s>>>(al, w, M, D, eqk, ev);
     return hipGetLastError();

@@ -370,28 +370,13 @@ __global__ __launch_bounds__(512, 4) void attn_small_kernel(const bf16 *__restri
 
 static hipError_t launch_attention_bf16(const bf16 *q, const bf16 *k, const bf16 *vt, bf16 *ctx, float *lse2, int batch,
                                         int n_tokens, int n_pad, int heads, float scale, hipStream_t s, int head_dim = 64) {
-    if (head_dim == 128) {  // 128-wide heads: the streaming kernel at every sequence length
-        const dim3 grid(((n_tokens + 31) / 32 + 3) / 4, batch * heads), block(256);
-        if (ctx)
-            attn_fwd_kernel<true, 128><<<grid, block, 0, s>>>(q, k, vt, ctx, lse2, n_tokens, n_pad, heads, scale * LOG2E);
-        else
-            attn_fwd_kernel<false, 128><<<grid, block, 0, s>>>(q, k, vt, ctx, lse2, n_tokens, n_pad, heads, scale * LOG2E);
-        return hipGetLastError();
-    }
-    if (n_tokens <= 256) {
-        const dim3 grid(batch * heads), block(512);
-        if (ctx)
-            attn_small_kernel<true><<<grid, block, 0, s>>>(q, k, vt, ctx, lse2, n_tokens, n_pad, heads, scale * LOG2E);
-        else
-            attn_small_kernel<false><<<grid, block, 0, s>>>(q, k, vt, ctx, lse2, n_tokens, n_pad, heads, scale * LOG2E);
-        return hipGetLastError();
-    }
-    const int qtiles = (n_tokens + 31) / 32;
-    const dim3 grid((qtiles + 3) / 4, batch * heads), block(256);
-    if (ctx)
-        attn_fwd_kernel<true><<<grid, block, 0, s>>>(q, k, vt, ctx, lse2, n_tokens, n_pad, heads, scale * LOG2E);
-    else
-        attn_fwd_kernel<false><<<grid, block, 0, s>>>(q, k, vt, ctx, lse2, n_tokens, n_pad, heads, scale * LOG2E);
+    // 128-wide heads: the streaming kernel at every sequence length; 64-wide: the whole-sequence kernel up to 256 tokens
+    const bool small = head_dim == 64 && n_tokens <= 256;
+    auto kern = head_dim == 128 ? (ctx ? attn_fwd_kernel<true, 128> : attn_fwd_kernel<false, 128>)
+                : small         ? (ctx ? attn_small_kernel<true> : attn_small_kernel<false>)
+                                : (ctx ? attn_fwd_kernel<true> : attn_fwd_kernel<false>);
+    const dim3 grid = small ? dim3(batch * heads) : dim3(((n_tokens + 31) / 32 + 3) / 4, batch * heads);
+    kern<<<grid, dim3(small ? 512 : 256), 0, s>>>(q, k, vt, ctx, lse2, n_tokens, n_pad, heads, scale * LOG2E);
     return hipGetLastError();
 }
 
@@ -658,214 +643,7 @@ __global__ __launch_bounds__(256) void attn_probs_f32_kernel(const float *__rest
     }
 }
 
-
 // ------------------------------------------------------------------------------------------
-// OCM_PREC_BF16X3: the flash kernel on split-bf16 pairs (common.h: sp32). q / k rows are 256 bytes
-// [hi d 0..31 | lo d 0..31 | hi d 32..63 | lo d 32..63]; V^T rows are key-contiguous in the same 128-byte groups of
-// 32 keys. Every product runs as three bf16 MFMAs (hi*hi + hi*lo + lo*hi), P is split in registers. An LDS tile of
-// 64 keys is two images (one per 128-byte group) of [64 rows][128 B] with the usual chunk swizzle, so the
-// fragment reads are the conflict-free pattern of the bf16 kernel and staging is a byte copy.
-// NW waves (4 or 8) of 32 queries share the K / V^T tiles: 8 waves halve the L2 -> LDS bytes per query at the same
-// waves per CU (one 8-wave workgroup instead of two 4-wave ones).
-// Register-staged form: kept behind knob 6 = 1 for A/B runs; attn_fwd_x3_dma_kernel below is the one dispatched
-// (ViT-S/16 B = 64: 35.0 -> 28.4 us per launch; N = 2305: 463 -> 371 us, same box, alternating runs).
-template <bool WANT_O, int NW>
-__global__ __launch_bounds__(NW * 64, 2) void attn_fwd_x3_kernel(const char *__restrict__ Q, const char *__restrict__ Kk,
-                                                             const char *__restrict__ Vt, char *__restrict__ ctx,
-                                                             float *__restrict__ lse2, int N, int npad, int H,
-                                                             float scale2, int wt) {
-    __shared__ __attribute__((aligned(16))) char smem[2 * 2 * 16384];  // K[2] | Vt[2], 16 KiB each
-    char *Ks = smem, *Vs = smem + 2 * 16384;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int r = lane & 31, h = lane >> 5;
-    int qblk, bh;
-    xcd_remap2(qblk, bh);
-    const int q0 = (qblk * NW + wave) * 32;
-    constexpr int NT = NW * 64, CH = 1024 / NT;  // 16-B chunks per thread per tile and operand
-    const bool active = q0 < N;  // wave-uniform
-    const char *Qb = Q + (int64_t)bh * npad * 256;
-    const char *Kb = Kk + (int64_t)bh * npad * 256;
-    const char *Vb = Vt + (int64_t)bh * 64 * npad * 4;
-
-    // Q^T as the B operand: lane (query r, half h) holds Q[q0+r][16s + 8h .. +7], hi and lo halves
-    bf16x8 qh[4], ql[4];
-    {
-        const char *qp = Qb + (int64_t)min(q0 + r, N - 1) * 256;
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            const char *p = qp + (s >> 1) * 128 + ((s & 1) * 16 + 8 * h) * 2;
-            qh[s] = *(const bf16x8 *)p;
-            ql[s] = *(const bf16x8 *)(p + 64);
-        }
-    }
-
-    // staging: 1024 K chunks + 1024 V^T chunks of 16 B per tile, NT threads -> CH + CH each
-    f32x4 rk[CH], rv[CH];
-    auto issue = [&](int kt) {
-#pragma unroll
-        for (int i = 0; i < CH; ++i) {
-            const int qd = tid + NT * i, row = qd >> 4, c16 = qd & 15;  // row: key (K) or d (V^T); 16 chunks per row
-            const int key = min(kt * 64 + row, N - 1);
-            rk[i] = *(const f32x4 *)(Kb + (int64_t)key * 256 + c16 * 16);
-            f32x4 v = {0.f, 0.f, 0.f, 0.f};
-            const int key0 = kt * 64 + (c16 >> 3) * 32 + (c16 & 3) * 8;  // first of the chunk's 8 keys (hi or lo halves)
-            if (WANT_O && key0 < N) {  // key0 < N <= npad: the chunk lies inside the row
-                v = *(const f32x4 *)(Vb + (int64_t)row * npad * 4 + (kt * 2 + (c16 >> 3)) * 128 + (c16 & 7) * 16);
-                if (key0 + 8 > N) {  // keys >= N are padding: force exact zeros (0 * garbage must not be NaN)
-                    bf16x8 t = __builtin_bit_cast(bf16x8, v);
-#pragma unroll
-                    for (int e = 0; e < 8; ++e)
-                        if (key0 + e >= N) t[e] = (bf16)0.f;
-                    v = __builtin_bit_cast(f32x4, t);
-                }
-            }
-            rv[i] = v;
-        }
-    };
-    auto commit = [&](int buf) {
-#pragma unroll
-        for (int i = 0; i < CH; ++i) {
-            const int qd = tid + NT * i, row = qd >> 4, c16 = qd & 15;
-            const int o = buf * 16384 + (c16 >> 3) * 8192 + lds_off(row, c16 & 7);
-            *(f32x4 *)(Ks + o) = rk[i];
-            *(f32x4 *)(Vs + o) = rv[i];
-        }
-    };
-
-    f32x16 O[2];
-#pragma unroll
-    for (int e = 0; e < 16; ++e) O[0][e] = O[1][e] = 0.f;
-    float m = -INFINITY, l = 0.f;
-    const int pr = pi_row(r);
-    const int ntiles = (N + 63) >> 6;
-
-    issue(0);
-    commit(0);
-    lds_barrier();
-    for (int kt = 0; kt < ntiles; ++kt) {
-        const int buf = kt & 1;
-#if !defined(OCM_ABL) || OCM_ABL != 5  // ablation 5: tile 0 reused, no staging after the prologue
-        if (kt + 1 < ntiles) issue(kt + 1);
-#endif
-#if defined(OCM_ABL) && OCM_ABL == 6  // ablation 6: staging only, no arithmetic
-        if (false) {
-#else
-        if (active) {
-#endif
-            const char *Kt = Ks + buf * 16384, *Vtile = Vs + buf * 16384;
-            // the second 32 keys of the tile are all padding in the last tile of N = 197 / 2305 (5 and 1 valid keys):
-            // skipping them leaves every result bit for bit (their p is exp2(-inf) = 0 and their V^T columns are 0)
-            const bool two = kt * 64 + 32 < N;  // wave-uniform
-            f32x16 S[2];
-#pragma unroll
-            for (int sub = 0; sub < 2; ++sub) {
-#pragma unroll
-                for (int e = 0; e < 16; ++e) S[sub][e] = (sub == 1 && !two) ? -INFINITY : 0.f;
-                if (sub == 1 && !two) continue;
-#pragma unroll
-                for (int s = 0; s < 4; ++s) {
-                    const char *kp = Kt + (s >> 1) * 8192 + sub * 32 * 128;
-                    const bf16x8 kh = *(const bf16x8 *)(kp + lds_off(pr, (s & 1) * 2 + h));
-                    const bf16x8 kl = *(const bf16x8 *)(kp + lds_off(pr, 4 + (s & 1) * 2 + h));
-                    S[sub] = mfma32x3(kh, kl, qh[s], ql[s], S[sub]);
-                }
-            }
-            if ((kt + 1) * 64 > N) {  // tail tile: padding keys -> -inf (wave-uniform branch)
-#pragma unroll
-                for (int sub = 0; sub < 2; ++sub)
-#pragma unroll
-                    for (int e = 0; e < 16; ++e)
-                        if (kt * 64 + sub * 32 + key_of_reg(e, h) >= N) S[sub][e] = -INFINITY;
-            }
-            float mx = fmaxf(S[0][0], S[1][0]);
-#pragma unroll
-            for (int e = 1; e < 16; ++e) mx = fmaxf(mx, fmaxf(S[0][e], S[1][e]));
-            mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-            const float alpha = defer_max_update(m, mx * scale2);  // every tile holds at least one valid key: finite
-            const float mn = m;
-            float ps = 0.f;
-#pragma unroll
-            for (int sub = 0; sub < 2; ++sub) {
-                if (sub == 1 && !two) continue;
-#pragma unroll
-                for (int e = 0; e < 16; ++e) {
-                    const float p = fast_exp2(fmaf(S[sub][e], scale2, -mn));
-                    S[sub][e] = p;
-                    ps += p;
-                }
-            }
-            l = fmaf(l, alpha, ps);
-            if (WANT_O) {
-                if (__any(alpha != 1.0f)) {  // the running max moved somewhere in this wave
-#pragma unroll
-                    for (int e = 0; e < 16; ++e) {
-                        O[0][e] *= alpha;
-                        O[1][e] *= alpha;
-                    }
-                }
-#pragma unroll
-                for (int sub = 0; sub < 2; ++sub) {
-                    if (sub == 1 && !two) continue;
-#pragma unroll
-                    for (int s2 = 0; s2 < 2; ++s2) {
-                        bf16x8 ph, pl;
-#pragma unroll
-                        for (int e = 0; e < 8; ++e) {
-                            const float pv = S[sub][8 * s2 + e];
-                            const bf16 t = (bf16)pv;
-                            ph[e] = t;
-                            pl[e] = (bf16)(pv - (float)t);
-                        }
-#pragma unroll
-                        for (int db = 0; db < 2; ++db) {
-                            const char *vp = Vtile + sub * 8192 + db * 32 * 128;
-                            const bf16x8 vh = *(const bf16x8 *)(vp + lds_off(r, 2 * s2 + h));
-                            const bf16x8 vl = *(const bf16x8 *)(vp + lds_off(r, 4 + 2 * s2 + h));
-                            O[db] = mfma32x3(vh, vl, ph, pl, O[db]);
-                        }
-                    }
-                }
-            }
-        }
-#if !defined(OCM_ABL) || OCM_ABL != 5
-        if (kt + 1 < ntiles) commit(buf ^ 1);
-#endif
-        lds_barrier();
-    }
-
-    if (!active) return;
-    const float lt = l + __shfl_xor(l, 32, 64);
-    const int qrow = q0 + r;
-    if (qrow < N) {
-        if (lse2 && h == 0) lse2[(int64_t)bh * N + qrow] = m + __log2f(lt);
-        if (WANT_O) {
-            const float inv = 1.0f / lt;
-            const int b = bh / H, head = bh - b * H;
-            char *dst = ctx + ((int64_t)b * N + qrow) * (H * 64) * 4 + head * 256;
-#pragma unroll
-            for (int db = 0; db < 2; ++db)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    f32x4 o;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) o[e] = O[db][4 * g + e] * inv;
-                    bf16x4 oh, ol;
-                    split4(o, oh, ol);
-                    char *p = dst + db * 128 + (8 * g + 4 * h) * 2;
-                    if (wt) {  // write-through: the context rows are consumed by another kernel, not by this one
-                        const f32x2 dh = __builtin_bit_cast(f32x2, oh), dl = __builtin_bit_cast(f32x2, ol);
-                        asm volatile("global_store_dwordx2 %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(dh) : "memory");
-                        asm volatile("global_store_dwordx2 %0, %1, off sc1\n\ts_nop 1" ::"v"(p + 64), "v"(dl) : "memory");
-                    } else {
-                        *(bf16x4 *)p = oh;
-                        *(bf16x4 *)(p + 64) = ol;
-                    }
-                }
-        }
-    }
-}
-
-
 #ifdef OCM_GEMM_STAMPS
 // development only (make stamps, tools/attn_stamps.py): per-wave timeline of attn_fwd_x3_dma_kernel,
 // [workgroup (blockIdx.y * gridDim.x + blockIdx.x) < 1024][wave < 8][point < 16]
@@ -891,15 +669,20 @@ extern "C" int ocm_debug_stamps_attn(unsigned long long *host, int n) {
 #define ASTAMP_RT(k) ((void)0)
 #endif
 
-// LDS-DMA form of attn_fwd_x3_kernel (the dispatched one). Same arithmetic per key, but
+// OCM_PREC_BF16X3: the flash kernel on split-bf16 pairs (common.h: sp32). q / k rows are 256 bytes
+// [hi d 0..31 | lo d 0..31 | hi d 32..63 | lo d 32..63]; V^T rows are key-contiguous in the same 128-byte groups of
+// 32 keys. Every product runs as three bf16 MFMAs (hi*hi + hi*lo + lo*hi), P is split in registers. LDS tiles carry the
+// usual chunk swizzle, so the fragment reads are the conflict-free pattern of the bf16 kernel.
+// NW waves (4 or 8) of 32 queries share the K / V^T tiles: 8 waves halve the L2 -> LDS bytes per query at the same
+// waves per CU (one 8-wave workgroup instead of two 4-wave ones).
 //   * K / V^T tiles of 32 keys go global -> LDS by `buffer_load ... lds` (1 KiB = 8 LDS rows per wave instruction, the
 //     chunk swizzle applied to the per-lane SOURCE offset, the tile index in the scalar offset): no staging registers,
-//     no ds_write, no per-tile address arithmetic (the register-staged kernel spent as many vector instructions on
-//     staging as on the softmax);
+//     no ds_write, no per-tile address arithmetic (a register-staged form, since removed, spent as many vector
+//     instructions on staging as on the softmax: ViT-S/16 B = 64 35.0 -> 28.4 us per launch, N = 2305 463 -> 371 us);
 //   * a ring of three 16 KiB stages (K: two [32 keys][128 B] images, V^T: one [64 d][128 B] image), two tiles in
 //     flight, one counted `s_waitcnt vmcnt` + one barrier per tile;
-//   * 48 KiB of LDS and <= 168 registers: three 4-wave workgroups per CU, so the 768 workgroups of ViT-S/16 at B = 64
-//     are resident at once (the 64 KiB / 198-register kernel ran them in one and a half rounds of two).
+//   * 48 KiB of LDS and <= 168 registers: on four waves, three workgroups per CU (the 768 workgroups of ViT-S/16 at
+//     B = 64 resident at once; those shapes now go to attn_fwd_x3_pp_kernel below).
 // Padding keys of the last tile: their K rows are inside the buffer (scores overwritten with -inf), their V^T columns
 // are zeroed in LDS after the tile has landed (the qkv epilogue never writes them; 0 * garbage must not be NaN).
 // HD = head width: 64 (the DINO ViTs), or 128 (the reference's SimMIM encoder, model.py:93-103) on a two-stage ring of
@@ -1700,176 +1483,6 @@ __global__ __launch_bounds__(256) void attn_merge_x3_kernel(const float *__restr
     if (lse2 && c == 0) lse2[row] = m + __log2f(L);
 }
 
-// Whole-sequence variant of attn_fwd_x3_kernel for N <= 256 (ViT-S/16 and ViT-B/16 at 224^2: N = 197): one workgroup
-// of 8 waves per (batch, head). ALL K and V^T tiles of the head (hi + lo halves: up to 128 KiB) are brought into LDS
-// by one burst of `buffer_load ... lds` DMAs (no staging registers, the chunk swizzle applied on the source address),
-// the V^T columns of padding keys are zeroed in LDS (0 * garbage must not reach the accumulator; the buffer's padding
-// columns are never written by the qkv epilogue), then every wave walks the key tiles of its 32 query rows with no
-// further synchronisation. K / V^T are read once per head instead of once per 128 queries and the per-tile
-// load -> barrier chain of the streaming kernel is gone.
-template <bool WANT_O>
-__global__ __launch_bounds__(512, 2) void attn_small_x3_kernel(const char *__restrict__ Q, const char *__restrict__ Kk,
-                                                               const char *__restrict__ Vt, char *__restrict__ ctx,
-                                                               float *__restrict__ lse2, int N, int npad, int H,
-                                                               float scale2) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int ntiles = (N + 63) >> 6;
-    char *Ks = smem, *Vs = smem + ntiles * 16384;  // per tile: 2 images x 64 rows x 128 B
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int r = lane & 31, h = lane >> 5;
-    const int bh = xcd_remap(blockIdx.x, gridDim.x);
-    const int q0 = wave * 32;
-    const char *Qb = Q + (int64_t)bh * npad * 256;
-    const char *Kb = Kk + (int64_t)bh * npad * 256;
-    const char *Vb = Vt + (int64_t)bh * 64 * npad * 4;
-
-    // ---- bulk fill: piece = 1 KiB = 8 LDS rows; K tile kt, image g holds rows (keys) of group g of the head row
-#if defined(__HIP_DEVICE_COMPILE__)
-    {
-        typedef __attribute__((address_space(3))) void *lds_ptr;
-        const auto rsK = __builtin_amdgcn_make_buffer_rsrc((void *)Kb, 0, (unsigned)(npad * 256), 0x00020000);
-        const auto rsV = __builtin_amdgcn_make_buffer_rsrc((void *)Vb, 0, (unsigned)(64 * npad * 4), 0x00020000);
-        const int lrow = lane >> 3, slot = lane & 7;
-        // K: ntiles * 2 images * 8 pieces; V^T: the same count. Waves take pieces round-robin.
-        for (int pc = wave; pc < ntiles * 16; pc += 8) {
-            const int kt = pc >> 4, g = (pc >> 3) & 1, rho = (pc & 7) * 8 + lrow;  // row inside the 64-row image
-            const int c = slot ^ ((rho >> 1) & 7);
-            const int key = min(kt * 64 + rho, N - 1);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsK, (lds_ptr)(Ks + pc * 1024), 16, key * 256 + g * 128 + c * 16, 0, 0, 0);
-            // V^T: row rho = d, the tile's key group g; groups past the padded row length read as zeros (bounds check)
-            const int grp = kt * 2 + g;
-            const int voff = grp * 128 < npad * 4 ? rho * npad * 4 + grp * 128 + c * 16 : 0x7FFFFFF0;
-            if (WANT_O)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsV, (lds_ptr)(Vs + pc * 1024), 16, voff, 0, 0, 0);
-        }
-    }
-#endif
-    // Q^T as the B operand (overlaps the DMA)
-    bf16x8 qh[4], ql[4];
-    {
-        const char *qp = Qb + (int64_t)min(q0 + r, N - 1) * 256;
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            const char *p = qp + (s >> 1) * 128 + ((s & 1) * 16 + 8 * h) * 2;
-            qh[s] = *(const bf16x8 *)p;
-            ql[s] = *(const bf16x8 *)(p + 64);
-        }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    if (WANT_O && (N & 63)) {  // zero the V^T halves of the padding keys of the last tile: keys N .. 64*ntiles - 1
-        const int kt = ntiles - 1, first = N - kt * 64;  // first padding key inside the tile
-        for (int i = tid; i < 64 * (64 - first); i += 512) {
-            const int d = i / (64 - first), key = first + i % (64 - first);
-            const int g = key >> 5, kk = key & 31;
-            char *base = Vs + kt * 16384 + g * 8192 + (kk & 7) * 2;
-            *(bf16 *)(base + lds_off(d, kk >> 3)) = (bf16)0.f;        // hi half: chunks 0..3 of the row
-            *(bf16 *)(base + lds_off(d, 4 + (kk >> 3))) = (bf16)0.f;  // lo half: chunks 4..7
-        }
-    }
-    __syncthreads();
-    if (q0 >= N) return;  // no barrier below
-
-    f32x16 O[2];
-#pragma unroll
-    for (int e = 0; e < 16; ++e) O[0][e] = O[1][e] = 0.f;
-    float m = -INFINITY, l = 0.f;
-    const int pr = pi_row(r);
-    for (int kt = 0; kt < ntiles; ++kt) {
-        const char *Kt = Ks + kt * 16384, *Vtile = Vs + kt * 16384;
-        f32x16 S[2];
-#pragma unroll
-        for (int sub = 0; sub < 2; ++sub) {
-#pragma unroll
-            for (int e = 0; e < 16; ++e) S[sub][e] = 0.f;
-#pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                const char *kp = Kt + (s >> 1) * 8192 + sub * 32 * 128;
-                const bf16x8 kh = *(const bf16x8 *)(kp + lds_off(pr, (s & 1) * 2 + h));
-                const bf16x8 kl = *(const bf16x8 *)(kp + lds_off(pr, 4 + (s & 1) * 2 + h));
-                S[sub] = mfma32x3(kh, kl, qh[s], ql[s], S[sub]);
-            }
-        }
-        if ((kt + 1) * 64 > N) {
-#pragma unroll
-            for (int sub = 0; sub < 2; ++sub)
-#pragma unroll
-                for (int e = 0; e < 16; ++e)
-                    if (kt * 64 + sub * 32 + key_of_reg(e, h) >= N) S[sub][e] = -INFINITY;
-        }
-        float mx = fmaxf(S[0][0], S[1][0]);
-#pragma unroll
-        for (int e = 1; e < 16; ++e) mx = fmaxf(mx, fmaxf(S[0][e], S[1][e]));
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        const float alpha = defer_max_update(m, mx * scale2);  // every tile holds at least one valid key: finite
-        const float mn = m;
-        float ps = 0.f;
-#pragma unroll
-        for (int sub = 0; sub < 2; ++sub)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const float p = fast_exp2(fmaf(S[sub][e], scale2, -mn));
-                S[sub][e] = p;
-                ps += p;
-            }
-        l = fmaf(l, alpha, ps);
-        if (WANT_O) {
-            if (__any(alpha != 1.0f)) {
-#pragma unroll
-                for (int e = 0; e < 16; ++e) {
-                    O[0][e] *= alpha;
-                    O[1][e] *= alpha;
-                }
-            }
-#pragma unroll
-            for (int sub = 0; sub < 2; ++sub)
-#pragma unroll
-                for (int s2 = 0; s2 < 2; ++s2) {
-                    bf16x8 ph, pl;
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) {
-                        const float pv = S[sub][8 * s2 + e];
-                        const bf16 t = (bf16)pv;
-                        ph[e] = t;
-                        pl[e] = (bf16)(pv - (float)t);
-                    }
-#pragma unroll
-                    for (int db = 0; db < 2; ++db) {
-                        const char *vp = Vtile + sub * 8192 + db * 32 * 128;
-                        const bf16x8 vh = *(const bf16x8 *)(vp + lds_off(r, 2 * s2 + h));
-                        const bf16x8 vl = *(const bf16x8 *)(vp + lds_off(r, 4 + 2 * s2 + h));
-                        O[db] = mfma32x3(vh, vl, ph, pl, O[db]);
-                    }
-                }
-        }
-    }
-    const float lt = l + __shfl_xor(l, 32, 64);
-    const int qrow = q0 + r;
-    if (qrow < N) {
-        if (lse2 && h == 0) lse2[(int64_t)bh * N + qrow] = m + __log2f(lt);
-        if (WANT_O) {
-            const float inv = 1.0f / lt;
-            const int b = bh / H, head = bh - b * H;
-            char *dst = ctx + ((int64_t)b * N + qrow) * (H * 64) * 4 + head * 256;
-#pragma unroll
-            for (int db = 0; db < 2; ++db)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    f32x4 o;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) o[e] = O[db][4 * g + e] * inv;
-                    bf16x4 oh, ol;
-                    split4(o, oh, ol);
-                    char *p = dst + db * 128 + (8 * g + 4 * h) * 2;
-                    *(bf16x4 *)p = oh;
-                    *(bf16x4 *)(p + 64) = ol;
-                }
-        }
-    }
-}
-
 template <int HD>
 __global__ __launch_bounds__(256) void attn_probs_x3_kernel(const char *__restrict__ Q, const char *__restrict__ Kk,
                                                             const float *__restrict__ lse2, float *__restrict__ attn,
@@ -2031,15 +1644,9 @@ hipError_t launch_attention_generic(int prec, const float *qkv, void *ctx, float
     if (nq <= 0) return hipSuccess;
     const size_t lds = (size_t)4 * (head_dim + n_tokens) * sizeof(float);
     if (lds > 160 * 1024) return hipErrorInvalidValue;
-    static unsigned long long optin_mask = 0;
-    int dev = 0;
-    if (hipError_t e = hipGetDevice(&dev); e != hipSuccess) return e;
-    if (lds > 64 * 1024 && !(optin_mask >> (dev & 63) & 1)) {
-        if (hipError_t e = hipFuncSetAttribute((const void *)attn_generic_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               160 * 1024);
-            e != hipSuccess)
-            return e;
-        optin_mask |= 1ull << (dev & 63);
+    if (lds > 64 * 1024) {
+        static OptinMask optin;
+        if (hipError_t e = lds_optin((const void *)attn_generic_kernel, 160 * 1024, optin); e != hipSuccess) return e;
     }
     attn_generic_kernel<<<dim3((nq + 3) / 4, batch * heads), dim3(256), lds, s>>>(
         qkv, (char *)ctx, attn, query_rows, n_rows, rows, batch, heads, n_tokens, head_dim, scale, prec, all);
@@ -2056,98 +1663,54 @@ size_t attention_ksplit_bytes(int prec, int batch, int n_tokens, int heads, int 
 hipError_t launch_attention(int prec, const void *q, const void *k, const void *vt, void *ctx, float *lse2, int batch,
                             int n_tokens, int n_pad, int heads, float scale, hipStream_t s, int head_dim, float *ksplit_ws,
                             size_t ksplit_bytes) {
-    if (head_dim == 128 && prec == 2) {  // 128-wide heads (model.py:93-103): split-bf16 only, four wavefronts, two stages
-        if (n_pad % 32) return hipErrorInvalidValue;
-        const dim3 g128(((n_tokens + 31) / 32 + 3) / 4, batch * heads), b128(256);
-        if (ctx)
-            attn_fwd_x3_dma_kernel<true, 4, 2, 128, 2><<<g128, b128, 0, s>>>((const char *)q, (const char *)k, (const char *)vt,
-                                                                             (char *)ctx, lse2, n_tokens, n_pad, heads,
-                                                                             scale * LOG2E, 0);
-        else
-            attn_fwd_x3_dma_kernel<false, 4, 2, 128, 2><<<g128, b128, 0, s>>>((const char *)q, (const char *)k, (const char *)vt,
-                                                                              (char *)ctx, lse2, n_tokens, n_pad, heads,
-                                                                              scale * LOG2E, 0);
-        return hipGetLastError();
-    }
     if (head_dim != 64 && head_dim != 128) return hipErrorInvalidValue;
     if (!prec)
         return launch_attention_bf16((const bf16 *)q, (const bf16 *)k, (const bf16 *)vt, (bf16 *)ctx, lse2, batch,
                                      n_tokens, n_pad, heads, scale, s, head_dim);
-    if (prec == 1 && head_dim == 128) {  // 128-wide heads in fp32 precision: the streaming kernel on 128 KiB of dynamic LDS
-        const dim3 g128(((n_tokens + 31) / 32 + 3) / 4, batch * heads), b128(256);
-        constexpr int LDSF = 4 * 128 * 256;
-        static unsigned long long optin[2] = {0, 0};
-        int dev = 0;
-        if (hipError_t e = hipGetDevice(&dev); e != hipSuccess) return e;
-        const void *kern = ctx ? (const void *)attn_fwd_f32_kernel<true, 128> : (const void *)attn_fwd_f32_kernel<false, 128>;
-        unsigned long long &mask = optin[ctx ? 1 : 0];
-        if (!(mask >> (dev & 63) & 1)) {
-            if (hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDSF); e != hipSuccess) return e;
-            mask |= 1ull << (dev & 63);
-        }
-        if (ctx)
-            attn_fwd_f32_kernel<true, 128><<<g128, b128, LDSF, s>>>((const float *)q, (const float *)k, (const float *)vt,
-                                                                    (float *)ctx, lse2, n_tokens, n_pad, heads, scale * LOG2E);
-        else
-            attn_fwd_f32_kernel<false, 128><<<g128, b128, LDSF, s>>>((const float *)q, (const float *)k, (const float *)vt,
-                                                                     (float *)ctx, lse2, n_tokens, n_pad, heads, scale * LOG2E);
-        return hipGetLastError();
-    }
-    if (head_dim != 64) return hipErrorInvalidValue;
     const int qtiles = (n_tokens + 31) / 32;
     const dim3 grid((qtiles + 3) / 4, batch * heads), block(256);
-    if (prec == 2) {
-        if (n_pad % 32) return hipErrorInvalidValue;
-        // Whole-sequence kernel (all K / V^T of a head in LDS, one DMA burst): built, parity-green, and measured SLOWER
-        // than the streaming kernel at ViT-S/16, B = 64 (40.3 us against 34.1 us per launch: 128 KiB of LDS leaves one
-        // workgroup per CU, so nothing overlaps the fill) — kept behind knob 6 = 2 for A/B runs, not dispatched.
-#ifdef OCM_DEV
-        if (n_tokens <= 256 && OCM_KNOB(6) == 2) {
-            const int nt = (n_tokens + 63) / 64, lds = nt * 2 * 16384;
-            static unsigned long long optin[2] = {0, 0};
-            int dev = 0;
-            if (hipError_t e = hipGetDevice(&dev); e != hipSuccess) return e;
-            const void *kern = ctx ? (const void *)attn_small_x3_kernel<true> : (const void *)attn_small_x3_kernel<false>;
-            unsigned long long &mask = optin[ctx ? 1 : 0];
-            if (!(mask >> (dev & 63) & 1)) {
-                if (hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * 16384);
-                    e != hipSuccess)
-                    return e;
-                mask |= 1ull << (dev & 63);
-            }
-            const dim3 g1(batch * heads), b1(512);
-            if (ctx)
-                attn_small_x3_kernel<true><<<g1, b1, lds, s>>>((const char *)q, (const char *)k, (const char *)vt, (char *)ctx,
-                                                               lse2, n_tokens, n_pad, heads, scale * LOG2E);
-            else
-                attn_small_x3_kernel<false><<<g1, b1, lds, s>>>((const char *)q, (const char *)k, (const char *)vt, (char *)ctx,
-                                                                lse2, n_tokens, n_pad, heads, scale * LOG2E);
-            return hipGetLastError();
+    const float scale2 = scale * LOG2E;
+    if (prec == 1) {
+        const float *Q = (const float *)q, *K = (const float *)k, *V = (const float *)vt;
+        if (head_dim == 128) {  // 128-wide heads: the streaming kernel on 128 KiB of dynamic LDS
+            constexpr int LDSF = 4 * 128 * 256;
+            static OptinMask optin[2];
+            auto kern = ctx ? attn_fwd_f32_kernel<true, 128> : attn_fwd_f32_kernel<false, 128>;
+            if (hipError_t e = lds_optin((const void *)kern, LDSF, optin[ctx ? 1 : 0]); e != hipSuccess) return e;
+            kern<<<grid, block, LDSF, s>>>(Q, K, V, (float *)ctx, lse2, n_tokens, n_pad, heads, scale2);
+        } else {
+            constexpr int LDSF64 = 4 * 64 * 256;  // 64 KiB: K[2] | Vt[2]
+            auto kern = ctx ? attn_fwd_f32_kernel<true> : attn_fwd_f32_kernel<false>;
+            kern<<<grid, block, LDSF64, s>>>(Q, K, V, (float *)ctx, lse2, n_tokens, n_pad, heads, scale2);
         }
-#endif
-        // long sequences: 8 waves per workgroup share each K / V^T tile (half the L2 -> LDS traffic per query)
-        // (the dozen workgroups of a one-tile call at N = 197 stay on four waves: eight measured 0.65 -> 0.68 ms per forward)
-        const bool wide = (n_tokens > 1024 && OCM_KNOB(7) != 1) || OCM_KNOB(7) == 2;
+        return hipGetLastError();
+    }
+    if (n_pad % 32) return hipErrorInvalidValue;
+    const char *Q = (const char *)q, *K = (const char *)k, *V = (const char *)vt;
+    if (head_dim == 128) {  // 128-wide heads (model.py:93-103): four wavefronts, two stages
+        auto kern = ctx ? attn_fwd_x3_dma_kernel<true, 4, 2, 128, 2> : attn_fwd_x3_dma_kernel<false, 4, 2, 128, 2>;
+        kern<<<grid, block, 0, s>>>(Q, K, V, (char *)ctx, lse2, n_tokens, n_pad, heads, scale2, 0, nullptr);
+        return hipGetLastError();
+    }
+    // long sequences: 8 waves per workgroup share each K / V^T tile (half the L2 -> LDS traffic per query)
+    // (the dozen workgroups of a one-tile call at N = 197 stay on four waves: eight measured 0.65 -> 0.68 ms per forward)
+    const bool wide = (n_tokens > 1024 && OCM_KNOB(7) != 1) || OCM_KNOB(7) == 2;
+    if (wide) {
         const dim3 grid8((qtiles + 7) / 8, batch * heads), block8(512);
         // Long sequence, few workgroups (one ViT-S/8 window per call: 60 of them, 73 key tiles each): cut the key range into
         // up to four slices per workgroup and merge (attn_merge_x3_kernel)
-        // (the statistics-only pass of get_last_selfattention takes the same slices, so the log-sum-exp — and with it the returned
-        // probabilities — has the same bits from both entry points)
-        if (wide && ksplit_ws && OCM_KNOB(7) == 0) {
-            const int wgs = (int)(grid8.x * grid8.y), ktiles = (n_tokens + 31) / 32;
+        // (the statistics-only pass of get_last_selfattention takes the same slices, so the log-sum-exp — and with it the
+        // returned probabilities — has the same bits from both entry points)
+        if (ksplit_ws && OCM_KNOB(7) == 0) {
+            const int wgs = (int)(grid8.x * grid8.y);
             // (eight slices of 9-10 tiles measure slower than four of 18-19: 36.6 + 7.4 us against 34.3 + 5.1 us with the merge)
             const int want = wgs <= 64 ? 4 : wgs <= 96 ? 3 : wgs <= 128 ? 2 : 1;
-            const int per = (ktiles + want - 1) / want, nslice = (ktiles + per - 1) / per;  // every slice owns >= 1 tile
+            const int per = (qtiles + want - 1) / want, nslice = (qtiles + per - 1) / per;  // every slice owns >= 1 tile
             const size_t need = (size_t)nslice * batch * heads * n_tokens * (64 + 4) * sizeof(float);
             if (nslice > 1 && need <= ksplit_bytes) {
-                if (ctx)
-                    attn_fwd_x3_dma_kernel<true, 8, 2, 64, 3, true><<<dim3(grid8.x, grid8.y, nslice), block8, 0, s>>>(
-                        (const char *)q, (const char *)k, (const char *)vt, (char *)ctx, lse2, n_tokens, n_pad, heads,
-                        scale * LOG2E, 0, ksplit_ws);
-                else
-                    attn_fwd_x3_dma_kernel<false, 8, 2, 64, 3, true><<<dim3(grid8.x, grid8.y, nslice), block8, 0, s>>>(
-                        (const char *)q, (const char *)k, (const char *)vt, (char *)ctx, lse2, n_tokens, n_pad, heads,
-                        scale * LOG2E, 0, ksplit_ws);
+                auto kern = ctx ? attn_fwd_x3_dma_kernel<true, 8, 2, 64, 3, true> : attn_fwd_x3_dma_kernel<false, 8, 2, 64, 3, true>;
+                kern<<<dim3(grid8.x, grid8.y, nslice), block8, 0, s>>>(Q, K, V, (char *)ctx, lse2, n_tokens, n_pad, heads, scale2,
+                                                                       0, ksplit_ws);
                 if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
                 const int64_t rows = (int64_t)batch * heads * n_tokens;
                 attn_merge_x3_kernel<64><<<dim3((unsigned)((rows + 15) / 16)), dim3(256), 0, s>>>(
@@ -2155,64 +1718,23 @@ hipError_t launch_attention(int prec, const void *q, const void *k, const void *
                 return hipGetLastError();
             }
         }
-#define OCM_X3_ATTN(WO, NW_, G, B_)                                                                                      \
-    attn_fwd_x3_kernel<WO, NW_><<<G, B_, 0, s>>>((const char *)q, (const char *)k, (const char *)vt, (char *)ctx, lse2, \
-                                                 n_tokens, n_pad, heads, scale * LOG2E, (ocm_wt_mask() >> 4) & 1)
-#define OCM_X3_ATTN_DMA(WO, NW_, WPS_, G, B_)                                                                          \
-    attn_fwd_x3_dma_kernel<WO, NW_, WPS_><<<G, B_, 0, s>>>((const char *)q, (const char *)k, (const char *)vt,          \
-                                                           (char *)ctx, lse2, n_tokens, n_pad, heads, scale * LOG2E,    \
-                                                           (ocm_wt_mask() >> 4) & 1)
-#ifdef OCM_DEV
-        if (OCM_KNOB(6) == 1) {  // the register-staged streaming kernel (A/B runs)
-            if (wide) {
-                if (ctx) OCM_X3_ATTN(true, 8, grid8, block8); else OCM_X3_ATTN(false, 8, grid8, block8);
-            } else {
-                if (ctx) OCM_X3_ATTN(true, 4, grid, block); else OCM_X3_ATTN(false, 4, grid, block);
-            }
-        } else
-#endif
-        if (wide) {
-            if (ctx) OCM_X3_ATTN_DMA(true, 8, 2, grid8, block8); else OCM_X3_ATTN_DMA(false, 8, 2, grid8, block8);
-        } else if (grid.x * grid.y < 128 && OCM_KNOB(6) != 4 && OCM_KNOB(6) != 3) {
-            // a handful of workgroups (one tile per call): the keys of a 32-query tile split over the four waves of a workgroup
-            const dim3 gws(qtiles, batch * heads);
-            constexpr int LDSWS = 4 * 2 * 2 * 8192;
-            static unsigned long long optin[2] = {0, 0};
-            int dev = 0;
-            if (hipError_t e = hipGetDevice(&dev); e != hipSuccess) return e;
-            const void *kern = ctx ? (const void *)attn_fwd_x3_ws_kernel<true> : (const void *)attn_fwd_x3_ws_kernel<false>;
-            unsigned long long &mask = optin[ctx ? 1 : 0];
-            if (!(mask >> (dev & 63) & 1)) {
-                if (hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDSWS); e != hipSuccess)
-                    return e;
-                mask |= 1ull << (dev & 63);
-            }
-            if (ctx)
-                attn_fwd_x3_ws_kernel<true><<<gws, block, LDSWS, s>>>((const char *)q, (const char *)k, (const char *)vt, (char *)ctx,
-                                                                      lse2, n_tokens, n_pad, heads, scale * LOG2E);
-            else
-                attn_fwd_x3_ws_kernel<false><<<gws, block, LDSWS, s>>>((const char *)q, (const char *)k, (const char *)vt, (char *)ctx,
-                                                                       lse2, n_tokens, n_pad, heads, scale * LOG2E);
-        } else if (OCM_KNOB(6) == 3) {  // development A/B: the round-3 loop on four waves (shipped: the software-pipelined kernel)
-            if (ctx) OCM_X3_ATTN_DMA(true, 4, 3, grid, block); else OCM_X3_ATTN_DMA(false, 4, 3, grid, block);
-        } else if (ctx) {
-            attn_fwd_x3_pp_kernel<true><<<grid, block, 0, s>>>((const char *)q, (const char *)k, (const char *)vt, (char *)ctx, lse2,
-                                                               n_tokens, n_pad, heads, scale * LOG2E);
-        } else {
-            attn_fwd_x3_pp_kernel<false><<<grid, block, 0, s>>>((const char *)q, (const char *)k, (const char *)vt, (char *)ctx, lse2,
-                                                                n_tokens, n_pad, heads, scale * LOG2E);
-        }
-#undef OCM_X3_ATTN_DMA
-#undef OCM_X3_ATTN
+        auto kern = ctx ? attn_fwd_x3_dma_kernel<true, 8, 2> : attn_fwd_x3_dma_kernel<false, 8, 2>;
+        kern<<<grid8, block8, 0, s>>>(Q, K, V, (char *)ctx, lse2, n_tokens, n_pad, heads, scale2, (ocm_wt_mask() >> 4) & 1,
+                                      nullptr);
         return hipGetLastError();
     }
-    constexpr int LDSF64 = 4 * 64 * 256;  // 64 KiB: K[2] | Vt[2]
-    if (ctx)
-        attn_fwd_f32_kernel<true><<<grid, block, LDSF64, s>>>((const float *)q, (const float *)k, (const float *)vt,
-                                                              (float *)ctx, lse2, n_tokens, n_pad, heads, scale * LOG2E);
-    else
-        attn_fwd_f32_kernel<false><<<grid, block, LDSF64, s>>>((const float *)q, (const float *)k, (const float *)vt,
-                                                               (float *)ctx, lse2, n_tokens, n_pad, heads, scale * LOG2E);
+    // a handful of workgroups (one tile per call): the keys of a 32-query tile split over the four waves of a workgroup;
+    // otherwise the software-pipelined kernel (knob 6 = 4: everywhere)
+    const bool split = grid.x * grid.y < 128 && OCM_KNOB(6) != 4;
+    auto kern = split ? (ctx ? attn_fwd_x3_ws_kernel<true> : attn_fwd_x3_ws_kernel<false>)
+                      : (ctx ? attn_fwd_x3_pp_kernel<true> : attn_fwd_x3_pp_kernel<false>);
+    constexpr int LDSWS = 4 * 2 * 2 * 8192;  // wave-split: four waves x two slots of K | V^T
+    if (split) {
+        static OptinMask optin[2];
+        if (hipError_t e = lds_optin((const void *)kern, LDSWS, optin[ctx ? 1 : 0]); e != hipSuccess) return e;
+    }
+    kern<<<split ? dim3(qtiles, batch * heads) : grid, block, split ? LDSWS : 0, s>>>(Q, K, V, (char *)ctx, lse2, n_tokens,
+                                                                                      n_pad, heads, scale2);
     return hipGetLastError();
 }
 

@@ -1110,32 +1110,14 @@ hipError_t launch_swin_lnlinear(int prec, const float *x, const float *g, const 
     constexpr int NW = 4;
     const dim3 grid((unsigned)((T + NW * 32 - 1) / (NW * 32))), block(NW * 64);
     const int lds = 3 * (C / 32 * 4096) + N * 4;
-    const void *kern = nullptr;
-#define OCM_LNL(CG_, G_)                                                                                                \
-    do {                                                                                                                \
-        kern = (const void *)swin_lnqkv_x3_kernel<CG_, NW, G_>;                                                         \
-        if (lds > 64 * 1024) {                                                                                          \
-            static unsigned long long optin = 0;                                                                        \
-            int dev = 0;                                                                                                \
-            if (hipError_t e = hipGetDevice(&dev); e != hipSuccess) return e;                                           \
-            if (!(optin >> (dev & 63) & 1)) {                                                                           \
-                if (hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);    \
-                    e != hipSuccess)                                                                                    \
-                    return e;                                                                                           \
-                optin |= 1ull << (dev & 63);                                                                            \
-            }                                                                                                           \
-        }                                                                                                               \
-        swin_lnqkv_x3_kernel<CG_, NW, G_><<<grid, block, lds, s>>>(x, g, be, (const char *)w, bias, (char *)out, (int)T, N, \
-                                                                   eps);                                                \
-    } while (0)
-    if (C == 96) {
-        if (gelu) OCM_LNL(3, true); else OCM_LNL(3, false);
-    } else if (C == 128) {
-        if (gelu) OCM_LNL(4, true); else OCM_LNL(4, false);
-    } else {
-        if (gelu) OCM_LNL(6, true); else OCM_LNL(6, false);
+    auto kern = C == 96    ? (gelu ? swin_lnqkv_x3_kernel<3, NW, true> : swin_lnqkv_x3_kernel<3, NW, false>)
+                : C == 128 ? (gelu ? swin_lnqkv_x3_kernel<4, NW, true> : swin_lnqkv_x3_kernel<4, NW, false>)
+                           : (gelu ? swin_lnqkv_x3_kernel<6, NW, true> : swin_lnqkv_x3_kernel<6, NW, false>);
+    if (lds > 64 * 1024) {  // 96 KiB: the most any N up to 4096 launches with
+        static OptinMask optin[6];
+        if (hipError_t e = lds_optin((const void *)kern, 96 * 1024, optin[(C / 64 - 1) * 2 + gelu]); e != hipSuccess) return e;
     }
-#undef OCM_LNL
+    kern<<<grid, block, lds, s>>>(x, g, be, (const char *)w, bias, (char *)out, (int)T, N, eps);
     return hipGetLastError();
 }
 
@@ -1155,22 +1137,10 @@ hipError_t launch_swin_mlp(int prec, float *x, const float *g, const float *be, 
     const int nw = C == 96 ? NW96 : NW128, nst = C == 96 ? NS96 : NS128;
     const dim3 grid((unsigned)((T + nw * 32 - 1) / (nw * 32))), block(nw * 64);
     const int lds = nst * (C / 32 * 4096 + C * 128) + hidden * 4;
-    static unsigned long long optin[2] = {0, 0};
-    int dev = 0;
-    if (hipError_t e = hipGetDevice(&dev); e != hipSuccess) return e;
-    const void *kern = C == 96 ? (const void *)swin_mlp_x3_kernel<3, 12, NW96, NS96>
-                               : (const void *)swin_mlp_x3_kernel<4, 16, NW128, NS128>;
-    unsigned long long &mask = optin[C == 96 ? 0 : 1];
-    if (!(mask >> (dev & 63) & 1)) {
-        if (hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds); e != hipSuccess) return e;
-        mask |= 1ull << (dev & 63);
-    }
-    if (C == 96)
-        swin_mlp_x3_kernel<3, 12, NW96, NS96><<<grid, block, lds, s>>>(x, g, be, (const char *)w1, b1, (const char *)w2, b2,
-                                                                        (int)T, eps);
-    else
-        swin_mlp_x3_kernel<4, 16, NW128, NS128><<<grid, block, lds, s>>>(x, g, be, (const char *)w1, b1, (const char *)w2, b2,
-                                                                          (int)T, eps);
+    auto kern = C == 96 ? swin_mlp_x3_kernel<3, 12, NW96, NS96> : swin_mlp_x3_kernel<4, 16, NW128, NS128>;
+    static OptinMask optin[2];
+    if (hipError_t e = lds_optin((const void *)kern, lds, optin[C == 96 ? 0 : 1]); e != hipSuccess) return e;
+    kern<<<grid, block, lds, s>>>(x, g, be, (const char *)w1, b1, (const char *)w2, b2, (int)T, eps);
     return hipGetLastError();
 }
 
@@ -1549,15 +1519,9 @@ static hipError_t launch_swin_attn_block_t(float *x, const float *g, const float
     static_assert(lds <= 160 * 1024, "LDS");
     const float scale2 = 0.17677669529663687f * 1.4426950408889634f;  // 32^-0.5 (SwinAttention.scaling :408) in the log2 domain
     const dim3 grid((unsigned)((total + NWIN - 1) / NWIN)), block(NW * 64);
-    static unsigned long long optin = 0;
-    int dev = 0;
-    if (hipError_t e = hipGetDevice(&dev); e != hipSuccess) return e;
     auto kern = swin_attn_block_x3_kernel<CG, WS, NW, FUSE_PROJ>;
-    if (!(optin >> (dev & 63) & 1)) {
-        if (hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds); e != hipSuccess)
-            return e;
-        optin |= 1ull << (dev & 63);
-    }
+    static OptinMask optin;
+    if (hipError_t e = lds_optin((const void *)kern, lds, optin); e != hipSuccess) return e;
     kern<<<grid, block, lds, s>>>(x, g, be, (const char *)wqkv, bqkv, (const char *)wo, bo, bias_perm, (char *)ctx, gm, (int)total,
                                   scale2, eps);
     return hipGetLastError();

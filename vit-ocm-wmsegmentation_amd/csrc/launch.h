@@ -1,7 +1,23 @@
 // launch.h — host-side launchers shared between the kernel translation units and the
 // engine (engine.hip). Every launcher only enqueues work on `s`; none synchronises.
 #pragma once
+#include <atomic>
 #include "common.h"
+
+// hipFuncAttributeMaxDynamicSharedMemorySize is a per-device property of a kernel. Each launch site keeps one OptinMask per
+// kernel it launches (a function-local static: bit d set = done on device d) and calls lds_optin before every launch. The
+// fast path is one atomic load; two host threads that both miss set the same value twice, which is harmless. A failure is
+// returned and not recorded. The mask is per kernel, not per size: a site passes the largest size it can launch with.
+typedef std::atomic<unsigned long long> OptinMask;
+static inline hipError_t lds_optin(const void *kern, int bytes, OptinMask &done) {
+    int dev = 0;
+    if (hipError_t e = hipGetDevice(&dev); e != hipSuccess) return e;
+    const unsigned long long bit = 1ull << (dev & 63);
+    if (done.load(std::memory_order_acquire) & bit) return hipSuccess;
+    const hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e == hipSuccess) done.fetch_or(bit, std::memory_order_release);
+    return e;
+}
 
 // ---- kernels_misc.hip
 // out_kind: 0 fp32, 1 bf16, 2 split-bf16 pairs

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define OCM_ABI_VERSION 11
+#define OCM_ABI_VERSION 12
 
 enum {
     OCM_OK = 0,
@@ -421,6 +421,53 @@ int ocm_op_bn_relu_backward(const float *dz, const float *y, const float *mean, 
  * bit exact). */
 int ocm_op_pixel_shuffle_backward(const float *grad_out, float *grad_lin, int32_t batch, int32_t hp, int32_t wp,
                                   int32_t c_out, int32_t s, void *stream);
+
+/* ---- training of the ViT encoder (SimMIM pre-training, model.py:55-83; kernels_train.hip, kernels_train_attn.hip) ----
+ * The forward runs the stand-alone operators above and keeps, per block, the LayerNorm inputs, qkv_f32, lse2, the context and the
+ * fp32 fc1 pre-activation; the backward below plus ocm_op_linear (data gradients, transposed weights) and ocm_op_weight_grad
+ * (weight and bias gradients). No atomics anywhere: the same inputs give the same bits on every run. Token-major rows
+ * m = b*N + n, all gradients fp32. */
+
+/* Attention backward for heads of head_dim = 64 or 128 (any other width: OCM_EINVAL), any N >= 1, batch * heads <= 65535:
+ *   qkv_f32 [3][B][H][N][hd] (ocm_op_qkv_proj_hd), lse2 [B*H][N] (ocm_op_attention_hd), dctx [B][N][H*hd] = dO,
+ *   delta [B*H][N] = rowsum(dO o O) (ocm_op_attention_backward_delta)
+ *   -> dqkv fp32 [B*N][3*H*hd]: columns (which, head, channel) in qkv.weight's row order, every element written.
+ * P = exp2(q.k * scale * log2e - lse2) is recomputed per tile, never stored. All products are fp32 on v_mfma_f32_32x32x2_f32 in
+ * every set_precision mode (the operands are the fp32 projections; the mode only decided the forward's lse2). dK / dV come from a
+ * key-block-major kernel, dQ from a query-block-major one: each output has one owner and one summation order. */
+int ocm_op_attention_backward(const float *qkv_f32, const float *lse2, const float *dctx, const float *delta, float *dqkv,
+                              int32_t batch, int32_t n_tokens, int32_t heads, int32_t head_dim, float scale, void *stream);
+/* delta[b*H + h][n] = sum_d dctx[b][n][h*hd + d] * ctx[b][n][h*hd + d] with ctx in the operand type E of `precision` (what
+ * ocm_op_attention_hd wrote), and, when ctx_f32 != NULL, ctx as fp32 [B*N][H*hd]. heads * head_dim % 32 == 0. */
+int ocm_op_attention_backward_delta(int32_t precision, const void *ctx, const float *dctx, float *delta, float *ctx_f32,
+                                    int32_t batch, int32_t n_tokens, int32_t heads, int32_t head_dim, void *stream);
+
+/* LayerNorm backward over rows of `dim` (statistics recomputed from x in two passes, so rows with a large mean stay accurate):
+ *   dx = rstd (gamma dy - mean(gamma dy) - xhat mean(gamma dy xhat)) + dres   (dres: the residual branch's gradient, or NULL;
+ *   it may alias dx), dgamma = sum_m dy xhat, dbeta = sum_m dy (fixed-order column sums). All fp32 [rows][dim]. */
+size_t ocm_layernorm_backward_workspace_bytes(int64_t rows, int32_t dim);
+int ocm_op_layernorm_backward(const float *dy, const float *x, const float *gamma, const float *dres, float *dx, float *dgamma,
+                              float *dbeta, int64_t rows, int32_t dim, float eps, void *workspace, size_t workspace_bytes,
+                              void *stream);
+
+/* erf GELU (nn.GELU()) of `count` fp32 values: out in the operand type E of `precision` (count % 32 == 0 for split pairs, rows
+ * whose length is a multiple of 32), out_f32 (optional) in fp32. */
+int ocm_op_gelu(int32_t precision, const float *h, void *out, float *out_f32, size_t count, void *stream);
+/* dh = dg * gelu'(h) (dh may alias dg); g_f32 (optional) = gelu(h). */
+int ocm_op_gelu_backward(const float *dg, const float *h, float *dh, float *g_f32, size_t count, void *stream);
+
+/* Patch rows of a contiguous fp32 image (B, C, H, W): cols [B*P][C*p*p], row b*P + py*wp + px, column c*p*p + ky*p + kx (the
+ * (D, C, p, p) weight's K order): the input of the patch-embedding weight gradient. H, W multiples of p. */
+int ocm_op_patch_unfold(const float *image, float *cols, int32_t batch, int32_t channels, int32_t height, int32_t width,
+                        int32_t patch, void *stream);
+/* Gradient dtok [B][N][D] of t = cat(cls, patch * (1 - w) + mask_token * w) + pos (model.py:28-41) split into
+ *   dpatch [B*(N-1)][D] = (1 - w) dtok[:, 1:],  dmask_token [D] = sum over (b, p) of w dtok (only when mask != NULL),
+ *   dpos [N][D] = sum_b dtok (row 0 is the cls token's gradient), images summed in order.
+ * mask [B][N-1] fp32 or NULL (w = 0). */
+size_t ocm_patch_embed_backward_workspace_bytes(int32_t batch, int32_t n_tokens, int32_t dim);
+int ocm_op_patch_embed_backward(const float *dtok, const float *mask, float *dpatch, float *dmask_token, float *dpos,
+                                int32_t batch, int32_t n_tokens, int32_t dim, void *workspace, size_t workspace_bytes,
+                                void *stream);
 
 /* ---- sliding-window index math (host, integer; sw_processing.py:151-163) ---- */
 /* Number of windows per axis: len(range(0, size - 2*stride, stride)). */

@@ -1,0 +1,264 @@
+"""MIM (SimMIM pre-training, the reference's mim.py) in training mode on the HIP path: every parameter's gradient against a
+float64 CPU twin (oracle.vit_oracle.mim_forward with requires_grad parameters and torch autograd), frozen subsets,
+accumulation, AdamW steps and the eval-mode forward afterwards. Needs an MI355X.
+
+Error measure: max |g - g64| / max |g64| per tensor. Limits: fp32 1e-4, bf16x3 1e-3, bf16 5e-2."""
+import functools
+from functools import partial
+
+import pytest
+import torch
+import torch.nn as nn
+
+from oracle import vit_oracle as O
+from tests.golden_cases import WRAPPER_CASES
+from vit_ocm_wmsegmentation_amd import model as M
+from vit_ocm_wmsegmentation_amd import synth
+
+pytestmark = pytest.mark.gpu
+
+TOL = {"fp32": 1e-4, "bf16x3": 1e-3, "bf16": 5e-2}
+FWD_TOL = {"fp32": 2e-5, "bf16x3": 2e-4, "bf16": 5e-2}  # test_wrappers.py's ladder (bf16 with 128-wide heads: 5e-2)
+LOSS_BIAS_SHIFT = 10.0  # moves x_rec (|x_rec| of a few units) off the tiles (values in [0, 0.3)): no |x - x_rec| near zero
+GEOMS = {
+    "wrap_mim_hd128": WRAPPER_CASES["wrap_mim_hd128"],
+    "wrap_p8_64": WRAPPER_CASES["wrap_p8_64"],
+    # mim.py: build_model()'s 3 x 128 heads at 384^2 (N = 2305) and the sweep's 320^2 (N = 1601), two blocks, two images
+    "mim384": dict(dim=384, depth=2, heads=3, patch=8, img_size=384, batch=2, seed=41, variant="sharp"),
+    "mim320": dict(dim=384, depth=2, heads=3, patch=8, img_size=320, batch=2, seed=42, variant="sharp"),
+}
+
+
+@pytest.fixture(scope="module")
+def dev():
+    if not torch.cuda.is_available():
+        pytest.skip("needs a HIP device")
+    return torch.device("cuda:0")
+
+
+def _inputs(name):
+    c = GEOMS[name]
+    sd = synth.synth_state_dict(c["dim"], c["depth"], c["patch"], seed=c["seed"], variant=c["variant"], img_size=224)
+    wp = synth.synth_wrapper_params(c["dim"], c["patch"], 3, seed=c["seed"])
+    x = synth.synth_tiles(c["batch"], c["img_size"], seed=c["seed"] + 100)
+    mask = synth.synth_patch_mask(c["batch"], c["img_size"] // c["patch"], seed=c["seed"])
+    return c, sd, wp, x, mask
+
+
+def _model(name, precision, dev):
+    c, sd, wp, x, mask = _inputs(name)
+    enc = M.VisionTransformerForSimMIM(patch_size=c["patch"], embed_dim=c["dim"], depth=c["depth"], num_heads=c["heads"],
+                                       mlp_ratio=4, img_size=[c["img_size"]], qkv_bias=True,
+                                       norm_layer=partial(nn.LayerNorm, eps=1e-6), interpolate_encoding=True)
+    assert not enc.load_state_dict(dict(sd, mask_token=wp["mask_token"]), strict=True).missing_keys
+    mim = M.MIM(enc, c["patch"])
+    mim.decoder[0].weight.data.copy_(wp["decoder.weight"])
+    mim.decoder[0].bias.data.copy_(wp["decoder.bias"])
+    enc.set_precision(precision)
+    return mim.to(dev).train(), x.to(dev), mask
+
+
+def _twin_params(name):
+    """float64 leaves keyed by the MIM's own parameter names."""
+    c, sd, wp, _, _ = _inputs(name)
+    prm = {"encoder." + k: v.double().clone().requires_grad_(True) for k, v in sd.items()}
+    prm["encoder.mask_token"] = wp["mask_token"].double().clone().requires_grad_(True)
+    prm["decoder.0.weight"] = wp["decoder.weight"].double().clone().requires_grad_(True)
+    prm["decoder.0.bias"] = wp["decoder.bias"].double().clone().requires_grad_(True)
+    return prm
+
+
+def _twin(name, prm, x, mask):
+    c = GEOMS[name]
+    sd = {k[len("encoder."):]: v for k, v in prm.items() if k.startswith("encoder.") and k != "encoder.mask_token"}
+    cfg = O.make_cfg(sd, c["patch"], c["heads"])
+    return O.mim_forward(sd, cfg, x.double(), mask, c["img_size"], prm["encoder.mask_token"], prm["decoder.0.weight"],
+                         prm["decoder.0.bias"], c["patch"], patch_size=c["patch"])
+
+
+@functools.lru_cache(maxsize=None)
+def _reference(name, kind):
+    """(x_rec64, loss64, {name: grad64}) of the twin; kind 'rec' back-propagates a fixed random G from x_rec, 'loss' the loss."""
+    c, _, _, x, mask = _inputs(name)
+    prm = _twin_params(name)
+    if kind == "loss":
+        with torch.no_grad():
+            prm["decoder.0.bias"] += LOSS_BIAS_SHIFT
+    loss, rec, _ = _twin(name, prm, x, mask)
+    if kind == "rec":
+        rec.backward(_upstream(rec.shape))
+    else:
+        loss.sum().backward()
+    return rec.detach(), float(loss.detach()), {k: v.grad.clone() for k, v in prm.items()}
+
+
+def _upstream(shape):
+    g = torch.Generator().manual_seed(5)
+    return torch.randn(shape, generator=g, dtype=torch.float64)
+
+
+def _rel(a, ref):
+    return float((a.detach().double().cpu() - ref).abs().max() / ref.abs().max().clamp_min(1e-30))
+
+
+def _check_grads(mim, ref, tol, skip=()):
+    errs = {}
+    for n, p in mim.named_parameters():
+        if n in skip:
+            assert p.grad is None, n
+            continue
+        assert p.grad is not None, n
+        errs[n] = _rel(p.grad, ref[n])
+    worst = max(errs, key=errs.get)
+    assert errs[worst] <= tol, f"{worst}: {errs[worst]:.3e} > {tol:.0e}"
+    return errs
+
+
+@pytest.mark.parametrize("precision", ["fp32", "bf16x3", "bf16"])
+@pytest.mark.parametrize("name", sorted(GEOMS))
+def test_xrec_backward_matches_float64(dev, name, precision):
+    mim, x, mask = _model(name, precision, dev)
+    loss, rec, _ = mim(x, mask)
+    assert rec.grad_fn is not None and loss.grad_fn is not None
+    rec64, _, ref = _reference(name, "rec")
+    assert _rel(rec, rec64) <= FWD_TOL[precision]
+    rec.backward(_upstream(rec.shape).to(device=dev, dtype=torch.float32))
+    _check_grads(mim, ref, TOL[precision])
+
+
+@pytest.mark.parametrize("precision", ["fp32", "bf16x3", "bf16"])
+@pytest.mark.parametrize("name", ["wrap_mim_hd128", "wrap_p8_64"])
+def test_loss_backward_matches_float64(dev, name, precision):
+    """mim.py's train_one_epoch: loss.sum().backward(). The L1 sign is stable: with the decoder bias moved by LOSS_BIAS_SHIFT,
+    every masked pixel's |x - x_rec64| exceeds the forward error bound."""
+    mim, x, mask = _model(name, precision, dev)
+    with torch.no_grad():
+        mim.decoder[0].bias += LOSS_BIAS_SHIFT
+    loss, rec, pm = mim(x, mask)
+    rec64, loss64, ref = _reference(name, "loss")
+    bound = FWD_TOL[precision] * float(rec64.abs().max())
+    m = pm.cpu().expand_as(rec64).bool()
+    gap = float((x.cpu().double() - rec64).abs()[m].min())
+    assert gap > bound, f"an L1 sign is within the forward error ({gap:.2e} <= {bound:.2e})"
+    assert abs(float(loss.detach()) - loss64) <= FWD_TOL[precision] * max(1.0, abs(loss64))
+    loss.sum().backward()
+    _check_grads(mim, ref, TOL[precision])
+
+
+def test_frozen_subsets_and_accumulation(dev):
+    name, precision = "wrap_mim_hd128", "bf16x3"
+    _, _, ref = _reference(name, "rec")
+    # encoder frozen, decoder trainable: only the decoder gets gradients
+    mim, x, mask = _model(name, precision, dev)
+    for p in mim.encoder.parameters():
+        p.requires_grad_(False)
+    _, rec, _ = mim(x, mask)
+    rec.backward(_upstream(rec.shape).to(device=dev, dtype=torch.float32))
+    enc_names = {n for n, _ in mim.named_parameters() if n.startswith("encoder.")}
+    _check_grads(mim, ref, TOL[precision], skip=enc_names)
+    # mask_token frozen
+    mim, x, mask = _model(name, precision, dev)
+    mim.encoder.mask_token.requires_grad_(False)
+    _, rec, _ = mim(x, mask)
+    rec.backward(_upstream(rec.shape).to(device=dev, dtype=torch.float32))
+    _check_grads(mim, ref, TOL[precision], skip={"encoder.mask_token"})
+    # two backward calls accumulate (the same bits twice: the sum is exactly 2 g)
+    mim, x, mask = _model(name, precision, dev)
+    G = _upstream(mim(x, mask)[1].shape).to(device=dev, dtype=torch.float32)
+    mim(x, mask)[1].backward(G)
+    first = {n: p.grad.clone() for n, p in mim.named_parameters()}
+    mim(x, mask)[1].backward(G)
+    for n, p in mim.named_parameters():
+        assert torch.equal(p.grad, first[n] + first[n]), n
+
+
+def test_unchanged_paths_have_no_graph(dev):
+    mim, x, mask = _model("wrap_p8_64", "bf16x3", dev)
+    mim.eval()
+    loss, rec, _ = mim(x, mask)
+    assert rec.grad_fn is None
+    mim.train()
+    with torch.no_grad():
+        assert mim(x, mask)[1].grad_fn is None
+    for p in mim.parameters():
+        p.requires_grad_(False)
+    assert mim(x, mask)[1].grad_fn is None
+
+
+@pytest.mark.parametrize("precision", ["fp32", "bf16x3"])
+def test_adamw_steps_track_float64_twin(dev, precision):
+    """Three AdamW steps against the float64 twin.
+    - Step 1 moves each weight by -lr * g / (|g| + eps) (plus the decay): wherever |g64| is well above round-off the product's
+      move must equal the twin's, so a gradient with a wrong sign or a missing gradient fails.
+    - Every forward after a step agrees with the twin's, and the twin's output moves by several times that tolerance from
+      step to step, so a forward that still ran the previous weights (no re-pack after optimizer.step()) fails.
+    - The eval-mode forward afterwards agrees with the twin.
+    lr 1e-3 moves x_rec by more than its own size per step on these weights, so the comparison is far from blind. Adam divides by
+    sqrt(v) + eps, which turns a gradient element at round-off level into a move of +-lr whose sign is noise; over three such
+    steps the two runs can part (measured: 1e-2 with the default eps in split-bf16). eps is set per precision above the gradient
+    error so that those elements move by a negligible amount instead (measured after three steps: fp32 6e-6, bf16x3 9e-5)."""
+    name = "wrap_mim_hd128"
+    eps = {"fp32": 1e-5, "bf16x3": 1e-6}[precision]
+    mim, x, mask = _model(name, precision, dev)
+    prm = _twin_params(name)
+    named = dict(mim.named_parameters())
+    lr = 1e-3
+    opt = torch.optim.AdamW([named[n] for n in prm], lr=lr, weight_decay=0.05, eps=eps)
+    opt64 = torch.optim.AdamW(list(prm.values()), lr=lr, weight_decay=0.05, eps=eps)
+    tol = 5 * FWD_TOL[precision]
+    prev64 = None
+    for step in range(1, 4):
+        opt.zero_grad()
+        opt64.zero_grad()
+        loss, rec, _ = mim(x, mask)
+        loss64, rec64, _ = _twin(name, prm, x.cpu(), mask)
+        assert _rel(rec, rec64.detach()) <= tol, step
+        if prev64 is not None:
+            assert _rel(prev64, rec64.detach()) >= 5 * tol, f"step {step}: the twin barely moved; the check sees no re-pack"
+        prev64 = rec64.detach()
+        assert abs(float(loss.detach()) - float(loss64.detach())) <= tol * max(1.0, abs(float(loss64.detach())))
+        loss.backward()
+        loss64.backward()
+        if step == 1:
+            before = {n: named[n].detach().double().cpu().clone() for n in prm}
+            before64 = {n: p.detach().clone() for n, p in prm.items()}
+            g64 = {n: p.grad.detach().clone() for n, p in prm.items()}
+        opt.step()
+        opt64.step()
+        if step == 1:
+            checked = 0
+            for n, p in prm.items():
+                d = named[n].detach().double().cpu() - before[n]
+                d64 = p.detach() - before64[n]
+                sure = g64[n].abs() >= max(1e-2 * float(g64[n].abs().max()), 10 * eps)  # |g| well above round-off and eps
+                checked += int(sure.sum())
+                if sure.any():
+                    err = float((d - d64).abs()[sure].max())
+                    assert err <= 0.05 * lr, (n, err)
+            assert checked > 0.1 * sum(p.numel() for p in prm.values())
+    mim.eval()
+    _, rec, _ = mim(x, mask)
+    with torch.no_grad():
+        _, rec64, _ = _twin(name, prm, x.cpu(), mask)
+    assert _rel(rec, rec64) <= tol
+
+
+def test_training_refuses_before_any_launch(dev):
+    mim, x, mask = _model("wrap_p8_64", "bf16x3", dev)
+    with pytest.raises(NotImplementedError, match="gradient of the input"):
+        mim(x.clone().requires_grad_(True), mask)
+
+
+def test_saved_activations_follow_autograd_rules(dev):
+    """The encoder keeps its activations through save_for_backward: a second backward over the same graph raises (they are freed
+    after the first), and so does a backward after a parameter was modified in place since the forward."""
+    mim, x, mask = _model("wrap_p8_64", "bf16x3", dev)
+    loss, _, _ = mim(x, mask)
+    loss.backward()
+    with pytest.raises(RuntimeError, match="backward through the graph a second time"):
+        loss.backward()
+    loss, _, _ = mim(x, mask)
+    with torch.no_grad():
+        mim.encoder.blocks[0].attn.qkv.weight.mul_(1.5)
+    with pytest.raises(RuntimeError, match="modified by an inplace operation"):
+        loss.backward()

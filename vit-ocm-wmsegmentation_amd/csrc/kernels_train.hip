@@ -6,6 +6,12 @@
 //                                        gradients, batch mean and (two-pass) variance, the ReLU + BatchNorm backward sums
 //   bn_relu_bwd_kernel                   dy = g (u - mean(u) - xhat mean(u xhat)), u = dz [y g + h > 0]
 //   pixel_shuffle_bwd_kernel             gather (B, c, H, W) -> (B*hp*wp, s*s*c), the exact inverse of pixel_shuffle_kernel
+// and the pieces of the ViT encoder backward (SimMIM pre-training) other than the attention (kernels_train_attn.hip):
+//   ln_bwd_kernel                        LayerNorm backward per row (two-pass statistics recomputed from x), + residual gradient
+//   chan_reduce_kernel<3>                dgamma / dbeta of the LayerNorm as fixed-order column sums
+//   gelu_kernel / gelu_bwd_kernel        erf GELU of the fp32 fc1 pre-activation (fc2's operand) and its backward
+//   patch_unfold_kernel                  image -> [B*P][C*p*p] rows of the patch-embedding weight gradient
+//   patch_grad_kernel / token_sum_kernel the mask blend's split of the token gradient, and the batch sum (cls / pos gradients)
 // The forward's BatchNorm-affine + ReLU operand writer is the AFFINE variant of im2col3x3_kernel (kernels_misc.hip).
 #include "host_common.h"
 #include "launch.h"
@@ -197,6 +203,7 @@ WgradPlan wgrad_plan(int M, int N, int K) {
 // the R partials of a channel in chunk order. Fixed order everywhere: the same bits on every run.
 //   MODE 0: sum x                           MODE 1: sum (x - mean)^2  (the second pass of the variance)
 //   MODE 2: sum u and sum u * xhat with u = dz [fma(y, g, h) > 0], xhat = (y - mean) * invstd
+//   MODE 3: sum a and sum a * xhat with xhat = (y - mean[m]) * invstd[m]: per-ROW statistics (LayerNorm), `mean` = [rows][2]
 int chan_chunks(int64_t rows) { return (int)std::min<int64_t>((rows + 255) / 256, 128); }
 
 template <int MODE>
@@ -210,7 +217,7 @@ __global__ __launch_bounds__(256) void chan_reduce_kernel(const float *__restric
     const int64_t r0 = (int64_t)blockIdx.y * chunk, r1 = std::min<int64_t>(rows, r0 + chunk);
     float s0 = 0.f, s1 = 0.f;
     if (c < C) {
-        const float mu = MODE ? mean[c] : 0.f;
+        const float mu = (MODE == 1 || MODE == 2) ? mean[c] : 0.f;
         const float is = MODE == 2 ? invstd[c] : 0.f, g = MODE == 2 ? scale[c] : 0.f, hh = MODE == 2 ? shift[c] : 0.f;
         for (int64_t m = r0 + rg; m < r1; m += 4) {
             const float v = a[m * C + c];
@@ -219,6 +226,10 @@ __global__ __launch_bounds__(256) void chan_reduce_kernel(const float *__restric
             } else if (MODE == 1) {
                 const float d = v - mu;
                 s0 = fmaf(d, d, s0);
+            } else if (MODE == 3) {
+                const float xh = (y[m * C + c] - mean[2 * m]) * mean[2 * m + 1];
+                s0 += v;
+                s1 = fmaf(v, xh, s1);
             } else {
                 const float yv = y[m * C + c];
                 const float u = fmaf(yv, g, hh) > 0.f ? v : 0.f;
@@ -232,7 +243,7 @@ __global__ __launch_bounds__(256) void chan_reduce_kernel(const float *__restric
     __syncthreads();
     if (rg == 0 && c < C) {
         part[(size_t)blockIdx.y * C + c] = ((red[0][0][tc] + red[0][1][tc]) + red[0][2][tc]) + red[0][3][tc];
-        if (MODE == 2)
+        if (MODE >= 2)
             part[((size_t)R + blockIdx.y) * C + c] = ((red[1][0][tc] + red[1][1][tc]) + red[1][2][tc]) + red[1][3][tc];
     }
 }
@@ -297,6 +308,129 @@ __global__ __launch_bounds__(256) void pixel_shuffle_bwd_kernel(const float *__r
         const int y = (int)(r2 % hp), b = (int)(r2 / hp);
         const int jj = o % sh, ii = (o / sh) % sh, c = o / (sh * sh);
         lin[i] = gout[(((size_t)b * c_out + c) * Hs + y * sh + ii) * Ws + x * sh + jj];
+    }
+}
+
+// ---- LayerNorm backward, per row: one wave per row, statistics recomputed in two passes from x (a row whose mean is large
+// against its spread loses nothing to cancellation), the wave's partial sums combined by a fixed butterfly.
+//   xhat = (x - mu) rstd,  dx = rstd (g dy - mean(g dy) - xhat mean(g dy xhat)) + dres
+// stats[row] = (mu, rstd) for the column sums of dgamma / dbeta (chan_reduce_kernel<3>).
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+    return v;
+}
+
+__global__ __launch_bounds__(256) void ln_bwd_kernel(const float *__restrict__ dy, const float *__restrict__ x,
+                                                     const float *__restrict__ gamma, const float *dres, float *dx,
+                                                     float *__restrict__ stats, int64_t rows, int dim, float eps) {
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const float *xr = x + row * dim, *gr = dy + row * dim;
+    float s = 0.f;
+    for (int c = lane; c < dim; c += 64) s += xr[c];
+    const float mu = wave_sum(s) / dim;
+    float v = 0.f;
+    for (int c = lane; c < dim; c += 64) {
+        const float d = xr[c] - mu;
+        v = fmaf(d, d, v);
+    }
+    const float rstd = 1.0f / sqrtf(wave_sum(v) / dim + eps);
+    float a = 0.f, bsum = 0.f;
+    for (int c = lane; c < dim; c += 64) {
+        const float g = gr[c] * gamma[c];
+        a += g;
+        bsum = fmaf(g, (xr[c] - mu) * rstd, bsum);
+    }
+    a = wave_sum(a) / dim;
+    bsum = wave_sum(bsum) / dim;
+    for (int c = lane; c < dim; c += 64) {
+        const float xh = (xr[c] - mu) * rstd;
+        float o = rstd * (gr[c] * gamma[c] - a - xh * bsum);
+        if (dres) o += dres[row * dim + c];
+        dx[row * dim + c] = o;
+    }
+    if (lane == 0) {
+        stats[2 * row] = mu;
+        stats[2 * row + 1] = rstd;
+    }
+}
+
+// ---- erf GELU (nn.GELU(), dino/vision_transformer.py:53) of the fp32 fc1 pre-activation: fc2's operand in the operand type of
+// the precision (E 0 bf16, 1 fp32, 2 split pairs: element i of a row-structured tensor at sp_off of its index), optionally fp32.
+template <int E>
+__global__ __launch_bounds__(256) void gelu_kernel(const float *__restrict__ hin, void *__restrict__ out,
+                                                   float *__restrict__ out32, size_t count) {
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < count; i += (size_t)gridDim.x * 256) {
+        const float g = gelu_erf(hin[i]);
+        if (out32) out32[i] = g;
+        if (E == 0) {
+            ((bf16 *)out)[i] = (bf16)g;
+        } else if (E == 1) {
+            ((float *)out)[i] = g;
+        } else {
+            bf16 hi, lo;
+            split1(g, hi, lo);
+            char *p = (char *)out + (i >> 5) * 128 + (i & 31) * 2;
+            *(bf16 *)p = hi;
+            *(bf16 *)(p + 64) = lo;
+        }
+    }
+}
+
+// dh = dg * gelu'(h), gelu'(h) = Phi(h) + h phi(h); optionally g = gelu(h) in fp32 (fc2's weight-gradient input)
+__global__ __launch_bounds__(256) void gelu_bwd_kernel(const float *dg, const float *__restrict__ hin, float *dh,
+                                                       float *__restrict__ g32, size_t count) {
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < count; i += (size_t)gridDim.x * 256) {
+        const float x = hin[i];
+        const float cdf = 0.5f * (1.0f + erf_as(x * 0.70710678118654752f));
+        const float pdf = 0.3989422804014327f * __builtin_amdgcn_exp2f(-0.7213475204444817f * x * x);  // exp(-x^2/2)/sqrt(2pi)
+        if (g32) g32[i] = x * cdf;
+        dh[i] = dg[i] * fmaf(x, pdf, cdf);
+    }
+}
+
+// ---- patch embedding (Conv2d(C, D, p, stride p)) backward ----
+// cols[b*P + py*wp + px][c*p*p + ky*p + kx] = image[b][c][py*p + ky][px*p + kx]: the K order of the (D, C, p, p) weight
+__global__ __launch_bounds__(256) void patch_unfold_kernel(const float *__restrict__ img, float *__restrict__ cols, int C,
+                                                           int Hh, int Ww, int p, size_t total) {
+    const int hp = Hh / p, wp = Ww / p, K = C * p * p;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+        const int k = (int)(i % K);
+        const size_t row = i / K;
+        const int px = (int)(row % wp);
+        const size_t r2 = row / wp;
+        const int py = (int)(r2 % hp), b = (int)(r2 / hp);
+        const int kx = k % p, ky = (k / p) % p, c = k / (p * p);
+        cols[i] = img[(((size_t)b * C + c) * Hh + py * p + ky) * Ww + px * p + kx];
+    }
+}
+
+// token gradient dT [B][N][D] of t = cat(cls, patch * (1 - w) + mask_token * w) + pos:
+//   dpatch[b*P + p][d] = (1 - w) dT[b][1 + p][d],  wdt[b*P + p][d] = w dT[b][1 + p][d]  (w = 0 without a mask)
+__global__ __launch_bounds__(256) void patch_grad_kernel(const float *__restrict__ dtok, const float *__restrict__ mask,
+                                                         float *__restrict__ dpatch, float *__restrict__ wdt, int N, int D,
+                                                         size_t total) {
+    const int P = N - 1;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+        const int d = (int)(i % D);
+        const size_t bp = i / D;
+        const int b = (int)(bp / P), pp = (int)(bp % P);
+        const float v = dtok[((size_t)b * N + 1 + pp) * D + d];
+        const float w = mask ? mask[bp] : 0.f;
+        dpatch[i] = (1.0f - w) * v;
+        wdt[i] = w * v;
+    }
+}
+
+// out[n][d] = sum_b dT[b][n][d], images in order
+__global__ __launch_bounds__(256) void token_sum_kernel(const float *__restrict__ dtok, float *__restrict__ out, int B,
+                                                        size_t nd) {
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < nd; i += (size_t)gridDim.x * 256) {
+        float s = 0.f;
+        for (int b = 0; b < B; ++b) s += dtok[(size_t)b * nd + i];
+        out[i] = s;
     }
 }
 
@@ -407,6 +541,91 @@ extern "C" int ocm_op_pixel_shuffle_backward(const float *grad_out, float *grad_
     const size_t total = (size_t)batch * hp * wp * c_out * sh * sh;
     pixel_shuffle_bwd_kernel<<<dim3((unsigned)grid_of(total, 8192)), dim3(256), 0, (hipStream_t)stream>>>(
         grad_out, grad_lin, hp, wp, c_out, sh, total);
+    HIP_TRY(hipGetLastError());
+    return OCM_OK;
+}
+
+// ---- C ABI (include/ocm_vit.h, "ViT encoder training") -------------------------------------------------------------------
+extern "C" size_t ocm_layernorm_backward_workspace_bytes(int64_t rows, int32_t dim) {
+    if (rows <= 0 || dim <= 0) return 0;
+    return ocm_channel_reduce_workspace_bytes(rows, dim) + (size_t)2 * rows * sizeof(float);
+}
+
+extern "C" int ocm_op_layernorm_backward(const float *dy, const float *x, const float *gamma, const float *dres, float *dx,
+                                         float *dgamma, float *dbeta, int64_t rows, int32_t dim, float eps, void *workspace,
+                                         size_t workspace_bytes, void *stream) {
+    if (!dy || !x || !gamma || !dx || !dgamma || !dbeta) return fail(OCM_EINVAL, "null argument");
+    if (rows <= 0 || dim <= 0) return fail(OCM_EINVAL, "bad shape rows=%lld dim=%d", (long long)rows, dim);
+    const size_t need = ocm_layernorm_backward_workspace_bytes(rows, dim);
+    if (!workspace || workspace_bytes < need)
+        return fail(OCM_ENOMEM, "layernorm_backward workspace: %zu bytes given, %zu needed", workspace_bytes, need);
+    const hipStream_t s = (hipStream_t)stream;
+    float *stats = (float *)workspace, *part = stats + 2 * rows;
+    ln_bwd_kernel<<<dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s>>>(dy, x, gamma, dres, dx, stats, rows, dim, eps);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(launch_chan_reduce<3>(dy, x, stats, nullptr, nullptr, nullptr, part, dbeta, dgamma, 0.f, rows, dim, s));
+    return OCM_OK;
+}
+
+extern "C" int ocm_op_gelu(int32_t precision, const float *h, void *out, float *out_f32, size_t count, void *stream) {
+    if (int rc = prec_ok(precision)) return rc;
+    if (!h || !out) return fail(OCM_EINVAL, "null argument");
+    if (count == 0 || (precision == OCM_PREC_BF16X3 && count % 32)) return fail(OCM_EINVAL, "bad count %zu", count);
+    const dim3 grid((unsigned)grid_of(count, 8192)), block(256);
+    const hipStream_t s = (hipStream_t)stream;
+    if (precision == OCM_PREC_BF16) gelu_kernel<0><<<grid, block, 0, s>>>(h, out, out_f32, count);
+    else if (precision == OCM_PREC_FP32) gelu_kernel<1><<<grid, block, 0, s>>>(h, out, out_f32, count);
+    else gelu_kernel<2><<<grid, block, 0, s>>>(h, out, out_f32, count);
+    HIP_TRY(hipGetLastError());
+    return OCM_OK;
+}
+
+extern "C" int ocm_op_gelu_backward(const float *dg, const float *h, float *dh, float *g_f32, size_t count, void *stream) {
+    if (!dg || !h || !dh) return fail(OCM_EINVAL, "null argument");
+    if (count == 0) return fail(OCM_EINVAL, "bad count");
+    gelu_bwd_kernel<<<dim3((unsigned)grid_of(count, 8192)), dim3(256), 0, (hipStream_t)stream>>>(dg, h, dh, g_f32, count);
+    HIP_TRY(hipGetLastError());
+    return OCM_OK;
+}
+
+extern "C" int ocm_op_patch_unfold(const float *image, float *cols, int32_t batch, int32_t channels, int32_t height,
+                                   int32_t width, int32_t patch, void *stream) {
+    if (!image || !cols) return fail(OCM_EINVAL, "null argument");
+    if (batch <= 0 || channels <= 0 || patch <= 0 || height <= 0 || width <= 0 || height % patch || width % patch)
+        return fail(OCM_EINVAL, "bad shape batch=%d channels=%d %dx%d patch=%d", batch, channels, height, width, patch);
+    const size_t total = (size_t)batch * (height / patch) * (width / patch) * channels * patch * patch;
+    patch_unfold_kernel<<<dim3((unsigned)grid_of(total, 8192)), dim3(256), 0, (hipStream_t)stream>>>(image, cols, channels,
+                                                                                                    height, width, patch, total);
+    HIP_TRY(hipGetLastError());
+    return OCM_OK;
+}
+
+extern "C" size_t ocm_patch_embed_backward_workspace_bytes(int32_t batch, int32_t n_tokens, int32_t dim) {
+    if (batch <= 0 || n_tokens <= 1 || dim <= 0) return 0;
+    const int64_t rows = (int64_t)batch * (n_tokens - 1);
+    return (size_t)rows * dim * sizeof(float) + ocm_channel_reduce_workspace_bytes(rows, dim);
+}
+
+extern "C" int ocm_op_patch_embed_backward(const float *dtok, const float *mask, float *dpatch, float *dmask_token,
+                                           float *dpos, int32_t batch, int32_t n_tokens, int32_t dim, void *workspace,
+                                           size_t workspace_bytes, void *stream) {
+    if (!dtok || !dpatch || !dpos || (mask && !dmask_token)) return fail(OCM_EINVAL, "null argument");
+    if (batch <= 0 || n_tokens <= 1 || dim <= 0)
+        return fail(OCM_EINVAL, "bad shape batch=%d n_tokens=%d dim=%d", batch, n_tokens, dim);
+    const size_t need = ocm_patch_embed_backward_workspace_bytes(batch, n_tokens, dim);
+    if (!workspace || workspace_bytes < need)
+        return fail(OCM_ENOMEM, "patch_embed_backward workspace: %zu bytes given, %zu needed", workspace_bytes, need);
+    const hipStream_t s = (hipStream_t)stream;
+    const int64_t rows = (int64_t)batch * (n_tokens - 1);
+    const size_t total = (size_t)rows * dim;
+    float *wdt = (float *)workspace, *part = wdt + total;
+    patch_grad_kernel<<<dim3((unsigned)grid_of(total, 8192)), dim3(256), 0, s>>>(dtok, mask, dpatch, wdt, n_tokens, dim, total);
+    HIP_TRY(hipGetLastError());
+    if (mask)
+        HIP_TRY(launch_chan_reduce<0>(wdt, nullptr, nullptr, nullptr, nullptr, nullptr, part, dmask_token, nullptr, 0.f, rows,
+                                      dim, s));
+    const size_t nd = (size_t)n_tokens * dim;
+    token_sum_kernel<<<dim3((unsigned)grid_of(nd, 4096)), dim3(256), 0, s>>>(dtok, dpos, batch, nd);
     HIP_TRY(hipGetLastError());
     return OCM_OK;
 }

@@ -371,11 +371,13 @@ class VisionTransformer(nn.Module):
             self.__dict__["_pos_cache"] = {key: pos}
         return pos
 
-    def _interpolated_pos(self, npatch, w, h):
+    def _interpolated_pos(self, npatch, w, h, pos=None):
         """reference interpolate_pos_encoding (:176-196), evaluated once per tile shape on the host
         (it does not depend on pixel values): identity for the native square grid, otherwise bicubic
-        resampling of the sqrt(N0) x sqrt(N0) grid with the +0.1 scale-factor trick."""
-        pos = self.pos_embed.detach().float().cpu()
+        resampling of the sqrt(N0) x sqrt(N0) grid with the +0.1 scale-factor trick. `pos` (a host copy of pos_embed
+        that requires grad) lets the training path back-propagate through the same resampling."""
+        if pos is None:
+            pos = self.pos_embed.detach().float().cpu()
         n0 = pos.shape[1] - 1
         if npatch == n0 and w == h:
             return pos

@@ -8,12 +8,15 @@
 
 Same constructor arguments, attributes and state_dict keys. The encoders run in one engine call (the mask
 blend is fused into the patch-embedding epilogue, the (B,C,H,W) permute is a device transpose); the 1x1-conv
-decoders run token-major as one MFMA GEMM + a pixel-shuffle kernel. The encoders are inference only. LinearProbing
+decoders run token-major as one MFMA GEMM + a pixel-shuffle kernel. The SimMIM encoder and MIM train: in training mode
+with grad mode on and a parameter that requires grad, the encoder runs as the stand-alone operators under one autograd
+Function (_EncoderTrain) whose backward is HIP (kernels_train.hip, kernels_train_attn.hip). LinearProbing
 also trains: in training mode with a frozen encoder (no encoder parameter requires grad: finetune.py's linear
 probing) its decoder runs with batch statistics and differentiates through HIP kernels (_DecoderTrain). The
 reference initialises mask_token with timm's trunc_normal_; here the package's own trunc_normal_ (dino/utils.py)
 with the same bounds is used.
 """
+import ctypes as C
 import os
 from functools import partial
 
@@ -66,6 +69,12 @@ class VisionTransformerForSimMIM(_FmapEncoder):
 
     def forward(self, x, mask):
         assert mask is not None
+        if _differentiable(self):
+            _check_trainable(self, x, mask=mask)
+            tokens = _encode_train(self, x, mask.to(x.device))
+            B, N, D = tokens.shape
+            side = int((N - 1) ** 0.5)  # model.py:50-52
+            return tokens[:, 1:].transpose(1, 2).reshape(B, D, side, side)
         return self._encode(x, mask=mask.to(x.device))
 
 
@@ -131,12 +140,29 @@ class MIM(nn.Module):
         self.in_chans, self.patch_size = 3, 8
         self.__dict__["_dec_cache"] = {}
 
-    @torch.no_grad()
     def forward(self, x, mask):
+        if _differentiable(self):  # training mode, grad mode on, something to train: the HIP backward (_EncoderTrain)
+            return self._forward(x, mask, train=True)
+        with torch.no_grad():
+            return self._forward(x, mask, train=False)
+
+    def _forward(self, x, mask, train):
+        enc = self.encoder
+        if train:
+            _check_trainable(enc, x, encoder=_differentiable(enc), mask=mask)
         _require_hip(x, "input")
         mask = mask.to(x.device)
-        tokens = self.encoder._encode(x, mask=mask, tokens=True)
-        x_rec = _conv1x1_pixel_shuffle(self.encoder, tokens, self.decoder[0], self.encoder_stride, self._dec_cache)
+        if train and _differentiable(enc):
+            tokens = _encode_train(enc, x, mask)
+        else:
+            with torch.no_grad():
+                tokens = enc._encode(x, mask=mask, tokens=True)
+        if train:
+            conv = self.decoder[0]
+            meta = {"enc": enc, "conv": conv, "stride": self.encoder_stride, "cache": self._dec_cache}
+            x_rec = _MIMHeadTrain.apply(meta, tokens, conv.weight, conv.bias)
+        else:
+            x_rec = _conv1x1_pixel_shuffle(enc, tokens, self.decoder[0], self.encoder_stride, self._dec_cache)
         # masked L1 reconstruction loss (model.py:71-73) — training bookkeeping, a handful of elementwise torch ops
         p = self.patch_size
         m32 = mask.to(torch.float32).contiguous()
@@ -448,6 +474,331 @@ def _update_running_stats(bn, mean, var, n):
     unbiased = var * (n / (n - 1))
     rm.mul_(1.0 - f).add_(mean.to(device=rm.device, dtype=rm.dtype), alpha=f)
     rv.mul_(1.0 - f).add_(unbiased.to(device=rv.device, dtype=rv.dtype), alpha=f)
+
+
+# ---- SimMIM pre-training (mim.py): the encoder forward as the stand-alone operators, keeping what the backward needs, and the
+# backward through kernels_train.hip / kernels_train_attn.hip. Token-major rows m = b*N + n, T = B*N. ----
+_LN_KIND = {_lib.OCM_PREC_BF16: _lib.OCM_LN_BF16, _lib.OCM_PREC_FP32: _lib.OCM_LN_F32, _lib.OCM_PREC_BF16X3: _lib.OCM_LN_SPLIT}
+
+
+def _differentiable(module):
+    """The training path runs when the module is in training mode, grad mode is on and a parameter requires grad."""
+    return module.training and torch.is_grad_enabled() and any(p.requires_grad for p in module.parameters())
+
+
+def _check_mask(enc, x, mask):
+    """The SimMIM mask must hold one entry per patch of every image (the kernels read B * P of them), as the eval path's
+    Engine.forward_tiles requires."""
+    p = enc.patch_embed.patch_size
+    B, npatch = x.shape[0], (x.shape[-2] // p) * (x.shape[-1] // p)
+    if mask is None or mask.numel() != B * npatch:
+        got = "no mask" if mask is None else f"mask has {mask.numel() / max(B, 1):g} entries per image"
+        raise ValueError(f"{got}, expected {npatch}")
+
+
+def _check_trainable(enc, x, encoder=True, mask=None):
+    """What the training path refuses, before anything is launched (`encoder`: the encoder itself is to be differentiated)."""
+    hd = enc.embed_dim // enc._hyper["num_heads"]
+    if encoder and hd not in (64, 128):
+        raise NotImplementedError(f"training the encoder needs 64- or 128-wide heads (the attention backward is built for "
+                                  f"those); this one has {hd}-wide heads")
+    if isinstance(x, torch.Tensor) and x.requires_grad:
+        raise NotImplementedError("the training path does not produce the gradient of the input image; pass an input that "
+                                  "does not require grad")
+    if encoder and enc._gray_fold:
+        raise NotImplementedError("the grayscale-folded patch embedding is inference only; disable it for training")
+    if encoder:
+        _check_mask(enc, x, mask)
+
+
+def _encoder_params(enc):
+    """(name, parameter) of everything the encoder's training path differentiates, in a fixed order."""
+    names = ["cls_token", "pos_embed", "mask_token", "patch_embed.proj.weight", "patch_embed.proj.bias"]
+    for i in range(len(enc.blocks)):
+        names += [f"blocks.{i}.{m}.{t}" for m in ("norm1", "attn.qkv", "attn.proj", "norm2", "mlp.fc1", "mlp.fc2")
+                  for t in ("weight", "bias")]
+    names += ["norm.weight", "norm.bias"]
+    out = []
+    for n in names:
+        prefix, _, key = n.rpartition(".")
+        mod = enc.get_submodule(prefix) if prefix else enc
+        p = mod._parameters.get(key)
+        if p is not None:
+            out.append((n, p))
+    return out
+
+
+def _encode_train(enc, x, mask):
+    """Differentiable VisionTransformerForSimMIM token path: (B, N, D) normed tokens with a graph into the encoder's parameters."""
+    x = enc._check_input(x).contiguous()
+    _check_mask(enc, x, mask)
+    eng = enc._engine(x.device)
+    npatch = (x.shape[-2] // eng.p) * (x.shape[-1] // eng.p)
+    side = enc.img_size[0]
+    if side == 224 and npatch != enc.pos_embed.shape[1] - 1:
+        raise RuntimeError(f"The size of tensor a ({npatch + 1}) must match the size of tensor b ({enc.pos_embed.shape[1]}) "
+                           "at non-singleton dimension 1")
+    pos = enc._pos_for(npatch, side, side, x.device)
+    named = _encoder_params(enc)
+    meta = {"enc": enc, "eng": eng, "names": [n for n, _ in named], "pos": pos, "side": side, "npatch": npatch,
+            "mask": mask.reshape(x.shape[0], -1).to(torch.float32).contiguous() if mask is not None else None}
+    with torch.cuda.device(x.device):
+        return _EncoderTrain.apply(meta, x, *[p for _, p in named])
+
+
+def _vec(t, n, dev):
+    return t.detach().to(device=dev, dtype=torch.float32).contiguous() if t is not None else torch.zeros(n, device=dev)
+
+
+def _ln(lib, x, w, b, kind, rows, dim, eps, dtype):
+    y = torch.empty((rows, dim), dtype=dtype, device=x.device)
+    _lib.check(lib.ocm_op_layernorm(_p(x), _p(w), _p(b), _p(y), kind, rows, dim, eps, _stream()))
+    return y
+
+
+def _ln_backward(lib, dy, x, w, dres, rows, dim, eps):
+    """(dx, dgamma, dbeta) of a LayerNorm, dres (the residual branch's gradient) added into dx."""
+    f32 = dict(device=dy.device, dtype=torch.float32)
+    dx, dg, db = torch.empty((rows, dim), **f32), torch.empty(dim, **f32), torch.empty(dim, **f32)
+    nbytes = lib.ocm_layernorm_backward_workspace_bytes(rows, dim)
+    ws = _ws(nbytes, dy.device)
+    _lib.check(lib.ocm_op_layernorm_backward(_p(dy), _p(x), _p(w), _p(dres), _p(dx), _p(dg), _p(db), rows, dim, eps, _p(ws),
+                                             nbytes, _stream()))
+    return dx, dg, db
+
+
+def _linear(lib, prec, a_op, w_op, bias, resid, M, N, K, epi=_lib.OCM_EPI_BIAS_F32):
+    out = torch.empty((M, N), dtype=torch.float32, device=bias.device)
+    _lib.check(lib.ocm_op_linear(prec, _p(a_op), _p(w_op), _p(bias), _p(resid), _p(out), M, N, K, epi, _stream()))
+    return out
+
+
+class _EncoderTrain(torch.autograd.Function):
+    """The SimMIM encoder in training mode: forward(meta, x, *params) -> normed tokens (B, N, D); backward -> parameter
+    gradients. Per block it keeps the block input (norm1's input), qkv_f32, lse2, the context in the operand type, norm2's input
+    and the fp32 fc1 pre-activation: (5 + mlp_ratio) * N * D * 4 bytes per image plus the context (2 or 4 bytes per element)
+    — 35 MB per block per image at 384^2, D = 384. The LayerNorm outputs are recomputed in fp32."""
+
+    @staticmethod
+    def forward(ctx, meta, x, *params):
+        enc, eng = meta["enc"], meta["eng"]
+        lib, dev = _lib.load(), x.device
+        prec = _lib.PRECISIONS[enc._precision]
+        P = dict(zip(meta["names"], params))
+        B, _, Hpx, Wpx = x.shape
+        N, D, H, L = eng.n_tokens(Hpx, Wpx), eng.D, eng.H, eng.L
+        hd, T, eps = D // H, B * N, float(enc.norm.eps)
+        Mh = enc.blocks[0].mlp.fc1.out_features if L else 4 * D
+        f32 = dict(device=dev, dtype=torch.float32)
+        adt = _OPERAND_DTYPE[prec]
+        kind = _LN_KIND[prec]
+        cache = enc.__dict__.setdefault("_train_cache", {})
+
+        def op(name):
+            w = P[name]
+            return _cached_operand(cache, name, w, prec, lambda: to_operand(w.detach().to(**f32), prec))
+
+        io = eng._io(x, (x.stride(0), x.stride(1), x.stride(2)), None, B, Hpx, Wpx, meta["pos"])
+        if meta["mask"] is not None:
+            io.patch_mask = meta["mask"].data_ptr()
+        t = torch.empty((T, D), **f32)
+        _lib.check(lib.ocm_vit_prepare_tokens(eng._h, C.byref(io), _p(t)))
+        npad = lib.ocm_n_pad_prec(prec, N)
+        saved = []
+        for i, blk in enumerate(enc.blocks):
+            pre = f"blocks.{i}."
+            xn = _ln(lib, t, P[pre + "norm1.weight"], _vec(P.get(pre + "norm1.bias"), D, dev), kind, T, D, eps, adt)
+            q = torch.empty((B * H, npad, hd), dtype=adt, device=dev)
+            k = torch.empty_like(q)
+            vt = torch.zeros((B * H, hd, npad), dtype=adt, device=dev)
+            qkv = torch.empty((3, B, H, N, hd), **f32)
+            _lib.check(lib.ocm_op_qkv_proj_hd(prec, _p(xn), _p(op(pre + "attn.qkv.weight")),
+                                              _p(_vec(P.get(pre + "attn.qkv.bias"), 3 * D, dev)), _p(q), _p(k), _p(vt),
+                                              _p(qkv), B, N, H, hd, _stream()))
+            cx = torch.empty((T, D), dtype=adt, device=dev)
+            lse = torch.empty((B * H, N), **f32)
+            _lib.check(lib.ocm_op_attention_hd(prec, _p(q), _p(k), _p(vt), _p(cx), _p(lse), B, N, H, hd,
+                                               float(blk.attn.scale), _stream()))
+            del q, k, vt, xn
+            x1 = _linear(lib, prec, cx, op(pre + "attn.proj.weight"), _vec(P.get(pre + "attn.proj.bias"), D, dev), t, T, D, D,
+                         _lib.OCM_EPI_BIAS_RESID_F32)
+            xn2 = _ln(lib, x1, P[pre + "norm2.weight"], _vec(P.get(pre + "norm2.bias"), D, dev), kind, T, D, eps, adt)
+            hpre = _linear(lib, prec, xn2, op(pre + "mlp.fc1.weight"), _vec(P.get(pre + "mlp.fc1.bias"), Mh, dev), None,
+                           T, Mh, D)
+            del xn2
+            g = torch.empty((T, Mh), dtype=adt, device=dev)
+            _lib.check(lib.ocm_op_gelu(prec, _p(hpre), _p(g), None, T * Mh, _stream()))
+            x2 = _linear(lib, prec, g, op(pre + "mlp.fc2.weight"), _vec(P.get(pre + "mlp.fc2.bias"), D, dev), x1, T, D, Mh,
+                         _lib.OCM_EPI_BIAS_RESID_F32)
+            del g
+            saved.append((t, qkv, lse, cx, x1, hpre))
+            t = x2
+        out = _ln(lib, t, P["norm.weight"], _vec(P.get("norm.bias"), D, dev), _lib.OCM_LN_F32, T, D, eps, torch.float32)
+        # through save_for_backward: autograd frees them after the backward, refuses a second backward over the same graph
+        # and raises if a parameter is modified in place between this forward and the backward
+        ctx.meta, ctx.nblocks = meta, len(saved)
+        ctx.dims = (B, N, D, H, hd, T, Mh, eps, prec)
+        ctx.save_for_backward(x, t, *[a for blk in saved for a in blk], *params)
+        return out.reshape(B, N, D)
+
+    @staticmethod
+    def backward(ctx, gout):
+        meta = ctx.meta
+        enc, names = meta["enc"], meta["names"]
+        B, N, D, H, hd, T, Mh, eps, prec = ctx.dims
+        need = dict(zip(names, ctx.needs_input_grad[2:]))
+        st = ctx.saved_tensors
+        x, xL, nb = st[0], st[1], ctx.nblocks
+        blocks = [st[2 + 6 * i:8 + 6 * i] for i in range(nb)]
+        params = dict(zip(names, st[2 + 6 * nb:]))
+        lib, dev = _lib.load(), gout.device
+        f32 = dict(device=dev, dtype=torch.float32)
+        cache = enc.__dict__.setdefault("_train_cache", {})
+        grads = {}
+
+        def op_t(name):  # operand copy of W^T: the data gradient dX = dY W runs as ocm_op_linear(dY, W^T)
+            w = params[name]
+            return _cached_operand(cache, name + ".T", w, prec, lambda: to_operand(w.detach().to(**f32).t().contiguous(), prec))
+
+        zeros = {}
+
+        def zero(n):
+            if n not in zeros:
+                zeros[n] = torch.zeros(n, **f32)
+            return zeros[n]
+
+        def wgrad(dy, xin, wname, bname):
+            if need.get(wname) or need.get(bname):
+                dw, db = _weight_grad(prec, dy, xin, bool(need.get(bname)))
+                if need.get(wname):
+                    grads[wname] = dw
+                if need.get(bname):
+                    grads[bname] = db
+
+        def lngrads(pre, dg, db):
+            if need.get(pre + ".weight"):
+                grads[pre + ".weight"] = dg
+            if need.get(pre + ".bias"):
+                grads[pre + ".bias"] = db
+
+        with torch.cuda.device(dev):
+            dT = gout.detach().to(torch.float32).contiguous().reshape(T, D)
+            dx, dg, db = _ln_backward(lib, dT, xL, params["norm.weight"], None, T, D, eps)
+            lngrads("norm", dg, db)
+            for i in reversed(range(len(enc.blocks))):
+                pre = f"blocks.{i}."
+                blk = enc.blocks[i]
+                xin, qkv, lse, cx, x1, hpre = blocks[i]
+                # mlp: x2 = x1 + fc2(gelu(fc1(norm2(x1))))
+                dh = _linear(lib, prec, to_operand(dx, prec), op_t(pre + "mlp.fc2.weight"), zero(Mh), None, T, Mh, D)
+                g32 = torch.empty((T, Mh), **f32)
+                _lib.check(lib.ocm_op_gelu_backward(_p(dh), _p(hpre), _p(dh), _p(g32), T * Mh, _stream()))
+                wgrad(dx, g32, pre + "mlp.fc2.weight", pre + "mlp.fc2.bias")
+                del g32
+                g2w, g2b = params[pre + "norm2.weight"], _vec(params.get(pre + "norm2.bias"), D, dev)
+                if need.get(pre + "mlp.fc1.weight") or need.get(pre + "mlp.fc1.bias"):
+                    xn2 = _ln(lib, x1, g2w, g2b, _lib.OCM_LN_F32, T, D, eps, torch.float32)
+                    wgrad(dh, xn2, pre + "mlp.fc1.weight", pre + "mlp.fc1.bias")
+                    del xn2
+                dxn2 = _linear(lib, prec, to_operand(dh, prec), op_t(pre + "mlp.fc1.weight"), zero(D), None, T, D, Mh)
+                del dh
+                dx1, dg, db = _ln_backward(lib, dxn2, x1, g2w, dx, T, D, eps)
+                lngrads(pre + "norm2", dg, db)
+                del dxn2, dx
+                # attention: x1 = xin + proj(attn(norm1(xin)))
+                dctx = _linear(lib, prec, to_operand(dx1, prec), op_t(pre + "attn.proj.weight"), zero(D), None, T, D, D)
+                delta = torch.empty((B * H, N), **f32)
+                c32 = torch.empty((T, D), **f32)
+                _lib.check(lib.ocm_op_attention_backward_delta(prec, _p(cx), _p(dctx), _p(delta), _p(c32), B, N, H, hd,
+                                                               _stream()))
+                wgrad(dx1, c32, pre + "attn.proj.weight", pre + "attn.proj.bias")
+                del c32
+                dqkv = torch.empty((T, 3 * D), **f32)
+                _lib.check(lib.ocm_op_attention_backward(_p(qkv), _p(lse), _p(dctx), _p(delta), _p(dqkv), B, N, H, hd,
+                                                         float(blk.attn.scale), _stream()))
+                del dctx, delta
+                g1w, g1b = params[pre + "norm1.weight"], _vec(params.get(pre + "norm1.bias"), D, dev)
+                if need.get(pre + "attn.qkv.weight") or need.get(pre + "attn.qkv.bias"):
+                    xn1 = _ln(lib, xin, g1w, g1b, _lib.OCM_LN_F32, T, D, eps, torch.float32)
+                    wgrad(dqkv, xn1, pre + "attn.qkv.weight", pre + "attn.qkv.bias")
+                    del xn1
+                dxn1 = _linear(lib, prec, to_operand(dqkv, prec), op_t(pre + "attn.qkv.weight"), zero(D), None, T, D, 3 * D)
+                del dqkv
+                dx, dg, db = _ln_backward(lib, dxn1, xin, g1w, dx1, T, D, eps)
+                lngrads(pre + "norm1", dg, db)
+                del dxn1, dx1
+            # tokens t = cat(cls, patch * (1 - w) + mask_token * w) + pos
+            mask = meta["mask"]
+            P_ = N - 1
+            dpatch, dmask, dpos = torch.empty((B * P_, D), **f32), torch.empty(D, **f32), torch.empty((N, D), **f32)
+            nbytes = lib.ocm_patch_embed_backward_workspace_bytes(B, N, D)
+            ws = _ws(nbytes, dev)
+            _lib.check(lib.ocm_op_patch_embed_backward(_p(dx), _p(mask), _p(dpatch), _p(dmask), _p(dpos), B, N, D, _p(ws),
+                                                       nbytes, _stream()))
+            if need.get("mask_token") and mask is not None:
+                grads["mask_token"] = dmask
+            if need.get("cls_token"):
+                grads["cls_token"] = dpos[0]
+            if need.get("patch_embed.proj.weight") or need.get("patch_embed.proj.bias"):
+                Cc, p = x.shape[1], enc.patch_embed.patch_size
+                cols = torch.empty((B * P_, Cc * p * p), **f32)
+                _lib.check(lib.ocm_op_patch_unfold(_p(x), _p(cols), B, Cc, x.shape[2], x.shape[3], p, _stream()))
+                wgrad(dpatch, cols, "patch_embed.proj.weight", "patch_embed.proj.bias")
+                del cols
+            if need.get("pos_embed"):
+                # back through the host-side bicubic resampling of _interpolated_pos, with torch autograd on the small table
+                pe = params["pos_embed"].detach().float().cpu().requires_grad_(True)
+                with torch.enable_grad():
+                    full = enc._interpolated_pos(meta["npatch"], meta["side"], meta["side"], pos=pe)
+                    (gpe,) = torch.autograd.grad(full, pe, dpos.cpu().reshape(full.shape))
+                grads["pos_embed"] = gpe
+        out = []
+        for n in names:
+            g = grads.get(n)
+            p = params[n]
+            out.append(None if g is None else g.reshape(p.shape).to(device=p.device, dtype=p.dtype))
+        return (None, None, *out)
+
+
+class _MIMHeadTrain(torch.autograd.Function):
+    """MIM's decoder (Conv2d(D, s*s*3, 1) + PixelShuffle) in training mode: forward as the eval path computes it; backward ->
+    the weight / bias gradients and, when the tokens carry a graph, their gradient (the CLS row gets zero)."""
+
+    @staticmethod
+    def forward(ctx, meta, tokens, weight, bias):
+        enc, conv, s = meta["enc"], meta["conv"], meta["stride"]
+        out = _conv1x1_pixel_shuffle(enc, tokens.detach(), conv, s, meta["cache"])
+        ctx.meta = meta
+        ctx.save_for_backward(tokens.detach(), weight)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        meta = ctx.meta
+        tokens, weight = ctx.saved_tensors
+        enc, conv, s = meta["enc"], meta["conv"], meta["stride"]
+        B, N, D = tokens.shape
+        hp = wp = int((N - 1) ** 0.5)
+        M, O = B * (N - 1), conv.out_channels
+        prec = _lib.PRECISIONS[enc._precision]
+        lib, dev = _lib.load(), tokens.device
+        f32 = dict(device=dev, dtype=torch.float32)
+        need_t, need_w, need_b = ctx.needs_input_grad[1], ctx.needs_input_grad[2], ctx.needs_input_grad[3]
+        dtok = dw = db = None
+        with torch.cuda.device(dev):
+            dlin = _pixel_shuffle_backward(grad_out, M, s, hp, wp)  # (M, O)
+            if need_w or need_b:
+                dw, db = _weight_grad(prec, dlin, tokens[:, 1:].reshape(M, D), need_b)
+                dw = dw.reshape(conv.weight.shape).to(conv.weight.dtype) if need_w else None
+                db = db.to(conv.bias.dtype) if need_b else None
+            if need_t:
+                cache = meta["cache"].setdefault("train", {})
+                wt = _cached_operand(cache, "w_dec_t", weight, prec,
+                                     lambda: to_operand(weight.detach().reshape(O, D).t().to(**f32).contiguous(), prec))
+                dp = _linear(lib, prec, to_operand(dlin, prec), wt, torch.zeros(D, **f32), None, M, D, O)
+                dtok = torch.zeros((B, N, D), **f32)
+                dtok[:, 1:] = dp.reshape(B, N - 1, D)
+        return None, dtok, dw, db
 
 
 def build_model(args):

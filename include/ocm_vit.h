@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define OCM_ABI_VERSION 12
+#define OCM_ABI_VERSION 13
 
 enum {
     OCM_OK = 0,
@@ -468,6 +468,34 @@ size_t ocm_patch_embed_backward_workspace_bytes(int32_t batch, int32_t n_tokens,
 int ocm_op_patch_embed_backward(const float *dtok, const float *mask, float *dpatch, float *dmask_token, float *dpos,
                                 int32_t batch, int32_t n_tokens, int32_t dim, void *workspace, size_t workspace_bytes,
                                 void *stream);
+
+/* ---- k-means feature clustering (eval.py --method k-means_feature_clustering, utils.py:171-197; kernels_cluster.hip) ----
+ * X is the fp32 [S*S][dim] feature matrix, row y*S + x; dim % 4 == 0 and 4 <= dim <= 1024. Every reduction runs in a fixed
+ * order (no atomics): the same inputs give the same bits. Null pointers, S < 1 or a bad dim return OCM_EINVAL. */
+/* X = keys of the patch tokens of `image` in qkv (3, batch, heads, n_tokens, head_dim) fp32, channel order (head, hd),
+ * bilinearly upsampled from the grid x grid token grid (n_tokens = grid^2 + 1, CLS first) to S x S with torch's
+ * align_corners=False rule. head_dim % 4 == 0. */
+int ocm_op_kmeans_features(const float *qkv, int32_t batch, int32_t heads, int32_t n_tokens, int32_t head_dim, int32_t image,
+                           int32_t grid, int32_t S, float *X, void *stream);
+/* In place: X = (X - mean) / std (torch.mean / unbiased torch.std per column, in fp32 arithmetic), then X -= X.mean(axis=0)
+ * (sklearn KMeans.fit's centring). Statistics in fp64, two passes. stats [4][dim] fp64: mean, std, the fp32 centring mean
+ * (as fp64; add it back to centres), and the biased variance of the final X per column (sklearn's _tolerance). */
+size_t ocm_kmeans_zscore_workspace_bytes(int32_t S, int32_t dim);
+int ocm_op_kmeans_zscore(float *X, int32_t S, int32_t dim, double *stats, void *workspace, size_t workspace_bytes,
+                         void *stream);
+/* dist [n_cand][S*S] fp64 = ||x - cand[k]||^2 accumulated in fp64; with `closest` [S*S] (or NULL) the running minimum
+ * min(closest, dist) of k-means++. cand [n_cand][dim] fp32, 1 <= n_cand <= 64. */
+int ocm_op_kmeans_dist(const float *X, int32_t S, int32_t dim, const float *cand, int32_t n_cand, const double *closest,
+                       double *dist, void *stream);
+/* One Lloyd step for two clusters: labels[r] = argmin_c ||x_r - centers[c]||^2 (fp64; a tie goes to cluster 0).
+ * Unless assign_only: centers_new [2][dim] = fp32 of the fp64 cluster sums / counts, and sums [2][dim] fp64 (or NULL).
+ * info [7] fp64: inertia sum ||x - centers[label]||^2, count0, count1, ||centers_new - centers||^2 per cluster (0 when
+ * assign_only), 1 when any label differs from labels_old (1 when labels_old is NULL), the number of empty clusters
+ * (centers_new of an empty cluster is 0: the caller treats a non-zero count as an error). */
+size_t ocm_kmeans_lloyd_workspace_bytes(int32_t S, int32_t dim);
+int ocm_op_kmeans_lloyd(const float *X, int32_t S, int32_t dim, const float *centers, const int32_t *labels_old,
+                        int32_t *labels, float *centers_new, double *sums, double *info, int32_t assign_only, void *workspace,
+                        size_t workspace_bytes, void *stream);
 
 /* ---- sliding-window index math (host, integer; sw_processing.py:151-163) ---- */
 /* Number of windows per axis: len(range(0, size - 2*stride, stride)). */

@@ -4,13 +4,15 @@ up resize to the image size -> threshold() masks. The reference runs it one imag
 crop) at a time at B = 1 with the maps going through numpy / scipy / cv2 on the host; here every image and crop of the
 batch goes through ONE forward and only the final masks leave the GPU.
 """
+import numpy as np
 import torch
 
 from . import _lib
 from .engine import _p, _stream
-from .utils import threshold
+from .utils import kmeans_feature_labels, threshold
 
 METHODS = {"ours": 0, "otsu": 1, "heatmap_threshold": 2}  # index into threshold()'s (th, th2, th3)
+KMEANS_FEATURE = "k-means_feature_clustering"
 
 
 def _head_mean_small(model, tiles, median_filter):
@@ -76,14 +78,45 @@ def tile_crops_image(images):
 def segment_images(model, images, method="ours", median_filter=1, as_numpy=False):
     """The mask eval.py scores for `method` in {"ours", "otsu", "heatmap_threshold"} for every image of a batch
     ((B,C,S,S), or (B,crops,C,s,s) for --crop 4 / 16), with --median_filter `median_filter`.
+    With method "k-means_feature_clustering" (eval.py:185-202, (B,C,S,S) only) the mask is kmeans_feature's clustering
+    of the last block's keys, upsampled to S x S, image by image (see kmeans_segment).
     Returns (masks (B,S,S) uint8 in {0,255}, average_attentions (B,S,S) fp32)."""
-    if method not in METHODS:
+    if method not in METHODS and method != KMEANS_FEATURE:
         raise ValueError(f"method {method!r} is not on this path (k-means / chan-vese stay on the host in the reference)")
     if not 1 <= int(median_filter) <= 15:
         raise ValueError("median_filter must be in 1..15")
+    if method == KMEANS_FEATURE:
+        if images.dim() != 4:
+            raise ValueError("k-means_feature_clustering clusters whole images: the crop path (5-D input) is not supported")
+        masks = kmeans_segment(model, images)
+        maps = average_attention_maps(model, images, median_filter)
+        return (masks.cpu().numpy(), maps.cpu().numpy()) if as_numpy else (masks, maps)
     maps = average_attention_maps(model, images, median_filter)
     gray_src = tile_crops_image(images) if images.dim() == 5 else images
     masks = torch.empty(maps.shape, dtype=torch.uint8, device=maps.device)
     for b in range(images.shape[0]):
         masks[b] = threshold(gray_src[b], maps[b], as_numpy=False)[METHODS[method]]
     return (masks.cpu().numpy(), maps.cpu().numpy()) if as_numpy else (masks, maps)
+
+
+@torch.no_grad()
+def kmeans_segment(model, images):
+    """eval.py:185-202 for every image of a (B,C,S,S) batch: the keys of the last block (qkv of one forward, channel order
+    (head, hd), CLS dropped) bilinearly upsampled to S x S on the device, then utils.kmeans_feature's z-score and
+    KMeans(n_clusters=2, n_init=10, random_state=0), one image at a time as the reference does. The (S*S, D) feature
+    matrix is allocated once and reused across the batch; it never leaves the device. Returns (B,S,S) uint8 {0, 255}."""
+    from .cluster import key_features
+    if images.dim() != 4 or images.shape[-1] != images.shape[-2]:
+        raise ValueError("k-means_feature_clustering needs square (B,C,S,S) images")
+    p = model.patch_embed.patch_size
+    S = images.shape[-1]
+    if images.shape[-2] % p or S % p:
+        raise ValueError(f"image size {tuple(images.shape[-2:])} is not a multiple of the patch size {p}")
+    qkv = model._run(images, flags=_lib.OCM_OUT_QKV, n_last=1)["qkv"][0]  # (3, B, H, N, hd)
+    X = None
+    masks = torch.empty((images.shape[0], S, S), dtype=torch.uint8, device=images.device)
+    for b in range(images.shape[0]):
+        X = key_features(qkv, b, S, out=X)
+        labels = kmeans_feature_labels(X)["labels"]
+        masks[b] = torch.from_numpy((labels.reshape(S, S) * 255).astype(np.uint8)).to(images.device)
+    return masks

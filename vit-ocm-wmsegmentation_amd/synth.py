@@ -224,3 +224,31 @@ def synth_swin_state_dict(cfg, *, seed=0, qk_gain=1.0):
                 t = t * (25.0 * qk_gain)
         sd[name] = t
     return sd
+
+
+# k-means feature clustering fixtures (tests/golden/kmeans_feature.npz, tools/make_golden_kmeans.py): name ->
+# (seed, token grid side g, channels D, pixel side S, two_region). A two-region grid adds one random offset vector to
+# the left half of the tokens: a boundary k-means finds every time.
+KMEANS_CASES = {
+    "g12_d64_s96": (101, 12, 64, 96, False),
+    "g24_d384_s192": (102, 24, 384, 192, False),
+    "two_region": (103, 16, 32, 64, True),
+}
+
+
+def synth_token_grid(seed, g, D, two_region=False):
+    """(g, g, D) fp32 key-like token grid from np.random.RandomState(seed): standard normal tokens, plus 3 x a random
+    normal vector on columns [0, g/2) when two_region."""
+    rs = np.random.RandomState(seed)
+    t = rs.standard_normal((g, g, D)).astype(np.float32)
+    if two_region:
+        t[:, : g // 2] += 3.0 * rs.standard_normal(D).astype(np.float32)
+    return t
+
+
+def upsample_token_grid(grid, S):
+    """eval.py:196-198 on the host: (g, g, D) -> permute -> F.interpolate(size=(S, S), bilinear, align_corners=False)
+    on the CPU -> (1, S, S, D) fp32, the `features` kmeans_feature receives."""
+    import torch.nn.functional as F
+    kt = torch.as_tensor(np.ascontiguousarray(grid))[None].permute(0, 3, 1, 2)
+    return F.interpolate(kt, size=(S, S), mode="bilinear", align_corners=False).permute(0, 2, 3, 1)

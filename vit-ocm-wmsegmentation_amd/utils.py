@@ -5,6 +5,7 @@ region-query index of analyse_attention.py, on device.
   region_query_index  reference analyse_attention.py:192-195, 234-236
   threshold           reference utils.py:55-115 (the three Otsu masks of eval.py's "ours" / "otsu" /
                       "heatmap_threshold" methods), on device
+  kmeans_feature      reference utils.py:171-197 (eval.py's "k-means_feature_clustering"), clustered on device
 """
 import ctypes as C
 
@@ -143,3 +144,41 @@ def threshold(img, attention, output_directory="", save=False, name=None, as_num
             _lib.check(lib.ocm_op_threshold_u8(_p(src), _p(masks[k]), n, levels[k], st))
     out = tuple(m.cpu().numpy() for m in masks) if as_numpy else tuple(masks)
     return (out + (levels,)) if return_levels else out
+
+
+def kmeans_feature_labels(X):
+    """KMeans(n_clusters=2, n_init=10, random_state=0).fit of the z-scored rows of X, a contiguous fp32 (S*S, D) device
+    tensor that is standardised IN PLACE (cluster.fit_two_means on the device backend). Returns the fit's dict."""
+    from . import cluster
+    return cluster.fit_two_means(cluster.DeviceBackend(X))
+
+
+def kmeans_feature(img, features, output_directory="", save=False, name=None):
+    """utils.py:171-197: z-score every channel of `features` (torch.mean / unbiased torch.std), cluster the rows with
+    sklearn's KMeans(n_clusters=2, n_init=10, random_state=0) — replayed on the device by cluster.py — and return the
+    labels times 255 as an int32 numpy array (S, S). features: the (1, S, S, D) map eval.py passes (any leading shape
+    whose rows are the S*S pixels), on the device or on the host (then it goes to img's device, or the current one); it
+    is not modified. img only picks the device: the reference does not use it either.
+    The reference reshapes the labels with features.shape[-1] (the channel count), which works only when D == S; here the
+    side is S = sqrt(rows). Saving a figure (save=True) is the reference's matplotlib side effect: not on this path."""
+    if save:
+        raise NotImplementedError("kmeans_feature(save=True) writes a figure with matplotlib in the reference; "
+                                  "not on this path")
+    if not isinstance(features, torch.Tensor):
+        features = torch.as_tensor(np.asarray(features))
+    D = features.shape[-1]
+    rows = features.numel() // max(D, 1)
+    S = int(round(rows ** 0.5))
+    if S * S != rows:
+        raise ValueError(f"features hold {rows} rows: not a square S x S pixel grid")
+    if features.is_cuda:
+        dev = features.device
+    elif isinstance(img, torch.Tensor) and img.is_cuda:
+        dev = img.device
+    elif torch.cuda.is_available():
+        dev = torch.device("cuda", torch.cuda.current_device())
+    else:
+        _require_hip(features, "features")  # there is no host k-means: the features need a device to go to
+    X = features.reshape(rows, D).to(device=dev, dtype=torch.float32, copy=True).contiguous()
+    labels = kmeans_feature_labels(X)["labels"]
+    return labels.reshape(S, S) * 255

@@ -107,6 +107,46 @@ int ocm_op_swin_window_attention(int32_t precision, const void *qkv, int32_t ld,
 int ocm_op_swin_merge_ln(int32_t precision, const float *x, const float *gamma, const float *beta, void *y, int32_t batch,
                          int32_t height, int32_t width, int32_t channels, int32_t ldy, void *stream);
 
+/* ---- training (SwinForImageClassification fine-tuning, train.py's Trainer loop; kernels_swin_train.hip) ----
+ * The training forward runs the stand-alone operators (ocm_op_layernorm, ocm_op_linear, ocm_op_swin_window_attention,
+ * ocm_op_gelu, ocm_op_swin_merge_ln); its backward the ViT training operators of ocm_vit.h plus the entry points below.
+ * Gradients are fp32; every sum runs in an order fixed by the shapes, without atomics, so reruns give the same bits.
+ * Null pointers and bad shapes return OCM_EINVAL. */
+
+/* Backward of ocm_op_swin_window_attention for 32-wide heads and windows of 2 to 7: qkv (B*H*W, 3 * 32 * heads) fp32 q | k | v
+ * per token in row-major token order, dctx (B*H*W, 32 * heads) fp32, rel_table (2*ws-1)^2 x heads fp32
+ *   -> dqkv (B*H*W, 3 * 32 * heads) fp32 in the q | k | v column order of q_proj / k_proj / v_proj (every element written)
+ *      and dtable (2*ws-1)^2 x heads = the sum over images, windows and position pairs of dS in each relative-position bin.
+ * S = q k^T / sqrt(32) + bias + shift mask (transformers' -100 additive mask) and P = softmax(S) are recomputed in fp32.
+ * One workgroup owns a (window, head) pair; the table gradient is per-window partials plus a fixed-order column sum in the
+ * workspace (ocm_swin_window_attention_backward_workspace_bytes). height and width multiples of window, 0 <= shift < window. */
+size_t ocm_swin_window_attention_backward_workspace_bytes(int32_t batch, int32_t height, int32_t width, int32_t window,
+                                                          int32_t heads);
+int ocm_op_swin_window_attention_backward(const float *qkv, const float *dctx, const float *rel_table, float *dqkv, float *dtable,
+                                          int32_t batch, int32_t height, int32_t width, int32_t window, int32_t shift,
+                                          int32_t heads, void *workspace, size_t workspace_bytes, void *stream);
+
+/* SwinPatchMerging's 2 x 2 gather (modeling_swin.py:309-326) as fp32 rows, even height and width only:
+ * y (batch * height/2 * width/2, 4 * channels) = x0 | x1 | x2 | x3 of x (batch, height, width, channels) fp32 — the merging
+ * LayerNorm's input; and its inverse in gather form, dx (batch, height, width, channels) from dy of y's shape (bit exact). */
+int ocm_op_swin_merge_gather(const float *x, float *y, int32_t batch, int32_t height, int32_t width, int32_t channels,
+                             void *stream);
+int ocm_op_swin_merge_scatter(const float *dy, float *dx, int32_t batch, int32_t height, int32_t width, int32_t channels,
+                              void *stream);
+
+/* The pooled head: pooled (batch, channels) = the token mean of x (batch, tokens, channels) fp32, tokens summed in order;
+ * its backward dx (batch, tokens, channels) = dpooled / tokens broadcast over the tokens. */
+int ocm_op_swin_pool(const float *x, float *pooled, int32_t batch, int32_t tokens, int32_t channels, void *stream);
+int ocm_op_swin_pool_backward(const float *dpooled, float *dx, int32_t batch, int32_t tokens, int32_t channels, void *stream);
+
+/* Stochastic depth on the attention branch (SwinDropPath, modeling_swin.py:567): out = x + branch * scale[image] (out may alias
+ * x), scale = mask / keep_prob per image, all (batch, tokens, channels) fp32 but scale (batch); and the branch's gradient
+ * dbranch = dout * scale[image] (the residual passes dout unchanged). */
+int ocm_op_swin_drop_path(const float *x, const float *branch, const float *scale, float *out, int32_t batch, int32_t tokens,
+                          int32_t channels, void *stream);
+int ocm_op_swin_drop_path_backward(const float *dout, const float *scale, float *dbranch, int32_t batch, int32_t tokens,
+                                   int32_t channels, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

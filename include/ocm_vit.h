@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define OCM_ABI_VERSION 13
+#define OCM_ABI_VERSION 14
 
 enum {
     OCM_OK = 0,

@@ -1,0 +1,90 @@
+"""Time one train.py fine-tuning step of SwinForImageClassification on the HIP path: Swin-T at 224^2, 5 labels, AdamW (lr 5e-5),
+drop_path_rate 0.1. Reports per phase (training forward, which repacks the weights an optimizer step changed; backward; AdamW;
+`step` is their sum) and, as a yardstick, an fp32 eager twin on the same GPU: the oracle's functions (oracle/swin_oracle.py)
+under torch autograd with the same weights, timed in alternation with the HIP step in one process. Also reports the activations
+the training forward keeps per image. The split by kernel class comes from a kernel trace of this tool
+(rocprofv3 --kernel-trace --stats).
+
+  python tools/bench_swin_train.py [--batch 8] [--precision bf16] [--reps 5]
+"""
+import argparse
+import json
+import os
+import socket
+import sys
+import time
+
+import torch
+import torch.nn.functional as F
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import vit_ocm_wmsegmentation_amd  # noqa: E402,F401
+from oracle import swin_oracle as SO  # noqa: E402
+from vit_ocm_wmsegmentation_amd import _lib, synth  # noqa: E402
+from vit_ocm_wmsegmentation_amd import swin as SW  # noqa: E402
+
+
+def _timed(fn):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    out = fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b), out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=8)
+    ap.add_argument("--precision", default="bf16", choices=sorted(_lib.PRECISIONS))
+    ap.add_argument("--reps", type=int, default=5)
+    args = ap.parse_args()
+    dev, B = torch.device("cuda:0"), args.batch
+    cfg = dict(synth.SWIN_TINY)
+    sd = synth.synth_swin_state_dict(cfg, seed=3)
+    m = SW.SwinForImageClassification(SW.SwinConfig(num_labels=5))
+    m.load_state_dict(sd)
+    m = m.to(dev).set_precision(args.precision).train().requires_grad_(True)
+    opt = torch.optim.AdamW(m.parameters(), lr=5e-5)
+    prm = {k: v.to(dev).requires_grad_(True) for k, v in sd.items()}
+    opt_t = torch.optim.AdamW(list(prm.values()), lr=5e-5)
+    torch.manual_seed(0)
+    x = torch.rand(B, 3, 224, 224, device=dev) * 0.3
+    y = torch.randint(0, 5, (B,), device=dev)
+
+    def hip_step():
+        opt.zero_grad(set_to_none=True)
+        tf, out = _timed(lambda: m(pixel_values=x, labels=y))
+        tb, _ = _timed(lambda: out.loss.backward())
+        to, _ = _timed(opt.step)
+        return tf, tb, to
+
+    def twin_step():
+        opt_t.zero_grad(set_to_none=True)
+        t0 = time.perf_counter()
+        with torch.device(dev):  # the oracle builds its index tables and shift masks on the default device
+            F.cross_entropy(SO.swin_forward.__wrapped__(prm, cfg, x)["logits"], y).backward()
+        opt_t.step()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3
+
+    for _ in range(2):
+        hip_step()
+        twin_step()
+    rows = {k: [] for k in ("fwd", "bwd", "opt", "step", "twin")}
+    for _ in range(args.reps):
+        tf, tb, to = hip_step()
+        rows["fwd"].append(tf)
+        rows["bwd"].append(tb)
+        rows["opt"].append(to)
+        rows["step"].append(tf + tb + to)
+        rows["twin"].append(twin_step())
+    med = {k: sorted(v)[len(v) // 2] for k, v in rows.items()}
+    res = dict(box=socket.gethostname(), gpu=torch.cuda.get_device_name(0), batch=B, precision=args.precision,
+               ms={k: round(v, 2) for k, v in med.items()}, speedup_vs_eager=round(med["twin"] / med["step"], 2),
+               kept_mib_per_image=round(m.__dict__["_train_kept_bytes"] / B / 2 ** 20, 1), reps=args.reps)
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()

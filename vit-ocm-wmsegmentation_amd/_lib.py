@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # OCM_VIT_LIB lets kernel experiments A/B two builds of the same ABI; the default is the in-tree build.
 LIB_PATH = os.environ.get("OCM_VIT_LIB") or os.path.join(_HERE, "libocm_vit.so")
 
-OCM_ABI_VERSION = 13
+OCM_ABI_VERSION = 14
 OCM_OK, OCM_EINVAL, OCM_ESTATE, OCM_EHIP, OCM_ENOMEM, OCM_ENAME = 0, 1, 2, 3, 4, 5
 
 OCM_PREC_BF16 = 0
@@ -164,6 +164,15 @@ SIGNATURES = {
                                                C.c_int32, C.c_void_p]),
     "ocm_op_swin_merge_ln": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                        C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "ocm_swin_window_attention_backward_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32, _i32]),
+    "ocm_op_swin_window_attention_backward": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _sz,
+                                                        _vp]),
+    "ocm_op_swin_merge_gather": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp]),
+    "ocm_op_swin_merge_scatter": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp]),
+    "ocm_op_swin_pool": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp]),
+    "ocm_op_swin_pool_backward": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp]),
+    "ocm_op_swin_drop_path": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
+    "ocm_op_swin_drop_path_backward": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     "ocm_op_pixel_shuffle": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "ocm_op_stitch_image_u8": (C.c_int, [_vp, _i64, _i64, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp]),
     "ocm_op_weighted_u8": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),

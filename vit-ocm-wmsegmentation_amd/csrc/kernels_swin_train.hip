@@ -1,0 +1,362 @@
+// kernels_swin_train.hip — the Swin-specific pieces of SwinForImageClassification's backward (modeling_swin.py, the model
+// Allen_data_Backbone/train.py fine-tunes). The rest of the Swin backward reuses the ViT training operators (ocm_op_linear for
+// data gradients, ocm_op_weight_grad, ocm_op_layernorm_backward, ocm_op_gelu_backward, ocm_op_patch_unfold):
+//   swin_wattn_bwd_kernel      (shifted-)window attention backward, one wavefront per (image, window, head): S = q k^T / sqrt(32)
+//                              + bias + shift mask and P = softmax(S) recomputed in fp32 from the fp32 q | k | v; dQ, dK, dV of
+//                              the window's tokens (each token lies in exactly one window: one writer per output) and the
+//                              window's dS summed into the (2ws-1)^2 relative-position bins
+//   swin_colsum_kernel         fixed-order column sums: the per-window bin partials -> the table gradient, in two levels
+//   swin_merge_gather_kernel   SwinPatchMerging's 2 x 2 gather (x0 | x1 | x2 | x3) as fp32 rows: the merging LayerNorm's input
+//   swin_merge_scatter_kernel  its inverse in gather form (a permutation: bit exact)
+//   swin_pool_kernel / _bwd    the token mean of the final LayerNorm's output and its broadcast backward
+//   swin_drop_path_kernel      residual + per-image-scaled branch (SwinDropPath), and the branch's gradient
+// No atomics anywhere: every sum has one order fixed by the shapes, so reruns give the same bits.
+#include "../../include/ocm_swin.h"
+#include "host_common.h"
+#include "launch.h"
+
+#define fail ocm_fail
+
+namespace {
+
+constexpr int WB_A = 49;      // positions of the largest window (7 x 7)
+constexpr int WB_LD = 33;     // LDS row of one 32-wide head, padded: a lane-strided row read hits 32 different banks
+constexpr int WB_CHUNK = 64;  // windows per first-level chunk of the table-gradient sum
+
+struct WbGeom {
+    int H, W, ws, shift, nWx, nW, heads;
+};
+
+// token of position p of window (b, wy, wx): the window tiles the grid rolled by -shift, so its source is (+shift) mod size
+// (the map of the forward's win_token, kernels_swin.hip)
+__device__ __forceinline__ int64_t wb_token(const WbGeom &g, int b, int wy, int wx, int p) {
+    const int py = p / g.ws, px = p - py * g.ws;
+    int y = wy * g.ws + py + g.shift, x = wx * g.ws + px + g.shift;
+    if (y >= g.H) y -= g.H;
+    if (x >= g.W) x -= g.W;
+    return ((int64_t)b * g.H + y) * g.W + x;
+}
+
+// region id of SwinLayer.get_attn_mask for position p of the window, in the shifted frame
+__device__ __forceinline__ int wb_region(const WbGeom &g, int wy, int wx, int p) {
+    const int py = p / g.ws, px = p - py * g.ws;
+    const int ys = wy * g.ws + py, xs = wx * g.ws + px;
+    const int ry = (ys >= g.H - g.ws) + (ys >= g.H - g.shift), rx = (xs >= g.W - g.ws) + (xs >= g.W - g.shift);
+    return ry * 3 + rx;
+}
+
+// One wavefront (= workgroup) per (image, window, head); lane i owns query i in the first pass and key i in the second.
+//   pass 1 (query rows): S_i. = q_i K^T scale + bias + mask (-100, transformers' additive mask), P_i. = softmax,
+//                        o_i = P_i. V, delta_i = dO_i . o_i, dS_ij = P_ij (dO_i . v_j - delta_i), dQ_i = scale sum_j dS_ij k_j
+//   pass 2 (key rows):   dK_j = scale sum_i dS_ij q_i,  dV_j = sum_i P_ij dO_i
+//   pass 3 (bins):       part[window][bin][head] = sum of dS_ij over the pairs (i, j) of that relative offset
+// Every sum runs in position order. q, k, v, dO of the window and P, dS live in LDS (44 KB); all products are fp32 FMAs.
+__global__ __launch_bounds__(64) void swin_wattn_bwd_kernel(const float *__restrict__ qkv, const float *__restrict__ dctx,
+                                                            const float *__restrict__ table, float *__restrict__ dqkv,
+                                                            float *__restrict__ part, WbGeom g, float scale) {
+    __shared__ float Qs[WB_A * WB_LD], Ks[WB_A * WB_LD], Vs[WB_A * WB_LD], Gs[WB_A * WB_LD];
+    __shared__ float Ps[WB_A * WB_A], Ds[WB_A * WB_A];
+    __shared__ int64_t Tok[64];
+    __shared__ int Rg[64];
+    const int lane = threadIdx.x;
+    const int id = blockIdx.x;
+    const int head = id % g.heads, wlin = (id / g.heads) % g.nW, b = id / (g.heads * g.nW);
+    const int wy = wlin / g.nWx, wx = wlin - wy * g.nWx;
+    const int ws = g.ws, A = ws * ws, AP = A | 1, C = g.heads * 32, ld = 3 * C, nb = 2 * ws - 1;
+    const bool masked = g.shift > 0;
+    if (lane < A) {
+        Tok[lane] = wb_token(g, b, wy, wx, lane);
+        Rg[lane] = masked ? wb_region(g, wy, wx, lane) : 0;
+    }
+    __syncthreads();
+    for (int idx = lane; idx < A * 32; idx += 64) {
+        const int p = idx >> 5, d = idx & 31;
+        const float *row = qkv + Tok[p] * ld + head * 32 + d;
+        Qs[p * WB_LD + d] = row[0];
+        Ks[p * WB_LD + d] = row[C];
+        Vs[p * WB_LD + d] = row[2 * C];
+        Gs[p * WB_LD + d] = dctx[Tok[p] * C + head * 32 + d];
+    }
+    __syncthreads();
+    if (lane < A) {
+        const int i = lane, yi = i / ws, xi = i - yi * ws;
+        float *prow = Ps + i * AP, *drow = Ds + i * AP;
+        float mx = -INFINITY;
+        for (int j = 0; j < A; ++j) {
+            float s = 0.f;
+#pragma unroll
+            for (int d = 0; d < 32; ++d) s = fmaf(Qs[i * WB_LD + d], Ks[j * WB_LD + d], s);
+            const int yj = j / ws, xj = j - yj * ws;
+            s = s * scale + table[((yi - yj + ws - 1) * nb + (xi - xj + ws - 1)) * g.heads + head];
+            if (masked && Rg[j] != Rg[i]) s += -100.0f;
+            prow[j] = s;
+            mx = fmaxf(mx, s);
+        }
+        float l = 0.f;
+        for (int j = 0; j < A; ++j) {
+            const float e = expf(prow[j] - mx);
+            prow[j] = e;
+            l += e;
+        }
+        const float inv = 1.0f / l;
+        float o[32];
+#pragma unroll
+        for (int d = 0; d < 32; ++d) o[d] = 0.f;
+        for (int j = 0; j < A; ++j) {
+            const float p = prow[j] * inv;
+            prow[j] = p;
+#pragma unroll
+            for (int d = 0; d < 32; ++d) o[d] = fmaf(p, Vs[j * WB_LD + d], o[d]);
+        }
+        float delta = 0.f;
+#pragma unroll
+        for (int d = 0; d < 32; ++d) delta = fmaf(Gs[i * WB_LD + d], o[d], delta);
+        float dq[32];
+#pragma unroll
+        for (int d = 0; d < 32; ++d) dq[d] = 0.f;
+        for (int j = 0; j < A; ++j) {
+            float dp = 0.f;
+#pragma unroll
+            for (int d = 0; d < 32; ++d) dp = fmaf(Gs[i * WB_LD + d], Vs[j * WB_LD + d], dp);
+            const float ds = prow[j] * (dp - delta);
+            drow[j] = ds;
+#pragma unroll
+            for (int d = 0; d < 32; ++d) dq[d] = fmaf(ds, Ks[j * WB_LD + d], dq[d]);
+        }
+        float *dst = dqkv + Tok[i] * ld + head * 32;
+#pragma unroll
+        for (int d = 0; d < 32; d += 4)
+            *(f32x4 *)(dst + d) = f32x4{dq[d] * scale, dq[d + 1] * scale, dq[d + 2] * scale, dq[d + 3] * scale};
+    }
+    __syncthreads();
+    if (lane < A) {
+        const int j = lane;
+        float dk[32], dv[32];
+#pragma unroll
+        for (int d = 0; d < 32; ++d) dk[d] = dv[d] = 0.f;
+        for (int i = 0; i < A; ++i) {
+            const float ds = Ds[i * AP + j], p = Ps[i * AP + j];
+#pragma unroll
+            for (int d = 0; d < 32; ++d) {
+                dk[d] = fmaf(ds, Qs[i * WB_LD + d], dk[d]);
+                dv[d] = fmaf(p, Gs[i * WB_LD + d], dv[d]);
+            }
+        }
+        float *dst = dqkv + Tok[j] * ld + head * 32;
+#pragma unroll
+        for (int d = 0; d < 32; d += 4) {
+            *(f32x4 *)(dst + C + d) = f32x4{dk[d] * scale, dk[d + 1] * scale, dk[d + 2] * scale, dk[d + 3] * scale};
+            *(f32x4 *)(dst + 2 * C + d) = f32x4{dv[d], dv[d + 1], dv[d + 2], dv[d + 3]};
+        }
+    }
+    const int nbb = nb * nb;
+    float *prt = part + ((size_t)b * g.nW + wlin) * nbb * g.heads + head;
+    for (int bin = lane; bin < nbb; bin += 64) {
+        const int ry = bin / nb - (ws - 1), rx = bin % nb - (ws - 1);  // yi - yj, xi - xj
+        float s = 0.f;
+        for (int i = 0; i < A; ++i) {
+            const int yi = i / ws, xi = i - yi * ws, yj = yi - ry, xj = xi - rx;
+            if (yj >= 0 && yj < ws && xj >= 0 && xj < ws) s += Ds[i * AP + yj * ws + xj];
+        }
+        prt[(size_t)bin * g.heads] = s;
+    }
+}
+
+// out[r][c] = sum of in[row][c] over rows [r * chunk, min(rows, (r + 1) * chunk)), in row order
+__global__ __launch_bounds__(256) void swin_colsum_kernel(const float *__restrict__ in, float *__restrict__ out, int64_t rows,
+                                                          int cols, int64_t chunk) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= cols) return;
+    const int64_t r0 = (int64_t)blockIdx.y * chunk, r1 = r0 + chunk < rows ? r0 + chunk : rows;
+    float s = 0.f;
+    for (int64_t r = r0; r < r1; ++r) s += in[r * cols + c];
+    out[(size_t)blockIdx.y * cols + c] = s;
+}
+
+// y[(b, i, j)][q * C + c] = x[b][2i + (q & 1)][2j + (q >> 1)][c]: the x0 | x1 | x2 | x3 order of SwinPatchMerging
+__global__ __launch_bounds__(256) void swin_merge_gather_kernel(const float *__restrict__ x, float *__restrict__ y, int H, int W,
+                                                                int C, size_t total) {
+    const int H2 = H / 2, W2 = W / 2, C4 = 4 * C;
+    for (size_t n = (size_t)blockIdx.x * 256 + threadIdx.x; n < total; n += (size_t)gridDim.x * 256) {
+        const int k = (int)(n % C4);
+        const size_t t = n / C4;
+        const int j = (int)(t % W2), i = (int)((t / W2) % H2);
+        const size_t b = t / ((size_t)W2 * H2);
+        const int q = k / C, c = k - q * C;
+        y[n] = x[((b * H + 2 * i + (q & 1)) * W + 2 * j + (q >> 1)) * C + c];
+    }
+}
+
+// dx[b][y][x][c] = dy[(b, y / 2, x / 2)][((x & 1) * 2 + (y & 1)) * C + c]
+__global__ __launch_bounds__(256) void swin_merge_scatter_kernel(const float *__restrict__ dy, float *__restrict__ dx, int H,
+                                                                 int W, int C, size_t total) {
+    const int H2 = H / 2, W2 = W / 2;
+    for (size_t n = (size_t)blockIdx.x * 256 + threadIdx.x; n < total; n += (size_t)gridDim.x * 256) {
+        const int c = (int)(n % C);
+        const size_t t = n / C;
+        const int xx = (int)(t % W), yy = (int)((t / W) % H);
+        const size_t b = t / ((size_t)W * H);
+        const int q = (xx & 1) * 2 + (yy & 1);
+        dx[n] = dy[((b * H2 + yy / 2) * W2 + xx / 2) * (size_t)(4 * C) + q * C + c];
+    }
+}
+
+// pooled[b][c] = (sum_l x[b][l][c]) / L, tokens in order
+__global__ __launch_bounds__(256) void swin_pool_kernel(const float *__restrict__ x, float *__restrict__ pooled, int L, int C,
+                                                        int total) {
+    const int n = blockIdx.x * 256 + threadIdx.x;
+    if (n >= total) return;
+    const int c = n % C, b = n / C;
+    const float *src = x + (size_t)b * L * C + c;
+    float s = 0.f;
+    for (int l = 0; l < L; ++l) s += src[(size_t)l * C];
+    pooled[n] = s / (float)L;
+}
+
+// dx[b][l][c] = dpooled[b][c] / L
+__global__ __launch_bounds__(256) void swin_pool_bwd_kernel(const float *__restrict__ dp, float *__restrict__ dx, int L, int C,
+                                                            size_t total) {
+    for (size_t n = (size_t)blockIdx.x * 256 + threadIdx.x; n < total; n += (size_t)gridDim.x * 256) {
+        const int c = (int)(n % C);
+        const size_t b = n / ((size_t)L * C);
+        dx[n] = dp[b * C + c] / (float)L;
+    }
+}
+
+// out = x + branch * scale[image] (out may alias x); the backward passes x = nullptr: out = branch * scale[image]
+__global__ __launch_bounds__(256) void swin_drop_path_kernel(const float *x, const float *__restrict__ branch,
+                                                             const float *__restrict__ scale, float *out, size_t per_image,
+                                                             size_t total) {
+    for (size_t n = (size_t)blockIdx.x * 256 + threadIdx.x; n < total; n += (size_t)gridDim.x * 256) {
+        const float v = branch[n] * scale[n / per_image];
+        out[n] = x ? x[n] + v : v;
+    }
+}
+
+unsigned grid_for(size_t work) {
+    const size_t g = (work + 255) / 256;
+    return (unsigned)(g < 1 ? 1 : g > 8192 ? 8192 : g);
+}
+
+int wb_geometry_ok(int batch, int height, int width, int window, int shift, int heads) {
+    if (batch <= 0 || heads <= 0 || window < 2 || window > 7 || height <= 0 || width <= 0 || height % window ||
+        width % window || shift < 0 || shift >= window)
+        return fail(OCM_EINVAL, "bad window geometry (batch %d, %d x %d, window %d, shift %d, heads %d)", batch, height, width,
+                    window, shift, heads);
+    if ((int64_t)batch * height * width * heads * 96 > 0x7fffffffLL) return fail(OCM_EINVAL, "too many tokens");
+    return OCM_OK;
+}
+
+int shape_ok(int batch, int tokens, int channels) {
+    if (batch <= 0 || tokens <= 0 || channels <= 0)
+        return fail(OCM_EINVAL, "bad shape batch=%d tokens=%d channels=%d", batch, tokens, channels);
+    return OCM_OK;
+}
+
+int merge_ok(int batch, int height, int width, int channels) {
+    if (batch <= 0 || height <= 0 || width <= 0 || height % 2 || width % 2 || channels <= 0)
+        return fail(OCM_EINVAL, "bad patch-merging geometry (batch %d, %d x %d, %d channels): even sides only", batch, height,
+                    width, channels);
+    return OCM_OK;
+}
+
+}  // namespace
+
+// ---- C ABI (include/ocm_swin.h, training) ------------------------------------------------------------------------------
+extern "C" size_t ocm_swin_window_attention_backward_workspace_bytes(int32_t batch, int32_t height, int32_t width,
+                                                                     int32_t window, int32_t heads) {
+    if (batch <= 0 || height <= 0 || width <= 0 || window < 2 || window > 7 || heads <= 0) return 0;
+    const int64_t nwin = (int64_t)batch * (height / window) * (width / window);
+    const int64_t cols = (int64_t)(2 * window - 1) * (2 * window - 1) * heads;
+    const int64_t R = (nwin + WB_CHUNK - 1) / WB_CHUNK;
+    return (size_t)((nwin + R) * cols) * sizeof(float);
+}
+
+extern "C" int ocm_op_swin_window_attention_backward(const float *qkv, const float *dctx, const float *rel_table, float *dqkv,
+                                                     float *dtable, int32_t batch, int32_t height, int32_t width, int32_t window,
+                                                     int32_t shift, int32_t heads, void *workspace, size_t workspace_bytes,
+                                                     void *stream) {
+    if (!qkv || !dctx || !rel_table || !dqkv || !dtable || !workspace) return fail(OCM_EINVAL, "null argument");
+    if (int rc = wb_geometry_ok(batch, height, width, window, shift, heads)) return rc;
+    const size_t need = ocm_swin_window_attention_backward_workspace_bytes(batch, height, width, window, heads);
+    if (workspace_bytes < need)
+        return fail(OCM_EINVAL, "window attention backward workspace: %zu bytes given, %zu needed", workspace_bytes, need);
+    const hipStream_t s = (hipStream_t)stream;
+    const WbGeom g{height, width, window, shift, width / window, (height / window) * (width / window), heads};
+    const int64_t nwin = (int64_t)batch * g.nW, total = nwin * heads;
+    const int cols = (2 * window - 1) * (2 * window - 1) * heads;
+    const int64_t R = (nwin + WB_CHUNK - 1) / WB_CHUNK;
+    if (total > 0x7fffffffLL || R > 65535) return fail(OCM_EINVAL, "too many (window, head) pairs");
+    float *part = (float *)workspace, *part2 = part + nwin * cols;
+    swin_wattn_bwd_kernel<<<dim3((unsigned)total), dim3(64), 0, s>>>(qkv, dctx, rel_table, dqkv, part, g, 0.17677669529663687f);
+    HIP_TRY(hipGetLastError());
+    const unsigned cx = (unsigned)((cols + 255) / 256);
+    swin_colsum_kernel<<<dim3(cx, (unsigned)R), dim3(256), 0, s>>>(part, part2, nwin, cols, WB_CHUNK);
+    HIP_TRY(hipGetLastError());
+    swin_colsum_kernel<<<dim3(cx, 1), dim3(256), 0, s>>>(part2, dtable, R, cols, R);
+    HIP_TRY(hipGetLastError());
+    return OCM_OK;
+}
+
+extern "C" int ocm_op_swin_merge_gather(const float *x, float *y, int32_t batch, int32_t height, int32_t width, int32_t channels,
+                                        void *stream) {
+    if (!x || !y) return fail(OCM_EINVAL, "null argument");
+    if (int rc = merge_ok(batch, height, width, channels)) return rc;
+    const size_t total = (size_t)batch * height * width * channels;
+    swin_merge_gather_kernel<<<dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream>>>(x, y, height, width, channels, total);
+    HIP_TRY(hipGetLastError());
+    return OCM_OK;
+}
+
+extern "C" int ocm_op_swin_merge_scatter(const float *dy, float *dx, int32_t batch, int32_t height, int32_t width,
+                                         int32_t channels, void *stream) {
+    if (!dy || !dx) return fail(OCM_EINVAL, "null argument");
+    if (int rc = merge_ok(batch, height, width, channels)) return rc;
+    const size_t total = (size_t)batch * height * width * channels;
+    swin_merge_scatter_kernel<<<dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream>>>(dy, dx, height, width, channels,
+                                                                                            total);
+    HIP_TRY(hipGetLastError());
+    return OCM_OK;
+}
+
+extern "C" int ocm_op_swin_pool(const float *x, float *pooled, int32_t batch, int32_t tokens, int32_t channels, void *stream) {
+    if (!x || !pooled) return fail(OCM_EINVAL, "null argument");
+    if (int rc = shape_ok(batch, tokens, channels)) return rc;
+    if ((int64_t)batch * channels > 0x7fffffffLL) return fail(OCM_EINVAL, "too many outputs");
+    const int total = batch * channels;
+    swin_pool_kernel<<<dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream>>>(x, pooled, tokens, channels,
+                                                                                                   total);
+    HIP_TRY(hipGetLastError());
+    return OCM_OK;
+}
+
+extern "C" int ocm_op_swin_pool_backward(const float *dpooled, float *dx, int32_t batch, int32_t tokens, int32_t channels,
+                                         void *stream) {
+    if (!dpooled || !dx) return fail(OCM_EINVAL, "null argument");
+    if (int rc = shape_ok(batch, tokens, channels)) return rc;
+    const size_t total = (size_t)batch * tokens * channels;
+    swin_pool_bwd_kernel<<<dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream>>>(dpooled, dx, tokens, channels, total);
+    HIP_TRY(hipGetLastError());
+    return OCM_OK;
+}
+
+extern "C" int ocm_op_swin_drop_path(const float *x, const float *branch, const float *scale, float *out, int32_t batch,
+                                     int32_t tokens, int32_t channels, void *stream) {
+    if (!x || !branch || !scale || !out) return fail(OCM_EINVAL, "null argument");
+    if (int rc = shape_ok(batch, tokens, channels)) return rc;
+    const size_t per = (size_t)tokens * channels, total = per * batch;
+    swin_drop_path_kernel<<<dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream>>>(x, branch, scale, out, per, total);
+    HIP_TRY(hipGetLastError());
+    return OCM_OK;
+}
+
+extern "C" int ocm_op_swin_drop_path_backward(const float *dout, const float *scale, float *dbranch, int32_t batch,
+                                              int32_t tokens, int32_t channels, void *stream) {
+    if (!dout || !scale || !dbranch) return fail(OCM_EINVAL, "null argument");
+    if (int rc = shape_ok(batch, tokens, channels)) return rc;
+    const size_t per = (size_t)tokens * channels, total = per * batch;
+    swin_drop_path_kernel<<<dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream>>>(nullptr, dout, scale, dbranch, per,
+                                                                                        total);
+    HIP_TRY(hipGetLastError());
+    return OCM_OK;
+}

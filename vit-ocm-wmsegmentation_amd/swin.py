@@ -1,26 +1,34 @@
-"""Swin-T inference behind the module surface the reference's Allen_data_Backbone/train.py:70-85 uses
-(transformers' `SwinConfig` / `SwinForImageClassification`): same constructor fields, same state_dict keys (a
-transformers checkpoint loads with `load_state_dict`), `model(pixel_values=...)` -> object with `.logits`
-(and `.pooler_output`, optionally `.last_hidden_state`). The arithmetic runs in libocm_vit.so
-(include/ocm_swin.h); there is no CPU fallback. Inference only (BASELINE config 5).
+"""Swin-T behind the module surface the reference's Allen_data_Backbone/train.py:70-85 uses (transformers' `SwinConfig` /
+`SwinForImageClassification`): same constructor fields, same state_dict keys (a transformers checkpoint loads with
+`load_state_dict`), `model(pixel_values=..., labels=...)` -> object with `.loss`, `.logits` (and `.pooler_output`, optionally
+`.last_hidden_state`). The arithmetic runs in libocm_vit.so (include/ocm_swin.h); there is no CPU fallback.
+
+Inference runs the engine (ocm_swin_forward). Training — train.py's Trainer loop — runs when the module is in training mode,
+grad mode is on and a parameter requires grad (the parameters are created with requires_grad=False: opt in with
+`model.requires_grad_(True)`): the stand-alone operators under one autograd Function (_SwinTrain) whose backward is HIP
+(kernels_swin_train.hip plus the ViT training operators).
 """
 import ctypes as C
 import types
 
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
 
 from . import _lib
 from .dino.utils import trunc_normal_
-from .engine import _p, _require_hip, _stream
+from .engine import _p, _require_hip, _stream, from_split, to_operand
+from .model import _OPERAND_DTYPE, _differentiable, _linear, _ln, _ln_backward, _weight_grad, _ws
 
 
 class SwinConfig:
-    """The fields of transformers.SwinConfig this path reads (defaults = swin-tiny-patch4-window7-224)."""
+    """The fields of transformers.SwinConfig this path reads (defaults = swin-tiny-patch4-window7-224). drop_path_rate and
+    the dropout probabilities act in training only, as in transformers."""
 
     def __init__(self, image_size=224, patch_size=4, num_channels=3, embed_dim=96, depths=(2, 2, 6, 2),
                  num_heads=(3, 6, 12, 24), window_size=7, mlp_ratio=4.0, qkv_bias=True, hidden_act="gelu",
-                 layer_norm_eps=1e-5, num_labels=2, label2id=None, id2label=None, **unused):
+                 layer_norm_eps=1e-5, num_labels=2, label2id=None, id2label=None, drop_path_rate=0.1,
+                 hidden_dropout_prob=0.0, attention_probs_dropout_prob=0.0, **unused):
         if hidden_act != "gelu" or not qkv_bias:
             raise ValueError("only hidden_act='gelu' with qkv_bias=True (the Swin-T defaults) is built")
         self.image_size, self.patch_size, self.num_channels, self.embed_dim = image_size, patch_size, num_channels, embed_dim
@@ -31,6 +39,42 @@ class SwinConfig:
         self.num_labels = len(id2label) if id2label else num_labels
         self.num_layers = len(self.depths)
         self.hidden_size = int(embed_dim * 2 ** (self.num_layers - 1))
+        self.drop_path_rate = drop_path_rate
+        self.hidden_dropout_prob, self.attention_probs_dropout_prob = hidden_dropout_prob, attention_probs_dropout_prob
+
+
+class SwinOutput(types.SimpleNamespace):
+    """What `forward` returns: the attributes loss, logits, pooler_output, last_hidden_state, and, as transformers'
+    ModelOutput does for a Trainer's compute_loss, out["loss"] and out[0] (the non-None of loss, logits, in that order)."""
+
+    def to_tuple(self):
+        return tuple(v for v in (self.loss, self.logits) if v is not None)
+
+    def __getitem__(self, key):
+        if isinstance(key, str):
+            return getattr(self, key)
+        return self.to_tuple()[key]
+
+
+def drop_path_rates(config):
+    """SwinEncoder's stochastic-depth rate of every layer in global order: drop_path_rate * i / max(sum(depths) - 1, 1)."""
+    n = sum(config.depths)
+    return [config.drop_path_rate * i / max(n - 1, 1) for i in range(n)]
+
+
+def draw_drop_path_masks(config, batch, device):
+    """The SwinDropPath draws of one training forward, in transformers' layer order: per layer None (rate 0: transformers
+    builds an Identity and draws nothing) or (keep_prob, mask) with mask = floor(torch.rand((B, 1, 1)) + keep_prob) drawn
+    exactly as SwinDropPath.forward draws it, so a seeded run draws the masks transformers would draw on that device."""
+    out = []
+    for rate in drop_path_rates(config):
+        if rate == 0.0:
+            out.append(None)
+            continue
+        keep = 1 - rate
+        rnd = torch.rand((batch, 1, 1), dtype=torch.float32, device=device)
+        out.append((keep, torch.floor(rnd + keep).reshape(batch)))
+    return out
 
 
 def _param_shapes(cfg):
@@ -124,13 +168,74 @@ class SwinForImageClassification(nn.Module):
         self.__dict__["_engine"] = eng
         return eng
 
-    @torch.no_grad()
     def forward(self, pixel_values=None, labels=None, output_hidden_states=False, **unused):
         _require_hip(pixel_values, "pixel_values")
         c = self.config
         if pixel_values.dim() != 4 or tuple(pixel_values.shape[1:]) != (c.num_channels, c.image_size, c.image_size):
             raise ValueError(f"expected (B, {c.num_channels}, {c.image_size}, {c.image_size}) pixel_values, got "
                              f"{tuple(pixel_values.shape)}")
+        if _differentiable(self):
+            return self._train_forward(pixel_values, labels, output_hidden_states)
+        with torch.no_grad():
+            return self._infer(pixel_values, labels, output_hidden_states)
+
+    # ---- training ----------------------------------------------------------------------------------------------------------
+    def _check_trainable(self, x, labels):
+        """What the training path refuses, before anything is launched."""
+        c = self.config
+        if x.requires_grad:
+            raise NotImplementedError("the training path does not produce the gradient of the input image; pass pixel_values "
+                                      "that do not require grad")
+        if c.hidden_dropout_prob or c.attention_probs_dropout_prob:
+            raise NotImplementedError(f"training is built without dropout (hidden_dropout_prob = {c.hidden_dropout_prob}, "
+                                      f"attention_probs_dropout_prob = {c.attention_probs_dropout_prob}); set both to 0. "
+                                      "Stochastic depth (drop_path_rate) is supported")
+        if c.patch_size != 4 or not 2 <= c.window_size <= 7:
+            raise NotImplementedError("training is built for patch_size 4 and windows of 2 to 7")
+        side = c.image_size // c.patch_size
+        for s in range(c.num_layers):
+            if c.embed_dim * 2 ** s != 32 * c.num_heads[s] or c.embed_dim % 32 or c.embed_dim > 128:
+                raise NotImplementedError(f"stage {s}: training is built for 32-wide heads and embed_dim a multiple of 32 "
+                                          "up to 128")
+            if side < c.window_size or side % c.window_size:
+                raise NotImplementedError(f"stage {s}: its {side} x {side} grid is not a multiple of window_size "
+                                          f"{c.window_size}; training is built for geometries without transformers' padding "
+                                          "paths (every stage grid a multiple of the window, even before each merge)")
+            if s + 1 < c.num_layers:
+                if side % 2:
+                    raise NotImplementedError(f"stage {s}: the odd {side} x {side} grid would be padded before the patch "
+                                              "merging; training is built for geometries without transformers' padding paths")
+                side //= 2
+        if labels is not None:
+            if c.num_labels < 2:
+                raise ValueError(f"training with labels is built for single-label classification with num_labels >= 2 (got "
+                                 f"{c.num_labels}); the regression and multi-label losses are not built")
+            if not isinstance(labels, torch.Tensor) or labels.dtype != torch.int64:
+                raise ValueError("labels must be int64 class indices (single-label classification), got "
+                                 f"{getattr(labels, 'dtype', type(labels))}")
+
+    def _train_forward(self, pixel_values, labels, output_hidden_states):
+        self._check_trainable(pixel_values, labels)
+        x = pixel_values.detach().to(torch.float32).contiguous()
+        dev = x.device
+        named = [(self._names[n], p) for n, p in self.named_parameters()]
+        for key, p in named:
+            if p.device != dev:
+                raise RuntimeError(f"parameters are on {p.device} but the input is on {dev}; call model.to(device)")
+        meta = {"model": self, "keys": [k for k, _ in named],
+                "masks": draw_drop_path_masks(self.config, x.shape[0], dev)}
+        with torch.cuda.device(dev):
+            logits, pooled = _SwinTrain.apply(meta, x, *[p for _, p in named])
+        self.__dict__["_train_kept_bytes"] = meta["kept_bytes"]  # what the backward holds (DESIGN.md 3.18)
+        loss = None
+        if labels is not None:
+            loss = nn.functional.cross_entropy(logits, labels.to(dev))
+        hidden = meta["hidden"] if output_hidden_states else None  # the final LayerNorm's output, without a graph
+        return SwinOutput(loss=loss, logits=logits, pooler_output=pooled, last_hidden_state=hidden)
+
+    # ---- inference ---------------------------------------------------------------------------------------------------------
+    def _infer(self, pixel_values, labels, output_hidden_states):
+        c = self.config
         x = pixel_values.detach().to(torch.float32).contiguous()
         dev, B = x.device, x.shape[0]
         eng, lib = self._get_engine(dev), _lib.load()
@@ -153,4 +258,346 @@ class SwinForImageClassification(nn.Module):
         loss = None
         if labels is not None:
             loss = nn.functional.cross_entropy(logits, labels.to(dev))
-        return types.SimpleNamespace(loss=loss, logits=logits, pooler_output=pooled, last_hidden_state=hidden)
+        return SwinOutput(loss=loss, logits=logits, pooler_output=pooled, last_hidden_state=hidden)
+
+
+# ---- training: SwinForImageClassification as stand-alone operators under one autograd Function. Token-major rows
+# m = (image, y, x); T = B * H * W tokens of a stage with C channels. ----
+def _kpad(K, prec):
+    """K rounded up to the GEMM operands' K step: 64 for bf16, 32 for fp32 and split pairs."""
+    step = 64 if prec == _lib.OCM_PREC_BF16 else 32
+    return -(-K // step) * step
+
+
+def _pad_cols(t, K):
+    return t if t.shape[1] == K else F.pad(t, (0, K - t.shape[1]))
+
+
+def _operand(t32, prec):
+    """fp32 [M][K] -> the GEMM operand [M][kpad(K)], padding columns zero."""
+    return to_operand(_pad_cols(t32, _kpad(t32.shape[1], prec)), prec)
+
+
+class _Weights:
+    """Operand copies of weight matrices ([N][K] and the transposes the data gradients read), K zero-padded to the operand's
+    K step, cached in the module per (data_ptr, _version) of the parameters they are made from: an optimizer step or
+    load_state_dict makes new copies, an unchanged parameter is not repacked."""
+
+    def __init__(self, model, P, prec):
+        self.cache, self.P, self.prec = model.__dict__.setdefault("_train_cache", {}), P, prec
+
+    def _get(self, tag, keys, make):
+        sig = (self.prec,) + tuple((self.P[k].data_ptr(), self.P[k]._version) for k in keys)
+        hit = self.cache.get(tag)
+        if hit is None or hit[0] != sig:
+            hit = (sig, make())
+            self.cache[tag] = hit
+        return hit[1]
+
+    def _mat(self, keys, rows):
+        w = torch.cat([self.P[k].detach().float().reshape(self.P[k].shape[0], -1) for k in keys])
+        return F.pad(w, (0, 0, 0, rows - w.shape[0])) if rows and rows > w.shape[0] else w
+
+    def w(self, *keys, rows=None):
+        """cat(keys) as [N][K] (rows zero-padded up to `rows`)."""
+        return self._get(keys, keys, lambda: _operand(self._mat(keys, rows), self.prec))
+
+    def wt(self, *keys, rows=None):
+        """The transpose [K][N] of w(*keys, rows=rows): the data gradient dX = dY W runs as a linear with W^T."""
+        return self._get(("T",) + keys, keys, lambda: _operand(self._mat(keys, rows).t().contiguous(), self.prec))
+
+
+def _ctx_f32(cx, C, prec):
+    """The window attention's context (operand rows of kpad(C) columns) as fp32 [T][C]."""
+    if prec == _lib.OCM_PREC_BF16X3:
+        return from_split(cx)
+    if prec == _lib.OCM_PREC_FP32:
+        return cx
+    return cx[:, :C].float().contiguous()
+
+
+class _SwinTrain(torch.autograd.Function):
+    """SwinForImageClassification in training mode: forward(meta, pixel_values, *params) -> (logits, pooled); backward ->
+    parameter gradients (the image gets none). The forward runs the stand-alone operators in the module's precision (not the
+    engine, not the fused Swin kernels): patch unfold + GEMM + LayerNorm, per layer LayerNorm -> q | k | v GEMM (fp32) ->
+    window attention -> o_proj (+ drop path) -> LayerNorm -> fc1 (fp32 pre-activation) -> GELU -> fc2, the merging LayerNorm +
+    reduction, the final LayerNorm, token mean and classifier (rows zero-padded to a multiple of 32). Kept per layer: the two
+    LayerNorm inputs, the fp32 q | k | v, the context in operand form and the fp32 fc1 pre-activation; per merge its input;
+    LayerNorm statistics and outputs are recomputed in the backward."""
+
+    @staticmethod
+    def forward(ctx, meta, x, *params):
+        model = meta["model"]
+        c = model.config
+        P = dict(zip(meta["keys"], params))
+        lib, dev = _lib.load(), x.device
+        prec = _lib.PRECISIONS[model._precision]
+        f32 = dict(device=dev, dtype=torch.float32)
+        adt = _OPERAND_DTYPE[prec]
+        W = _Weights(model, P, prec)
+        eps, F32 = float(c.layer_norm_eps), _lib.OCM_LN_F32
+        B, Cin, S = x.shape[0], c.num_channels, c.image_size
+        H, C = S // c.patch_size, c.embed_dim
+        ctx.set_materialize_grads(False)
+
+        # embeddings: Conv2d(p = 4, stride 4) as patch rows (K = Cin * 16 zero-padded) x weight, then embeddings.norm (eps 1e-5)
+        e = "swin.embeddings."
+        T = B * H * H
+        cols = torch.empty((T, Cin * 16), **f32)
+        _lib.check(lib.ocm_op_patch_unfold(_p(x), _p(cols), B, Cin, S, S, c.patch_size, _stream()))
+        tok = _linear(lib, prec, _operand(cols, prec), W.w(e + "patch_embeddings.projection.weight"),
+                      P[e + "patch_embeddings.projection.bias"], None, T, C, _kpad(Cin * 16, prec))
+        del cols
+        t = _ln(lib, tok, P[e + "norm.weight"], P[e + "norm.bias"], F32, T, C, 1e-5, torch.float32)
+        keep = [tok]  # tensors for the backward, in this order: tok, per layer 6, per merge 1, final input, pooled
+        masks, li = meta["masks"], 0
+        for s in range(c.num_layers):
+            heads, M, ws = c.num_heads[s], int(c.mlp_ratio * C), c.window_size
+            T, Kc, Km = B * H * H, _kpad(C, prec), _kpad(M, prec)
+            for b in range(c.depths[s]):
+                pre = f"swin.encoder.layers.{s}.blocks.{b}."
+                a = pre + "attention."
+                shift = ws // 2 if b % 2 and H > ws else 0  # set_shift_and_window_size: no shift when the grid is the window
+                xn = _ln(lib, t, P[pre + "layernorm_before.weight"], P[pre + "layernorm_before.bias"], F32, T, C, eps,
+                         torch.float32)
+                qkv = _linear(lib, prec, _operand(xn, prec), W.w(a + "q_proj.weight", a + "k_proj.weight", a + "v_proj.weight"),
+                              torch.cat([P[a + n + "_proj.bias"] for n in "qkv"]), None, T, 3 * C, Kc)
+                del xn
+                cx = torch.zeros((T, Kc), dtype=adt, device=dev)
+                scratch = torch.empty(heads * (4096 + ws ** 4), **f32)
+                table = P[a + "relative_position_bias.relative_position_bias_table"]
+                _lib.check(lib.ocm_op_swin_window_attention(prec, _p(to_operand(qkv, prec)), 3 * C, _p(cx), Kc, _p(table),
+                                                            _p(scratch), B, H, H, ws, shift, heads, _stream()))
+                wo, bo = W.w(a + "o_proj.weight"), P[a + "o_proj.bias"]
+                scale = None
+                if masks[li] is None:
+                    x1 = _linear(lib, prec, cx, wo, bo, t, T, C, Kc, _lib.OCM_EPI_BIAS_RESID_F32)
+                else:  # SwinDropPath on the attention branch: x1 = t + branch * mask / keep_prob per image
+                    kp, mask = masks[li]
+                    scale = (mask / kp).contiguous()
+                    br = _linear(lib, prec, cx, wo, bo, None, T, C, Kc)
+                    x1 = torch.empty((T, C), **f32)
+                    _lib.check(lib.ocm_op_swin_drop_path(_p(t), _p(br), _p(scale), _p(x1), B, H * H, C, _stream()))
+                    del br
+                xn2 = _ln(lib, x1, P[pre + "layernorm_after.weight"], P[pre + "layernorm_after.bias"], F32, T, C, eps,
+                          torch.float32)
+                hpre = _linear(lib, prec, _operand(xn2, prec), W.w(pre + "mlp.fc1.weight"), P[pre + "mlp.fc1.bias"], None, T,
+                               M, Kc)
+                del xn2
+                if Km == M:
+                    g = torch.empty((T, M), dtype=adt, device=dev)
+                    _lib.check(lib.ocm_op_gelu(prec, _p(hpre), _p(g), None, T * M, _stream()))
+                else:
+                    g32 = torch.empty((T, M), **f32)
+                    _lib.check(lib.ocm_op_gelu(_lib.OCM_PREC_FP32, _p(hpre), _p(g32), None, T * M, _stream()))
+                    g = _operand(g32, prec)
+                    del g32
+                x2 = _linear(lib, prec, g, W.w(pre + "mlp.fc2.weight"), P[pre + "mlp.fc2.bias"], x1, T, C, Km,
+                             _lib.OCM_EPI_BIAS_RESID_F32)
+                del g
+                keep += [t, qkv, cx, x1, hpre, scale]
+                t, li = x2, li + 1
+            if s + 1 < c.num_layers:  # SwinPatchMerging: gather + LayerNorm(4C) in one kernel, then the reduction
+                dn = f"swin.encoder.layers.{s}.downsample."
+                T4, K4 = B * (H // 2) ** 2, _kpad(4 * C, prec)
+                y = torch.empty((T4, K4), dtype=adt, device=dev)
+                _lib.check(lib.ocm_op_swin_merge_ln(prec, _p(t), _p(P[dn + "norm.weight"]), _p(P[dn + "norm.bias"]), _p(y), B,
+                                                    H, H, C, K4, _stream()))
+                keep.append(t)
+                t = _linear(lib, prec, y, W.w(dn + "reduction.weight"), torch.zeros(2 * C, **f32), None, T4, 2 * C, K4)
+                del y
+                H, C = H // 2, 2 * C
+        # head: final LayerNorm, token mean, classifier
+        L, nl = H * H, c.num_labels
+        NLp = -(-nl // 32) * 32
+        seq = _ln(lib, t, P["swin.layernorm.weight"], P["swin.layernorm.bias"], F32, B * L, C, eps, torch.float32)
+        pooled = torch.empty((B, C), **f32)
+        _lib.check(lib.ocm_op_swin_pool(_p(seq), _p(pooled), B, L, C, _stream()))
+        meta["hidden"] = seq.view(B, L, C)
+        logits = _linear(lib, prec, _operand(pooled, prec), W.w("classifier.weight", rows=NLp),
+                         F.pad(P["classifier.bias"].detach(), (0, NLp - nl)), None, B, NLp, _kpad(C, prec))
+        keep += [t, pooled]
+        meta["kept_bytes"] = sum(k.numel() * k.element_size() for k in keep if k is not None)
+        # through save_for_backward: autograd frees them after the backward, refuses a second backward over the same graph and
+        # raises if a parameter is modified in place between this forward and the backward
+        ctx.meta, ctx.prec = meta, prec
+        ctx.save_for_backward(x, *keep, *params)
+        return logits[:, :nl].contiguous(), pooled
+
+    @staticmethod
+    def backward(ctx, dlogits, dpooled):
+        meta, prec = ctx.meta, ctx.prec
+        model, keys = meta["model"], meta["keys"]
+        c = model.config
+        lib = _lib.load()
+        st = ctx.saved_tensors
+        nkeep = len(st) - 1 - len(keys)
+        x, keep, P = st[0], list(st[1:1 + nkeep]), dict(zip(keys, st[1 + nkeep:]))
+        need = dict(zip(keys, ctx.needs_input_grad[2:]))
+        dev = x.device
+        f32 = dict(device=dev, dtype=torch.float32)
+        W = _Weights(model, P, prec)
+        eps = float(c.layer_norm_eps)
+        grads = {}
+
+        # units in forward order: the backward walks them in reverse and stops after the earliest one that has a parameter
+        # needing a gradient (a classifier-only fine-tune does not walk the encoder)
+        units = [("emb", "swin.embeddings.")]
+        for s in range(c.num_layers):
+            units += [("layer", f"swin.encoder.layers.{s}.blocks.{b}.") for b in range(c.depths[s])]
+            if s + 1 < c.num_layers:
+                units.append(("merge", f"swin.encoder.layers.{s}.downsample."))
+        units.append(("head", None))
+        heads_keys = ("swin.layernorm.weight", "swin.layernorm.bias", "classifier.weight", "classifier.bias")
+        wanted = [any(need[k] for k in keys if (k.startswith(pre) if pre else k in heads_keys)) for _, pre in units]
+        stop = wanted.index(True)
+
+        def wgrad(dy, xin, wkey, bkey, rows=None):
+            if need.get(wkey) or (bkey and need.get(bkey)):
+                dw, db = _weight_grad(prec, dy, xin, bool(bkey and need.get(bkey)))
+                if need.get(wkey):
+                    grads[wkey] = dw[:rows] if rows else dw
+                if bkey and need.get(bkey):
+                    grads[bkey] = db[:rows] if rows else db
+
+        def lngrads(pre, dg, db):
+            for k, v in ((pre + "weight", dg), (pre + "bias", db)):
+                if need[k]:
+                    grads[k] = v
+
+        # geometry of every unit, walking forward
+        geo, H, C = [], c.image_size // c.patch_size, c.embed_dim
+        B = x.shape[0]
+        for s in range(c.num_layers):
+            geo += [(s, b, H, C) for b in range(c.depths[s])]
+            if s + 1 < c.num_layers:
+                geo.append((s, None, H, C))
+                H, C = H // 2, 2 * C
+        L, nl = H * H, c.num_labels
+        NLp = -(-nl // 32) * 32
+        tL, pooled = keep[-2], keep[-1]
+        with torch.cuda.device(dev):
+            # head: logits = pooled W^T + b (rows padded to NLp), pooled = mean_l LayerNorm(tL)
+            dl = torch.zeros((B, NLp), **f32)
+            if dlogits is not None:
+                dl[:, :nl] = dlogits
+            wgrad(dl, pooled, "classifier.weight", "classifier.bias", rows=nl)
+            dx = None
+            if stop < len(units) - 1 or need["swin.layernorm.weight"] or need["swin.layernorm.bias"]:
+                dp = _linear(lib, prec, _operand(dl, prec), W.wt("classifier.weight", rows=NLp), torch.zeros(C, **f32), None,
+                             B, C, _kpad(NLp, prec))
+                if dpooled is not None:
+                    dp = dp + dpooled
+                dseq = torch.empty((B * L, C), **f32)
+                _lib.check(lib.ocm_op_swin_pool_backward(_p(dp), _p(dseq), B, L, C, _stream()))
+                dx, dg, db = _ln_backward(lib, dseq, tL, P["swin.layernorm.weight"], None, B * L, C, eps)
+                lngrads("swin.layernorm.", dg, db)
+            ki = len(keep) - 2
+            for u in reversed(range(1, len(units) - 1)):
+                if u < stop:
+                    break
+                kind, pre = units[u]
+                s, b, H, C = geo[u - 1]
+                T = B * H * H
+                if kind == "merge":
+                    ki -= 1
+                    xin = keep[ki]
+                    T4, C2 = B * (H // 2) ** 2, 2 * C
+                    if need[pre + "reduction.weight"]:
+                        y32 = torch.empty((T4, 4 * C), **f32)
+                        _lib.check(lib.ocm_op_swin_merge_ln(_lib.OCM_PREC_FP32, _p(xin), _p(P[pre + "norm.weight"]),
+                                                            _p(P[pre + "norm.bias"]), _p(y32), B, H, H, C, 4 * C, _stream()))
+                        wgrad(dx, y32, pre + "reduction.weight", None)
+                        del y32
+                    dy = _linear(lib, prec, _operand(dx, prec), W.wt(pre + "reduction.weight"), torch.zeros(4 * C, **f32), None,
+                                 T4, 4 * C, _kpad(C2, prec))
+                    gth = torch.empty((T4, 4 * C), **f32)
+                    _lib.check(lib.ocm_op_swin_merge_gather(_p(xin), _p(gth), B, H, H, C, _stream()))
+                    dg4, dg, db = _ln_backward(lib, dy, gth, P[pre + "norm.weight"], None, T4, 4 * C, 1e-5)
+                    lngrads(pre + "norm.", dg, db)
+                    del dy, gth
+                    dx = torch.empty((T, C), **f32)
+                    _lib.check(lib.ocm_op_swin_merge_scatter(_p(dg4), _p(dx), B, H, H, C, _stream()))
+                    continue
+                # a SwinLayer: x1 = t + drop_path(o_proj(attn(LN1(t)))), x2 = x1 + fc2(gelu(fc1(LN2(x1))))
+                ki -= 6
+                t, qkv, cx, x1, hpre, scale = keep[ki:ki + 6]
+                heads, M, ws = c.num_heads[s], int(c.mlp_ratio * C), c.window_size
+                shift = ws // 2 if b % 2 and H > ws else 0
+                a = pre + "attention."
+                dh = _linear(lib, prec, _operand(dx, prec), W.wt(pre + "mlp.fc2.weight"), torch.zeros(M, **f32), None, T, M,
+                             _kpad(C, prec))
+                g32 = torch.empty((T, M), **f32)
+                _lib.check(lib.ocm_op_gelu_backward(_p(dh), _p(hpre), _p(dh), _p(g32), T * M, _stream()))
+                wgrad(dx, g32, pre + "mlp.fc2.weight", pre + "mlp.fc2.bias")
+                del g32
+                g2 = P[pre + "layernorm_after.weight"]
+                if need[pre + "mlp.fc1.weight"] or need[pre + "mlp.fc1.bias"]:
+                    xn2 = _ln(lib, x1, g2, P[pre + "layernorm_after.bias"], _lib.OCM_LN_F32, T, C, eps, torch.float32)
+                    wgrad(dh, xn2, pre + "mlp.fc1.weight", pre + "mlp.fc1.bias")
+                    del xn2
+                dxn2 = _linear(lib, prec, _operand(dh, prec), W.wt(pre + "mlp.fc1.weight"), torch.zeros(C, **f32), None, T, C,
+                               _kpad(M, prec))
+                del dh
+                dx1, dg, db = _ln_backward(lib, dxn2, x1, g2, dx, T, C, eps)
+                lngrads(pre + "layernorm_after.", dg, db)
+                del dxn2, dx
+                dbr = dx1
+                if scale is not None:
+                    dbr = torch.empty((T, C), **f32)
+                    _lib.check(lib.ocm_op_swin_drop_path_backward(_p(dx1), _p(scale), _p(dbr), B, H * H, C, _stream()))
+                if need[a + "o_proj.weight"] or need[a + "o_proj.bias"]:
+                    wgrad(dbr, _ctx_f32(cx, C, prec), a + "o_proj.weight", a + "o_proj.bias")
+                dctx = _linear(lib, prec, _operand(dbr, prec), W.wt(a + "o_proj.weight"), torch.zeros(C, **f32), None, T, C,
+                               _kpad(C, prec))
+                del dbr
+                tkey = a + "relative_position_bias.relative_position_bias_table"
+                dqkv = torch.empty((T, 3 * C), **f32)
+                dtab = torch.empty(P[tkey].shape, **f32)
+                nbytes = lib.ocm_swin_window_attention_backward_workspace_bytes(B, H, H, ws, heads)
+                wsb = _ws(nbytes, dev)
+                _lib.check(lib.ocm_op_swin_window_attention_backward(_p(qkv), _p(dctx), _p(P[tkey]), _p(dqkv), _p(dtab), B,
+                                                                     H, H, ws, shift, heads, _p(wsb), nbytes, _stream()))
+                if need[tkey]:
+                    grads[tkey] = dtab
+                del dctx, wsb
+                g1 = P[pre + "layernorm_before.weight"]
+                pk = [a + n + "_proj." for n in "qkv"]
+                if any(need[k + "weight"] or need[k + "bias"] for k in pk):
+                    xn1 = _ln(lib, t, g1, P[pre + "layernorm_before.bias"], _lib.OCM_LN_F32, T, C, eps, torch.float32)
+                    dw, dbq = _weight_grad(prec, dqkv, xn1, True)
+                    for i, k in enumerate(pk):
+                        if need[k + "weight"]:
+                            grads[k + "weight"] = dw[i * C:(i + 1) * C]
+                        if need[k + "bias"]:
+                            grads[k + "bias"] = dbq[i * C:(i + 1) * C]
+                    del xn1
+                dxn1 = _linear(lib, prec, _operand(dqkv, prec), W.wt(*[k + "weight" for k in pk]), torch.zeros(C, **f32), None,
+                               T, C, _kpad(3 * C, prec))
+                del dqkv
+                dx, dg, db = _ln_backward(lib, dxn1, t, g1, dx1, T, C, eps)
+                lngrads(pre + "layernorm_before.", dg, db)
+                del dxn1, dx1
+            if stop == 0:  # embeddings: tok = patch rows x W^T + b, t0 = LayerNorm(tok)
+                e = "swin.embeddings."
+                C, H = c.embed_dim, c.image_size // c.patch_size
+                T, Cin = B * H * H, c.num_channels
+                dtok, dg, db = _ln_backward(lib, dx, keep[0], P[e + "norm.weight"], None, T, C, 1e-5)
+                lngrads(e + "norm.", dg, db)
+                wk = e + "patch_embeddings.projection."
+                if need[wk + "weight"] or need[wk + "bias"]:
+                    cols = torch.empty((T, Cin * 16), **f32)
+                    _lib.check(lib.ocm_op_patch_unfold(_p(x), _p(cols), B, Cin, c.image_size, c.image_size, c.patch_size,
+                                                       _stream()))
+                    cols = _pad_cols(cols, -(-Cin * 16 // 32) * 32)
+                    dw, dbe = _weight_grad(prec, dtok, cols, True)
+                    if need[wk + "weight"]:
+                        grads[wk + "weight"] = dw[:, :Cin * 16]
+                    if need[wk + "bias"]:
+                        grads[wk + "bias"] = dbe
+        out = []
+        for k in keys:
+            g = grads.get(k)
+            p = P[k]
+            out.append(None if g is None else g.contiguous().reshape(p.shape).to(dtype=p.dtype))
+        return (None, None, *out)

@@ -27,6 +27,16 @@ GEOMS = {
     "mim384": dict(dim=384, depth=2, heads=3, patch=8, img_size=384, batch=2, seed=41, variant="sharp"),
     "mim320": dict(dim=384, depth=2, heads=3, patch=8, img_size=320, batch=2, seed=42, variant="sharp"),
 }
+# the same two shapes on the precision stress weights (qkv gain 8): split-bf16 and fp32 hold TOL, single bf16 is not claimed on
+# peaked attention (README) and only has to stay finite
+PEAKED_GEOMS = {
+    "wrap_mim_hd128_peaked": dict(WRAPPER_CASES["wrap_mim_hd128"], variant="peaked"),
+    "mim320_peaked": dict(GEOMS["mim320"], variant="peaked"),
+}
+GEOMS.update(PEAKED_GEOMS)
+# x_rec on the stress weights: test_model_gpu.py's stress-set ladder (10x the unpeaked one). The forward is that ill-conditioned
+# there: torch's fp32 eager twin on the CPU is itself 2.8e-5 (wrap_mim_hd128_peaked) and 1.5e-5 (mim320_peaked) from float64.
+FWD_TOL_STRESS = {"fp32": 2e-4, "bf16x3": 2e-3}
 
 
 @pytest.fixture(scope="module")
@@ -121,9 +131,20 @@ def test_xrec_backward_matches_float64(dev, name, precision):
     loss, rec, _ = mim(x, mask)
     assert rec.grad_fn is not None and loss.grad_fn is not None
     rec64, _, ref = _reference(name, "rec")
-    assert _rel(rec, rec64) <= FWD_TOL[precision]
+    unclaimed = name in PEAKED_GEOMS and precision == "bf16"
+    if not unclaimed:
+        assert _rel(rec, rec64) <= (FWD_TOL_STRESS if name in PEAKED_GEOMS else FWD_TOL)[precision]
     rec.backward(_upstream(rec.shape).to(device=dev, dtype=torch.float32))
-    _check_grads(mim, ref, TOL[precision])
+    if unclaimed:
+        errs = {n: _rel(p.grad, ref[n]) for n, p in mim.named_parameters()}
+        worst = max(errs, key=errs.get)
+        print(f"GPUTEST mim train {name} bf16 (not claimed): x_rec {_rel(rec, rec64):.3e}, worst gradient {worst} {errs[worst]:.3e}")
+        assert all(bool(torch.isfinite(p.grad).all()) for p in mim.parameters()) and bool(torch.isfinite(rec).all())
+        return
+    errs = _check_grads(mim, ref, TOL[precision])
+    if name in PEAKED_GEOMS:
+        worst = max(errs, key=errs.get)
+        print(f"GPUTEST mim train {name} {precision}: x_rec {_rel(rec, rec64):.3e}, worst gradient {worst} {errs[worst]:.3e}")
 
 
 @pytest.mark.parametrize("precision", ["fp32", "bf16x3", "bf16"])

@@ -20,7 +20,9 @@ pytestmark = pytest.mark.gpu
 # measured worst (MI355X): fp32 2.9e-5, bf16x3 9.4e-5, bf16 5.3e-2 (geometry F, 1000 labels); limits about 3x that
 TOL = {"fp32": 1e-4, "bf16x3": 3e-4, "bf16": 1.5e-1}
 # Swin-T at 224^2 with train.py's 5 labels and per-device batch 8, and the unpadded geometries of tests/golden_cases.py
-CASES = {"swin_t": dict(cfg=dict(synth.SWIN_TINY), batch=8, seed=71, qk_gain=4.0)}
+CASES = {"swin_t": dict(cfg=dict(synth.SWIN_TINY), batch=8, seed=71, qk_gain=4.0),
+         # q / k projections x8 and the relative-position table x200: peaked windows. Single bf16 is not claimed there (README)
+         "swin_t_peaked": dict(cfg=dict(synth.SWIN_TINY), batch=8, seed=71, qk_gain=8.0)}
 CASES.update({f"geom_{k}": dict(cfg=dict(synth.SWIN_TINY, **SWIN_GEOMETRIES[k]["cfg"]), batch=SWIN_GEOMETRIES[k]["batch"],
                                 seed=SWIN_GEOMETRIES[k]["seed"], qk_gain=SWIN_GEOMETRIES[k]["qk_gain"]) for k in "BCEFH"})
 
@@ -152,6 +154,10 @@ def test_grads_match_float64(dev, name, precision):
     """Drop-path rate 0: loss.backward() fills every parameter's .grad, relative-position tables and classifier included."""
     m, x, labels, up = _model(name, precision, dev)
     _loss(m, x, labels, up).backward()
+    if name == "swin_t_peaked" and precision == "bf16":  # printed, finite
+        _check(m, _reference(name), float("inf"), f"{name} {precision} (not claimed)")
+        assert all(bool(torch.isfinite(p.grad).all()) for p in m.parameters())
+        return
     _check(m, _reference(name), TOL[precision], f"{name} {precision}")
 
 

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define OCM_ABI_VERSION 14
+#define OCM_ABI_VERSION 15
 
 enum {
     OCM_OK = 0,
@@ -468,6 +468,19 @@ size_t ocm_patch_embed_backward_workspace_bytes(int32_t batch, int32_t n_tokens,
 int ocm_op_patch_embed_backward(const float *dtok, const float *mask, float *dpatch, float *dmask_token, float *dpos,
                                 int32_t batch, int32_t n_tokens, int32_t dim, void *workspace, size_t workspace_bytes,
                                 void *stream);
+
+/* ---- sigmoid Dice loss (utils.py:410-424: finetune.py's loss; kernels_train.hip) ----
+ * loss = 1 - (2 I + smooth) / (sum p + sum t + smooth) with p = sigmoid(logits), I = sum p t over `count` >= 1 fp32 elements.
+ * One pass writes per-workgroup partial sums into the workspace, a finishing launch adds them in a fixed order (no atomics:
+ * the same bits on every run) and writes sums_out[3] = (I, sum p, sum t) and loss_out[1] to device memory; nothing
+ * synchronises with the host. 16-byte loads when both pointers are 16-byte aligned, a scalar tail for any count. */
+size_t ocm_dice_loss_workspace_bytes(size_t count);
+int ocm_op_dice_loss(const float *logits, const float *targets, float *loss_out, float *sums_out, size_t count, float smooth,
+                     void *workspace, size_t workspace_bytes, void *stream);
+/* dlogits = -g (2 t S - (2 I + smooth)) / S^2 * p (1 - p), S = sum p + sum t + smooth, g = grad_loss[0]; `sums` (what
+ * ocm_op_dice_loss wrote) and grad_loss are device memory. Elementwise, every element of dlogits written. */
+int ocm_op_dice_loss_backward(const float *logits, const float *targets, const float *sums, const float *grad_loss,
+                              float *dlogits, size_t count, float smooth, void *stream);
 
 /* ---- k-means feature clustering (eval.py --method k-means_feature_clustering, utils.py:171-197; kernels_cluster.hip) ----
  * X is the fp32 [S*S][dim] feature matrix, row y*S + x; dim % 4 == 0 and 4 <= dim <= 1024. Every reduction runs in a fixed

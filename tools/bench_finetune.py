@@ -1,0 +1,172 @@
+"""Time one finetune.py --finetune True training step on the HIP path: B = 3 images of 384^2, build_finetune_model()'s encoder
+(ViT-S/8: depth 12, 6 heads of 64, patch 8) under LinearProbing(encoder, 8, layer_num=2), utils.DiceLoss, Adam on every parameter.
+Reports medians per phase (the weight re-pack that every forward after optimizer.step() runs, training forward + loss, backward,
+optimizer step; `step` is their sum), the attention-backward kernels alone at (B 3, H 6, N 2305, hd 64) with their FLOP rate, the
+peak memory of a step and, as a yardstick, a plain-PyTorch fp32 eager twin of the same step on the same GPU, timed in alternation in
+the same process. The backward's split by kernel class comes from a kernel trace of this tool (rocprofv3 --kernel-trace --stats).
+
+  python tools/bench_finetune.py [--batch 3] [--img 384] [--depth 12] [--precision bf16x3] [--reps 5]
+"""
+import argparse
+import json
+import math
+import os
+import socket
+import sys
+import time
+from functools import partial
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import vit_ocm_wmsegmentation_amd  # noqa: E402,F401
+from vit_ocm_wmsegmentation_amd import _lib  # noqa: E402
+from vit_ocm_wmsegmentation_amd import model as M  # noqa: E402
+from vit_ocm_wmsegmentation_amd import utils as U  # noqa: E402
+
+
+class EagerTwin(nn.Module):
+    """VisionTransformerForFinetune + LinearProbing's two-layer decoder (model.py:110-174) in plain torch fp32."""
+
+    def __init__(self, D, depth, heads, p, img):
+        super().__init__()
+        self.p, self.h, self.img = p, heads, img
+        self.proj = nn.Conv2d(3, D, p, p)
+        self.cls = nn.Parameter(torch.randn(1, 1, D) * .02)
+        self.pos = nn.Parameter(torch.randn(1, (224 // p) ** 2 + 1, D) * .02)
+        self.blocks = nn.ModuleList([nn.ModuleDict(dict(n1=nn.LayerNorm(D, eps=1e-6), qkv=nn.Linear(D, 3 * D),
+                                                        proj=nn.Linear(D, D), n2=nn.LayerNorm(D, eps=1e-6),
+                                                        fc1=nn.Linear(D, 4 * D), fc2=nn.Linear(4 * D, D)))
+                                     for _ in range(depth)])
+        self.norm = nn.LayerNorm(D, eps=1e-6)
+        s2 = p * p
+        self.dec = nn.Sequential(nn.Conv2d(D, 4 * s2, 3, padding=1), nn.BatchNorm2d(4 * s2), nn.ReLU(inplace=True),
+                                 nn.Conv2d(4 * s2, s2, 3, padding=1), nn.PixelShuffle(p))
+
+    def forward(self, x):
+        t = self.proj(x).flatten(2).transpose(1, 2)
+        B, L, D = t.shape
+        t = torch.cat((self.cls.expand(B, -1, -1), t), 1)
+        n0 = self.pos.shape[1] - 1
+        side, s = int(math.sqrt(n0)), self.img // self.p + 0.1
+        g = F.interpolate(self.pos[:, 1:].reshape(1, side, side, D).permute(0, 3, 1, 2),
+                          scale_factor=(s / math.sqrt(n0), s / math.sqrt(n0)), mode="bicubic")
+        t = t + torch.cat((self.pos[:, :1], g.permute(0, 2, 3, 1).reshape(1, -1, D)), 1)
+        H = self.h
+        for b in self.blocks:
+            q, k, v = b["qkv"](b["n1"](t)).reshape(B, L + 1, 3, H, D // H).permute(2, 0, 3, 1, 4)
+            a = ((q @ k.transpose(-2, -1)) * (D // H) ** -0.5).softmax(-1)
+            t = t + b["proj"]((a @ v).transpose(1, 2).reshape(B, L + 1, D))
+            t = t + b["fc2"](F.gelu(b["fc1"](b["n2"](t))))
+        z = self.norm(t)[:, 1:].transpose(1, 2).reshape(B, D, int(L ** .5), int(L ** .5))
+        return self.dec(z)
+
+
+def eager_dice(inputs, targets, smooth=1):
+    p = torch.sigmoid(inputs).view(-1)
+    t = targets.view(-1)
+    return 1 - (2. * (p * t).sum() + smooth) / (p.sum() + t.sum() + smooth)
+
+
+def _timed(fn):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    out = fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b), out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=3)
+    ap.add_argument("--img", type=int, default=384)
+    ap.add_argument("--depth", type=int, default=12)
+    ap.add_argument("--precision", default="bf16x3", choices=sorted(_lib.PRECISIONS))
+    ap.add_argument("--reps", type=int, default=5)
+    args = ap.parse_args()
+    dev = torch.device("cuda:0")
+    B, S, p, D, H = args.batch, args.img, 8, 384, 6
+    torch.manual_seed(0)
+    enc = M.VisionTransformerForFinetune(patch_size=p, embed_dim=D, depth=args.depth, num_heads=H, mlp_ratio=4, img_size=[S],
+                                         qkv_bias=True, norm_layer=partial(nn.LayerNorm, eps=1e-6), interpolate_encoding=True)
+    enc.enable_finetune()  # what build_finetune_model does
+    lp = M.LinearProbing(enc, p, layer_num=2).to(dev).train()
+    enc.set_precision(args.precision)
+    loss_fn = U.DiceLoss()
+    opt = torch.optim.Adam(lp.parameters(), lr=1e-4)
+    twin = EagerTwin(D, args.depth, H, p, S).to(dev).train()
+    opt_t = torch.optim.Adam(twin.parameters(), lr=1e-4)
+    x = torch.rand(B, 3, S, S, device=dev) * 0.3
+    y = (torch.rand(B, 1, S, S, device=dev) < 0.3).float()
+
+    def hip_step():
+        opt.zero_grad(set_to_none=True)
+        # the engine re-packs its weight copies on their new (data_ptr, _version) inside the forward; timed on its own here
+        tr, _ = _timed(lambda: enc._engine(dev))
+        tf, loss = _timed(lambda: loss_fn(lp(x), y))
+        tb, _ = _timed(lambda: loss.backward())
+        to, _ = _timed(opt.step)
+        return tr, tf, tb, to
+
+    def twin_step():
+        opt_t.zero_grad(set_to_none=True)
+        t0 = time.perf_counter()
+        eager_dice(twin(x), y).backward()
+        opt_t.step()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3
+
+    # the attention-backward kernels alone at the step's shape
+    N = (S // p) ** 2 + 1
+    lib = _lib.load()
+    qkv = torch.randn(3, B, H, N, D // H, device=dev)
+    do, lse, delta = torch.randn(B * N, D, device=dev), torch.randn(B * H, N, device=dev) + 10, torch.randn(B * H, N, device=dev)
+    dqkv = torch.empty(B * N, 3 * D, device=dev)
+
+    def attn_bwd():
+        _lib.check(lib.ocm_op_attention_backward(qkv.data_ptr(), lse.data_ptr(), do.data_ptr(), delta.data_ptr(),
+                                                 dqkv.data_ptr(), B, N, H, D // H, (D // H) ** -0.5, None))
+
+    def peak_of(step):
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        rest = torch.cuda.memory_allocated()
+        step()
+        torch.cuda.synchronize()
+        return torch.cuda.max_memory_allocated(), torch.cuda.max_memory_allocated() - rest
+
+    for _ in range(2):  # warm-up: packing, LDS opt-in, allocator, Adam state
+        hip_step()
+        twin_step()
+        attn_bwd()
+    torch.cuda.synchronize()
+    rows = {k: [] for k in ("repack", "fwd", "bwd", "opt", "step", "twin", "attn_bwd")}
+    for _ in range(args.reps):
+        tr, tf, tb, to = hip_step()
+        rows["repack"].append(tr)
+        rows["fwd"].append(tf)
+        rows["bwd"].append(tb)
+        rows["opt"].append(to)
+        rows["step"].append(tr + tf + tb + to)
+        rows["twin"].append(twin_step())
+        rows["attn_bwd"].append(_timed(attn_bwd)[0])
+    med = {k: sorted(v)[len(v) // 2] for k, v in rows.items()}
+    peak_hip, step_hip = peak_of(hip_step)
+    peak_twin, step_twin = peak_of(twin_step)
+    flops = 14 * B * H * N * N * (D // H)  # dK/dV kernel: S, dP, dV, dK; dQ kernel: S, dP, dQ (2 N^2 hd each)
+    res = dict(box=socket.gethostname(), gpu=torch.cuda.get_device_name(0), batch=B, img=S, depth=args.depth,
+               precision=args.precision, ms={k: round(v, 3) for k, v in med.items()},
+               attn_bwd_tflops=round(flops / (med["attn_bwd"] * 1e-3) / 1e12, 1),
+               attn_bwd_ms_all_blocks=round(med["attn_bwd"] * args.depth, 3),
+               speedup_vs_eager=round(med["twin"] / med["step"], 2),
+               peak_mib=dict(hip_total=round(peak_hip / 2 ** 20, 1), hip_step=round(step_hip / 2 ** 20, 1),
+                             eager_total=round(peak_twin / 2 ** 20, 1), eager_step=round(step_twin / 2 ** 20, 1)),
+               reps=args.reps)
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()

@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # OCM_VIT_LIB lets kernel experiments A/B two builds of the same ABI; the default is the in-tree build.
 LIB_PATH = os.environ.get("OCM_VIT_LIB") or os.path.join(_HERE, "libocm_vit.so")
 
-OCM_ABI_VERSION = 14
+OCM_ABI_VERSION = 15
 OCM_OK, OCM_EINVAL, OCM_ESTATE, OCM_EHIP, OCM_ENOMEM, OCM_ENAME = 0, 1, 2, 3, 4, 5
 
 OCM_PREC_BF16 = 0
@@ -202,6 +202,9 @@ SIGNATURES = {
     "ocm_op_patch_unfold": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "ocm_patch_embed_backward_workspace_bytes": (_sz, [_i32, _i32, _i32]),
     "ocm_op_patch_embed_backward": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _sz, _vp]),
+    "ocm_dice_loss_workspace_bytes": (_sz, [_sz]),
+    "ocm_op_dice_loss": (C.c_int, [_vp, _vp, _vp, _vp, _sz, _f32, _vp, _sz, _vp]),
+    "ocm_op_dice_loss_backward": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _sz, _f32, _vp]),
     "ocm_op_kmeans_features": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "ocm_kmeans_zscore_workspace_bytes": (_sz, [_i32, _i32]),
     "ocm_op_kmeans_zscore": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _sz, _vp]),

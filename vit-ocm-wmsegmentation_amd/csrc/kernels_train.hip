@@ -12,6 +12,9 @@
 //   gelu_kernel / gelu_bwd_kernel        erf GELU of the fp32 fc1 pre-activation (fc2's operand) and its backward
 //   patch_unfold_kernel                  image -> [B*P][C*p*p] rows of the patch-embedding weight gradient
 //   patch_grad_kernel / token_sum_kernel the mask blend's split of the token gradient, and the batch sum (cls / pos gradients)
+// and finetune.py's loss:
+//   dice_partial_kernel / dice_finish    sigmoid Dice loss: per-workgroup sums of p t, p and t, added in a fixed order
+//   dice_bwd_kernel                      its gradient into the logits, elementwise
 // The forward's BatchNorm-affine + ReLU operand writer is the AFFINE variant of im2col3x3_kernel (kernels_misc.hip).
 #include "host_common.h"
 #include "launch.h"
@@ -434,6 +437,124 @@ __global__ __launch_bounds__(256) void token_sum_kernel(const float *__restrict_
     }
 }
 
+// ---- sigmoid Dice loss (utils.py:410-424: finetune.py's loss) ----
+// p = sigmoid(x) and p (1 - p) from one exponential of -|x|: no overflow at any x, no cancellation in 1 - p.
+__device__ __forceinline__ void sigmoid_parts(float x, float &p, float &pq) {
+    const float e = expf(-fabsf(x)), r = 1.0f / (1.0f + e);
+    p = x >= 0.f ? r : e * r;
+    pq = e * r * r;
+}
+
+// The count is cut into G spans (a function of the count alone, every span a multiple of four elements); workgroup g sums
+// p t, p and t over span g: per thread in index order, the wave by the fixed butterfly, the four waves in wave order, and
+// writes part[k][g]. dice_finish_kernel adds the G partials of each sum (lane l takes g = l, l + 64, ..., then the same
+// butterfly) and writes the three sums and the loss. Fixed order everywhere: the same bits on every run. VEC: 16-byte
+// loads (both pointers 16-byte aligned), the last span's tail of fewer than four elements scalar.
+constexpr int DICE_SPAN = 4096, DICE_MAX_WG = 1024;
+
+struct DicePlan {
+    size_t span;
+    int groups;
+};
+
+DicePlan dice_plan(size_t count) {
+    const size_t g0 = std::min<size_t>((count + DICE_SPAN - 1) / DICE_SPAN, DICE_MAX_WG);
+    DicePlan p;
+    p.span = ((count + g0 - 1) / g0 + 3) / 4 * 4;
+    p.groups = (int)((count + p.span - 1) / p.span);
+    return p;
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void dice_partial_kernel(const float *__restrict__ x, const float *__restrict__ t,
+                                                           float *__restrict__ part, size_t count, size_t span) {
+    __shared__ float red[3][4];
+    const size_t begin = (size_t)blockIdx.x * span, end = std::min<size_t>(count, begin + span);
+    const size_t n = end - begin, nv = VEC ? n / 4 : 0;
+    const float *xs = x + begin, *ts = t + begin;
+    float s_pt = 0.f, s_p = 0.f, s_t = 0.f;
+    for (size_t i = threadIdx.x; i < nv; i += 256) {
+        const f32x4 xv = ((const f32x4 *)xs)[i], tv = ((const f32x4 *)ts)[i];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            float p, pq;
+            sigmoid_parts(xv[e], p, pq);
+            s_pt = fmaf(p, tv[e], s_pt);
+            s_p += p;
+            s_t += tv[e];
+        }
+    }
+    for (size_t i = 4 * nv + threadIdx.x; i < n; i += 256) {
+        float p, pq;
+        sigmoid_parts(xs[i], p, pq);
+        s_pt = fmaf(p, ts[i], s_pt);
+        s_p += p;
+        s_t += ts[i];
+    }
+    s_pt = wave_sum(s_pt);
+    s_p = wave_sum(s_p);
+    s_t = wave_sum(s_t);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) {
+        red[0][wave] = s_pt;
+        red[1][wave] = s_p;
+        red[2][wave] = s_t;
+    }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        const float *r = red[threadIdx.x];
+        part[(size_t)threadIdx.x * gridDim.x + blockIdx.x] = ((r[0] + r[1]) + r[2]) + r[3];
+    }
+}
+
+__global__ __launch_bounds__(64) void dice_finish_kernel(const float *__restrict__ part, int G, float smooth,
+                                                         float *__restrict__ sums, float *__restrict__ loss) {
+    float s[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        float a = 0.f;
+        for (int g = threadIdx.x; g < G; g += 64) a += part[(size_t)k * G + g];
+        s[k] = wave_sum(a);
+    }
+    if (threadIdx.x == 0) {
+        sums[0] = s[0];
+        sums[1] = s[1];
+        sums[2] = s[2];
+        *loss = 1.0f - (2.0f * s[0] + smooth) / (s[1] + s[2] + smooth);
+    }
+}
+
+// dx = -g (2 t S - (2 I + s)) / S^2 p (1 - p) with S = sum p + sum t + s: c1 t + c0 times p (1 - p), c1 = -2 g / S,
+// c0 = g (2 I + s) / S^2 (sums and g read from device memory by every thread: three cached words)
+template <bool VEC>
+__global__ __launch_bounds__(256) void dice_bwd_kernel(const float *__restrict__ x, const float *__restrict__ t,
+                                                       const float *__restrict__ sums, const float *__restrict__ gloss,
+                                                       float *__restrict__ dx, size_t count, float smooth) {
+    const float g = *gloss, S = sums[1] + sums[2] + smooth;
+    const float c1 = -2.0f * g / S, c0 = g * (2.0f * sums[0] + smooth) / (S * S);
+    const size_t nv = VEC ? count / 4 : 0, stride = (size_t)gridDim.x * 256, tid = (size_t)blockIdx.x * 256 + threadIdx.x;
+    for (size_t i = tid; i < nv; i += stride) {
+        const f32x4 xv = ((const f32x4 *)x)[i], tv = ((const f32x4 *)t)[i];
+        f32x4 o;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            float p, pq;
+            sigmoid_parts(xv[e], p, pq);
+            o[e] = fmaf(c1, tv[e], c0) * pq;
+        }
+        ((f32x4 *)dx)[i] = o;
+    }
+    for (size_t i = 4 * nv + tid; i < count; i += stride) {
+        float p, pq;
+        sigmoid_parts(x[i], p, pq);
+        dx[i] = fmaf(c1, t[i], c0) * pq;
+    }
+}
+
+bool aligned16(const void *a, const void *b, const void *c = nullptr) {
+    return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15) == 0;
+}
+
 size_t grid_of(size_t work, size_t cap) { return std::max<size_t>(1, std::min<size_t>((work + 255) / 256, cap)); }
 
 int prec_ok(int32_t precision) {
@@ -626,6 +747,46 @@ extern "C" int ocm_op_patch_embed_backward(const float *dtok, const float *mask,
                                       dim, s));
     const size_t nd = (size_t)n_tokens * dim;
     token_sum_kernel<<<dim3((unsigned)grid_of(nd, 4096)), dim3(256), 0, s>>>(dtok, dpos, batch, nd);
+    HIP_TRY(hipGetLastError());
+    return OCM_OK;
+}
+
+// ---- C ABI (include/ocm_vit.h, "Dice loss") ------------------------------------------------------------------------------
+extern "C" size_t ocm_dice_loss_workspace_bytes(size_t count) {
+    if (count == 0) return 0;
+    return (size_t)3 * dice_plan(count).groups * sizeof(float);
+}
+
+extern "C" int ocm_op_dice_loss(const float *logits, const float *targets, float *loss_out, float *sums_out, size_t count,
+                                float smooth, void *workspace, size_t workspace_bytes, void *stream) {
+    if (!logits || !targets || !loss_out || !sums_out) return fail(OCM_EINVAL, "null argument");
+    if (count == 0) return fail(OCM_EINVAL, "bad count");
+    const size_t need = ocm_dice_loss_workspace_bytes(count);
+    if (!workspace || workspace_bytes < need)
+        return fail(OCM_ENOMEM, "dice_loss workspace: %zu bytes given, %zu needed", workspace_bytes, need);
+    const hipStream_t s = (hipStream_t)stream;
+    const DicePlan p = dice_plan(count);
+    float *part = (float *)workspace;
+    if (aligned16(logits, targets))
+        dice_partial_kernel<true><<<dim3(p.groups), dim3(256), 0, s>>>(logits, targets, part, count, p.span);
+    else
+        dice_partial_kernel<false><<<dim3(p.groups), dim3(256), 0, s>>>(logits, targets, part, count, p.span);
+    HIP_TRY(hipGetLastError());
+    dice_finish_kernel<<<dim3(1), dim3(64), 0, s>>>(part, p.groups, smooth, sums_out, loss_out);
+    HIP_TRY(hipGetLastError());
+    return OCM_OK;
+}
+
+extern "C" int ocm_op_dice_loss_backward(const float *logits, const float *targets, const float *sums, const float *grad_loss,
+                                         float *dlogits, size_t count, float smooth, void *stream) {
+    if (!logits || !targets || !sums || !grad_loss || !dlogits) return fail(OCM_EINVAL, "null argument");
+    if (count == 0) return fail(OCM_EINVAL, "bad count");
+    const dim3 grid((unsigned)grid_of((count + 3) / 4, 4096)), block(256);
+    const hipStream_t s = (hipStream_t)stream;
+    if (aligned16(logits, targets, dlogits))
+        dice_bwd_kernel<true><<<grid, block, 0, s>>>(logits, targets, sums, grad_loss, dlogits, count, smooth);
+    else
+        dice_bwd_kernel<false><<<grid, block, 0, s>>>(logits, targets, sums, grad_loss, dlogits, count, smooth);
     HIP_TRY(hipGetLastError());
     return OCM_OK;
 }

@@ -12,8 +12,10 @@ decoders run token-major as one MFMA GEMM + a pixel-shuffle kernel. The SimMIM e
 with grad mode on and a parameter that requires grad, the encoder runs as the stand-alone operators under one autograd
 Function (_EncoderTrain) whose backward is HIP (kernels_train.hip, kernels_train_attn.hip). LinearProbing
 also trains: in training mode with a frozen encoder (no encoder parameter requires grad: finetune.py's linear
-probing) its decoder runs with batch statistics and differentiates through HIP kernels (_DecoderTrain). The
-reference initialises mask_token with timm's trunc_normal_; here the package's own trunc_normal_ (dino/utils.py)
+probing) its decoder runs with batch statistics and differentiates through HIP kernels (_DecoderTrain). With a
+trainable VisionTransformerForFinetune that has opted in (enable_finetune(): build_finetune_model does) the same decoder also
+returns the gradient of the patch tokens and the encoder differentiates through _EncoderTrain without a mask: finetune.py
+--finetune True. The reference initialises mask_token with timm's trunc_normal_; here the package's own trunc_normal_ (dino/utils.py)
 with the same bounds is used.
 """
 import ctypes as C
@@ -83,11 +85,25 @@ class VisionTransformerForFinetune(_FmapEncoder):
         super().__init__(**kwargs)
         self.img_size = img_size
         self.interpolate_encoding = interpolate_encoding
+        self.finetune_backward = False  # a plain attribute: not a parameter, not a buffer, not in the state_dict
 
     def _trunc_normal_(self, tensor, mean=0., std=1.):
         trunc_normal_(tensor, mean=mean, std=std, a=-std, b=std)
 
+    def enable_finetune(self, flag=True):
+        """Opt this encoder in to (or out of) the HIP backward: in training mode with grad mode on and a trainable parameter,
+        forward() and LinearProbing.forward() then build a graph into the encoder's parameters (finetune.py --finetune True).
+        build_finetune_model() turns it on; a directly constructed encoder keeps the graph-free behaviour."""
+        self.finetune_backward = bool(flag)
+        return self
+
     def forward(self, x):
+        if _finetunes(self):
+            _check_trainable(self, x, masked=False)
+            tokens = _encode_train(self, x, None)
+            B, N, D = tokens.shape
+            side = int((N - 1) ** 0.5)  # model.py:136-138
+            return tokens[:, 1:].transpose(1, 2).reshape(B, D, side, side)
         return self._encode(x)
 
 
@@ -204,8 +220,9 @@ class LinearProbing(nn.Module):
         conv1, bn, _, conv2, _ = self.two_layer_decoder
         if bn.training:
             raise NotImplementedError("training mode runs on the HIP path only with a frozen encoder (linear probing: set "
-                                      "requires_grad=False on every encoder parameter); the ViT backward is not "
-                                      "implemented. For inference call .eval()")
+                                      "requires_grad=False on every encoder parameter) or with an encoder that has opted "
+                                      "in to fine-tuning (encoder.enable_finetune(); build_finetune_model does). For "
+                                      "inference call .eval()")
         enc, dev, lib = self.encoder, tokens.device, _lib.load()
         prec = _lib.PRECISIONS[enc._precision]
         B, N, D = tokens.shape
@@ -246,9 +263,13 @@ class LinearProbing(nn.Module):
         return not any(p.requires_grad for p in self.encoder.parameters())
 
     def forward(self, x):
+        if self.training and _finetunes(self.encoder):  # finetune.py --finetune True: the encoder trains too
+            _check_trainable(self.encoder, x, masked=False)
+            _require_hip(x, "input")
+            return _train_forward(self, _encode_train(self.encoder, x, None))
         _require_hip(x, "input")
-        if self.training and self._encoder_frozen():
-            with torch.no_grad():
+        if self.training and (self._encoder_frozen() or getattr(self.encoder, "finetune_backward", False)):
+            with torch.no_grad():  # (an opted-in encoder that is not differentiated right now: no_grad, or its own eval mode)
                 tokens = self.encoder._encode(x, tokens=True)
             return _train_forward(self, tokens)
         with torch.no_grad():
@@ -306,7 +327,9 @@ def _cached_operand(cache, name, w, prec, make):
 
 class _DecoderTrain(torch.autograd.Function):
     """One training-mode decoder call: forward(patches, *params) -> (B, c_out, hp*s, wp*s); backward -> parameter gradients
-    only (the patch tokens come from the frozen encoder and get none). `meta` carries the module, its precision and, for the
+    and, when the patch tokens carry a graph (a trainable encoder), dPatches (B, P, D) fp32: dlin W for the 1x1 head, conv1's
+    data gradient (the 3x3 pad-1 convolution of dy1 with the flipped, channel-transposed kernel) for the two-layer decoder.
+    Patch tokens from a frozen encoder get none and cost nothing. `meta` carries the module, its precision and, for the
     caller, the batch statistics of the forward (the running-statistics update happens outside the graph)."""
 
     @staticmethod
@@ -375,8 +398,11 @@ class _DecoderTrain(torch.autograd.Function):
         lp, prec = meta["module"], meta["prec"]
         B, hp, wp, D, M = ctx.shape
         s, lib = lp.encoder_stride, _lib.load()
-        need = ctx.needs_input_grad[2:]
+        need, need_x = ctx.needs_input_grad[2:], ctx.needs_input_grad[1]
         dev = grad_out.device
+        f32 = dict(device=dev, dtype=torch.float32)
+        cache = lp._dec_cache.setdefault("train", {})
+        dpatches = None
 
         def put(t, like):  # the gradient on the parameter's own device and dtype
             return None if t is None else t.reshape(like.shape).to(device=like.device, dtype=like.dtype)
@@ -386,13 +412,20 @@ class _DecoderTrain(torch.autograd.Function):
             conv = lp.one_layer_decoder[0]
             with torch.cuda.device(dev):
                 dlin = _pixel_shuffle_backward(grad_out, M, s, hp, wp)
-                dw, db = _weight_grad(prec, dlin, x2d, need[1])
+                dw = db = None
+                if need[0] or need[1]:
+                    dw, db = _weight_grad(prec, dlin, x2d, need[1])
+                if need_x:  # dX = dlin W as ocm_op_linear on the operand copy of W^T
+                    O = conv.out_channels
+                    wt = _cached_operand(cache, "w_head_t", conv.weight, prec,
+                                         lambda: to_operand(conv.weight.detach().reshape(O, D).t().to(**f32).contiguous(), prec))
+                    dpatches = _linear(lib, prec, to_operand(dlin, prec), wt, torch.zeros(D, **f32), None, M, D, O)
+                    dpatches = dpatches.reshape(B, M // B, D)
             grads = [put(dw, conv.weight) if need[0] else None, put(db, conv.bias) if need[1] else None]
-            return (None, None, *grads)
+            return (None, dpatches, *grads)
         patches, y1, mean, invstd, g, h = ctx.saved_tensors
         conv1, bn, _, conv2, _ = lp.two_layer_decoder
         mid, oc = conv1.out_channels, conv2.out_channels
-        f32 = dict(device=dev, dtype=torch.float32)
         grads = [None] * 6
         with torch.cuda.device(dev):
             dy2 = _pixel_shuffle_backward(grad_out, M, s, hp, wp)  # (M, oc)
@@ -404,9 +437,8 @@ class _DecoderTrain(torch.autograd.Function):
                 del a2
                 grads[4] = put(dw2.reshape(oc, 3, 3, mid).permute(0, 3, 1, 2), conv2.weight) if need[4] else None
                 grads[5] = put(db2, conv2.bias) if need[5] else None
-            if any(need[:4]):
+            if any(need[:4]) or need_x:
                 # conv2's data gradient: a 3x3 pad-1 convolution of dY2 with the flipped, channel-transposed kernel
-                cache = lp._dec_cache.setdefault("train", {})
                 w2f = _cached_operand(cache, "w2_flip", conv2.weight, prec,
                                       lambda: to_operand(flip_conv3x3(conv2.weight.detach().to(**f32)).contiguous(), prec))
                 d2 = torch.empty((M, 9 * oc), dtype=_OPERAND_DTYPE[prec], device=dev)
@@ -433,13 +465,21 @@ class _DecoderTrain(torch.autograd.Function):
                     del a1
                     grads[0] = put(dw1.reshape(mid, 3, 3, D).permute(0, 3, 1, 2), conv1.weight) if need[0] else None
                     grads[1] = put(db1, conv1.bias) if need[1] else None
-        return (None, None, *grads)
+                if need_x:  # conv1's data gradient, by the same construction (K = 9 mid, N = D)
+                    w1f = _cached_operand(cache, "w1_flip", conv1.weight, prec,
+                                          lambda: to_operand(flip_conv3x3(conv1.weight.detach().to(**f32)).contiguous(), prec))
+                    d1 = torch.empty((M, 9 * mid), dtype=_OPERAND_DTYPE[prec], device=dev)
+                    _lib.check(lib.ocm_op_im2col3x3(prec, _p(dy1), _p(d1), B, hp, wp, mid, 0, _stream()))
+                    dpatches = _linear(lib, prec, d1, w1f, torch.zeros(D, **f32), None, M, D, 9 * mid).reshape(B, hp * wp, D)
+                    del d1
+        return (None, dpatches, *grads)
 
 
 def _train_forward(lp, tokens):
-    """LinearProbing.forward in training mode on a frozen encoder: the decoder with batch statistics (layer_num 2), the
-    running statistics updated as nn.BatchNorm2d updates them, and a graph into the decoder's parameters when grad mode is
-    on. The normed tokens (B, N, D) come from the encoder without a graph."""
+    """LinearProbing.forward in training mode: the decoder with batch statistics (layer_num 2), the running statistics
+    updated as nn.BatchNorm2d updates them, and a graph into the decoder's parameters when grad mode is on. The normed tokens
+    (B, N, D) come from a frozen encoder without a graph, or carry one (a trainable encoder, or a leaf that requires grad):
+    then the patch gradient of _DecoderTrain goes back into rows 1..N-1 and the CLS row, which no decoder reads, gets zeros."""
     B, N, D = tokens.shape
     patches = tokens[:, 1:].contiguous()
     prec = _lib.PRECISIONS[lp.encoder._precision]
@@ -486,6 +526,11 @@ def _differentiable(module):
     return module.training and torch.is_grad_enabled() and any(p.requires_grad for p in module.parameters())
 
 
+def _finetunes(enc):
+    """A VisionTransformerForFinetune that has opted in (enable_finetune) and has something to train right now."""
+    return getattr(enc, "finetune_backward", False) and _differentiable(enc)
+
+
 def _check_mask(enc, x, mask):
     """The SimMIM mask must hold one entry per patch of every image (the kernels read B * P of them), as the eval path's
     Engine.forward_tiles requires."""
@@ -496,8 +541,9 @@ def _check_mask(enc, x, mask):
         raise ValueError(f"{got}, expected {npatch}")
 
 
-def _check_trainable(enc, x, encoder=True, mask=None):
-    """What the training path refuses, before anything is launched (`encoder`: the encoder itself is to be differentiated)."""
+def _check_trainable(enc, x, encoder=True, mask=None, masked=True):
+    """What the training path refuses, before anything is launched (`encoder`: the encoder itself is to be differentiated;
+    `masked`: it blends a mask token in, VisionTransformerForSimMIM, and needs one mask entry per patch)."""
     hd = enc.embed_dim // enc._hyper["num_heads"]
     if encoder and hd not in (64, 128):
         raise NotImplementedError(f"training the encoder needs 64- or 128-wide heads (the attention backward is built for "
@@ -507,7 +553,7 @@ def _check_trainable(enc, x, encoder=True, mask=None):
                                   "does not require grad")
     if encoder and enc._gray_fold:
         raise NotImplementedError("the grayscale-folded patch embedding is inference only; disable it for training")
-    if encoder:
+    if encoder and masked:
         _check_mask(enc, x, mask)
 
 
@@ -528,10 +574,22 @@ def _encoder_params(enc):
     return out
 
 
+def _first_block_to_train(enc, named):
+    """The lowest block with a trainable parameter (len(blocks) when none has one) when nothing below the blocks trains — the
+    patch embedding, cls_token, pos_embed and a mask_token are all frozen — else 0. Below it the forward keeps nothing and the
+    backward does not go: the remaining gradients come from the same operators in the same order, so they keep their bits."""
+    if any(p.requires_grad for n, p in named if not n.startswith(("blocks.", "norm."))):
+        return 0
+    trainable = [int(n.split(".")[1]) for n, p in named if n.startswith("blocks.") and p.requires_grad]
+    return min(trainable) if trainable else len(enc.blocks)
+
+
 def _encode_train(enc, x, mask):
-    """Differentiable VisionTransformerForSimMIM token path: (B, N, D) normed tokens with a graph into the encoder's parameters."""
+    """Differentiable token path of VisionTransformerForSimMIM (with its mask) and of VisionTransformerForFinetune (mask None:
+    no blend): (B, N, D) normed tokens with a graph into the encoder's parameters."""
     x = enc._check_input(x).contiguous()
-    _check_mask(enc, x, mask)
+    if mask is not None or "mask_token" in enc._parameters:
+        _check_mask(enc, x, mask)
     eng = enc._engine(x.device)
     npatch = (x.shape[-2] // eng.p) * (x.shape[-1] // eng.p)
     side = enc.img_size[0]
@@ -541,6 +599,7 @@ def _encode_train(enc, x, mask):
     pos = enc._pos_for(npatch, side, side, x.device)
     named = _encoder_params(enc)
     meta = {"enc": enc, "eng": eng, "names": [n for n, _ in named], "pos": pos, "side": side, "npatch": npatch,
+            "first": _first_block_to_train(enc, named),
             "mask": mask.reshape(x.shape[0], -1).to(torch.float32).contiguous() if mask is not None else None}
     with torch.cuda.device(x.device):
         return _EncoderTrain.apply(meta, x, *[p for _, p in named])
@@ -574,8 +633,8 @@ def _linear(lib, prec, a_op, w_op, bias, resid, M, N, K, epi=_lib.OCM_EPI_BIAS_F
 
 
 class _EncoderTrain(torch.autograd.Function):
-    """The SimMIM encoder in training mode: forward(meta, x, *params) -> normed tokens (B, N, D); backward -> parameter
-    gradients. Per block it keeps the block input (norm1's input), qkv_f32, lse2, the context in the operand type, norm2's input
+    """The SimMIM / fine-tuning encoder in training mode: forward(meta, x, *params) -> normed tokens (B, N, D); backward ->
+    parameter gradients. Per block from meta["first"] on (_first_block_to_train) it keeps the block input (norm1's input), qkv_f32, lse2, the context in the operand type, norm2's input
     and the fp32 fc1 pre-activation: (5 + mlp_ratio) * N * D * 4 bytes per image plus the context (2 or 4 bytes per element)
     — 35 MB per block per image at 384^2, D = 384. The LayerNorm outputs are recomputed in fp32."""
 
@@ -631,7 +690,8 @@ class _EncoderTrain(torch.autograd.Function):
             x2 = _linear(lib, prec, g, op(pre + "mlp.fc2.weight"), _vec(P.get(pre + "mlp.fc2.bias"), D, dev), x1, T, D, Mh,
                          _lib.OCM_EPI_BIAS_RESID_F32)
             del g
-            saved.append((t, qkv, lse, cx, x1, hpre))
+            if i >= meta["first"]:
+                saved.append((t, qkv, lse, cx, x1, hpre))
             t = x2
         out = _ln(lib, t, P["norm.weight"], _vec(P.get("norm.bias"), D, dev), _lib.OCM_LN_F32, T, D, eps, torch.float32)
         # through save_for_backward: autograd frees them after the backward, refuses a second backward over the same graph
@@ -648,8 +708,8 @@ class _EncoderTrain(torch.autograd.Function):
         B, N, D, H, hd, T, Mh, eps, prec = ctx.dims
         need = dict(zip(names, ctx.needs_input_grad[2:]))
         st = ctx.saved_tensors
-        x, xL, nb = st[0], st[1], ctx.nblocks
-        blocks = [st[2 + 6 * i:8 + 6 * i] for i in range(nb)]
+        x, xL, nb, first = st[0], st[1], ctx.nblocks, meta["first"]
+        blocks = {first + i: st[2 + 6 * i:8 + 6 * i] for i in range(nb)}
         params = dict(zip(names, st[2 + 6 * nb:]))
         lib, dev = _lib.load(), gout.device
         f32 = dict(device=dev, dtype=torch.float32)
@@ -675,6 +735,10 @@ class _EncoderTrain(torch.autograd.Function):
                 if need.get(bname):
                     grads[bname] = db
 
+        def put(n):  # the gradient on the parameter's own device and dtype
+            g, p = grads.get(n), params[n]
+            return None if g is None else g.reshape(p.shape).to(device=p.device, dtype=p.dtype)
+
         def lngrads(pre, dg, db):
             if need.get(pre + ".weight"):
                 grads[pre + ".weight"] = dg
@@ -685,7 +749,7 @@ class _EncoderTrain(torch.autograd.Function):
             dT = gout.detach().to(torch.float32).contiguous().reshape(T, D)
             dx, dg, db = _ln_backward(lib, dT, xL, params["norm.weight"], None, T, D, eps)
             lngrads("norm", dg, db)
-            for i in reversed(range(len(enc.blocks))):
+            for i in reversed(range(first, len(enc.blocks))):
                 pre = f"blocks.{i}."
                 blk = enc.blocks[i]
                 xin, qkv, lse, cx, x1, hpre = blocks[i]
@@ -727,6 +791,8 @@ class _EncoderTrain(torch.autograd.Function):
                 dx, dg, db = _ln_backward(lib, dxn1, xin, g1w, dx1, T, D, eps)
                 lngrads(pre + "norm1", dg, db)
                 del dxn1, dx1
+            if first > 0 or not any(need.get(n) for n in names if not n.startswith(("blocks.", "norm."))):
+                return (None, None, *[put(n) for n in names])  # nothing below the blocks trains
             # tokens t = cat(cls, patch * (1 - w) + mask_token * w) + pos
             mask = meta["mask"]
             P_ = N - 1
@@ -752,12 +818,7 @@ class _EncoderTrain(torch.autograd.Function):
                     full = enc._interpolated_pos(meta["npatch"], meta["side"], meta["side"], pos=pe)
                     (gpe,) = torch.autograd.grad(full, pe, dpos.cpu().reshape(full.shape))
                 grads["pos_embed"] = gpe
-        out = []
-        for n in names:
-            g = grads.get(n)
-            p = params[n]
-            out.append(None if g is None else g.reshape(p.shape).to(device=p.device, dtype=p.dtype))
-        return (None, None, *out)
+        return (None, None, *[put(n) for n in names])
 
 
 class _MIMHeadTrain(torch.autograd.Function):
@@ -816,7 +877,7 @@ def build_finetune_model(args):
                                            norm_layer=partial(nn.LayerNorm, eps=1e-6), interpolate_encoding=True)
     state_dict = get_state_dict(args)
     encoder.load_state_dict(state_dict, strict=False)
-    return encoder
+    return encoder.enable_finetune()  # finetune.py trains every parameter of this encoder (args.finetune = True)
 
 
 def get_state_dict(args):

@@ -6,11 +6,13 @@ region-query index of analyse_attention.py, on device.
   threshold           reference utils.py:55-115 (the three Otsu masks of eval.py's "ours" / "otsu" /
                       "heatmap_threshold" methods), on device
   kmeans_feature      reference utils.py:171-197 (eval.py's "k-means_feature_clustering"), clustered on device
+  DiceLoss            reference utils.py:410-424 (finetune.py's loss), forward and backward on device
 """
 import ctypes as C
 
 import numpy as np
 import torch
+import torch.nn as nn
 
 from . import _lib
 from .engine import _p, _require_hip, _stream
@@ -182,3 +184,53 @@ def kmeans_feature(img, features, output_directory="", save=False, name=None):
     X = features.reshape(rows, D).to(device=dev, dtype=torch.float32, copy=True).contiguous()
     labels = kmeans_feature_labels(X)["labels"]
     return labels.reshape(S, S) * 255
+
+
+class _DiceLossFn(torch.autograd.Function):
+    """loss = 1 - (2 sum(p t) + smooth) / (sum p + sum t + smooth), p = sigmoid(logits): two launches forward (per-workgroup
+    partial sums, then their fixed-order sum and the loss, all in device memory), one elementwise launch backward."""
+
+    @staticmethod
+    def forward(ctx, logits, targets, smooth):
+        lib, dev, n = _lib.load(), logits.device, logits.numel()
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        sums = torch.empty(3, dtype=torch.float32, device=dev)
+        nbytes = lib.ocm_dice_loss_workspace_bytes(n)
+        ws = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(lib.ocm_op_dice_loss(_p(logits), _p(targets), _p(loss), _p(sums), n, smooth, _p(ws), nbytes, _stream()))
+        ctx.smooth = smooth
+        ctx.save_for_backward(logits, targets, sums)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_loss):
+        logits, targets, sums = ctx.saved_tensors
+        g = grad_loss.detach().to(device=logits.device, dtype=torch.float32).reshape(1).contiguous()
+        dlogits = torch.empty_like(logits)
+        with torch.cuda.device(logits.device):
+            _lib.check(_lib.load().ocm_op_dice_loss_backward(_p(logits), _p(targets), _p(sums), _p(g), _p(dlogits),
+                                                             logits.numel(), ctx.smooth, _stream()))
+        return dlogits, None, None
+
+
+class DiceLoss(nn.Module):
+    """utils.py:410-424: sigmoid Dice loss over all elements, forward(inputs, targets, smooth=1) -> 0-dim fp32 tensor,
+    differentiable into `inputs` (the gradient arrives in the inputs' own dtype and layout through torch's cast / contiguous
+    nodes). Both tensors must live on a HIP device; they are made contiguous fp32 first. Works under torch.no_grad()."""
+
+    def __init__(self):
+        super().__init__()
+
+    def forward(self, inputs, targets, smooth=1):
+        if isinstance(targets, torch.Tensor) and targets.requires_grad:
+            raise NotImplementedError("DiceLoss does not produce the gradient of the targets; pass targets that do not "
+                                      "require grad")
+        _require_hip(inputs, "inputs")
+        _require_hip(targets, "targets")
+        if inputs.numel() != targets.numel() or inputs.numel() == 0:
+            raise ValueError(f"inputs {tuple(inputs.shape)} and targets {tuple(targets.shape)} must hold the same, non-zero "
+                             "number of elements")
+        x = inputs.to(torch.float32).contiguous().reshape(-1)
+        t = targets.detach().to(device=inputs.device, dtype=torch.float32).contiguous().reshape(-1)
+        return _DiceLossFn.apply(x, t, float(smooth))

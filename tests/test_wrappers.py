@@ -202,3 +202,105 @@ def test_reference_build_model_runs_with_128_channel_heads(dev):
     assert float((a16.cpu() - oattn[0]).abs().max()) <= 1e-3
     r16 = enc.get_last_attention_rows(x.to(dev), torch.tensor([0, 7], dtype=torch.int32, device=dev))
     assert float((r16 - a16[:, :, [0, 7], 1:]).abs().max()) < 2e-5
+
+
+# ---- a decoder bias that moves while its weight stays put: the next forward reads the new bias ------------------------------
+# Each check compares, with torch.equal, against a freshly constructed module that holds the same parameter values: it has no
+# cached operand to be stale and runs the same kernels, so no tolerance is needed. (The head once kept its bias under the
+# weight's cache key. An fp32 bias on the device was cached as an alias of the parameter's storage, so an in-place update
+# still showed; a bias given new storage under the same Parameter — "rebound" — did not.)
+def _mim(c, state, precision, dev):
+    enc = M.VisionTransformerForSimMIM(**_kw(c))
+    mim = M.MIM(enc, c["patch"])
+    mim.patch_size = c["patch"]
+    msg = mim.load_state_dict(state, strict=True)
+    assert not msg.missing_keys and not msg.unexpected_keys
+    enc.set_precision(precision)
+    return mim.to(dev)
+
+
+def _mim_state(c, sd):
+    wp3 = synth.synth_wrapper_params(c["dim"], c["patch"], 3, seed=c["seed"])
+    state = {"encoder." + k: v for k, v in sd.items()}
+    state.update({"encoder.mask_token": wp3["mask_token"], "decoder.0.weight": wp3["decoder.weight"],
+                  "decoder.0.bias": wp3["decoder.bias"]})
+    return state
+
+
+def _shift_bias(conv, how):
+    """Move the bias by 0.5 and leave the weight untouched: in place, or as new storage under the same Parameter."""
+    if how == "in_place":
+        conv.bias.data.add_(0.5)
+    else:
+        conv.bias.data = conv.bias.data + 0.5
+
+
+def _only_decoder_bias_trains(mim):
+    for p in mim.encoder.parameters():
+        p.requires_grad_(False)
+    mim.decoder[0].weight.requires_grad_(False)
+    return mim.train()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("how", ["in_place", "rebound"])
+@pytest.mark.parametrize("precision", ["fp32", "bf16x3"])
+def test_mim_eval_follows_decoder_bias(dev, precision, how):
+    c, sd, x, mask = _case("wrap_p8_64")
+    mim = _mim(c, _mim_state(c, sd), precision, dev).eval()
+    first = mim(x.to(dev), mask)[1]
+    _shift_bias(mim.decoder[0], how)
+    second = mim(x.to(dev), mask)[1]
+    fresh = _mim(c, mim.state_dict(), precision, dev).eval()
+    assert torch.equal(fresh.decoder[0].bias, mim.decoder[0].bias)
+    assert torch.equal(second, fresh(x.to(dev), mask)[1])
+    assert not torch.equal(second, first)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("how", ["in_place", "rebound"])
+@pytest.mark.parametrize("precision", ["fp32", "bf16x3"])
+def test_linear_probing_eval_follows_decoder_bias(dev, precision, how):
+    c, sd, x, _ = _case("wrap_p8_64")
+    wp1 = synth.synth_wrapper_params(c["dim"], c["patch"], 1, seed=c["seed"])
+
+    def build(state):
+        fin = M.VisionTransformerForFinetune(**_kw(c))
+        lp = M.LinearProbing(fin, c["patch"], layer_num=1)
+        msg = lp.load_state_dict(state, strict=False)  # (the unused two-layer decoder keeps its own initial values)
+        assert not msg.unexpected_keys and all(k.startswith("two_layer_decoder.") for k in msg.missing_keys)
+        fin.set_precision(precision)
+        return lp.to(dev).eval()
+
+    state = {"encoder." + k: v for k, v in sd.items()}
+    state.update({"one_layer_decoder.0.weight": wp1["decoder.weight"], "one_layer_decoder.0.bias": wp1["decoder.bias"]})
+    lp = build(state)
+    first = lp(x.to(dev))
+    _shift_bias(lp.one_layer_decoder[0], how)
+    second = lp(x.to(dev))
+    fresh = build({k: v for k, v in lp.state_dict().items() if not k.startswith("two_layer_decoder.")})
+    assert torch.equal(fresh.one_layer_decoder[0].bias, lp.one_layer_decoder[0].bias)
+    assert torch.equal(second, fresh(x.to(dev)))
+    assert not torch.equal(second, first)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("precision", ["fp32", "bf16x3"])
+def test_mim_training_follows_decoder_bias_after_a_step_on_it_alone(dev, precision):
+    """The decoder's weight and the encoder are frozen and one SGD step moves the bias: the next training-mode forward
+    reconstructs with the stepped bias."""
+    c, sd, x, mask = _case("wrap_p8_64")
+    mim = _only_decoder_bias_trains(_mim(c, _mim_state(c, sd), precision, dev))
+    opt = torch.optim.SGD([mim.decoder[0].bias], lr=1.0)
+    loss, first, _ = mim(x.to(dev), mask)
+    loss.backward()
+    before = mim.decoder[0].bias.detach().clone()
+    opt.step()
+    assert not torch.equal(mim.decoder[0].bias, before)
+    second = mim(x.to(dev), mask)[1]
+    fresh = _only_decoder_bias_trains(_mim(c, mim.state_dict(), precision, dev))
+    assert torch.equal(fresh.decoder[0].bias, mim.decoder[0].bias)
+    want = fresh(x.to(dev), mask)[1]
+    assert second.grad_fn is not None and want.grad_fn is not None
+    assert torch.equal(second, want)
+    assert not torch.equal(second, first)

@@ -134,10 +134,10 @@ def main():
 
     tokens = torch.randn(B, N, D, device=dev, requires_grad=True)
     conv = mim.decoder[0]
-    dmeta = {"enc": enc, "conv": conv, "stride": p, "cache": mim._dec_cache}
+    dmeta = M._head_meta(mim)
 
-    def decoder():  # MIM's decoder alone: forward + backward into its weights and the tokens
-        M._MIMHeadTrain.apply(dmeta, tokens, conv.weight, conv.bias).sum().backward()
+    def decoder():  # MIM's decoder alone: forward + backward into its weight, its bias and the tokens (the CLS row gets zeros)
+        M._PixelShuffleHead.apply(dmeta, tokens[:, 1:].contiguous(), conv.weight, conv.bias).sum().backward()
 
     def attn_bwd():
         _lib.check(lib.ocm_op_attention_backward(qkv.data_ptr(), lse.data_ptr(), do.data_ptr(), delta.data_ptr(),

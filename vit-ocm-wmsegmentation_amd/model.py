@@ -8,15 +8,17 @@
 
 Same constructor arguments, attributes and state_dict keys. The encoders run in one engine call (the mask
 blend is fused into the patch-embedding epilogue, the (B,C,H,W) permute is a device transpose); the 1x1-conv
-decoders run token-major as one MFMA GEMM + a pixel-shuffle kernel. The SimMIM encoder and MIM train: in training mode
-with grad mode on and a parameter that requires grad, the encoder runs as the stand-alone operators under one autograd
-Function (_EncoderTrain) whose backward is HIP (kernels_train.hip, kernels_train_attn.hip). LinearProbing
+decoders run token-major as one MFMA GEMM + a pixel-shuffle kernel: one head (_head_forward, differentiable as
+_PixelShuffleHead) serves MIM and LinearProbing(layer_num=1) in eval and in training mode. The SimMIM encoder and MIM train:
+in training mode with grad mode on and a parameter that requires grad, the encoder runs as the stand-alone operators under
+one autograd Function (_EncoderTrain) whose backward is HIP (kernels_train.hip, kernels_train_attn.hip). LinearProbing
 also trains: in training mode with a frozen encoder (no encoder parameter requires grad: finetune.py's linear
-probing) its decoder runs with batch statistics and differentiates through HIP kernels (_DecoderTrain). With a
-trainable VisionTransformerForFinetune that has opted in (enable_finetune(): build_finetune_model does) the same decoder also
-returns the gradient of the patch tokens and the encoder differentiates through _EncoderTrain without a mask: finetune.py
---finetune True. The reference initialises mask_token with timm's trunc_normal_; here the package's own trunc_normal_ (dino/utils.py)
-with the same bounds is used.
+probing) its decoder differentiates through HIP kernels (_PixelShuffleHead; the two-layer decoder, with batch statistics,
+_DecoderTrain). With a trainable VisionTransformerForFinetune that has opted in (enable_finetune(): build_finetune_model
+does) the same decoders also return the gradient of the patch tokens and the encoder differentiates through _EncoderTrain
+without a mask: finetune.py --finetune True. Every cached operand copy of a decoder weight is keyed on the tensors it is made
+from (_cached_operand); biases are read on every call. The reference initialises mask_token with timm's trunc_normal_; here
+the package's own trunc_normal_ (dino/utils.py) with the same bounds is used.
 """
 import ctypes as C
 import os
@@ -35,19 +37,19 @@ class _FmapEncoder(VisionTransformer):
     """Shared body of the two encoders: prepare tokens (optionally masked), all blocks, final norm, drop the
     CLS token and return the (B, C, H, W) map."""
 
+    def _positions(self, npatch, device):
+        """The (N, D) position table of a forward over npatch patches: interpolated for the CONFIGURED size (model.py:38-39,
+        124-125); at 224 the reference adds pos_embed itself (model.py:40-41,126-127), which needs the native token count."""
+        side = self.img_size[0]
+        if side == 224 and npatch != self.pos_embed.shape[1] - 1:
+            raise RuntimeError(f"The size of tensor a ({npatch + 1}) must match the size of tensor b "
+                               f"({self.pos_embed.shape[1]}) at non-singleton dimension 1")
+        return self._pos_for(npatch, side, side, device)
+
     def _encode(self, x, mask=None, tokens=False):
         x = self._check_input(x)
         eng = self._engine(x.device)
-        npatch = (x.shape[-2] // eng.p) * (x.shape[-1] // eng.p)
-        side = self.img_size[0]
-        if side != 224:  # model.py:38-39,124-125: positions interpolated for the CONFIGURED size
-            pos = self._pos_for(npatch, side, side, x.device)
-        else:  # model.py:40-41,126-127: x + self.pos_embed needs the native token count
-            n0 = self.pos_embed.shape[1] - 1
-            if npatch != n0:
-                raise RuntimeError(f"The size of tensor a ({npatch + 1}) must match the size of tensor b ({n0 + 1}) "
-                                   "at non-singleton dimension 1")
-            pos = self._pos_for(n0, 224, 224, x.device)
+        pos = self._positions((x.shape[-2] // eng.p) * (x.shape[-1] // eng.p), x.device)
         flags = _lib.OCM_OUT_FEAT if tokens else _lib.OCM_OUT_FMAP
         out = eng.forward(x, pos, flags=flags, patch_mask=mask)
         if tokens:
@@ -73,10 +75,7 @@ class VisionTransformerForSimMIM(_FmapEncoder):
         assert mask is not None
         if _differentiable(self):
             _check_trainable(self, x, mask=mask)
-            tokens = _encode_train(self, x, mask.to(x.device))
-            B, N, D = tokens.shape
-            side = int((N - 1) ** 0.5)  # model.py:50-52
-            return tokens[:, 1:].transpose(1, 2).reshape(B, D, side, side)
+            return _tokens_to_fmap(_encode_train(self, x, mask.to(x.device)))
         return self._encode(x, mask=mask.to(x.device))
 
 
@@ -100,44 +99,20 @@ class VisionTransformerForFinetune(_FmapEncoder):
     def forward(self, x):
         if _finetunes(self):
             _check_trainable(self, x, masked=False)
-            tokens = _encode_train(self, x, None)
-            B, N, D = tokens.shape
-            side = int((N - 1) ** 0.5)  # model.py:136-138
-            return tokens[:, 1:].transpose(1, 2).reshape(B, D, side, side)
+            return _tokens_to_fmap(_encode_train(self, x, None))
         return self._encode(x)
 
 
-def _conv1x1_pixel_shuffle(encoder, tokens, conv, stride, cache):
-    """Conv2d(D, s*s*c, 1) + PixelShuffle(s) evaluated on the token-major normed tokens (B, N, D): one GEMM over
-    the patch rows and a scatter. Returns (B, c, hp*s, wp*s) fp32."""
+def _tokens_to_fmap(tokens):
+    """Normed tokens (B, N, D) -> the (B, D, side, side) map of the patch rows (model.py:50-52,136-138: H = W = int(L ** 0.5))."""
     B, N, D = tokens.shape
-    O = conv.out_channels
-    c_out = O // (stride * stride)
-    hp = wp = int((N - 1) ** 0.5)
-    prec = _lib.PRECISIONS[encoder._precision]
-    dev = tokens.device
-    lib = _lib.load()
-    key = (conv.weight.data_ptr(), conv.weight._version, prec)
-    if cache.get("key") != key:  # operand copy of the (O, D, 1, 1) weight in the engine's element type
-        w32 = conv.weight.detach().reshape(O, D).to(device=dev, dtype=torch.float32).contiguous()
-        w = to_operand(w32, prec)
-        bias = (conv.bias.detach() if conv.bias is not None else torch.zeros(O)).to(device=dev, dtype=torch.float32)
-        cache.update(key=key, w=w, bias=bias.contiguous())
-    patches = tokens[:, 1:].contiguous()  # (B, P, D) fp32: drop the CLS row
-    M = B * (N - 1)
-    lin = torch.empty((M, O), dtype=torch.float32, device=dev)
-    out = torch.empty((B, c_out, hp * stride, wp * stride), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        a = to_operand(patches.reshape(M, D), prec)
-        _lib.check(lib.ocm_op_linear(prec, _p(a), _p(cache["w"]), _p(cache["bias"]), None, _p(lin), M, O, D,
-                                     _lib.OCM_EPI_BIAS_F32, _stream()))
-        _lib.check(lib.ocm_op_pixel_shuffle(_p(lin), _p(out), B, hp, wp, c_out, stride, _stream()))
-    return out
+    side = int((N - 1) ** 0.5)
+    return tokens[:, 1:].transpose(1, 2).reshape(B, D, side, side)
 
 
 def _pixel_shuffle_head(channels, stride, out_mult):
     """Conv2d(channels, stride^2 * out_mult, 1) -> PixelShuffle(stride): the decoder head of model.py:60-66,147-152.
-    Kept as torch modules for their parameters / state_dict keys; the arithmetic runs in _conv1x1_pixel_shuffle."""
+    Kept as torch modules for their parameters / state_dict keys; the arithmetic runs in _head_forward."""
     return nn.Sequential(nn.Conv2d(channels, stride * stride * out_mult, kernel_size=1), nn.PixelShuffle(stride))
 
 
@@ -173,12 +148,9 @@ class MIM(nn.Module):
         else:
             with torch.no_grad():
                 tokens = enc._encode(x, mask=mask, tokens=True)
-        if train:
-            conv = self.decoder[0]
-            meta = {"enc": enc, "conv": conv, "stride": self.encoder_stride, "cache": self._dec_cache}
-            x_rec = _MIMHeadTrain.apply(meta, tokens, conv.weight, conv.bias)
-        else:
-            x_rec = _conv1x1_pixel_shuffle(enc, tokens, self.decoder[0], self.encoder_stride, self._dec_cache)
+        conv = self.decoder[0]
+        head = _PixelShuffleHead.apply if train else _head_forward
+        x_rec = head(_head_meta(self), tokens[:, 1:].contiguous(), conv.weight, conv.bias)
         # masked L1 reconstruction loss (model.py:71-73) — training bookkeeping, a handful of elementwise torch ops
         p = self.patch_size
         m32 = mask.to(torch.float32).contiguous()
@@ -223,66 +195,71 @@ class LinearProbing(nn.Module):
                                       "requires_grad=False on every encoder parameter) or with an encoder that has opted "
                                       "in to fine-tuning (encoder.enable_finetune(); build_finetune_model does). For "
                                       "inference call .eval()")
-        enc, dev, lib = self.encoder, tokens.device, _lib.load()
-        prec = _lib.PRECISIONS[enc._precision]
+        dev, cache = tokens.device, self._dec_cache
+        prec = _lib.PRECISIONS[self.encoder._precision]
         B, N, D = tokens.shape
         hp = wp = int((N - 1) ** 0.5)
-        key = tuple((t.data_ptr(), t._version) for t in (conv1.weight, conv1.bias, bn.weight, bn.bias, bn.running_mean,
-                                                         bn.running_var, conv2.weight, conv2.bias)) + (prec,)
-        c = self._dec_cache
-        if c.get("key2") != key:
-            f32 = dict(device=dev, dtype=torch.float32)
-            g = (bn.weight.detach().to(**f32) / torch.sqrt(bn.running_var.detach().to(**f32) + bn.eps))
-            w1 = conv1.weight.detach().to(**f32) * g[:, None, None, None]
-            b1 = (conv1.bias.detach().to(**f32) - bn.running_mean.detach().to(**f32)) * g + bn.bias.detach().to(**f32)
-            # (O, C, 3, 3) -> (O, 3, 3, C): the K order of ocm_op_im2col3x3
-            w1 = w1.permute(0, 2, 3, 1).reshape(w1.shape[0], -1).contiguous()
-            w2 = conv2.weight.detach().to(**f32).permute(0, 2, 3, 1).reshape(conv2.out_channels, -1).contiguous()
-            c.update(key2=key, w1=to_operand(w1, prec), b1=b1.contiguous(), w2=to_operand(w2, prec),
-                     b2=conv2.bias.detach().to(**f32).contiguous())
-        M, mid, out_c = B * hp * wp, conv1.out_channels, conv2.out_channels
-        esz_t = {_lib.OCM_PREC_BF16: torch.bfloat16, _lib.OCM_PREC_FP32: torch.float32, _lib.OCM_PREC_BF16X3: torch.int32}[prec]
+        mid, out_c = conv1.out_channels, conv2.out_channels
+        f32 = dict(device=dev, dtype=torch.float32)
+
+        def gain():  # the BatchNorm scale per channel, from the running statistics
+            return bn.weight.detach().to(**f32) / torch.sqrt(bn.running_var.detach().to(**f32) + bn.eps)
+
+        w1 = _cached_operand(cache, "conv1.folded", (conv1.weight, bn.weight, bn.running_var), prec, lambda: to_operand(
+            _rows3x3(conv1.weight.detach().to(**f32) * gain()[:, None, None, None]).contiguous(), prec))
+        b1 = _cached_operand(cache, "conv1.folded_bias", (conv1.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var), prec,
+                             lambda: ((conv1.bias.detach().to(**f32) - bn.running_mean.detach().to(**f32)) * gain()
+                                      + bn.bias.detach().to(**f32)).contiguous())
+        w2 = _weight_operand(cache, "conv2", conv2.weight, prec, dev, _rows3x3)
         patches = tokens[:, 1:].contiguous()  # (B, hp*wp, D) fp32
-        out = torch.empty((B, 1, hp * self.encoder_stride, wp * self.encoder_stride), dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
-            a1 = torch.empty((M, 9 * D), dtype=esz_t, device=dev)
-            _lib.check(lib.ocm_op_im2col3x3(prec, _p(patches), _p(a1), B, hp, wp, D, 0, _stream()))
-            y1 = torch.empty((M, mid), dtype=torch.float32, device=dev)
-            _lib.check(lib.ocm_op_linear(prec, _p(a1), _p(c["w1"]), _p(c["b1"]), None, _p(y1), M, mid, 9 * D,
-                                         _lib.OCM_EPI_BIAS_F32, _stream()))
-            a2 = torch.empty((M, 9 * mid), dtype=esz_t, device=dev)
-            _lib.check(lib.ocm_op_im2col3x3(prec, _p(y1), _p(a2), B, hp, wp, mid, 1, _stream()))  # ReLU on the way
-            y2 = torch.empty((M, out_c), dtype=torch.float32, device=dev)
-            _lib.check(lib.ocm_op_linear(prec, _p(a2), _p(c["w2"]), _p(c["b2"]), None, _p(y2), M, out_c, 9 * mid,
-                                         _lib.OCM_EPI_BIAS_F32, _stream()))
-            _lib.check(lib.ocm_op_pixel_shuffle(_p(y2), _p(out), B, hp, wp, out_c // self.encoder_stride ** 2,
-                                                self.encoder_stride, _stream()))
-        return out
+            y1 = _conv3x3(prec, patches, w1, b1, (B, hp, wp), D, mid)
+            y2 = _conv3x3(prec, y1, w2, _vec(conv2.bias, out_c, dev), (B, hp, wp), mid, out_c, relu=True)  # ReLU on the way
+            return _pixel_shuffle(y2, B, hp, wp, self.encoder_stride)
 
     def _encoder_frozen(self):
         return not any(p.requires_grad for p in self.encoder.parameters())
 
     def forward(self, x):
-        if self.training and _finetunes(self.encoder):  # finetune.py --finetune True: the encoder trains too
-            _check_trainable(self.encoder, x, masked=False)
-            _require_hip(x, "input")
-            return _train_forward(self, _encode_train(self.encoder, x, None))
+        enc = self.encoder
+        finetune = self.training and _finetunes(enc)  # finetune.py --finetune True: the encoder trains too
+        if finetune:
+            _check_trainable(enc, x, masked=False)
         _require_hip(x, "input")
-        if self.training and (self._encoder_frozen() or getattr(self.encoder, "finetune_backward", False)):
-            with torch.no_grad():  # (an opted-in encoder that is not differentiated right now: no_grad, or its own eval mode)
-                tokens = self.encoder._encode(x, tokens=True)
+        if finetune:
+            tokens = _encode_train(enc, x, None)
+        else:
+            with torch.no_grad():
+                tokens = enc._encode(x, tokens=True)
+        # the training decoder: a frozen encoder (linear probing), or one that has opted in to fine-tuning — differentiated
+        # above, or not right now (no_grad, or its own eval mode). Any other encoder keeps the eval decoder.
+        if self.training and (self._encoder_frozen() or getattr(enc, "finetune_backward", False)):
             return _train_forward(self, tokens)
         with torch.no_grad():
-            tokens = self.encoder._encode(x, tokens=True)
             if self.layer_num == 2:
                 return self._two_layer(tokens)
-            return _conv1x1_pixel_shuffle(self.encoder, tokens, self.one_layer_decoder[0], self.encoder_stride,
-                                          self._dec_cache)
+            conv = self.one_layer_decoder[0]
+            return _head_forward(_head_meta(self), tokens[:, 1:].contiguous(), conv.weight, conv.bias)
 
 
-# ---- training-mode decoders on a frozen encoder (finetune.py --finetune False): forward with batch statistics and
-# backward through kernels_train.hip. Token-major rows m = (image, y, x), M = B*hp*wp; s = stride, mid = 4 s^2. ----
+# ---- the decoders' pieces. Token-major rows m = (image, y, x), M = B*hp*wp; s = stride, mid = 4 s^2. Training (finetune.py,
+# mim.py) runs the forward with batch statistics and the backward through kernels_train.hip. ----
 _OPERAND_DTYPE = {_lib.OCM_PREC_BF16: torch.bfloat16, _lib.OCM_PREC_FP32: torch.float32, _lib.OCM_PREC_BF16X3: torch.int32}
+
+
+def _rows1x1(w):
+    """(O, C, 1, 1) kernel -> the (O, C) weight of ocm_op_linear over the token rows."""
+    return w.reshape(w.shape[0], -1)
+
+
+def _rows1x1_t(w):
+    """(O, C, 1, 1) kernel -> (C, O): the data gradient dX = dY W runs as ocm_op_linear(dY, W^T)."""
+    return _rows1x1(w).t()
+
+
+def _rows3x3(w):
+    """(O, C, 3, 3) kernel -> (O, 9*C) with K = (ky*3 + kx)*C + c: the K order of ocm_op_im2col3x3."""
+    return w.permute(0, 2, 3, 1).reshape(w.shape[0], -1)
 
 
 def flip_conv3x3(w):
@@ -296,6 +273,11 @@ def _ws(nbytes, dev):
     return torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
 
 
+def _put(t, like):
+    """A gradient in the parameter's own shape, on its device and in its dtype."""
+    return None if t is None else t.reshape(like.shape).to(device=like.device, dtype=like.dtype)
+
+
 def _weight_grad(prec, dy, x, want_bias):
     """dW = dy^T x (and db = column sums of dy) on the weight-gradient kernel; dy (M, N), x (M, K) fp32."""
     lib, (M, N), K = _lib.load(), dy.shape, x.shape[1]
@@ -307,6 +289,14 @@ def _weight_grad(prec, dy, x, want_bias):
     return dw, db
 
 
+def _pixel_shuffle(lin, B, hp, wp, s):
+    """PixelShuffle(s) of the token-major rows lin (B*hp*wp, c*s*s) -> (B, c, hp*s, wp*s) fp32."""
+    c_out = lin.shape[1] // (s * s)
+    out = torch.empty((B, c_out, hp * s, wp * s), dtype=torch.float32, device=lin.device)
+    _lib.check(_lib.load().ocm_op_pixel_shuffle(_p(lin), _p(out), B, hp, wp, c_out, s, _stream()))
+    return out
+
+
 def _pixel_shuffle_backward(g, M, s, hp, wp):
     g = g.detach().to(torch.float32).contiguous()
     B, c_out = g.shape[0], g.shape[1]
@@ -315,9 +305,13 @@ def _pixel_shuffle_backward(g, M, s, hp, wp):
     return lin
 
 
-def _cached_operand(cache, name, w, prec, make):
-    """Operand copy of a weight, rebuilt when the parameter is replaced or updated in place (data_ptr, _version)."""
-    key = (w.data_ptr(), w._version, prec)
+def _cached_operand(cache, name, srcs, prec, make):
+    """What make() builds from `srcs` (a parameter, or a tuple of parameters and buffers), rebuilt when one of them is replaced
+    or updated in place: the key is every source's own (data_ptr, _version), and the precision."""
+    if isinstance(srcs, tuple):
+        key = (*((t.data_ptr(), t._version) for t in srcs), prec)
+    else:
+        key = (srcs.data_ptr(), srcs._version, prec)
     hit = cache.get(name)
     if hit is None or hit[0] != key:
         hit = (key, make())
@@ -325,53 +319,107 @@ def _cached_operand(cache, name, w, prec, make):
     return hit[1]
 
 
+def _weight_operand(cache, name, w, prec, dev, layout):
+    """Operand copy of a convolution kernel in one of the layouts above, cached under the kernel's own key."""
+    return _cached_operand(cache, f"{name}.{layout.__name__}", w, prec, lambda: to_operand(
+        layout(w.detach().to(device=dev, dtype=torch.float32)).contiguous(), prec))
+
+
+def _zeros(cache, n, dev):
+    """The all-zero fp32 bias of a GEMM that adds none: one vector per length."""
+    z = cache.get(("zeros", n))
+    if z is None or z.device != dev:
+        z = cache[("zeros", n)] = torch.zeros(n, device=dev, dtype=torch.float32)
+    return z
+
+
+def _im2col3x3(prec, x, grid, C, relu=False, affine=None):
+    """The (M, 9*C) rows of a 3x3 pad-1 convolution over x (M, C) fp32, in the operand type of `prec`: gathered as they are,
+    through a ReLU, or through the per-channel affine (g, h) of a BatchNorm and a ReLU."""
+    lib, (B, hp, wp) = _lib.load(), grid
+    a = torch.empty((B * hp * wp, 9 * C), dtype=_OPERAND_DTYPE[prec], device=x.device)
+    if affine is not None:
+        _lib.check(lib.ocm_op_bn_relu_im2col3x3(prec, _p(x), _p(affine[0]), _p(affine[1]), _p(a), B, hp, wp, C, _stream()))
+    else:
+        _lib.check(lib.ocm_op_im2col3x3(prec, _p(x), _p(a), B, hp, wp, C, int(relu), _stream()))
+    return a
+
+
+def _conv3x3(prec, x, w_op, bias, grid, C, O, **gather):
+    """One 3x3 pad-1 convolution on the token-major rows: _im2col3x3, then ocm_op_linear on the (O, 9*C) operand -> (M, O)."""
+    B, hp, wp = grid
+    return _linear(_lib.load(), prec, _im2col3x3(prec, x, grid, C, **gather), w_op, bias, None, B * hp * wp, O, 9 * C)
+
+
+def _head_meta(module):
+    """What the pixel-shuffle head needs of its wrapper (MIM, LinearProbing): precision, stride and the operand cache."""
+    return {"prec": _lib.PRECISIONS[module.encoder._precision], "stride": module.encoder_stride, "cache": module._dec_cache}
+
+
+def _head_forward(meta, patches, weight, bias):
+    """Conv2d(D, s*s*c, 1) + PixelShuffle(s) on the normed patch rows (B, P, D) fp32 (the caller has dropped the CLS row): one
+    GEMM over the rows and a scatter. Returns (B, c, hp*s, wp*s) fp32."""
+    prec, dev = meta["prec"], patches.device
+    B, P, D = patches.shape
+    hp = wp = int(P ** 0.5)
+    M, O = B * P, weight.shape[0]
+    w = _weight_operand(meta["cache"], "head", weight, prec, dev, _rows1x1)
+    with torch.cuda.device(dev):
+        lin = _linear(_lib.load(), prec, to_operand(patches.reshape(M, D), prec), w, _vec(bias, O, dev), None, M, O, D)
+        return _pixel_shuffle(lin, B, hp, wp, meta["stride"])
+
+
+class _PixelShuffleHead(torch.autograd.Function):
+    """The head of MIM and of LinearProbing(layer_num=1) in training mode: forward(meta, patches, weight, bias) as _head_forward
+    computes it; backward -> the weight / bias gradients and, when the patch rows carry a graph (a trainable encoder), dPatches
+    (B, P, D) fp32 = dlin W. Patch rows from a frozen encoder get none and cost nothing. The callers slice the CLS row off the
+    tokens themselves, so autograd gives it its zero gradient."""
+
+    @staticmethod
+    def forward(ctx, meta, patches, weight, bias):
+        ctx.meta, ctx.bias = meta, bias
+        ctx.save_for_backward(patches, weight)
+        return _head_forward(meta, patches, weight, bias)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        meta, (patches, weight) = ctx.meta, ctx.saved_tensors
+        prec, s, cache, dev = meta["prec"], meta["stride"], meta["cache"], grad_out.device
+        B, P, D = patches.shape
+        hp = wp = int(P ** 0.5)
+        M, O = B * P, weight.shape[0]
+        _, need_x, need_w, need_b = ctx.needs_input_grad
+        dx = dw = db = None
+        with torch.cuda.device(dev):
+            dlin = _pixel_shuffle_backward(grad_out, M, s, hp, wp)  # (M, O)
+            if need_w or need_b:
+                dw, db = _weight_grad(prec, dlin, patches.reshape(M, D), need_b)
+            if need_x:
+                wt = _weight_operand(cache, "head", weight, prec, dev, _rows1x1_t)
+                dx = _linear(_lib.load(), prec, to_operand(dlin, prec), wt, _zeros(cache, D, dev), None, M, D, O)
+                dx = dx.reshape(B, P, D)
+        return None, dx, _put(dw, weight) if need_w else None, _put(db, ctx.bias) if need_b else None
+
+
 class _DecoderTrain(torch.autograd.Function):
-    """One training-mode decoder call: forward(patches, *params) -> (B, c_out, hp*s, wp*s); backward -> parameter gradients
-    and, when the patch tokens carry a graph (a trainable encoder), dPatches (B, P, D) fp32: dlin W for the 1x1 head, conv1's
-    data gradient (the 3x3 pad-1 convolution of dy1 with the flipped, channel-transposed kernel) for the two-layer decoder.
-    Patch tokens from a frozen encoder get none and cost nothing. `meta` carries the module, its precision and, for the
-    caller, the batch statistics of the forward (the running-statistics update happens outside the graph)."""
+    """One training-mode call of the two-layer decoder: forward(patches, *params) -> (B, 1, hp*s, wp*s); backward -> parameter
+    gradients and, when the patch tokens carry a graph (a trainable encoder), dPatches (B, P, D) fp32: conv1's data gradient
+    (the 3x3 pad-1 convolution of dy1 with the flipped, channel-transposed kernel). Patch tokens from a frozen encoder get
+    none and cost nothing. `meta` carries the module, its precision and, for the caller, the batch statistics of the forward
+    (the running-statistics update happens outside the graph)."""
 
     @staticmethod
     def forward(ctx, meta, patches, *params):
         lp, prec, dev = meta["module"], meta["prec"], patches.device
-        lib, s = _lib.load(), lp.encoder_stride
+        lib, s, cache = _lib.load(), lp.encoder_stride, lp._dec_cache
+        conv1, bn, _, conv2, _ = lp.two_layer_decoder
         B, P, D = patches.shape
         hp = wp = int(P ** 0.5)
-        M = B * P
+        M, mid, oc = B * P, conv1.out_channels, conv2.out_channels
         f32 = dict(device=dev, dtype=torch.float32)
-        cache = lp._dec_cache.setdefault("train", {})
-        out = torch.empty((B, 1 if lp.layer_num == 2 else lp.one_layer_decoder[0].out_channels // (s * s), hp * s, wp * s),
-                          **f32)
         ctx.meta, ctx.shape = meta, (B, hp, wp, D, M)
-        x2d = patches.reshape(M, D)
-        if lp.layer_num != 2:
-            conv = lp.one_layer_decoder[0]
-            O = conv.out_channels
-            w = _cached_operand(cache, "w_head", conv.weight, prec,
-                                lambda: to_operand(conv.weight.detach().reshape(O, D).to(**f32), prec))
-            b = conv.bias.detach().to(**f32).contiguous() if conv.bias is not None else torch.zeros(O, **f32)
-            lin = torch.empty((M, O), **f32)
-            _lib.check(lib.ocm_op_linear(prec, _p(to_operand(x2d, prec)), _p(w), _p(b), None, _p(lin), M, O, D,
-                                         _lib.OCM_EPI_BIAS_F32, _stream()))
-            _lib.check(lib.ocm_op_pixel_shuffle(_p(lin), _p(out), B, hp, wp, O // (s * s), s, _stream()))
-            ctx.save_for_backward(x2d)
-            return out
-        conv1, bn, _, conv2, _ = lp.two_layer_decoder
-        mid, oc = conv1.out_channels, conv2.out_channels
-        w1 = _cached_operand(cache, "w1", conv1.weight, prec,
-                             lambda: to_operand(conv1.weight.detach().to(**f32).permute(0, 2, 3, 1).reshape(mid, -1), prec))
-        w2 = _cached_operand(cache, "w2", conv2.weight, prec,
-                             lambda: to_operand(conv2.weight.detach().to(**f32).permute(0, 2, 3, 1).reshape(oc, -1), prec))
-        b1 = conv1.bias.detach().to(**f32).contiguous() if conv1.bias is not None else torch.zeros(mid, **f32)
-        b2 = conv2.bias.detach().to(**f32).contiguous() if conv2.bias is not None else torch.zeros(oc, **f32)
-        esz_t = _OPERAND_DTYPE[prec]
-        a1 = torch.empty((M, 9 * D), dtype=esz_t, device=dev)
-        _lib.check(lib.ocm_op_im2col3x3(prec, _p(patches), _p(a1), B, hp, wp, D, 0, _stream()))
-        y1 = torch.empty((M, mid), **f32)
-        _lib.check(lib.ocm_op_linear(prec, _p(a1), _p(w1), _p(b1), None, _p(y1), M, mid, 9 * D, _lib.OCM_EPI_BIAS_F32,
-                                     _stream()))
-        del a1
+        y1 = _conv3x3(prec, patches, _weight_operand(cache, "conv1", conv1.weight, prec, dev, _rows3x3),
+                      _vec(conv1.bias, mid, dev), (B, hp, wp), D, mid)
         mean, var = torch.empty(mid, **f32), torch.empty(mid, **f32)
         nbytes = lib.ocm_channel_reduce_workspace_bytes(M, mid)
         ws = _ws(nbytes, dev)
@@ -379,126 +427,80 @@ class _DecoderTrain(torch.autograd.Function):
         # per-channel affine of the normalisation (mid-length vectors): z = relu(y1 * g + h)
         invstd = torch.rsqrt(var + bn.eps)
         gamma = bn.weight.detach().to(**f32) if bn.weight is not None else torch.ones(mid, **f32)
-        beta = bn.bias.detach().to(**f32) if bn.bias is not None else torch.zeros(mid, **f32)
         g = (gamma * invstd).contiguous()
-        h = (beta - mean * g).contiguous()
-        a2 = torch.empty((M, 9 * mid), dtype=esz_t, device=dev)
-        _lib.check(lib.ocm_op_bn_relu_im2col3x3(prec, _p(y1), _p(g), _p(h), _p(a2), B, hp, wp, mid, _stream()))
-        y2 = torch.empty((M, oc), **f32)
-        _lib.check(lib.ocm_op_linear(prec, _p(a2), _p(w2), _p(b2), None, _p(y2), M, oc, 9 * mid, _lib.OCM_EPI_BIAS_F32,
-                                     _stream()))
-        _lib.check(lib.ocm_op_pixel_shuffle(_p(y2), _p(out), B, hp, wp, oc // (s * s), s, _stream()))
+        h = (_vec(bn.bias, mid, dev) - mean * g).contiguous()
+        y2 = _conv3x3(prec, y1, _weight_operand(cache, "conv2", conv2.weight, prec, dev, _rows3x3),
+                      _vec(conv2.bias, oc, dev), (B, hp, wp), mid, oc, affine=(g, h))
         meta["mean"], meta["var"] = mean, var
         ctx.save_for_backward(patches, y1, mean, invstd, g, h)
-        return out
+        return _pixel_shuffle(y2, B, hp, wp, s)
 
     @staticmethod
     def backward(ctx, grad_out):
         meta = ctx.meta
         lp, prec = meta["module"], meta["prec"]
         B, hp, wp, D, M = ctx.shape
-        s, lib = lp.encoder_stride, _lib.load()
+        s, lib, cache = lp.encoder_stride, _lib.load(), lp._dec_cache
         need, need_x = ctx.needs_input_grad[2:], ctx.needs_input_grad[1]
-        dev = grad_out.device
+        dev, grid = grad_out.device, (B, hp, wp)
         f32 = dict(device=dev, dtype=torch.float32)
-        cache = lp._dec_cache.setdefault("train", {})
-        dpatches = None
-
-        def put(t, like):  # the gradient on the parameter's own device and dtype
-            return None if t is None else t.reshape(like.shape).to(device=like.device, dtype=like.dtype)
-
-        if lp.layer_num != 2:
-            (x2d,) = ctx.saved_tensors
-            conv = lp.one_layer_decoder[0]
-            with torch.cuda.device(dev):
-                dlin = _pixel_shuffle_backward(grad_out, M, s, hp, wp)
-                dw = db = None
-                if need[0] or need[1]:
-                    dw, db = _weight_grad(prec, dlin, x2d, need[1])
-                if need_x:  # dX = dlin W as ocm_op_linear on the operand copy of W^T
-                    O = conv.out_channels
-                    wt = _cached_operand(cache, "w_head_t", conv.weight, prec,
-                                         lambda: to_operand(conv.weight.detach().reshape(O, D).t().to(**f32).contiguous(), prec))
-                    dpatches = _linear(lib, prec, to_operand(dlin, prec), wt, torch.zeros(D, **f32), None, M, D, O)
-                    dpatches = dpatches.reshape(B, M // B, D)
-            grads = [put(dw, conv.weight) if need[0] else None, put(db, conv.bias) if need[1] else None]
-            return (None, dpatches, *grads)
         patches, y1, mean, invstd, g, h = ctx.saved_tensors
         conv1, bn, _, conv2, _ = lp.two_layer_decoder
         mid, oc = conv1.out_channels, conv2.out_channels
-        grads = [None] * 6
+        dpatches, grads = None, [None] * 6
         with torch.cuda.device(dev):
             dy2 = _pixel_shuffle_backward(grad_out, M, s, hp, wp)  # (M, oc)
             if need[4] or need[5]:
-                a2 = torch.empty((M, 9 * mid), **f32)  # conv2's operand again, in fp32
-                _lib.check(lib.ocm_op_bn_relu_im2col3x3(_lib.OCM_PREC_FP32, _p(y1), _p(g), _p(h), _p(a2), B, hp, wp, mid,
-                                                        _stream()))
+                a2 = _im2col3x3(_lib.OCM_PREC_FP32, y1, grid, mid, affine=(g, h))  # conv2's operand again, in fp32
                 dw2, db2 = _weight_grad(prec, dy2, a2, need[5])
                 del a2
-                grads[4] = put(dw2.reshape(oc, 3, 3, mid).permute(0, 3, 1, 2), conv2.weight) if need[4] else None
-                grads[5] = put(db2, conv2.bias) if need[5] else None
+                grads[4] = _put(dw2.reshape(oc, 3, 3, mid).permute(0, 3, 1, 2), conv2.weight) if need[4] else None
+                grads[5] = _put(db2, conv2.bias) if need[5] else None
             if any(need[:4]) or need_x:
                 # conv2's data gradient: a 3x3 pad-1 convolution of dY2 with the flipped, channel-transposed kernel
-                w2f = _cached_operand(cache, "w2_flip", conv2.weight, prec,
-                                      lambda: to_operand(flip_conv3x3(conv2.weight.detach().to(**f32)).contiguous(), prec))
-                d2 = torch.empty((M, 9 * oc), dtype=_OPERAND_DTYPE[prec], device=dev)
-                _lib.check(lib.ocm_op_im2col3x3(prec, _p(dy2), _p(d2), B, hp, wp, oc, 0, _stream()))
-                dz = torch.empty((M, mid), **f32)
-                zero = cache.get("zero_mid")
-                if zero is None or zero.numel() != mid or zero.device != dev:
-                    zero = cache["zero_mid"] = torch.zeros(mid, **f32)
-                _lib.check(lib.ocm_op_linear(prec, _p(d2), _p(w2f), _p(zero), None, _p(dz), M, mid, 9 * oc,
-                                             _lib.OCM_EPI_BIAS_F32, _stream()))
-                del d2
+                dz = _conv3x3(prec, dy2, _weight_operand(cache, "conv2", conv2.weight, prec, dev, flip_conv3x3),
+                              _zeros(cache, mid, dev), grid, oc, mid)
                 dy1, dgam, dbet = torch.empty((M, mid), **f32), torch.empty(mid, **f32), torch.empty(mid, **f32)
                 nbytes = lib.ocm_channel_reduce_workspace_bytes(M, mid)
                 ws = _ws(nbytes, dev)
                 _lib.check(lib.ocm_op_bn_relu_backward(_p(dz), _p(y1), _p(mean), _p(invstd), _p(g), _p(h), _p(dy1), _p(dgam),
                                                        _p(dbet), M, mid, _p(ws), nbytes, _stream()))
                 del dz
-                grads[2] = put(dgam, bn.weight) if need[2] else None
-                grads[3] = put(dbet, bn.bias) if need[3] else None
+                grads[2] = _put(dgam, bn.weight) if need[2] else None
+                grads[3] = _put(dbet, bn.bias) if need[3] else None
                 if need[0] or need[1]:
-                    a1 = torch.empty((M, 9 * D), **f32)  # im2col of the patch tokens again, in fp32
-                    _lib.check(lib.ocm_op_im2col3x3(_lib.OCM_PREC_FP32, _p(patches), _p(a1), B, hp, wp, D, 0, _stream()))
+                    a1 = _im2col3x3(_lib.OCM_PREC_FP32, patches, grid, D)  # im2col of the patch tokens again, in fp32
                     dw1, db1 = _weight_grad(prec, dy1, a1, need[1])
                     del a1
-                    grads[0] = put(dw1.reshape(mid, 3, 3, D).permute(0, 3, 1, 2), conv1.weight) if need[0] else None
-                    grads[1] = put(db1, conv1.bias) if need[1] else None
+                    grads[0] = _put(dw1.reshape(mid, 3, 3, D).permute(0, 3, 1, 2), conv1.weight) if need[0] else None
+                    grads[1] = _put(db1, conv1.bias) if need[1] else None
                 if need_x:  # conv1's data gradient, by the same construction (K = 9 mid, N = D)
-                    w1f = _cached_operand(cache, "w1_flip", conv1.weight, prec,
-                                          lambda: to_operand(flip_conv3x3(conv1.weight.detach().to(**f32)).contiguous(), prec))
-                    d1 = torch.empty((M, 9 * mid), dtype=_OPERAND_DTYPE[prec], device=dev)
-                    _lib.check(lib.ocm_op_im2col3x3(prec, _p(dy1), _p(d1), B, hp, wp, mid, 0, _stream()))
-                    dpatches = _linear(lib, prec, d1, w1f, torch.zeros(D, **f32), None, M, D, 9 * mid).reshape(B, hp * wp, D)
-                    del d1
+                    dpatches = _conv3x3(prec, dy1, _weight_operand(cache, "conv1", conv1.weight, prec, dev, flip_conv3x3),
+                                        _zeros(cache, D, dev), grid, mid, D).reshape(B, hp * wp, D)
         return (None, dpatches, *grads)
 
 
 def _train_forward(lp, tokens):
-    """LinearProbing.forward in training mode: the decoder with batch statistics (layer_num 2), the running statistics
-    updated as nn.BatchNorm2d updates them, and a graph into the decoder's parameters when grad mode is on. The normed tokens
-    (B, N, D) come from a frozen encoder without a graph, or carry one (a trainable encoder, or a leaf that requires grad):
-    then the patch gradient of _DecoderTrain goes back into rows 1..N-1 and the CLS row, which no decoder reads, gets zeros."""
+    """LinearProbing.forward in training mode: the decoder (layer_num 2: with batch statistics, the running statistics updated as
+    nn.BatchNorm2d updates them) and a graph into its parameters when grad mode is on. The normed tokens (B, N, D) come from a
+    frozen encoder without a graph, or carry one (a trainable encoder, or a leaf that requires grad): then the decoder's patch
+    gradient goes back into rows 1..N-1 and the CLS row, which no decoder reads, gets zeros."""
     B, N, D = tokens.shape
     patches = tokens[:, 1:].contiguous()
-    prec = _lib.PRECISIONS[lp.encoder._precision]
-    meta = {"module": lp, "prec": prec}
-    if lp.layer_num == 2:
-        conv1, bn, _, conv2, _ = lp.two_layer_decoder
-        if not bn.training:
-            raise NotImplementedError("the training-mode decoder normalises with batch statistics: BatchNorm2d in eval "
-                                      "mode inside a training LinearProbing is not supported on the HIP path")
-        if B * (N - 1) < 2:
-            raise ValueError(f"Expected more than 1 value per channel when training, got input size "
-                             f"{[B, conv1.out_channels, 1, 1]}")
-        params = (conv1.weight, conv1.bias, bn.weight, bn.bias, conv2.weight, conv2.bias)
-    else:
+    if lp.layer_num != 2:
         conv = lp.one_layer_decoder[0]
-        params = (conv.weight, conv.bias)
+        return _PixelShuffleHead.apply(_head_meta(lp), patches, conv.weight, conv.bias)
+    conv1, bn, _, conv2, _ = lp.two_layer_decoder
+    if not bn.training:
+        raise NotImplementedError("the training-mode decoder normalises with batch statistics: BatchNorm2d in eval "
+                                  "mode inside a training LinearProbing is not supported on the HIP path")
+    if B * (N - 1) < 2:
+        raise ValueError(f"Expected more than 1 value per channel when training, got input size "
+                         f"{[B, conv1.out_channels, 1, 1]}")
+    meta = {"module": lp, "prec": _lib.PRECISIONS[lp.encoder._precision]}
     with torch.cuda.device(tokens.device):
-        out = _DecoderTrain.apply(meta, patches, *params)
-        if lp.layer_num == 2 and bn.track_running_stats and bn.running_mean is not None:
+        out = _DecoderTrain.apply(meta, patches, conv1.weight, conv1.bias, bn.weight, bn.bias, conv2.weight, conv2.bias)
+        if bn.track_running_stats and bn.running_mean is not None:
             _update_running_stats(bn, meta["mean"], meta["var"], B * (N - 1))
     return out
 
@@ -592,13 +594,9 @@ def _encode_train(enc, x, mask):
         _check_mask(enc, x, mask)
     eng = enc._engine(x.device)
     npatch = (x.shape[-2] // eng.p) * (x.shape[-1] // eng.p)
-    side = enc.img_size[0]
-    if side == 224 and npatch != enc.pos_embed.shape[1] - 1:
-        raise RuntimeError(f"The size of tensor a ({npatch + 1}) must match the size of tensor b ({enc.pos_embed.shape[1]}) "
-                           "at non-singleton dimension 1")
-    pos = enc._pos_for(npatch, side, side, x.device)
     named = _encoder_params(enc)
-    meta = {"enc": enc, "eng": eng, "names": [n for n, _ in named], "pos": pos, "side": side, "npatch": npatch,
+    meta = {"enc": enc, "eng": eng, "names": [n for n, _ in named], "pos": enc._positions(npatch, x.device),
+            "side": enc.img_size[0], "npatch": npatch,
             "first": _first_block_to_train(enc, named),
             "mask": mask.reshape(x.shape[0], -1).to(torch.float32).contiguous() if mask is not None else None}
     with torch.cuda.device(x.device):
@@ -735,9 +733,8 @@ class _EncoderTrain(torch.autograd.Function):
                 if need.get(bname):
                     grads[bname] = db
 
-        def put(n):  # the gradient on the parameter's own device and dtype
-            g, p = grads.get(n), params[n]
-            return None if g is None else g.reshape(p.shape).to(device=p.device, dtype=p.dtype)
+        def put(n):
+            return _put(grads.get(n), params[n])
 
         def lngrads(pre, dg, db):
             if need.get(pre + ".weight"):
@@ -819,47 +816,6 @@ class _EncoderTrain(torch.autograd.Function):
                     (gpe,) = torch.autograd.grad(full, pe, dpos.cpu().reshape(full.shape))
                 grads["pos_embed"] = gpe
         return (None, None, *[put(n) for n in names])
-
-
-class _MIMHeadTrain(torch.autograd.Function):
-    """MIM's decoder (Conv2d(D, s*s*3, 1) + PixelShuffle) in training mode: forward as the eval path computes it; backward ->
-    the weight / bias gradients and, when the tokens carry a graph, their gradient (the CLS row gets zero)."""
-
-    @staticmethod
-    def forward(ctx, meta, tokens, weight, bias):
-        enc, conv, s = meta["enc"], meta["conv"], meta["stride"]
-        out = _conv1x1_pixel_shuffle(enc, tokens.detach(), conv, s, meta["cache"])
-        ctx.meta = meta
-        ctx.save_for_backward(tokens.detach(), weight)
-        return out
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        meta = ctx.meta
-        tokens, weight = ctx.saved_tensors
-        enc, conv, s = meta["enc"], meta["conv"], meta["stride"]
-        B, N, D = tokens.shape
-        hp = wp = int((N - 1) ** 0.5)
-        M, O = B * (N - 1), conv.out_channels
-        prec = _lib.PRECISIONS[enc._precision]
-        lib, dev = _lib.load(), tokens.device
-        f32 = dict(device=dev, dtype=torch.float32)
-        need_t, need_w, need_b = ctx.needs_input_grad[1], ctx.needs_input_grad[2], ctx.needs_input_grad[3]
-        dtok = dw = db = None
-        with torch.cuda.device(dev):
-            dlin = _pixel_shuffle_backward(grad_out, M, s, hp, wp)  # (M, O)
-            if need_w or need_b:
-                dw, db = _weight_grad(prec, dlin, tokens[:, 1:].reshape(M, D), need_b)
-                dw = dw.reshape(conv.weight.shape).to(conv.weight.dtype) if need_w else None
-                db = db.to(conv.bias.dtype) if need_b else None
-            if need_t:
-                cache = meta["cache"].setdefault("train", {})
-                wt = _cached_operand(cache, "w_dec_t", weight, prec,
-                                     lambda: to_operand(weight.detach().reshape(O, D).t().to(**f32).contiguous(), prec))
-                dp = _linear(lib, prec, to_operand(dlin, prec), wt, torch.zeros(D, **f32), None, M, D, O)
-                dtok = torch.zeros((B, N, D), **f32)
-                dtok[:, 1:] = dp.reshape(B, N - 1, D)
-        return None, dtok, dw, db
 
 
 def build_model(args):

@@ -673,18 +673,139 @@ extern "C" int ocm_debug_stamps_attn(unsigned long long *host, int n) {
 // [hi d 0..31 | lo d 0..31 | hi d 32..63 | lo d 32..63]; V^T rows are key-contiguous in the same 128-byte groups of
 // 32 keys. Every product runs as three bf16 MFMAs (hi*hi + hi*lo + lo*hi), P is split in registers. LDS tiles carry the
 // usual chunk swizzle, so the fragment reads are the conflict-free pattern of the bf16 kernel.
+//
+// The tile steps below are shared by attn_fwd_x3_dma_kernel, attn_fwd_x3_pp_kernel and attn_fwd_x3_ws_kernel, which differ in
+// their schedule only (rings, LDS-DMA batches, counted waits, barriers, epilogues). The steps are the only place where the
+// arithmetic of a key tile and its order are written, with the exceptions marked "own copy" in the kernels (the two matrix steps
+// everywhere, mask and softmax in the ws kernel). The kernels must return the same bits per (m, l, O) update
+// (get_last_selfattention and get_intermediate_feat, the statistics-only pass and the full one rely on it): for the shared steps
+// that holds by construction, for the marked copies by convention — they are kept textually the same by hand, and
+// tools/ab_attn.py checks every shape class with NaN-poisoned padding.
+
+// Q^T as the B operand of the score product: lane (query r, half h) holds channels 16 s + 8 h .. + 7 of its row `qp` as a
+// split pair. Issued first in every kernel, so that the first counted wait covers it too (vmcnt retires in order).
+template <int NQ>
+__device__ __forceinline__ void x3_load_q(const char *qp, int h, bf16x8 (&qh)[NQ], bf16x8 (&ql)[NQ]) {
+#pragma unroll
+    for (int s = 0; s < NQ; ++s) {
+        const char *p = qp + (s >> 1) * 128 + ((s & 1) * 16 + 8 * h) * 2;
+        qh[s] = *(const bf16x8 *)p;
+        ql[s] = *(const bf16x8 *)(p + 64);
+    }
+}
+
+// Per-lane source offsets of the LDS-DMA pieces of a 32-key tile. `buffer_load ... lds` moves 1 KiB = 8 LDS rows of 128 B per
+// wave instruction; the chunk swizzle of lds_off is applied to the per-lane SOURCE offset and the tile index goes in the
+// scalar offset: no staging registers, no ds_write, no per-tile address arithmetic. A tile is HD / 8 pieces per operand and
+// wave `wave` of NW owns pieces pc = j * NW + wave (a wave that fills whole tiles by itself: NW = 1, wave = 0).
+// K piece pc = image pc >> 2 ([32 keys][128 B]), key rows (pc & 3) * 8 .. + 7; V^T piece pc = d rows pc * 8 .. + 7.
+template <int HD, int NW, int KP, int VP>
+__device__ __forceinline__ void x3_piece_offsets(int lane, int wave, int npad, int (&voffK)[KP], int (&voffV)[VP ? VP : 1]) {
+    const int lrow = lane >> 3, slot = lane & 7;
+#pragma unroll
+    for (int j = 0; j < KP; ++j) {
+        const int pc = j * NW + wave, rho = (pc & 3) * 8 + lrow;
+        voffK[j] = rho * (HD * 4) + (pc >> 2) * 128 + ((slot ^ ((rho >> 1) & 7)) << 4);
+    }
+#pragma unroll
+    for (int j = 0; j < VP; ++j) {
+        const int rho = (j * NW + wave) * 8 + lrow;
+        voffV[j] = rho * npad * 4 + ((slot ^ ((rho >> 1) & 7)) << 4);
+    }
+}
+#if defined(__HIP_DEVICE_COMPILE__)  // (hipcc's host pass mis-handles the LDS-DMA builtins: the kernels guard their use too)
+typedef __attribute__((address_space(3))) void *lds_ptr;
+// buffer descriptor of one (image, head)'s K rows or V^T rows: npad * HD split pairs either way
+template <int HD>
+__device__ __forceinline__ auto x3_tile_rsrc(const char *base, int npad) {
+    return __builtin_amdgcn_make_buffer_rsrc((void *)base, 0, (unsigned)(npad * HD * 4), 0x00020000);
+}
+#endif
+
+// Padding keys of the last tile: their K rows are inside the buffer (x3_mask_pad_keys overwrites the scores with -inf), their V^T
+// columns are zeroed in LDS after the tile has landed (the qkv epilogue never writes them; 0 * garbage must not be NaN).
+// The calling thread owns the 8-key chunk kc (0..3) of the d rows d0, d0 + DSTEP, ... < HD.
+template <int HD, int DSTEP>
+__device__ __forceinline__ void x3_zero_pad_keys(char *Vtile, int d0, int kc, int first_pad) {
+    if (kc * 8 + 8 > first_pad) {
+#pragma unroll
+        for (int d = d0; d < HD; d += DSTEP)
+#pragma unroll
+            for (int half = 0; half < 2; ++half) {
+                bf16x8 *p = (bf16x8 *)(Vtile + lds_off(d, half * 4 + kc));
+                bf16x8 t = *p;
+#pragma unroll
+                for (int e = 0; e < 8; ++e)
+                    if (kc * 8 + e >= first_pad) t[e] = (bf16)0.f;
+                *p = t;
+            }
+    }
+}
+
+// The two matrix steps, S = K . Q^T (four mfma32x3 on lds_off(pi_row(lane & 31), ...): registers 8 s2 .. + 7 of S hold the keys
+// of MFMA k slice s2) and O += V^T . P, are NOT shared: through a call hipcc folds the swizzled row offsets out of the key loop
+// and allocates other register counts (dma 124 for 128, pp accumulator offset 124 for 128, ws 168 for 172). Each kernel keeps
+// its own copy, marked "own copy"; they must stay textually the same.
+
+// padding keys of the last tile of the sequence (first_pad = 1..31 valid ones) -> -inf, under a wave-uniform branch of the kernel
+__device__ __forceinline__ void x3_mask_pad_keys(f32x16 &S, int first_pad, int h) {
+#pragma unroll
+    for (int e = 0; e < 16; ++e)
+        if (key_of_reg(e, h) >= first_pad) S[e] = -INFINITY;
+}
+
+// Online softmax of one tile: scores in S -> probabilities in S (relative to the running reference point m), l updated.
+// Padding keys are masked before (x3_mask_pad_keys); every tile holds at least one valid key, so the maximum is finite.
+// Returns the factor for O (defer_max_update).
+__device__ __forceinline__ float x3_softmax(f32x16 &S, float scale2, float &m, float &l) {
+    float mx = S[0];
+#pragma unroll
+    for (int e = 1; e < 16; ++e) mx = fmaxf(mx, S[e]);
+    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+    const float alpha = defer_max_update(m, mx * scale2);
+    const float mn = m;
+    float ps = 0.f;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+        const float p = fast_exp2(fmaf(S[e], scale2, -mn));
+        S[e] = p;
+        ps += p;
+    }
+    l = fmaf(l, alpha, ps);
+    return alpha;
+}
+
+// O *= alpha, skipped while the running maximum moved nowhere in this wave
+template <int ND>
+__device__ __forceinline__ void x3_rescale(f32x16 (&O)[ND], float alpha) {
+    if (__any(alpha != 1.0f)) {
+#pragma unroll
+        for (int e = 0; e < 16; ++e)
+#pragma unroll
+            for (int db = 0; db < ND; ++db) O[db][e] *= alpha;
+    }
+}
+
+// keys 16 s2 + 8 h .. + 7 of P (registers 8 s2 .. + 7 of S) as a split pair: the B operand of O += V^T . P
+__device__ __forceinline__ void x3_split_p(const f32x16 &S, int s2, bf16x8 &ph, bf16x8 &pl) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const float pv = S[8 * s2 + e];
+        const bf16 t = (bf16)pv;
+        ph[e] = t;
+        pl[e] = (bf16)(pv - (float)t);
+    }
+}
+
+// attn_fwd_x3_dma_kernel: the flash kernel on these steps.
 // NW waves (4 or 8) of 32 queries share the K / V^T tiles: 8 waves halve the L2 -> LDS bytes per query at the same
 // waves per CU (one 8-wave workgroup instead of two 4-wave ones).
-//   * K / V^T tiles of 32 keys go global -> LDS by `buffer_load ... lds` (1 KiB = 8 LDS rows per wave instruction, the
-//     chunk swizzle applied to the per-lane SOURCE offset, the tile index in the scalar offset): no staging registers,
-//     no ds_write, no per-tile address arithmetic (a register-staged form, since removed, spent as many vector
-//     instructions on staging as on the softmax: ViT-S/16 B = 64 35.0 -> 28.4 us per launch, N = 2305 463 -> 371 us);
+//   * K / V^T tiles of 32 keys go global -> LDS by LDS-DMA (x3_piece_offsets; a register-staged form, since removed, spent
+//     as many vector instructions on staging as on the softmax: ViT-S/16 B = 64 35.0 -> 28.4 us per launch, N = 2305 463 -> 371 us);
 //   * a ring of three 16 KiB stages (K: two [32 keys][128 B] images, V^T: one [64 d][128 B] image), two tiles in
 //     flight, one counted `s_waitcnt vmcnt` + one barrier per tile;
 //   * 48 KiB of LDS and <= 168 registers: on four waves, three workgroups per CU (the 768 workgroups of ViT-S/16 at
 //     B = 64 resident at once; those shapes now go to attn_fwd_x3_pp_kernel below).
-// Padding keys of the last tile: their K rows are inside the buffer (scores overwritten with -inf), their V^T columns
-// are zeroed in LDS after the tile has landed (the qkv epilogue never writes them; 0 * garbage must not be NaN).
 // HD = head width: 64 (the DINO ViTs), or 128 (the reference's SimMIM encoder, model.py:93-103) on a two-stage ring of
 // 32 KiB stages (K: four [32 keys][128 B] images, V^T: [128 d][128 B]) with twice the Q fragments and context accumulators.
 // KSPLIT: long sequences at small batch (one 384^2 window of ViT-S/8 per call: 60 workgroups walking 73 key tiles each).
@@ -720,37 +841,12 @@ __global__ __launch_bounds__(NW * 64, WPS) void attn_fwd_x3_dma_kernel(const cha
         nt = min(per, ntiles - tb);  // >= 1: the launcher sizes gridDim.z so
     }
 
-    // Q^T as the B operand: issued first, so the counted waits below cover it too (vmcnt retires in order)
     bf16x8 qh[NQ], ql[NQ];
-    {
-        const char *qp = Qb + (int64_t)min(q0 + r, N - 1) * (HD * 4);
-#pragma unroll
-        for (int s = 0; s < NQ; ++s) {
-            const char *p = qp + (s >> 1) * 128 + ((s & 1) * 16 + 8 * h) * 2;
-            qh[s] = *(const bf16x8 *)p;
-            ql[s] = *(const bf16x8 *)(p + 64);
-        }
-    }
-
-    // piece pc = j * NW + wave of a stage: K pieces 0..7 = image (pc >> 2), rows (pc & 3) * 8 .. + 7; V^T pieces = d rows
+    x3_load_q(Qb + (int64_t)min(q0 + r, N - 1) * (HD * 4), h, qh, ql);
     int voffK[KP], voffV[VP ? VP : 1];
-    {
-        const int lrow = lane >> 3, slot = lane & 7;
-#pragma unroll
-        for (int j = 0; j < KP; ++j) {
-            const int pc = j * NW + wave, rho = (pc & 3) * 8 + lrow;
-            voffK[j] = rho * (HD * 4) + (pc >> 2) * 128 + ((slot ^ ((rho >> 1) & 7)) << 4);
-        }
-#pragma unroll
-        for (int j = 0; j < VP; ++j) {
-            const int rho = (j * NW + wave) * 8 + lrow;
-            voffV[j] = rho * npad * 4 + ((slot ^ ((rho >> 1) & 7)) << 4);
-        }
-    }
+    x3_piece_offsets<HD, NW, KP, VP>(lane, wave, npad, voffK, voffV);
 #if defined(__HIP_DEVICE_COMPILE__)
-    typedef __attribute__((address_space(3))) void *lds_ptr;
-    const auto rsK = __builtin_amdgcn_make_buffer_rsrc((void *)Kb, 0, (unsigned)(npad * HD * 4), 0x00020000);
-    const auto rsV = __builtin_amdgcn_make_buffer_rsrc((void *)Vb, 0, (unsigned)(HD * npad * 4), 0x00020000);
+    const auto rsK = x3_tile_rsrc<HD>(Kb, npad), rsV = x3_tile_rsrc<HD>(Vb, npad);
 #define OCM_ATTN_DMA(t, st)                                                                                              \
     do {                                                                                                                 \
         char *st_ = smem + (st) * STAGE;                                                                                 \
@@ -801,22 +897,7 @@ __global__ __launch_bounds__(NW * 64, WPS) void attn_fwd_x3_dma_kernel(const cha
 #endif
         char *Kt = smem + sc * STAGE, *Vtile = Kt + KB;
         if (WANT_O && last_of_seq && first_pad < 32) {  // zero the V^T columns of the padding keys (wave-uniform)
-            if (tid < 256) {
-                const int kc = tid & 3;
-                if (kc * 8 + 8 > first_pad) {
-#pragma unroll
-                    for (int d = tid >> 2; d < HD; d += 64)
-#pragma unroll
-                        for (int half = 0; half < 2; ++half) {
-                            bf16x8 *p = (bf16x8 *)(Vtile + lds_off(d, half * 4 + kc));
-                            bf16x8 t = *p;
-#pragma unroll
-                            for (int e = 0; e < 8; ++e)
-                                if (kc * 8 + e >= first_pad) t[e] = (bf16)0.f;
-                            *p = t;
-                        }
-                }
-            }
+            if (tid < 256) x3_zero_pad_keys<HD, 64>(Vtile, tid >> 2, tid & 3, first_pad);
             lds_barrier();
         }
 #if defined(OCM_ABL) && OCM_ABL == 6  // ablation 6: staging only, no arithmetic
@@ -824,6 +905,7 @@ __global__ __launch_bounds__(NW * 64, WPS) void attn_fwd_x3_dma_kernel(const cha
 #else
         if (active) {
 #endif
+            // own copy of the score step (see the steps above)
             f32x16 S;
 #pragma unroll
             for (int e = 0; e < 16; ++e) S[e] = 0.f;
@@ -834,42 +916,15 @@ __global__ __launch_bounds__(NW * 64, WPS) void attn_fwd_x3_dma_kernel(const cha
                 const bf16x8 kl = *(const bf16x8 *)(kp + lds_off(pr, 4 + (s & 1) * 2 + h));
                 S = mfma32x3(kh, kl, qh[s], ql[s], S);
             }
-            if (last_of_seq && first_pad < 32) {  // padding keys -> -inf (wave-uniform branch)
-#pragma unroll
-                for (int e = 0; e < 16; ++e)
-                    if (key_of_reg(e, h) >= first_pad) S[e] = -INFINITY;
-            }
-            float mx = S[0];
-#pragma unroll
-            for (int e = 1; e < 16; ++e) mx = fmaxf(mx, S[e]);
-            mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-            const float alpha = defer_max_update(m, mx * scale2);  // every tile holds at least one valid key: finite
-            const float mn = m;
-            float ps = 0.f;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const float p = fast_exp2(fmaf(S[e], scale2, -mn));
-                S[e] = p;
-                ps += p;
-            }
-            l = fmaf(l, alpha, ps);
+            if (last_of_seq && first_pad < 32) x3_mask_pad_keys(S, first_pad, h);
+            const float alpha = x3_softmax(S, scale2, m, l);
             if (WANT_O) {
-                if (__any(alpha != 1.0f)) {  // the running max moved somewhere in this wave
-#pragma unroll
-                    for (int e = 0; e < 16; ++e)
-#pragma unroll
-                        for (int db = 0; db < ND; ++db) O[db][e] *= alpha;
-                }
+                x3_rescale(O, alpha);
 #pragma unroll
                 for (int s2 = 0; s2 < 2; ++s2) {
                     bf16x8 ph, pl;
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) {
-                        const float pv = S[8 * s2 + e];
-                        const bf16 t = (bf16)pv;
-                        ph[e] = t;
-                        pl[e] = (bf16)(pv - (float)t);
-                    }
+                    x3_split_p(S, s2, ph, pl);
+                    // own copy of the P.V step
 #pragma unroll
                     for (int db = 0; db < ND; ++db) {
                         const char *vp = Vtile + db * 32 * 128;
@@ -956,8 +1011,7 @@ __global__ __launch_bounds__(NW * 64, WPS) void attn_fwd_x3_dma_kernel(const cha
 // that closes iteration t, one whole iteration before its first reader. One barrier per tile, as before.
 // The context rows leave as 16-byte stores: a lane holds four consecutive channels per accumulator group, v_permlane32_swap
 // between the two lane halves (same query) makes them eight.
-// Same arithmetic per key and the same order of accumulation as attn_fwd_x3_dma_kernel: bit-identical results
-// (tools/ab_attn.py checks every shape class with NaN-poisoned padding).
+// Same arithmetic per key and the same order of accumulation as attn_fwd_x3_dma_kernel (the shared steps): bit-identical results.
 // Measured and NOT shipped (round 4, git history has both): (i) the same blocks with EIGHT waves whose halves run them in
 // opposite phases (waves 0-3 in M while waves 4-7 are in V, a barrier between blocks): S, P, O and Q^T live at once need 209-237
 // registers, i.e. ONE workgroup per CU where the kernel above (128 registers) runs two — N = 2305, 21 windows: 502 -> 683-787 us
@@ -982,34 +1036,12 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_x3_pp_kernel(const char *__re
     const char *Vb = Vt + (int64_t)bh * HD * npad * 4;
     const int nt = (N + 31) >> 5;
 
-    bf16x8 qh[4], ql[4];  // Q^T as the B operand (issued first: the prologue's wait covers it)
-    {
-        const char *qp = Qb + (int64_t)min(q0 + r, N - 1) * (HD * 4);
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            const char *p = qp + (s >> 1) * 128 + ((s & 1) * 16 + 8 * h) * 2;
-            qh[s] = *(const bf16x8 *)p;
-            ql[s] = *(const bf16x8 *)(p + 64);
-        }
-    }
+    bf16x8 qh[4], ql[4];
+    x3_load_q(Qb + (int64_t)min(q0 + r, N - 1) * (HD * 4), h, qh, ql);
     int voffK[KP], voffV[VP ? VP : 1];
-    {
-        const int lrow = lane >> 3, slot = lane & 7;
-#pragma unroll
-        for (int j = 0; j < KP; ++j) {
-            const int pc = j * NW + wave, rho = (pc & 3) * 8 + lrow;
-            voffK[j] = rho * (HD * 4) + (pc >> 2) * 128 + ((slot ^ ((rho >> 1) & 7)) << 4);
-        }
-#pragma unroll
-        for (int j = 0; j < VP; ++j) {
-            const int rho = (j * NW + wave) * 8 + lrow;
-            voffV[j] = rho * npad * 4 + ((slot ^ ((rho >> 1) & 7)) << 4);
-        }
-    }
+    x3_piece_offsets<HD, NW, KP, VP>(lane, wave, npad, voffK, voffV);
 #if defined(__HIP_DEVICE_COMPILE__)
-    typedef __attribute__((address_space(3))) void *lds_ptr;
-    const auto rsK = __builtin_amdgcn_make_buffer_rsrc((void *)Kb, 0, (unsigned)(npad * HD * 4), 0x00020000);
-    const auto rsV = __builtin_amdgcn_make_buffer_rsrc((void *)Vb, 0, (unsigned)(HD * npad * 4), 0x00020000);
+    const auto rsK = x3_tile_rsrc<HD>(Kb, npad), rsV = x3_tile_rsrc<HD>(Vb, npad);
 #define OCM_PP_DMA_K(t, slot)                                                                                        \
     do {                                                                                                             \
         _Pragma("unroll") for (int j = 0; j < KP; ++j)                                                               \
@@ -1057,7 +1089,7 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_x3_pp_kernel(const char *__re
     const int first_pad = N - (nt - 1) * 32;  // valid keys of the last tile (1..32)
 
     // S = K(tile in K slot `ks`) . Q^T
-    auto qk = [&](int ks) {
+    auto qk = [&](int ks) {  // own copy of the score step (see the steps above)
         const char *Kt = smem + ks * KB;
 #pragma unroll
         for (int e = 0; e < 16; ++e) S[e] = 0.f;
@@ -1071,7 +1103,7 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_x3_pp_kernel(const char *__re
     };
     // block M(t): P.V of tile t (V^T slot vs), then the scores of tile t + 1 (K slot ks) — P's registers are free for them
     auto Mblk = [&](int vs, int ks, bool more) {
-        if (WANT_O) {
+        if (WANT_O) {  // own copy of the P.V step
             const char *Vtile = smem + (3 + vs) * KB;
 #pragma unroll
             for (int s2 = 0; s2 < 2; ++s2)
@@ -1087,42 +1119,12 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_x3_pp_kernel(const char *__re
     };
     // block V(t): softmax of the scores in S (tile t), P as split pairs
     auto Vblk = [&](bool last_of_seq) {
-        if (last_of_seq && first_pad < 32) {  // padding keys -> -inf (wave-uniform branch)
-#pragma unroll
-            for (int e = 0; e < 16; ++e)
-                if (key_of_reg(e, h) >= first_pad) S[e] = -INFINITY;
-        }
-        float mx = S[0];
-#pragma unroll
-        for (int e = 1; e < 16; ++e) mx = fmaxf(mx, S[e]);
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        const float alpha = defer_max_update(m, mx * scale2);  // every tile holds at least one valid key: finite
-        const float mn = m;
-        float ps = 0.f;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-            const float p = fast_exp2(fmaf(S[e], scale2, -mn));
-            S[e] = p;
-            ps += p;
-        }
-        l = fmaf(l, alpha, ps);
+        if (last_of_seq && first_pad < 32) x3_mask_pad_keys(S, first_pad, h);
+        const float alpha = x3_softmax(S, scale2, m, l);
         if (WANT_O) {
-            if (__any(alpha != 1.0f)) {  // the running max moved somewhere in this wave
+            x3_rescale(O, alpha);
 #pragma unroll
-                for (int e = 0; e < 16; ++e) {
-                    O[0][e] *= alpha;
-                    O[1][e] *= alpha;
-                }
-            }
-#pragma unroll
-            for (int s2 = 0; s2 < 2; ++s2)
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const float pv = S[8 * s2 + e];
-                    const bf16 t = (bf16)pv;
-                    ph[s2][e] = t;
-                    pl[s2][e] = (bf16)(pv - (float)t);
-                }
+            for (int s2 = 0; s2 < 2; ++s2) x3_split_p(S, s2, ph[s2], pl[s2]);
         }
     };
 
@@ -1141,22 +1143,8 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_x3_pp_kernel(const char *__re
         if (WANT_O && kt + 2 < nt) OCM_PP_DMA_V(kt + 2, s2n);
         const bool last = kt + 1 == nt;
         if (WANT_O && last && first_pad < 32) {
-            // zero the V^T columns of the padding keys of the last tile (it has landed: waited for in front of the previous
-            // barrier; the qkv epilogue never writes them and 0 * garbage must not be NaN)
-            const int kc = tid & 3;
-            if (kc * 8 + 8 > first_pad) {
-                char *Vtile = smem + (3 + s0) * KB;
-                const int d = tid >> 2;
-#pragma unroll
-                for (int half = 0; half < 2; ++half) {
-                    bf16x8 *p = (bf16x8 *)(Vtile + lds_off(d, half * 4 + kc));
-                    bf16x8 t = *p;
-#pragma unroll
-                    for (int e = 0; e < 8; ++e)
-                        if (kc * 8 + e >= first_pad) t[e] = (bf16)0.f;
-                    *p = t;
-                }
-            }
+            // the last tile has landed: waited for in front of the previous barrier
+            x3_zero_pad_keys<HD, 64>(smem + (3 + s0) * KB, tid >> 2, tid & 3, first_pad);
             block_barrier();
         }
         if (active) {
@@ -1248,33 +1236,11 @@ __global__ __launch_bounds__(256) void attn_fwd_x3_ws_kernel(const char *__restr
     char *mine = smem + wave * 2 * SLOT;
 
     bf16x8 qh[4], ql[4];
-    {
-        const char *qp = Qb + (int64_t)min(q0 + r, N - 1) * (HD * 4);
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            const char *p = qp + (s >> 1) * 128 + ((s & 1) * 16 + 8 * h) * 2;
-            qh[s] = *(const bf16x8 *)p;
-            ql[s] = *(const bf16x8 *)(p + 64);
-        }
-    }
-    // one wave fills a whole tile: pieces 0..7 of K (image pc >> 2, rows (pc & 3) * 8 ..) and of V^T (d rows pc * 8 ..)
-    int voffK[8], voffV[WANT_O ? 8 : 1];
-    {
-        const int lrow = lane >> 3, slot = lane & 7;
-#pragma unroll
-        for (int pc = 0; pc < 8; ++pc) {
-            const int rho = (pc & 3) * 8 + lrow;
-            voffK[pc] = rho * (HD * 4) + (pc >> 2) * 128 + ((slot ^ ((rho >> 1) & 7)) << 4);
-            if (WANT_O) {
-                const int rv = pc * 8 + lrow;
-                voffV[pc] = rv * npad * 4 + ((slot ^ ((rv >> 1) & 7)) << 4);
-            }
-        }
-    }
+    x3_load_q(Qb + (int64_t)min(q0 + r, N - 1) * (HD * 4), h, qh, ql);
+    int voffK[8], voffV[WANT_O ? 8 : 1];  // one wave fills a whole tile
+    x3_piece_offsets<HD, 1, 8, WANT_O ? 8 : 0>(lane, 0, npad, voffK, voffV);
 #if defined(__HIP_DEVICE_COMPILE__)
-    typedef __attribute__((address_space(3))) void *lds_ptr;
-    const auto rsK = __builtin_amdgcn_make_buffer_rsrc((void *)Kb, 0, (unsigned)(npad * HD * 4), 0x00020000);
-    const auto rsV = __builtin_amdgcn_make_buffer_rsrc((void *)Vb, 0, (unsigned)(HD * npad * 4), 0x00020000);
+    const auto rsK = x3_tile_rsrc<HD>(Kb, npad), rsV = x3_tile_rsrc<HD>(Vb, npad);
 #define OCM_WS_DMA(t, sl)                                                                                              \
     do {                                                                                                               \
         char *st_ = mine + (sl) * SLOT;                                                                                \
@@ -1317,23 +1283,10 @@ __global__ __launch_bounds__(256) void attn_fwd_x3_ws_kernel(const char *__restr
         char *Kt = mine + sl * SLOT, *Vtile = Kt + KB;
         const bool last_of_seq = t + 1 == nt;
         if (WANT_O && last_of_seq && first_pad < 32) {  // zero the V^T columns of the padding keys (my own slot: no barrier)
-            const int kc = lane & 3;
-            if (kc * 8 + 8 > first_pad) {
-#pragma unroll
-                for (int d = lane >> 2; d < HD; d += 16)
-#pragma unroll
-                    for (int half = 0; half < 2; ++half) {
-                        bf16x8 *p = (bf16x8 *)(Vtile + lds_off(d, half * 4 + kc));
-                        bf16x8 tv = *p;
-#pragma unroll
-                        for (int e = 0; e < 8; ++e)
-                            if (kc * 8 + e >= first_pad) tv[e] = (bf16)0.f;
-                        *p = tv;
-                    }
-            }
+            x3_zero_pad_keys<HD, 16>(Vtile, lane >> 2, lane & 3, first_pad);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         }
-        f32x16 S;
+        f32x16 S;  // own copy of the score step (see the steps above)
 #pragma unroll
         for (int e = 0; e < 16; ++e) S[e] = 0.f;
 #pragma unroll
@@ -1343,6 +1296,7 @@ __global__ __launch_bounds__(256) void attn_fwd_x3_ws_kernel(const char *__restr
             const bf16x8 kl = *(const bf16x8 *)(kp + lds_off(pr, 4 + (s & 1) * 2 + h));
             S = mfma32x3(kh, kl, qh[s], ql[s], S);
         }
+        // own copy of x3_mask_pad_keys and x3_softmax: through the calls the statistics-only kernel is allocated 92 registers for 104
         if (last_of_seq && first_pad < 32) {
 #pragma unroll
             for (int e = 0; e < 16; ++e)
@@ -1362,25 +1316,13 @@ __global__ __launch_bounds__(256) void attn_fwd_x3_ws_kernel(const char *__restr
         }
         l = fmaf(l, alpha, ps);
         if (WANT_O) {
-            if (__any(alpha != 1.0f)) {
-#pragma unroll
-                for (int e = 0; e < 16; ++e) {
-                    O[0][e] *= alpha;
-                    O[1][e] *= alpha;
-                }
-            }
+            x3_rescale(O, alpha);
 #pragma unroll
             for (int s2 = 0; s2 < 2; ++s2) {
                 bf16x8 ph, pl;
+                x3_split_p(S, s2, ph, pl);
 #pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const float pv = S[8 * s2 + e];
-                    const bf16 tb = (bf16)pv;
-                    ph[e] = tb;
-                    pl[e] = (bf16)(pv - (float)tb);
-                }
-#pragma unroll
-                for (int db = 0; db < 2; ++db) {
+                for (int db = 0; db < 2; ++db) {  // own copy of the P.V step
                     const char *vp = Vtile + db * 32 * 128;
                     const bf16x8 vh = *(const bf16x8 *)(vp + lds_off(r, 2 * s2 + h));
                     const bf16x8 vl = *(const bf16x8 *)(vp + lds_off(r, 4 + 2 * s2 + h));
@@ -1738,40 +1680,32 @@ hipError_t launch_attention(int prec, const void *q, const void *k, const void *
     return hipGetLastError();
 }
 
+// gridz: the split-bf16 kernel's grid (key chunks in grid.z); the other two walk all keys
+template <int HD>
+static hipError_t launch_probs_hd(int prec, const void *q, const void *k, const float *lse2, float *attn, int n_tokens, int n_pad,
+                                  float scale2, dim3 grid, dim3 gridz, hipStream_t s) {
+    const dim3 block(256);
+    if (prec == 2)
+        attn_probs_x3_kernel<HD><<<gridz, block, 0, s>>>((const char *)q, (const char *)k, lse2, attn, n_tokens, n_pad, scale2);
+    else if (prec)
+        attn_probs_f32_kernel<HD><<<grid, block, 0, s>>>((const float *)q, (const float *)k, lse2, attn, n_tokens, n_pad, scale2);
+    else
+        attn_probs_kernel<HD><<<grid, block, 0, s>>>((const bf16 *)q, (const bf16 *)k, lse2, attn, n_tokens, n_pad, scale2);
+    return hipGetLastError();
+}
+
 hipError_t launch_attention_probs(int prec, const void *q, const void *k, const float *lse2, float *attn, int batch,
                                   int n_tokens, int n_pad, int heads, float scale, hipStream_t s, int head_dim) {
     const int qtiles = (n_tokens + 31) / 32;
-    const dim3 grid((qtiles + 3) / 4, batch * heads), block(256);
+    const dim3 grid((qtiles + 3) / 4, batch * heads);
     // split-bf16 kernels: key chunks in grid.z until there are ~512 workgroups (a one-tile call is 12 .. 114 otherwise)
     const int wgs = (int)(grid.x * grid.y), ktiles = qtiles;
     int nz = wgs >= 256 ? 1 : min(ktiles, min(16, (512 + wgs - 1) / wgs));
     if (OCM_KNOB(2) > 0) nz = min(ktiles, OCM_KNOB(2));  // development A/B
     const dim3 gridz(grid.x, grid.y, nz);
-    if (head_dim == 128 && prec == 2) {
-        attn_probs_x3_kernel<128><<<gridz, block, 0, s>>>((const char *)q, (const char *)k, lse2, attn, n_tokens, n_pad,
-                                                          scale * LOG2E);
-        return hipGetLastError();
-    }
-    if (head_dim == 128) {  // 128-wide heads in the fp32 / single-bf16 precisions
-        if (prec)
-            attn_probs_f32_kernel<128><<<grid, block, 0, s>>>((const float *)q, (const float *)k, lse2, attn, n_tokens, n_pad,
-                                                              scale * LOG2E);
-        else
-            attn_probs_kernel<128><<<grid, block, 0, s>>>((const bf16 *)q, (const bf16 *)k, lse2, attn, n_tokens, n_pad,
-                                                          scale * LOG2E);
-        return hipGetLastError();
-    }
+    if (head_dim == 128) return launch_probs_hd<128>(prec, q, k, lse2, attn, n_tokens, n_pad, scale * LOG2E, grid, gridz, s);
     if (head_dim != 64) return hipErrorInvalidValue;
-    if (prec == 2)
-        attn_probs_x3_kernel<64><<<gridz, block, 0, s>>>((const char *)q, (const char *)k, lse2, attn, n_tokens, n_pad,
-                                                     scale * LOG2E);
-    else if (prec)
-        attn_probs_f32_kernel<64><<<grid, block, 0, s>>>((const float *)q, (const float *)k, lse2, attn, n_tokens, n_pad,
-                                                         scale * LOG2E);
-    else
-        attn_probs_kernel<64><<<grid, block, 0, s>>>((const bf16 *)q, (const bf16 *)k, lse2, attn, n_tokens, n_pad,
-                                                     scale * LOG2E);
-    return hipGetLastError();
+    return launch_probs_hd<64>(prec, q, k, lse2, attn, n_tokens, n_pad, scale * LOG2E, grid, gridz, s);
 }
 
 // ------------------------------------------------------------------------------------------

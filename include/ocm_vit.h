@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define OCM_ABI_VERSION 15
+#define OCM_ABI_VERSION 16
 
 enum {
     OCM_OK = 0,
@@ -385,6 +385,45 @@ int ocm_op_pixel_shuffle(const float *lin, float *out, int32_t batch, int32_t hp
  * matching weight is the (O, C, 3, 3) kernel permuted to (O, 3, 3, C). */
 int ocm_op_im2col3x3(int32_t precision, const float *in, void *out, int32_t batch, int32_t h, int32_t w,
                      int32_t channels, int32_t relu, void *stream);
+
+/* ---- U-Net inference (model.py:227-320: build_unet; kernels_conv.hip) ----
+ * Activations are fp32 and token-major (NHWC): row m = (b, y, x). Every activation argument has a leading dimension in floats
+ * (>= its channel count, a multiple of 4), so an operator reads or writes a channel slice of a wider buffer:
+ * torch.cat([up, skip], 1) is the up-convolution writing columns [0, O) and the encoder's second convolution writing columns
+ * [O, 2 O) of one 2 O-wide buffer. Activation and weight pointers are 16-byte aligned. No atomics: the same inputs give the
+ * same bits on every run. */
+
+/* Conv2d(C, O, 3, padding=1): out[m][o] = act(bias[o] + sum_{ky,kx,c} in[(b, y+ky-1, x+kx-1)][c] * W[o][(ky*3+kx)*C + c]), zeros
+ * outside the image, act = ReLU when relu != 0. W: operand copy (type E of `precision`) of the (O, C, 3, 3) kernel permuted to
+ * (O, 3, 3, C), rows of 9 C elements (ocm_op_im2col3x3's K order). The rows of the 3x3 neighbourhood are gathered and converted
+ * on the way into LDS: no 9 C-wide operand exists in memory. C % 32 == 0 (C <= 4096), O % 32 == 0. */
+int ocm_op_conv3x3(int32_t precision, const float *in, int64_t ld_in, const void *w, const float *bias, float *out,
+                   int64_t ld_out, int32_t batch, int32_t h, int32_t w_px, int32_t channels, int32_t out_channels, int32_t relu,
+                   void *stream);
+/* nn.Linear + ReLU into a column slice: out[m][0..N) = max(A[M][K] . W[N][K]^T + bias[N], 0) in fp32, rows ld_out floats apart;
+ * A, W of type E as for ocm_op_linear (same shape rules, same tile dispatch). With ocm_op_im2col3x3 in front it is the 3x3
+ * convolution as a composition: what build_unet runs where that measures faster than ocm_op_conv3x3 (few rows, long K). */
+int ocm_op_linear_relu(int32_t precision, const void *a, const void *w, const float *bias, float *out, int64_t ld_out, int32_t M,
+                       int32_t N, int32_t K, void *stream);
+/* The same for a three-channel image read in place: pixel (b, c, y, x) = image[b*stride_b + c*stride_c + y*stride_y + x] (element
+ * strides, any alignment). W: operand copy of the (O, 3, 3, 3) kernel permuted to (O, 3, 3, 3 = c), its 27 columns followed by zero
+ * columns up to one K step: rows of 32 elements (fp32, split pairs) or 64 (bf16). */
+int ocm_op_conv3x3_image(int32_t precision, const float *image, int64_t stride_b, int64_t stride_c, int64_t stride_y,
+                         const void *w, const float *bias, float *out, int64_t ld_out, int32_t batch, int32_t h, int32_t w_px,
+                         int32_t out_channels, int32_t relu, void *stream);
+/* nn.MaxPool2d((2, 2)): out[(b, y, x)][c] = max over in[(b, 2y+i, 2x+j)][c], bit exact with torch (NaN propagates). h, w even,
+ * C % 4 == 0. */
+int ocm_op_maxpool2x2(const float *in, int64_t ld_in, float *out, int64_t ld_out, int32_t batch, int32_t h, int32_t w,
+                      int32_t channels, void *stream);
+/* nn.ConvTranspose2d(C, O, 2, stride=2): out[(b, 2y+i, 2x+j)][o] = bias[o] + sum_c in[(b, y, x)][c] * Wt[c][o][i][j]; h, w_px are
+ * the INPUT grid. One GEMM with N = 4 O whose epilogue places the four O-wide groups at their pixels. W: operand copy of the
+ * (C, O, 2, 2) kernel permuted to (2, 2, O, C): row (i*2 + j)*O + o, C elements. C % 32 == 0, O % 32 == 0, bias 16-byte aligned. */
+int ocm_op_upconv2x2(int32_t precision, const float *in, int64_t ld_in, const void *w, const float *bias, float *out,
+                     int64_t ld_out, int32_t batch, int32_t h, int32_t w_px, int32_t channels, int32_t out_channels, void *stream);
+/* Conv2d(C, 1, 1) written as planes: out[b][0][p] = bias[0] + sum_c in[b*hw + p][c] * w[c] in fp32 (bias may be NULL), out
+ * (B, 1, hw) contiguous. C % 4 == 0. */
+int ocm_op_conv1x1_planes(const float *in, int64_t ld_in, const float *w, const float *bias, float *out, int32_t batch,
+                          int64_t hw, int32_t channels, void *stream);
 
 /* ---- training of the LinearProbing decoders on a frozen encoder (model.py:142-174; kernels_train.hip) ----
  * Token-major rows m = (image, y, x), M = B*hp*wp. Every reduction runs in a fixed order decided by the shapes alone (no

@@ -1,0 +1,120 @@
+"""Memory behaviour of the U-Net operators and of build_unet.forward (tests/memcheck.py): outputs between guard bands, payload
+columns outside an operator's slice unchanged, every buffer NaN-poisoned before the call, and one whole-model forward whose
+activation buffers all come from poisoned, guard-banded memory — bit for bit the logits of a clean run."""
+import pytest
+import torch
+
+from tests.memcheck import PATTERNS, Guarded, assert_same_bits
+from tests.unet_twin import make_case
+from vit_ocm_wmsegmentation_amd import _lib
+from vit_ocm_wmsegmentation_amd import model as M
+from vit_ocm_wmsegmentation_amd.engine import to_operand
+
+pytestmark = pytest.mark.gpu
+
+NAN_WORD = PATTERNS["nan"] - (1 << 32) if PATTERNS["nan"] >= 1 << 31 else PATTERNS["nan"]
+
+
+def _s():
+    return torch.cuda.current_stream().cuda_stream
+
+
+def _guarded_out(rows, ld, dev):
+    g = Guarded(rows * ld * 4, dev, pattern="nan")
+    return g, g.payload(torch.int32, (rows, ld))
+
+
+def _check_slice(g, view, lo, width, what):
+    """Guards intact, columns outside [lo, lo + width) still the poison, columns inside all written with finite values."""
+    torch.cuda.synchronize()
+    assert g.check() is None, f"{what}: {g.check()}"
+    outside = torch.cat([view[:, :lo], view[:, lo + width:]], dim=1)
+    assert bool((outside == NAN_WORD).all()), f"{what}: payload columns outside the operator's slice changed"
+    inside = view[:, lo:lo + width].view(torch.float32)
+    assert bool(torch.isfinite(inside).all()), f"{what}: unwritten or non-finite output elements"
+    return inside.clone()
+
+
+def _poisoned_in(rows, dev, lo=4, hi=4):
+    buf = torch.full((rows.shape[0], lo + rows.shape[1] + hi), float("nan"), device=dev)
+    buf[:, lo:lo + rows.shape[1]] = rows.to(dev)
+    return buf, buf.data_ptr() + 4 * lo, buf.shape[1]
+
+
+@pytest.mark.parametrize("precision", ("fp32", "bf16x3", "bf16"))
+def test_gemm_operators_in_guarded_outputs(lib, dev, precision):
+    pc = _lib.PRECISIONS[precision]
+    g = torch.Generator().manual_seed(31)
+    # conv3x3: B=3, 5x7, C=32 -> O=32 into columns [32, 64) of a 72-wide payload
+    B, h, w, C, O = 3, 5, 7, 32, 32
+    rows = torch.randn(B * h * w, C, generator=g)
+    w_op = to_operand(torch.randn(O, 9 * C, generator=g).to(dev), pc)
+    bias = torch.randn(O, generator=g).to(dev)
+    inbuf, in_ptr, ld_in = _poisoned_in(rows, dev)
+    outs = []
+    for _ in range(2):
+        gd, view = _guarded_out(B * h * w, 72, dev)
+        assert lib.ocm_op_conv3x3(pc, in_ptr, ld_in, w_op.data_ptr(), bias.data_ptr(), gd.ptr + 4 * 32, 72, B, h, w, C, O, 1, _s()) == 0
+        outs.append(_check_slice(gd, view, 32, O, f"conv3x3 {precision}"))
+    assert_same_bits(outs[0], outs[1], "conv3x3 run to run")
+    # conv3x3_image: B=2, 16x24 -> O=32 into columns [0, 32) of a 40-wide payload
+    img = torch.randn(2, 3, 16, 24, generator=g).to(dev)
+    kp = 64 if precision == "bf16" else 32
+    wi = to_operand(torch.nn.functional.pad(torch.randn(32, 27, generator=g), (0, kp - 27)).to(dev), pc)
+    gd, view = _guarded_out(2 * 16 * 24, 40, dev)
+    assert lib.ocm_op_conv3x3_image(pc, img.data_ptr(), img.stride(0), img.stride(1), img.stride(2), wi.data_ptr(), bias.data_ptr(),
+                                    gd.ptr, 40, 2, 16, 24, 32, 0, _s()) == 0
+    _check_slice(gd, view, 0, 32, f"conv3x3_image {precision}")
+    # upconv2x2: B=2, 3x5, C=64 -> O=32 into the left half of a 64-wide payload
+    rows = torch.randn(2 * 3 * 5, 64, generator=g)
+    wu = to_operand(torch.randn(4 * 32, 64, generator=g).to(dev), pc)
+    inbuf, in_ptr, ld_in = _poisoned_in(rows, dev)
+    gd, view = _guarded_out(2 * 6 * 10, 64, dev)
+    assert lib.ocm_op_upconv2x2(pc, in_ptr, ld_in, wu.data_ptr(), bias.data_ptr(), gd.ptr, 64, 2, 3, 5, 64, 32, _s()) == 0
+    _check_slice(gd, view, 0, 32, f"upconv2x2 {precision}")
+
+
+def test_fp32_operators_in_guarded_outputs(lib, dev):
+    g = torch.Generator().manual_seed(32)
+    rows = torch.randn(2 * 6 * 10, 64, generator=g)
+    inbuf, in_ptr, ld_in = _poisoned_in(rows, dev)
+    gd, view = _guarded_out(2 * 3 * 5, 72, dev)
+    assert lib.ocm_op_maxpool2x2(in_ptr, ld_in, gd.ptr + 16, 72, 2, 6, 10, 64, _s()) == 0
+    _check_slice(gd, view, 4, 64, "maxpool2x2")
+    rows = torch.randn(2 * 35, 64, generator=g)
+    inbuf, in_ptr, ld_in = _poisoned_in(rows, dev)
+    wv, bias = torch.randn(64, generator=g).to(dev), torch.randn(1, generator=g).to(dev)
+    gd, view = _guarded_out(1, 2 * 35, dev)
+    assert lib.ocm_op_conv1x1_planes(in_ptr, ld_in, wv.data_ptr(), bias.data_ptr(), gd.ptr, 2, 35, 64, _s()) == 0
+    _check_slice(gd, view, 0, 70, "conv1x1_planes")
+
+
+def test_whole_model_on_poisoned_activation_buffers(dev):
+    x = torch.randn(1, 3, 32, 32, generator=torch.Generator().manual_seed(41), dtype=torch.float64)
+    twin = make_case(41, x)
+    net = M.build_unet()
+    net.load_state_dict({k: v.float() if v.is_floating_point() else v for k, v in twin.state_dict().items()}, strict=True)
+    net = net.to(dev).eval()
+    xd = x.float().to(dev)
+    clean = net(xd)
+    held = []
+
+    def poisoned(shape, device):
+        n = 1
+        for s in shape:
+            n *= s
+        gd = Guarded(n * 4, device, pattern="nan")
+        held.append(gd)
+        return gd.payload(torch.float32, tuple(shape))
+
+    net.__dict__["_alloc"] = poisoned
+    out = net(xd)
+    torch.cuda.synchronize()
+    # per encoder level t, [up | skip], pooled; the bottleneck's two; per decoder level two; and the im2col operand of the six
+    # layers that split-bf16 runs as a composition (e4, b, d1: model._unet_composed)
+    assert len(held) == 4 * 3 + 2 + 4 * 2 + 6
+    for i, gd in enumerate(held):
+        assert gd.check() is None, f"activation buffer {i}: {gd.check()}"
+        assert bool(torch.isfinite(gd.payload(torch.float32)).all()), f"activation buffer {i} holds unwritten elements"
+    assert bool(torch.isfinite(out).all())
+    assert_same_bits(out, clean, "poisoned buffers vs clean run", ("image", "channel", "y", "x"))

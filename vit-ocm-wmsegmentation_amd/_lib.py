@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # OCM_VIT_LIB lets kernel experiments A/B two builds of the same ABI; the default is the in-tree build.
 LIB_PATH = os.environ.get("OCM_VIT_LIB") or os.path.join(_HERE, "libocm_vit.so")
 
-OCM_ABI_VERSION = 15
+OCM_ABI_VERSION = 16
 OCM_OK, OCM_EINVAL, OCM_ESTATE, OCM_EHIP, OCM_ENOMEM, OCM_ENAME = 0, 1, 2, 3, 4, 5
 
 OCM_PREC_BF16 = 0
@@ -180,6 +180,12 @@ SIGNATURES = {
     "ocm_op_median_filter": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "ocm_op_downscale_centre": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "ocm_op_im2col3x3": (C.c_int, [_i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "ocm_op_conv3x3": (C.c_int, [_i32, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "ocm_op_conv3x3_image": (C.c_int, [_i32, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "ocm_op_linear_relu": (C.c_int, [_i32, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp]),
+    "ocm_op_maxpool2x2": (C.c_int, [_vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _vp]),
+    "ocm_op_upconv2x2": (C.c_int, [_i32, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "ocm_op_conv1x1_planes": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _i32, _i64, _i32, _vp]),
     "ocm_op_head_mean": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "ocm_op_image_to_gray_u8": (C.c_int, [_vp, _i64, _i32, _i64, _vp, _vp, _vp]),
     "ocm_op_blend_u8": (C.c_int, [_vp, _vp, _i64, C.c_double, C.c_double, _vp, _vp, _vp]),

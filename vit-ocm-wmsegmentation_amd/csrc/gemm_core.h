@@ -20,6 +20,7 @@
 // The accumulator can be produced transposed (SWAP): acc^T has the token index on the lanes, which is
 // how the V projection is written key-contiguous (V^T) with coalesced stores.
 #pragma once
+#include <type_traits>
 #include "common.h"
 
 // Development instrumentation (make stamps -> exp_libs/stamps.so, tools/stamps.py): thread 0 of every workgroup
@@ -123,6 +124,18 @@ struct RowLoader {
         return *(const Raw *)(h + t * 128 + c * 16);
     }
     __device__ __forceinline__ static Raw finish(const Raw &r, int) { return r; }
+};
+
+// A loader may declare W_TAIL = true and carry w_row_bytes: the W rows then end inside the last K step (a contraction length that is
+// no multiple of KROW) and the chunks past the row's end are staged as zeros instead of being read. Loaders without the member
+// compile to the plain load.
+template <class AL, class = void>
+struct aload_w_tail {
+    static constexpr bool v = false;
+};
+template <class AL>
+struct aload_w_tail<AL, std::void_t<decltype(AL::W_TAIL)>> {
+    static constexpr bool v = AL::W_TAIL;
 };
 
 // One K step of MFMAs on the LDS tiles at Ab / Bb (already offset to the wave's rows).
@@ -285,7 +298,14 @@ __device__ __forceinline__ void gemm_mainloop(const ALoad &al, const E *__restri
 #if defined(OCM_ABL) && (OCM_ABL == 9 || OCM_ABL == 10)  // ablation 9 (10: both operands): the W operand re-reads its first K step (cache hits)
         for (int i = 0; i < B_CH; ++i) sl.b[i] = *(const Chunk *)(b_h[i]);
 #else
-        for (int i = 0; i < B_CH; ++i) sl.b[i] = *(const Chunk *)(b_h[i] + t * 128);
+        for (int i = 0; i < B_CH; ++i) {
+            if constexpr (aload_w_tail<ALoad>::v) {
+                sl.b[i] = Chunk{};
+                if (t * 128 + cc * 16 < al.w_row_bytes) sl.b[i] = *(const Chunk *)(b_h[i] + t * 128);
+            } else {
+                sl.b[i] = *(const Chunk *)(b_h[i] + t * 128);
+            }
+        }
 #endif
     };
     auto commit = [&](int buf, const Slot &sl) {

@@ -100,6 +100,7 @@ __device__ __forceinline__ void store_act1(sp32 *, char *rowp, int col, float v)
 // out = epilogue(acc) with the bias already in the accumulator (gemm_mainloop).
 //   MODE 0: fp32 out            MODE 1: fp32 out = resid + acc (resid may alias out)
 //   MODE 2: OE out = gelu(acc)  MODE 3: OE out = acc          (OE = operand type of the next GEMM)
+//   MODE 4: fp32 out = max(acc, 0)  (the U-Net's 3x3 layers that run as im2col + GEMM, kernels_conv.hip)
 // Every lane moves 16 B per chunk. The residual of ALL of a lane's chunks is requested in one burst
 // before the first use (one exposed L2 round trip instead of one per unrolled group).
 // (mu, rstd) of row m from the sums its producers accumulated (launch.h: LnFold)
@@ -171,6 +172,10 @@ struct EpiLinear {
             f32x4 v0 = *(const f32x4 *)(C + row * BN + col);
             if (!ACT_OUT) {
                 if (MODE == 1) v0 += rs[i];
+                if (MODE == 4) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v0[e] = fmaxf(v0[e], 0.f);
+                }
                 *(f32x4 *)((float *)out + o) = v0;
             } else {
                 f32x4 v1 = v0;
@@ -520,6 +525,15 @@ hipError_t launch_linear_mode(const E *a, const E *w, const float *bias, const f
         if (OCM_KNOB(6) == 2) epi.ln.nslot = 1;         // development timing probe (wrong results): one slot load per row
     }
     return launch_linear_epi<MODE, E>(a, w, epi, M, N, K, s);
+}
+
+// out[m][ldo] columns [0, N) = max(A W^T + bias, 0) in fp32: nn.Linear + ReLU into a column slice, on the same tile dispatch
+// (instantiated in kernels_conv.hip's objects)
+template <class E>
+hipError_t launch_linear_relu_e(const E *a, const E *w, const float *bias, float *out, int64_t ldo, int M, int N, int K,
+                                hipStream_t s) {
+    EpiLinear<4, E> epi{bias, nullptr, out, M, N, ldo};
+    return launch_linear_epi<4, E>(a, w, epi, M, N, K, s);
 }
 
 // Split-K form of the LDS-DMA nn.Linear kernel for few rows and a long contraction (launch.h: StatsOut::part): blockIdx.y is
@@ -1077,6 +1091,31 @@ hipError_t launch_qkv_e(const E *a, const E *w, const float *bias, E *q, E *k, E
 // chunk is 8 (bf16) or 4 (fp32) consecutive dx of one (c, dy): float4 loads from one image row,
 // converted to bf16 on the way into LDS in the bf16 path. Consecutive threads walk consecutive
 // chunks of a row, so a wave reads whole row segments of neighbouring patches (coalesced along x).
+// What the fp32-gathering loaders share (PatchLoader; kernels_conv.hip). First contraction index of chunk cc of K step t:
+// bf16 -> k = 64t + 8cc; fp32 -> k = 32t + 4cc; split pairs -> the hi (cc < 4) or lo (cc >= 4) halves of k = 32t + 8(cc & 3) .. +7
+template <class E>
+__device__ __forceinline__ int gather_k_of(int t, int cc) {
+    constexpr int MODE = Elem<E>::MODE;
+    return MODE == 0 ? t * 64 + cc * 8 : MODE == 1 ? t * 32 + cc * 4 : t * 32 + (cc & 3) * 8;
+}
+// ... and eight (four in fp32: `lo` alone) consecutive fp32 values as that chunk in the operand type
+struct GatherRaw {
+    f32x4 lo, hi;
+};
+template <class E>
+__device__ __forceinline__ typename Elem<E>::Chunk gather_finish(const GatherRaw &r, int cc) {
+    if constexpr (Elem<E>::MODE == 0) {
+        return cvt8(r.lo, r.hi);
+    } else if constexpr (Elem<E>::MODE == 1) {
+        return r.lo;
+    } else {
+        bf16x8 hi, lo;
+        split8(r.lo, r.hi, hi, lo);
+        const bf16x8 sel = cc < 4 ? hi : lo;
+        return __builtin_bit_cast(f32x4, sel);
+    }
+}
+
 template <class E>
 struct PatchLoader {
     const float *image;
@@ -1084,9 +1123,7 @@ struct PatchLoader {
     const int32_t *origins;
     int P, wp, p, pp;
     typedef const float *Handle;
-    struct Raw {
-        f32x4 lo, hi;
-    };
+    typedef GatherRaw Raw;
     __device__ __forceinline__ Handle row(int m) const {
         const int b = m / P, pi = m - b * P;
         const int py = pi / wp, px = pi - py * wp;
@@ -1097,11 +1134,9 @@ struct PatchLoader {
         }
         return image + (int64_t)b * sb + (int64_t)(y0 + py * p) * sy + x0 + px * p;
     }
-    // chunk cc of K step t: bf16 -> k = 64t + 8cc .. +7; fp32 -> k = 32t + 4cc .. +3; split pairs -> the hi (cc < 4)
-    // or lo (cc >= 4) halves of k = 32t + 8(cc & 3) .. +7
     __device__ __forceinline__ Raw load(Handle h, int t, int cc) const {
         constexpr int MODE = Elem<E>::MODE;
-        const int k = MODE == 0 ? t * 64 + cc * 8 : MODE == 1 ? t * 32 + cc * 4 : t * 32 + (cc & 3) * 8;
+        const int k = gather_k_of<E>(t, cc);
         const int c = k / pp, rem = k - c * pp;
         const int dy = rem / p, dx = rem - dy * p;
         const float *ptr = h + (int64_t)c * sc + (int64_t)dy * sy + dx;
@@ -1111,18 +1146,7 @@ struct PatchLoader {
         if (MODE != 1) r.hi = *(const f32x4 *)(ptr + 4);
         return r;
     }
-    __device__ __forceinline__ static typename Elem<E>::Chunk finish(const Raw &r, int cc) {
-        if constexpr (Elem<E>::MODE == 0) {
-            return cvt8(r.lo, r.hi);
-        } else if constexpr (Elem<E>::MODE == 1) {
-            return r.lo;
-        } else {
-            bf16x8 hi, lo;
-            split8(r.lo, r.hi, hi, lo);
-            const bf16x8 sel = cc < 4 ? hi : lo;
-            return __builtin_bit_cast(f32x4, sel);
-        }
-    }
+    __device__ __forceinline__ static typename Elem<E>::Chunk finish(const Raw &r, int cc) { return gather_finish<E>(r, cc); }
 };
 
 // x[b][1 + pi][n] = acc + pos[1 + pi][n]   (prepare_tokens :200-207, patch rows; bias is in acc)

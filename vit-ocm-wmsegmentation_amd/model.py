@@ -5,6 +5,7 @@
   VisionTransformerForFinetune  model.py:110-139  trunk -> (B,C,H,W)
   LinearProbing                 model.py:142-174  encoder + one-layer (1x1 conv + PixelShuffle) decoder
   build_model / build_finetune_model / get_state_dict   model.py:85-108,176-226
+  build_unet (convolution_block, encoder_block, decoder_block)   model.py:227-320  U-Net inference on the direct 3x3 convolution
 
 Same constructor arguments, attributes and state_dict keys. The encoders run in one engine call (the mask
 blend is fused into the patch-embedding epilogue, the (B,C,H,W) permute is a device transpose); the 1x1-conv
@@ -816,6 +817,184 @@ class _EncoderTrain(torch.autograd.Function):
                     (gpe,) = torch.autograd.grad(full, pe, dpos.cpu().reshape(full.shape))
                 grads["pos_embed"] = gpe
         return (None, None, *[put(n) for n in names])
+
+
+# ---- the U-Net (model.py:227-320). The nn modules hold the parameters and buffers (same tree, same state_dict keys); the
+# arithmetic of the eval-mode forward runs through kernels_conv.hip on token-major fp32 rows (build_unet.forward). ----
+class convolution_block(nn.Module):
+    def __init__(self, in_c, out_c):
+        super().__init__()
+        self.conv1 = nn.Conv2d(in_c, out_c, kernel_size=3, padding=1)
+        self.bn1 = nn.BatchNorm2d(out_c)
+        self.conv2 = nn.Conv2d(out_c, out_c, kernel_size=3, padding=1)
+        self.bn2 = nn.BatchNorm2d(out_c)
+        self.relu = nn.ReLU()
+
+
+class encoder_block(nn.Module):
+    def __init__(self, in_c, out_c):
+        super().__init__()
+        self.conv = convolution_block(in_c, out_c)
+        self.pool = nn.MaxPool2d((2, 2))
+
+
+class decoder_block(nn.Module):
+    def __init__(self, in_c, out_c):
+        super().__init__()
+        self.up = nn.ConvTranspose2d(in_c, out_c, kernel_size=2, stride=2, padding=0)
+        self.conv = convolution_block(out_c + out_c, out_c)
+
+
+def _rows_up2x2(w):
+    """(C, O, 2, 2) ConvTranspose2d kernel -> (4*O, C), row (i*2 + j)*O + o: the N order of ocm_op_upconv2x2."""
+    return w.permute(2, 3, 1, 0).reshape(-1, w.shape[0])
+
+
+def _unet_composed(prec, out_channels):
+    """Whether a 3x3 layer of the U-Net runs as ocm_op_im2col3x3 + ocm_op_linear_relu instead of ocm_op_conv3x3: the layer classes
+    at which the direct kernel measured slower at 384^2, batch 8 — in split-bf16 the three deepest levels (512 and
+    1024 output channels: e4, b, d1), in fp32 and bf16 the bottleneck. Decided by the layer, not by the batch, so that an image's
+    logits do not depend on the batch it is in."""
+    return out_channels >= (512 if prec == _lib.OCM_PREC_BF16X3 else 1024)
+
+
+def _unet_empty(shape, device):
+    """Activation buffers of build_unet.forward (fp32). Every element an operator reads was written by the operator before it."""
+    return torch.empty(shape, dtype=torch.float32, device=device)
+
+
+class build_unet(nn.Module):
+    """model.py:280-320: the U-Net PGT.py trains on pseudo ground truth and unet.py trains supervised. Inference runs on the
+    HIP path: every BatchNorm is folded, from its running statistics, into the convolution in front of it; ReLU sits in the
+    convolution's epilogue (the deepest layers run as im2col + GEMM, _unet_composed); torch.cat([up, skip], 1) is two writers of one 2 O-wide buffer (the up-convolution its left half,
+    the encoder's second convolution its right half, which the max-pool reads in place). Training is not on this path."""
+
+    def __init__(self):
+        super().__init__()
+        self.e1 = encoder_block(3, 64)
+        self.e2 = encoder_block(64, 128)
+        self.e3 = encoder_block(128, 256)
+        self.e4 = encoder_block(256, 512)
+        self.b = convolution_block(512, 1024)
+        self.d1 = decoder_block(1024, 512)
+        self.d2 = decoder_block(512, 256)
+        self.d3 = decoder_block(256, 128)
+        self.d4 = decoder_block(128, 64)
+        self.outputs = nn.Conv2d(64, 1, kernel_size=1, padding=0)
+        self.__dict__["_precision"] = _lib.DEFAULT_PRECISION
+        self.__dict__["_op_cache"] = {}
+        self.__dict__["_alloc"] = _unet_empty  # a test seam: the memory tests swap in an allocator of poisoned, guard-banded buffers
+
+    @property
+    def precision(self):
+        return self._precision
+
+    @precision.setter
+    def precision(self, name):
+        if name not in _lib.PRECISIONS:
+            raise ValueError(f"precision must be one of {sorted(_lib.PRECISIONS)}, got {name!r}")
+        self.__dict__["_precision"] = name
+
+    def _folded(self, name, conv, bn, prec, dev, image=False):
+        """(operand copy of the convolution's weight, fp32 bias) with the BatchNorm's running statistics folded in."""
+        f32 = dict(device=dev, dtype=torch.float32)
+
+        def gain():
+            return bn.weight.detach().to(**f32) / torch.sqrt(bn.running_var.detach().to(**f32) + bn.eps)
+
+        def weight():
+            rows = _rows3x3(conv.weight.detach().to(**f32) * gain()[:, None, None, None])
+            if image:  # 27 columns and zeros up to one K step of the operand type
+                rows = nn.functional.pad(rows, (0, (64 if prec == _lib.OCM_PREC_BF16 else 32) - rows.shape[1]))
+            return to_operand(rows.contiguous(), prec)
+
+        w = _cached_operand(self._op_cache, name + ".weight", (conv.weight, bn.weight, bn.running_var), prec, weight)
+        b = _cached_operand(self._op_cache, name + ".bias", (conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var),
+                            prec, lambda: ((conv.bias.detach().to(**f32) - bn.running_mean.detach().to(**f32)) * gain()
+                                           + bn.bias.detach().to(**f32)).contiguous())
+        return w, b
+
+    def forward(self, inputs):
+        if self.training and torch.is_grad_enabled():
+            raise NotImplementedError("build_unet runs inference on the HIP path; training (batch statistics, the backward of the "
+                                      "convolutions, pool and up-convolution) is not implemented. A new module is in training "
+                                      "mode: call .eval() (PGT.py's evaluate / fully_test do), or wrap the call in torch.no_grad()")
+        if any(m.training for m in self.modules() if isinstance(m, nn.BatchNorm2d)):
+            raise NotImplementedError("a BatchNorm2d of this build_unet is in training mode: inference is what runs on the HIP "
+                                      "path (running statistics are folded into the convolutions); call .eval()")
+        if not isinstance(inputs, torch.Tensor) or inputs.dim() != 4 or inputs.shape[1] != 3:
+            raise RuntimeError(f"build_unet expects a (B, 3, H, W) input, got {tuple(getattr(inputs, 'shape', ()))}")
+        B, _, H, W = inputs.shape
+        if H % 16 or W % 16 or H == 0 or W == 0 or B == 0:
+            raise RuntimeError(f"build_unet needs H and W that are multiples of 16 (four 2x2 pools, then four stride-2 "
+                               f"up-convolutions whose outputs are concatenated with the skips); got H={H}, W={W}")
+        _require_hip(inputs, "input")
+        with torch.no_grad(), torch.cuda.device(inputs.device):
+            return self._forward(inputs.detach().to(torch.float32))
+
+    def _forward(self, x):
+        lib, dev, prec = _lib.load(), x.device, _lib.PRECISIONS[self._precision]
+        B, _, H, W = x.shape
+        if x.stride(3) != 1:
+            x = x.contiguous()
+        alloc, st = self._alloc, _stream()
+
+        def conv(name, blk, which, src, ld_in, dst, ld_out, grid, C, O):
+            cv, bn = (blk.conv1, blk.bn1) if which == 1 else (blk.conv2, blk.bn2)
+            w, b = self._folded(f"{name}.conv{which}", cv, bn, prec, dev)
+            if _unet_composed(prec, O) and ld_in == C:
+                # few rows, long K: im2col + the LDS-DMA GEMM (ReLU and the output slice in its epilogue) measures faster
+                M = B * grid[0] * grid[1]
+                cols = alloc((M, 9 * C * _OPERAND_DTYPE[prec].itemsize // 4), dev)  # operand rows, in fp32-sized words
+                _lib.check(lib.ocm_op_im2col3x3(prec, src, _p(cols), B, grid[0], grid[1], C, 0, st))
+                _lib.check(lib.ocm_op_linear_relu(prec, _p(cols), _p(w), _p(b), dst, ld_out, M, O, 9 * C, st))
+                return
+            _lib.check(lib.ocm_op_conv3x3(prec, src, ld_in, _p(w), _p(b), dst, ld_out, B, grid[0], grid[1], C, O, 1, st))
+
+        widths = (64, 128, 256, 512)
+        encs, decs = (self.e1, self.e2, self.e3, self.e4), (self.d4, self.d3, self.d2, self.d1)
+        cats = []  # per level: the (M, 2 O) buffer [up | skip]
+        h, w, cur, Cin = H, W, None, 3
+        for lvl, (enc, O) in enumerate(zip(encs, widths)):
+            M = B * h * w
+            t = alloc((M, O), dev)
+            if lvl == 0:
+                wi, bi = self._folded("e1.conv1", enc.conv.conv1, enc.conv.bn1, prec, dev, image=True)
+                _lib.check(lib.ocm_op_conv3x3_image(prec, _p(x), x.stride(0), x.stride(1), x.stride(2), _p(wi), _p(bi), _p(t), O,
+                                                    B, h, w, O, 1, st))
+            else:
+                conv(f"e{lvl + 1}", enc.conv, 1, _p(cur), Cin, _p(t), O, (h, w), Cin, O)
+            cat = alloc((M, 2 * O), dev)
+            cats.append(cat)
+            skip_ptr = cat.data_ptr() + 4 * O
+            conv(f"e{lvl + 1}", enc.conv, 2, _p(t), O, skip_ptr, 2 * O, (h, w), O, O)
+            pooled = alloc((M // 4, O), dev)
+            _lib.check(lib.ocm_op_maxpool2x2(skip_ptr, 2 * O, _p(pooled), O, B, h, w, O, st))
+            cur, Cin, h, w = pooled, O, h // 2, w // 2
+        t = alloc((B * h * w, 1024), dev)
+        conv("b", self.b, 1, _p(cur), 512, _p(t), 1024, (h, w), 512, 1024)
+        cur = alloc((B * h * w, 1024), dev)
+        conv("b", self.b, 2, _p(t), 1024, _p(cur), 1024, (h, w), 1024, 1024)
+        Cin = 1024
+        for lvl in (3, 2, 1, 0):
+            dec, O, cat = decs[lvl], widths[lvl], cats[lvl]
+            name = f"d{4 - lvl}"
+            wu = _weight_operand(self._op_cache, name + ".up", dec.up.weight, prec, dev, _rows_up2x2)
+            bu = _cached_operand(self._op_cache, name + ".up.bias", dec.up.bias, prec, lambda: _vec(dec.up.bias, O, dev))
+            _lib.check(lib.ocm_op_upconv2x2(prec, _p(cur), Cin, _p(wu), _p(bu), _p(cat), 2 * O, B, h, w, Cin, O, st))
+            h, w = 2 * h, 2 * w
+            t = alloc((B * h * w, O), dev)
+            conv(name, dec.conv, 1, _p(cat), 2 * O, _p(t), O, (h, w), 2 * O, O)
+            cur = alloc((B * h * w, O), dev)
+            conv(name, dec.conv, 2, _p(t), O, _p(cur), O, (h, w), O, O)
+            Cin = O
+        out = torch.empty((B, 1, H, W), dtype=torch.float32, device=dev)
+        head = self.outputs
+        wo = _cached_operand(self._op_cache, "outputs.weight", head.weight, prec,
+                             lambda: head.weight.detach().to(device=dev, dtype=torch.float32).reshape(-1).contiguous())
+        bo = _cached_operand(self._op_cache, "outputs.bias", head.bias, prec, lambda: _vec(head.bias, 1, dev))
+        _lib.check(lib.ocm_op_conv1x1_planes(_p(cur), 64, _p(wo), _p(bo), _p(out), B, H * W, 64, st))
+        return out
 
 
 def build_model(args):

@@ -10,22 +10,17 @@ Tile dispatch of ocm_op_conv3x3 (kernels_conv.hip: conv_gemm), by rows M = B*h*w
   otherwise                                          -> 64 x 64 tiles
 CONV_CASES sits one shape on each side of both thresholds.
 """
-import functools
-
 import pytest
 import torch
 import torch.nn.functional as F
 
-from tests.memcheck import PATTERNS, assert_same_bits
+from tests.conv_helpers import FILL, PRECS, TOL, _check_out, _conv_case, _gen, _rows, _run_conv3x3, _s, _slice_in, _slice_out
+from tests.memcheck import assert_same_bits
 from vit_ocm_wmsegmentation_amd import _lib
 from vit_ocm_wmsegmentation_amd import model as M
 from vit_ocm_wmsegmentation_amd.engine import to_operand
 
 pytestmark = pytest.mark.gpu
-
-TOL = {"fp32": 2e-5, "bf16x3": 2e-4, "bf16": 3e-2}
-PRECS = ("fp32", "bf16x3", "bf16")
-FILL = PATTERNS["big"]  # 0x7F7F7F7F: finite, unmistakable
 
 # (B, h, w, C, O)
 CONV_CASES = {
@@ -37,76 +32,6 @@ CONV_CASES = {
     "m65536_n128": (1, 256, 256, 32, 128),  # 512 tiles of 128 x 128: the first shape on them (M = 65 408 has 511)
 }
 BOTTLENECK = (1, 2, 2, 1024, 1024)  # K = 9216, every output touches padding; split-bf16 only
-
-
-def _s():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _gen(seed):
-    return torch.Generator().manual_seed(seed)
-
-
-@functools.lru_cache(maxsize=None)
-def _conv_case(shape):
-    B, h, w, C, O = shape
-    g = _gen(B * 1000 + h * 100 + C + O)
-    x = torch.randn(B, C, h, w, generator=g)
-    wt = torch.randn(O, C, 3, 3, generator=g) / (9 * C) ** 0.5
-    bias = torch.randn(O, generator=g)
-    ref = F.conv2d(x.double(), wt.double(), bias.double(), padding=1)
-    return x, wt, bias, ref.permute(0, 2, 3, 1).reshape(B * h * w, O)
-
-
-def _rows(x):
-    """(B, C, h, w) -> token-major (B*h*w, C)"""
-    return x.permute(0, 2, 3, 1).reshape(-1, x.shape[1]).contiguous()
-
-
-def _slice_in(rows, dev, pad_left=4, pad_right=8):
-    """rows (M, C) as columns [pad_left, pad_left + C) of a NaN-filled buffer: (buffer, pointer of the slice, ld)"""
-    Mr, C = rows.shape
-    buf = torch.full((Mr, pad_left + C + pad_right), float("nan"), dtype=torch.float32, device=dev)
-    buf[:, pad_left:pad_left + C] = rows.to(dev)
-    return buf, buf.data_ptr() + 4 * pad_left, buf.shape[1]
-
-
-def _slice_out(Mr, O, dev, pad_left=8, pad_right=4):
-    buf = torch.full((Mr, pad_left + O + pad_right), FILL - (1 << 32) if FILL >= 1 << 31 else FILL, dtype=torch.int32, device=dev)
-    return buf, buf.data_ptr() + 4 * pad_left, buf.shape[1], pad_left
-
-
-def _check_out(buf, pad_left, O, ref, tol, what):
-    got = buf[:, pad_left:pad_left + O].view(torch.float32).cpu().double()
-    others = torch.cat([buf[:, :pad_left], buf[:, pad_left + O:]], dim=1)
-    assert bool((others == FILL).all()), f"{what}: columns outside the output slice were written"
-    assert bool(torch.isfinite(got).all()), f"{what}: non-finite output (a NaN column of the input buffer was read?)"
-    err = float((got - ref).abs().max() / ref.abs().max())
-    print(f"{what}: relative error {err:.3e} (bound {tol:.0e})")
-    assert err <= tol, f"{what}: relative error {err:.3e} > {tol:.0e}"
-    return buf[:, pad_left:pad_left + O].clone()
-
-
-def _run_conv3x3(lib, dev, shape, precision):
-    B, h, w, C, O = shape
-    x, wt, bias, ref = _conv_case(shape)
-    pc = _lib.PRECISIONS[precision]
-    w_op = to_operand(M._rows3x3(wt.to(dev)).contiguous(), pc)
-    b_d = bias.to(dev)
-    inbuf, in_ptr, ld_in = _slice_in(_rows(x), dev)
-    for relu in (0, 1):
-        want = ref.clamp_min(0) if relu else ref
-        first = None
-        for _ in range(2):
-            outbuf, out_ptr, ld_out, pl = _slice_out(B * h * w, O, dev)
-            rc = lib.ocm_op_conv3x3(pc, in_ptr, ld_in, w_op.data_ptr(), b_d.data_ptr(), out_ptr, ld_out, B, h, w, C, O, relu, _s())
-            assert rc == 0, lib.ocm_last_error()
-            torch.cuda.synchronize()
-            got = _check_out(outbuf, pl, O, want, TOL[precision], f"conv3x3 {shape} {precision} relu={relu}")
-            if first is not None:
-                assert_same_bits(first, got, "conv3x3 run to run", ("row", "channel"))
-            first = got
-    assert bool(torch.isnan(inbuf[:, :4]).all()) and bool(torch.isnan(inbuf[:, 4 + C:]).all())
 
 
 @pytest.mark.parametrize("precision", PRECS)

@@ -9,6 +9,7 @@ different rounding model). Distances are max |difference| / max |float64 logits|
 Measured on an MI355X (emulation distance / HIP distance):
   B=2 32x32: fp32 1.23e-6 / 3.30e-6, bf16x3 2.58e-5 / 3.02e-5, bf16 1.66e-2 / 1.75e-2
   B=1 48x32: fp32 1.46e-6 / 3.00e-6, bf16x3 2.66e-5 / 3.48e-5, bf16 1.64e-2 / 1.48e-2
+B=3 16x16 (a 1 x 1 bottleneck grid) and B=1 16x48 (1 x 3) run under the same bound; the test prints their distances.
 """
 import functools
 
@@ -21,7 +22,9 @@ from vit_ocm_wmsegmentation_amd import model as M
 
 pytestmark = pytest.mark.gpu
 
-SHAPES = {"b2_32x32": (2, 32, 32), "b1_48x32": (1, 48, 32)}
+SHAPES = {"b2_32x32": (2, 32, 32), "b1_48x32": (1, 48, 32),
+          "b3_16x16": (3, 16, 16),  # the smallest image forward accepts: the bottleneck is a 1 x 1 grid
+          "b1_16x48": (1, 16, 48)}  # a 1 x 3 bottleneck, 2 x 6 and 4 x 12 grids above it
 FACTOR = 4.0
 
 

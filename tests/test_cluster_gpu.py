@@ -9,7 +9,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from tests.helpers import CASES, build_module, case_state_dict, load_golden
+from tests.helpers import (CASES, build_module, case_state_dict, check_key_features, check_kmeans_dist, check_kmeans_lloyd,
+                           kmeans_matrix, load_golden, sq_dist64)
 from vit_ocm_wmsegmentation_amd import _lib, cluster, synth
 from vit_ocm_wmsegmentation_amd.engine import _p
 
@@ -28,15 +29,8 @@ def _rand_qkv(dev, B=2, H=3, g=12, hd=16, seed=0):
 @pytest.mark.parametrize("g,S", [(12, 96), (7, 40), (5, 5), (4, 3)])
 def test_features_match_torch_interpolate(dev, lib, g, S):
     qkv = _rand_qkv(dev, g=g)
-    _, B, H, N, hd = qkv.shape
-    for image in range(B):
-        X = cluster.key_features(qkv, image, S)
-        torch.cuda.synchronize()
-        k = qkv[1, image].cpu().transpose(0, 1).reshape(N, H * hd)[1:]  # eval.py:188-195
-        kt = k.reshape(1, g, g, H * hd).permute(0, 3, 1, 2)
-        want = F.interpolate(kt, size=(S, S), mode="bilinear", align_corners=False).permute(0, 2, 3, 1).reshape(S * S, -1)
-        err = (X.cpu() - want).abs()
-        assert bool((err <= 2e-7 * want.abs() + 2e-7 * k.abs().max()).all()), float(err.max())
+    for image in range(qkv.shape[1]):
+        check_key_features(qkv, image, S)
 
 
 def test_features_reject_bad_arguments(dev, lib):
@@ -54,8 +48,7 @@ def test_features_reject_bad_arguments(dev, lib):
 
 
 def _matrix(dev, S, D, seed):
-    rs = np.random.RandomState(seed)
-    x = (rs.standard_normal((S * S, D)) * rs.uniform(0.5, 3, D) + rs.uniform(-5, 5, D)).astype(np.float32)
+    x = kmeans_matrix(S, D, seed)
     return x, torch.from_numpy(x).to(dev)
 
 
@@ -75,45 +68,10 @@ def test_zscore_against_float64(dev, S, D):
 @pytest.mark.parametrize("S,D", [(48, 64), (37, 384), (9, 4), (20, 1024), (13, 100)])
 def test_dist_and_lloyd_against_float64(dev, S, D):
     x, X = _matrix(dev, S, D, 2)
-    b, ref = cluster.DeviceBackend(X), cluster.NumpyBackend(x)
+    b = cluster.DeviceBackend(X)
     cand = x[[3, 17, 40]]
-    d = b.to_host(b.dist(cand))
-    want = ((x[None].astype(np.float64) - cand[:, None].astype(np.float64)) ** 2).sum(-1)
-    np.testing.assert_allclose(d, want, rtol=1e-12)
-    closest = b.dist(cand[:1])[0]
-    dmin = b.to_host(b.dist(cand[1:], closest))
-    np.testing.assert_array_equal(dmin, np.minimum(d[0][None], d[1:]))  # the same fp64 sums, min'ed
-
-    centers = x[[5, 11]]
-    labels, new, info = b.lloyd(centers)
-    lab = labels.cpu().numpy()
-    dd = ((x[None].astype(np.float64) - centers[:, None].astype(np.float64)) ** 2).sum(-1)
-    want_lab = (dd[1] < dd[0]).astype(np.int32)
-    np.testing.assert_array_equal(lab, want_lab)
-    cnt = np.array([(want_lab == 0).sum(), (want_lab == 1).sum()], np.float64)
-    np.testing.assert_array_equal(info[1:3], cnt)
-    sums = np.stack([x[want_lab == j].astype(np.float64).sum(0) for j in range(2)])
-    np.testing.assert_allclose(new, (sums / cnt[:, None]).astype(np.float32), rtol=2e-7, atol=1e-6)
-    np.testing.assert_allclose(info[0], np.where(want_lab == 1, dd[1], dd[0]).sum(), rtol=1e-12)
-    np.testing.assert_allclose(info[3:5], ((new.astype(np.float64) - centers.astype(np.float64)) ** 2).sum(1), rtol=1e-12)
-    assert info[5] == 1.0 and info[6] == 0.0
-    # the fp64 sums themselves, through the C ABI
-    lib = _lib.load()
-    sums_dev = torch.empty((2, D), dtype=torch.float64, device=dev)
-    new_dev = torch.empty((2, D), dtype=torch.float32, device=dev)
-    info_dev = torch.empty(7, dtype=torch.float64, device=dev)
-    c_dev = torch.from_numpy(centers).to(dev)
-    _lib.check(lib.ocm_op_kmeans_lloyd(_p(X), S, D, _p(c_dev), _p(labels), _p(labels.clone()), _p(new_dev), _p(sums_dev),
-                                       _p(info_dev), 0, _p(b.ws), b.ws.numel(), _s()))
-    np.testing.assert_allclose(sums_dev.cpu().numpy(), sums, rtol=1e-11, atol=1e-9)
-    assert float(info_dev[5]) == 0.0  # labels_old == the same assignment: nothing changed
-    # assign-only: labels and inertia against the given centres
-    labels2, none, info2 = b.lloyd(new, labels, assign_only=True)
-    assert none is None
-    dn = ((x[None].astype(np.float64) - new[:, None].astype(np.float64)) ** 2).sum(-1)
-    lab2 = (dn[1] < dn[0]).astype(np.int32)
-    np.testing.assert_array_equal(labels2.cpu().numpy(), lab2)
-    np.testing.assert_allclose(info2[0], np.where(lab2 == 1, dn[1], dn[0]).sum(), rtol=1e-12)
+    check_kmeans_dist(b, cand, sq_dist64(x, cand))
+    check_kmeans_lloyd(b, x, x[[5, 11]])
 
 
 def test_lloyd_tie_goes_to_cluster_zero(dev):

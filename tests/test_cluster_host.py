@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 import torch
 
-from tests.helpers import load_golden
+from tests.helpers import KMEANS_WIDE_FITS, load_golden
 from vit_ocm_wmsegmentation_amd import cluster, synth
 
 
@@ -45,6 +45,23 @@ def test_driver_matches_live_sklearn(seed):
     assert np.array_equal(r["labels"], km.labels_)
     assert abs(r["inertia"] / km.inertia_ - 1) <= 1e-6
     assert r["n_iter"] == km.n_iter_
+
+
+@pytest.mark.parametrize("name", list(KMEANS_WIDE_FITS))
+def test_driver_matches_live_sklearn_at_model_widths(name):
+    """The two-region grids at the ViT-T and ViT-B widths that tests/test_cluster_shapes_gpu.py fits on the device."""
+    pytest.importorskip("sklearn")
+    from sklearn.cluster import KMeans
+    seed, g, D, S = KMEANS_WIDE_FITS[name]
+    kt = synth.upsample_token_grid(synth.synth_token_grid(seed, g, D, True), S)
+    f = torch.reshape(kt, (-1, kt.shape[-1]))
+    f = (f - torch.mean(f, axis=0)) / torch.std(f, axis=0)
+    for n_init in (10, 3):  # sklearn's default call, and the three initialisations the device test runs
+        km = KMeans(n_init=n_init, n_clusters=2, random_state=0).fit(f)
+        r = cluster.fit_two_means(cluster.NumpyBackend(kt.numpy()), n_init=n_init)
+        assert np.array_equal(r["labels"], km.labels_)
+        assert abs(r["inertia"] / km.inertia_ - 1) <= 1e-6
+        assert r["n_iter"] == km.n_iter_
 
 
 def test_same_clustering_rule():

@@ -66,7 +66,7 @@ def _run(dev, lib, S, D, ws_pattern, out_pattern, inputs):
     return res
 
 
-@pytest.mark.parametrize("S,D", [(24, 384), (7, 12), (33, 1024)])
+@pytest.mark.parametrize("S,D", [(24, 384), (7, 12), (33, 1024), (5, 192), (6, 640), (5, 768), (6, 896)])
 @pytest.mark.parametrize("poison", POISON)
 def test_kmeans_kernels_guarded(dev, lib, S, D, poison):
     rs = np.random.RandomState(S + D)

@@ -85,6 +85,17 @@ __device__ __forceinline__ void split8(const f32x4 &a, const f32x4 &b, bf16x8 &h
         lo[4 + e] = (bf16)(b[e] - (float)u);
     }
 }
+// keys 16 s2 + 8 h .. + 7 of P (registers 8 s2 .. + 7 of S) as a split pair: the B operand of O += V^T . P
+// (the flash kernels of kernels_attn.hip and the window kernels of kernels_swin.hip)
+__device__ __forceinline__ void x3_split_p(const f32x16 &S, int s2, bf16x8 &ph, bf16x8 &pl) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const float pv = S[8 * s2 + e];
+        const bf16 t = (bf16)pv;
+        ph[e] = t;
+        pl[e] = (bf16)(pv - (float)t);
+    }
+}
 // acc += a*b for split operands: small terms first
 __device__ __forceinline__ f32x16 mfma32x3(bf16x8 ah, bf16x8 al, bf16x8 bh, bf16x8 bl, f32x16 c) {
 #if defined(OCM_ABL) && OCM_ABL == 1  // ablation 1: operands fetched, no matrix instructions

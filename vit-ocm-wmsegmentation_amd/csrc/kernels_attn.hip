@@ -786,16 +786,7 @@ __device__ __forceinline__ void x3_rescale(f32x16 (&O)[ND], float alpha) {
     }
 }
 
-// keys 16 s2 + 8 h .. + 7 of P (registers 8 s2 .. + 7 of S) as a split pair: the B operand of O += V^T . P
-__device__ __forceinline__ void x3_split_p(const f32x16 &S, int s2, bf16x8 &ph, bf16x8 &pl) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const float pv = S[8 * s2 + e];
-        const bf16 t = (bf16)pv;
-        ph[e] = t;
-        pl[e] = (bf16)(pv - (float)t);
-    }
-}
+// (x3_split_p, the split of P into the B operand of O += V^T . P, is in common.h: the Swin window kernels share it)
 
 // attn_fwd_x3_dma_kernel: the flash kernel on these steps.
 // NW waves (4 or 8) of 32 queries share the K / V^T tiles: 8 waves halve the L2 -> LDS bytes per query at the same

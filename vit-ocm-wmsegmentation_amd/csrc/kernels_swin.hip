@@ -12,6 +12,7 @@
 //   swin_wattn_f32_kernel  the same in plain fp32 FMAs (OCM_PREC_FP32)
 //   swin_pool_head_kernel  final LayerNorm + mean over tokens + classifier       (SwinModel :887-892, :1052)
 #include "launch.h"
+#include "swin_geom.h"
 
 // ------------------------------------------------------------------------------------------
 // patch embedding + LayerNorm (SwinEmbeddings :273-291: Conv2d(k = 4, stride 4), flatten, LayerNorm) on the exact-fp32 MFMA
@@ -329,8 +330,7 @@ __global__ __launch_bounds__(256) void swin_bias_perm_kernel(const float *__rest
         if (j >= A) {
             v = -1e30f;
         } else if (i < A) {
-            const int yi = i / ws, xi = i - yi * ws, yj = j / ws, xj = j - yj * ws;
-            v = table[((yi - yj + ws - 1) * (2 * ws - 1) + (xi - xj + ws - 1)) * heads + head] * 1.4426950408889634f;
+            v = table[rel_bias_index(ws, heads, i, j, head)] * 1.4426950408889634f;
         }
         perm[idx] = v;
     }
@@ -338,8 +338,7 @@ __global__ __launch_bounds__(256) void swin_bias_perm_kernel(const float *__rest
         const int tot2 = heads * A * A;
         for (int idx = blockIdx.x * 256 + threadIdx.x; idx < tot2; idx += gridDim.x * 256) {
             const int j = idx % A, i = (idx / A) % A, head = idx / (A * A);
-            const int yi = i / ws, xi = i - yi * ws, yj = j / ws, xj = j - yj * ws;
-            dense[idx] = table[((yi - yj + ws - 1) * (2 * ws - 1) + (xi - xj + ws - 1)) * heads + head];
+            dense[idx] = table[rel_bias_index(ws, heads, i, j, head)];
         }
     }
 }
@@ -352,27 +351,8 @@ hipError_t launch_swin_bias_perm(const float *table, float *perm, float *dense, 
 // ------------------------------------------------------------------------------------------
 // window attention
 // ------------------------------------------------------------------------------------------
-struct WinGeom {
-    int H, W, ws, shift, nWx, nW, heads;
-};
-// token (row of the (B, H*W, C) stream) of position p of window (b, wy, wx): the window tiles the image rolled
-// by -shift (cyclic_shift :617-626 + window_partition :486-495), so its source pixel is (+shift) mod size; the
-// output goes back to the same token (window_reverse + reverse roll).
-// (`ws` is passed separately: a compile-time 7 in the Swin-T instantiation turns the divisions into multiplies)
-__device__ __forceinline__ size_t win_token(const WinGeom &g, int ws, int b, int wy, int wx, int p) {
-    const int py = p / ws, px = p - py * ws;
-    int y = wy * ws + py + g.shift, x = wx * ws + px + g.shift;
-    if (y >= g.H) y -= g.H;
-    if (x >= g.W) x -= g.W;
-    return ((size_t)b * g.H + y) * g.W + x;
-}
-// region id of get_attn_mask (:584-607) for position p of the window, in the SHIFTED frame
-__device__ __forceinline__ int win_region(const WinGeom &g, int ws, int wy, int wx, int p) {
-    const int py = p / ws, px = p - py * ws;
-    const int ys = wy * ws + py, xs = wx * ws + px;
-    const int ry = (ys >= g.H - ws) + (ys >= g.H - g.shift), rx = (xs >= g.W - ws) + (xs >= g.W - g.shift);
-    return ry * 3 + rx;
-}
+// (the window geometry — WinGeom, win_token, win_region, win_decode, win_masked, rel_bias_index — is swin_geom.h, shared with
+// the backward)
 
 // bf16 / MFMA: one wavefront per (b, window, head), head_dim 32, ws*ws <= 64 positions.
 // S^T = K.Q^T with the K rows in pi order (common.h): registers hold keys, the lane holds the query, so the
@@ -390,8 +370,7 @@ __global__ __launch_bounds__(256) void swin_wattn_kernel(const bf16 *__restrict_
     char *Ks = smem + wave * (64 * 64 + 32 * 128 + 64);  // K: 64 keys x 64 B
     char *Vs = Ks + 64 * 64;                             // V: [64 keys][32 dims] row-major, 64-byte rows (read transposed)
     unsigned char *Rg = (unsigned char *)(Vs + 32 * 128);
-    const int head = id % g.heads, wlin = (id / g.heads) % g.nW, b = id / (g.heads * g.nW);
-    const int wy = wlin / g.nWx, wx = wlin - wy * g.nWx;
+    const auto [head, b, wy, wx] = win_decode(g, id, g.heads);
     const int ws = WS ? WS : g.ws;
     const int A = ws * ws, C = g.heads * 32;
     const bf16 *base = qkv + head * 32;
@@ -423,7 +402,7 @@ __global__ __launch_bounds__(256) void swin_wattn_kernel(const bf16 *__restrict_
         *(bf16x8 *)(Ks + key * 64 + ((ch ^ ((key >> 2) & 3)) << 4)) = kreg[i];  // chunk swizzle: conflict-free b128 reads
         *(bf16x8 *)(Vs + key * 64 + ch * 16) = vreg[i];  // V row-major [64 keys][32 dims]: read transposed below (tr_read8)
     }
-    const bool masked = g.shift > 0 && (wy == g.H / ws - 1 || wx == g.nWx - 1);  // wave-uniform
+    const bool masked = win_masked(g, ws, wy, wx);
     if (masked) Rg[lane] = (unsigned char)(lane < A ? win_region(g, ws, wy, wx, lane) : 0);
     const int pr = pi_row(r);
     const float *bp = bias_perm + (size_t)head * 2 * 64 * 32 + lane * 4;
@@ -528,7 +507,113 @@ __global__ __launch_bounds__(256) void swin_wattn_kernel(const bf16 *__restrict_
     }
 }
 
-// split-bf16 (OCM_PREC_BF16X3): swin_wattn_kernel on [hi | lo] pairs. One head of one token is exactly one 128-byte
+// ------------------------------------------------------------------------------------------
+// split-bf16 (OCM_PREC_BF16X3). The steps below are shared by the split-bf16 MFMA kernels (swin_wattn_x3_kernel, swin_mlp_x3_kernel,
+// swin_lnqkv_x3_kernel, swin_attn_block_x3_kernel): where a kernel calls a step, that step is the only place the arithmetic
+// lives and the kernel adds its schedule — the OCM_*_DMA macros, which chunk goes to which stage, where the waits and barriers
+// sit, the order of the q / k / v / o steps. Blocks that are still written out in several kernels (the LayerNorm of the rows,
+// the two matrix steps, the softmax of a score tile) changed those kernels' register allocation when called: DESIGN.md §3.7.
+// ------------------------------------------------------------------------------------------
+constexpr int SWIN_W_IMG = 4096;  // LDS image of 32 weight rows x one k group of 32 (128-byte rows, lds_off swizzle): four 1-KiB pieces
+constexpr int SWIN_K_IMG = 64 * 128, SWIN_V_IMG = 32 * 128;  // a window's K (64 keys x [hi | lo]) and V hi (or lo: 64 keys x 64 B)
+constexpr int SWIN_KV = SWIN_K_IMG + 2 * SWIN_V_IMG + 64;    // K | V hi | V lo | region ids of one window
+// bytes of a weight chunk of 32 rows x C (C / 32 images) = one stage of the rings
+constexpr int swin_w_chunk(int C) { return C / 32 * SWIN_W_IMG; }
+
+// Per-lane source offset of 1-KiB LDS-DMA piece pc of a chunk of 32 pi-ordered weight rows of C split pairs: image pc >> 2 =
+// k group, rows (pc & 3) * 8 .. + 7 (lane >> 3 = row of the piece, lane & 7 = its 16-byte slot, swizzled as lds_off reads it)
+__device__ __forceinline__ int swin_w_piece_off(int pc, int lane, int C) {
+    const int rho = (pc & 3) * 8 + (lane >> 3);
+    return rho * (C * 4) + (pc >> 2) * 128 + (((lane & 7) ^ ((rho >> 1) & 7)) << 4);
+}
+// The same for a column group (one k group of 32 of every output row; W2 of the MLP, Wo): piece pc = rows pc * 8 .. + 7 of
+// a matrix with K contraction elements per row
+__device__ __forceinline__ int swin_w2_piece_off(int pc, int lane, int K) {
+    const int c = pc * 8 + (lane >> 3);
+    return c * (K * 4) + (((lane & 7) ^ ((c >> 1) & 7)) << 4);
+}
+
+// registers 8 s2 .. 8 s2 + 7 of S (features 16 s2 + 8 h .. + 7 of the chunk whose bias is bvec) + bias [-> exact-erf GELU],
+// as a split pair: a B fragment of the next product, or a 16-byte piece of the tokens' pair rows
+template <bool GELU>
+__device__ __forceinline__ void swin_bias_run(const f32x16 &S, const float *bvec, int s2, int h, bf16x8 &ph, bf16x8 &pl) {
+    const float *bp = bvec + 16 * s2 + 8 * h;
+    const f32x4 c0 = *(const f32x4 *)bp, c1 = *(const f32x4 *)(bp + 4);
+    f32x4 u0, u1;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        u0[e] = S[8 * s2 + e] + c0[e];
+        u1[e] = S[8 * s2 + 4 + e] + c1[e];
+    }
+    if (GELU) {
+#pragma unroll
+        for (int e = 0; e < 4; e += 2) {
+            const f32x2 a = gelu_erf2(f32x2{u0[e], u0[e + 1]}), b = gelu_erf2(f32x2{u1[e], u1[e + 1]});
+            u0[e] = a[0]; u0[e + 1] = a[1];
+            u1[e] = b[0]; u1[e + 1] = b[1];
+        }
+    }
+    split8(u0, u1, ph, pl);
+}
+
+// workgroup barrier behind the wave's own LDS traffic; vector-memory operations (LDS-DMA included) stay in flight across it
+__device__ __forceinline__ void swin_ring_barrier() {
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+}
+// Top of a ring step: the wave's own LDS-DMA pieces of the step's chunk have landed (`more`: a younger chunk, VM vector-memory
+// operations in all, may still be on its way), everybody's have after the barrier, and everybody is past the stage that the
+// next DMA goes into.
+template <int VM>
+__device__ __forceinline__ void swin_ring_top(bool more) {
+    if (more)
+        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(VM) : "memory");
+    else
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    swin_ring_barrier();
+}
+// the stage that is computed on (sc) and the one that is filled (si) move on by one
+template <int NSTAGE>
+__device__ __forceinline__ void swin_ring_next(int &sc, int &si) {
+    sc = sc == NSTAGE - 1 ? 0 : sc + 1;
+    si = si == NSTAGE - 1 ? 0 : si + 1;
+}
+
+// O / l as pairs into the head's 128-byte group `dst` of the lane's token: lane (r, h) holds dims {8 g + 4 h + e} in fp32, the
+// pair halves go out as four 8-byte pieces per half
+__device__ __forceinline__ void swin_store_ctx_pairs(const f32x16 &O, float l, char *dst, int h) {
+    const float inv = 1.0f / l;
+#pragma unroll
+    for (int gq = 0; gq < 4; ++gq) {
+        f32x4 o;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o[e] = O[4 * gq + e] * inv;
+        bf16x4 oh, ol;
+        split4(o, oh, ol);
+        char *p = dst + (8 * gq + 4 * h) * 2;
+        *(bf16x4 *)p = oh;
+        *(bf16x4 *)(p + 64) = ol;
+    }
+}
+
+// x row += y^T + bias, fp32, in place: lane (r, h) register 4 g + e of fragment mf = channel 32 mf + 8 g + 4 h + e of its token
+template <int CG>
+__device__ __forceinline__ void swin_resid_store(const f32x16 (&Y)[CG], const float *bias, float *xo, int h) {
+#pragma unroll
+    for (int mf = 0; mf < CG; ++mf)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const int c = 32 * mf + 8 * g + 4 * h;
+            const f32x4 old = *(const f32x4 *)(xo + c), bb = *(const f32x4 *)(bias + c);
+            f32x4 o;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) o[e] = Y[mf][4 * g + e] + bb[e] + old[e];
+            *(f32x4 *)(xo + c) = o;
+        }
+}
+
+// swin_wattn_kernel on [hi | lo] pairs. One head of one token is exactly one 128-byte
 // group of the operand row (head_dim 32: 32 x hi | 32 x lo), so q / k / v fragments are 16-byte pieces of it; scores and
 // context are three MFMAs per product (mfma32x3), the probabilities are split in registers, the context leaves as pairs.
 // LDS per wavefront: K 64 keys x 128 B (hi | lo), V as two row-major [64 keys][64 B] images (hi, lo) read transposed.
@@ -537,18 +622,17 @@ template <int WS>
 __global__ __launch_bounds__(WATTN_X3_WAVES * 64) void swin_wattn_x3_kernel(const char *__restrict__ qkv, int ld, char *__restrict__ ctx,
                                                             int ldc, const float *__restrict__ bias_perm, WinGeom g,
                                                             int total, float scale2) {
-    constexpr int PER_WAVE = 64 * 128 + 2 * 32 * 128 + 64;
+    constexpr int PER_WAVE = SWIN_KV;
     __shared__ __attribute__((aligned(16))) char smem[WATTN_X3_WAVES * PER_WAVE];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int r = lane & 31, h = lane >> 5;
     const int id = blockIdx.x * WATTN_X3_WAVES + wave;
     if (id >= total) return;  // no workgroup barrier below: every wave owns its LDS slice
     char *Ks = smem + wave * PER_WAVE;  // K: 64 keys x 128 B, chunks 0..3 = hi, 4..7 = lo (lds_off swizzle)
-    char *Vh = Ks + 64 * 128;           // V hi: [64 keys][32 dims] row-major (64-byte rows); V lo follows
-    char *Vl = Vh + 32 * 128;
-    unsigned char *Rg = (unsigned char *)(Vl + 32 * 128);
-    const int head = id % g.heads, wlin = (id / g.heads) % g.nW, b = id / (g.heads * g.nW);
-    const int wy = wlin / g.nWx, wx = wlin - wy * g.nWx;
+    char *Vh = Ks + SWIN_K_IMG;         // V hi: [64 keys][32 dims] row-major (64-byte rows); V lo follows
+    char *Vl = Vh + SWIN_V_IMG;
+    unsigned char *Rg = (unsigned char *)(Vl + SWIN_V_IMG);
+    const auto [head, b, wy, wx] = win_decode(g, id, g.heads);
     const int ws = WS ? WS : g.ws;
     const int A = ws * ws, C = g.heads * 32;
     const size_t ldb = (size_t)ld * 4, ldcb = (size_t)ldc * 4;  // row strides in bytes (4 bytes per element)
@@ -587,7 +671,7 @@ __global__ __launch_bounds__(WATTN_X3_WAVES * 64) void swin_wattn_x3_kernel(cons
         // (ds_read_b64_tr_b16 below) instead of scattering sixteen-bit elements into a V^T image here
         *(bf16x8 *)((ch < 4 ? Vh : Vl) + key * 64 + (ch & 3) * 16) = vreg[i];
     }
-    const bool masked = g.shift > 0 && (wy == g.H / ws - 1 || wx == g.nWx - 1);  // wave-uniform
+    const bool masked = win_masked(g, ws, wy, wx);
     if (masked) Rg[lane] = (unsigned char)(lane < A ? win_region(g, ws, wy, wx, lane) : 0);
     const int pr = pi_row(r);
     const float *bp = bias_perm + (size_t)head * 2 * 64 * 32 + lane * 4;
@@ -654,13 +738,7 @@ __global__ __launch_bounds__(WATTN_X3_WAVES * 64) void swin_wattn_x3_kernel(cons
 #pragma unroll
             for (int s2 = 0; s2 < 2; ++s2) {
                 bf16x8 ph, pl;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const float pv = S[sub][8 * s2 + e];
-                    const bf16 t = (bf16)pv;
-                    ph[e] = t;
-                    pl[e] = (bf16)(pv - (float)t);
-                }
+                x3_split_p(S[sub], s2, ph, pl);
                 // A operand V^T[d = lane & 31][8 keys from sub * 32 + 16 s2 + 8 h]: two transposed reads of 4 keys x 16 dims
                 // per 16-lane group (lane 4 q + p of a group addresses key row q, dims 4 p .. 4 p + 3 of the block; lane i
                 // receives dim i of the four keys). Every lane is active here (whole wavefronts leave the kernel together).
@@ -668,22 +746,7 @@ __global__ __launch_bounds__(WATTN_X3_WAVES * 64) void swin_wattn_x3_kernel(cons
                 const bf16x8 vh = tr_read8(Vh + voff), vl = tr_read8(Vl + voff);
                 O = mfma32x3(vh, vl, ph, pl, O);
             }
-        // Lane (r, h) holds dims {8g + 4h + e} in fp32: the pair halves go out as four 8-byte pieces per half
-        if (qi < A) {
-            const float inv = 1.0f / l;
-            char *dst = ctx + qtok[qt] * ldcb + head * 128;
-#pragma unroll
-            for (int gq = 0; gq < 4; ++gq) {
-                f32x4 o;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) o[e] = O[4 * gq + e] * inv;
-                bf16x4 oh, ol;
-                split4(o, oh, ol);
-                char *p = dst + (8 * gq + 4 * h) * 2;
-                *(bf16x4 *)p = oh;
-                *(bf16x4 *)(p + 64) = ol;
-            }
-        }
+        if (qi < A) swin_store_ctx_pairs(O, l, ctx + qtok[qt] * ldcb + head * 128, h);
     }
 }
 
@@ -697,8 +760,7 @@ __global__ __launch_bounds__(256) void swin_wattn_f32_kernel(const float *__rest
     const int id = blockIdx.x * 4 + wave;
     if (id >= total) return;
     float *Ks = smem + wave * (2 * 49 * 32), *Vs = Ks + 49 * 32;
-    const int head = id % g.heads, wlin = (id / g.heads) % g.nW, b = id / (g.heads * g.nW);
-    const int wy = wlin / g.nWx, wx = wlin - wy * g.nWx;
+    const auto [head, b, wy, wx] = win_decode(g, id, g.heads);
     const int ws = g.ws;
     const int A = ws * ws, C = g.heads * 32;
     const float *base = qkv + head * 32;
@@ -803,7 +865,7 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 2 : 3) void swin_mlp_x3_kernel(f
                                                              const float *__restrict__ bet, const char *__restrict__ w1,
                                                              const float *__restrict__ b1, const char *__restrict__ w2,
                                                              const float *__restrict__ b2, int T, float eps) {
-    constexpr int C = CG * 32, HID = HG * 32, W1B = CG * 4096, STAGE = W1B + C * 128;
+    constexpr int C = CG * 32, HID = HG * 32, W1B = swin_w_chunk(C), STAGE = W1B + C * 128;
     constexpr int PIECES = STAGE / 1024, PPW = PIECES / NW, NS = 2 * CG;  // 1-KiB DMA pieces per step / per wave; k slices of 16
     static_assert(PIECES % NW == 0, "the wavefronts share the pieces of a step evenly");
     static_assert(NSTAGE == 2 || NSTAGE == 3, "one or two steps in flight");
@@ -821,6 +883,8 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 2 : 3) void swin_mlp_x3_kernel(f
     // piece pc = jj * NW + wave of a step: pieces [0, 4 CG) = W1 (image pc >> 2 = k group, rows (pc & 3) * 8 .. + 7 of the
     // step's 32 hidden units), the rest = W2 (rows (pc - 4 CG) * 8 .. + 7 of the C outputs, the step's k group)
     int voff[PPW];
+    // own copy: through swin_w_piece_off / swin_w2_piece_off the C = 96 kernel's vmcnt wait sequence changes
+    // (... 4, 4, 10, 12, 14, 19 ... -> ... 4, 2, 8, 10, 12, 14 ...)
     {
         const int lrow = lane >> 3, slot = lane & 7;
 #pragma unroll
@@ -900,13 +964,7 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 2 : 3) void swin_mlp_x3_kernel(f
     const int pr = pi_row(r);
     int sc = 0, si = NSTAGE - 1;
     for (int j = 0; j < HG; ++j) {
-        if (NSTAGE == 3 && j + 1 < HG)
-            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PPW) : "memory");  // the younger step may still be on its way
-        else
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
+        swin_ring_top<PPW>(NSTAGE == 3 && j + 1 < HG);  // the younger step may still be on its way
         if (j + NSTAGE - 1 < HG) OCM_MLP_DMA(j + NSTAGE - 1, si);  // into the stage of step j - 1: everybody is past it
         const char *W1s = smem + sc * STAGE, *W2s = W1s + W1B;
         f32x16 S;
@@ -922,19 +980,7 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 2 : 3) void swin_mlp_x3_kernel(f
         // register e of lane half h holds hidden unit 32 j + key_of_reg(e, h): registers 0..7 and 8..15 are runs of eight
         bf16x8 ph[2], pl[2];
 #pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2) {
-            const float *bp = b1s + 32 * j + 16 * s2 + 8 * h;
-            const f32x4 c0 = *(const f32x4 *)bp, c1 = *(const f32x4 *)(bp + 4);
-            f32x4 u0, u1;
-#pragma unroll
-            for (int e = 0; e < 4; e += 2) {
-                const f32x2 a = gelu_erf2(f32x2{S[8 * s2 + e] + c0[e], S[8 * s2 + e + 1] + c0[e + 1]});
-                const f32x2 b = gelu_erf2(f32x2{S[8 * s2 + 4 + e] + c1[e], S[8 * s2 + 4 + e + 1] + c1[e + 1]});
-                u0[e] = a[0]; u0[e + 1] = a[1];
-                u1[e] = b[0]; u1[e + 1] = b[1];
-            }
-            split8(u0, u1, ph[s2], pl[s2]);
-        }
+        for (int s2 = 0; s2 < 2; ++s2) swin_bias_run<true>(S, b1s + 32 * j, s2, h, ph[s2], pl[s2]);
 #pragma unroll
         for (int mf = 0; mf < CG; ++mf)
 #pragma unroll
@@ -943,24 +989,11 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 2 : 3) void swin_mlp_x3_kernel(f
                 const bf16x8 vl = *(const bf16x8 *)(W2s + lds_off(32 * mf + r, 4 + 2 * s2 + h));
                 Y[mf] = mfma32x3(vh, vl, ph[s2], pl[s2], Y[mf]);
             }
-        sc = sc == NSTAGE - 1 ? 0 : sc + 1;
-        si = si == NSTAGE - 1 ? 0 : si + 1;
+        swin_ring_next<NSTAGE>(sc, si);
     }
 #undef OCM_MLP_DMA
     if (!live) return;
-    // y^T: lane (r, h) register 4 g + e of fragment mf = channel 32 mf + 8 g + 4 h + e of token r
-    float *xo = x + tok * C;
-#pragma unroll
-    for (int mf = 0; mf < CG; ++mf)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const int c = 32 * mf + 8 * g + 4 * h;
-            const f32x4 old = *(const f32x4 *)(xo + c), bb = *(const f32x4 *)(b2 + c);
-            f32x4 o;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) o[e] = Y[mf][4 * g + e] + bb[e] + old[e];
-            *(f32x4 *)(xo + c) = o;
-        }
+    swin_resid_store<CG>(Y, b2, x + tok * C, h);
 }
 
 // layernorm_before + the fused q | k | v projection of a narrow-stage SwinLayer in one kernel (split-bf16, C = 96 / 128):
@@ -977,7 +1010,7 @@ __global__ __launch_bounds__(NW * 64, CG <= 4 ? 4 : 2) void swin_lnqkv_x3_kernel
                                                                   const float *__restrict__ bet, const char *__restrict__ w,
                                                                   const float *__restrict__ bias, char *__restrict__ qkv, int T,
                                                                   int N, float eps) {
-    constexpr int C = CG * 32, STAGE = CG * 4096, NSTAGE = 3, PIECES = 4 * CG, PPW = PIECES / NW, NS = 2 * CG;
+    constexpr int C = CG * 32, STAGE = swin_w_chunk(C), NSTAGE = 3, PIECES = 4 * CG, PPW = PIECES / NW, NS = 2 * CG;
     const int NF = N >> 5;  // chunks of 32 output features
     static_assert(PIECES % NW == 0, "the wavefronts share the pieces of a step evenly");
     extern __shared__ __attribute__((aligned(1024))) char smem[];
@@ -990,14 +1023,8 @@ __global__ __launch_bounds__(NW * 64, CG <= 4 ? 4 : 2) void swin_lnqkv_x3_kernel
     const size_t tok = (size_t)min(tok0 + r, T - 1);
     for (int i = tid; i < N; i += NW * 64) bs[i] = bias[i];
     int voff[PPW];
-    {
-        const int lrow = lane >> 3, slot = lane & 7;
 #pragma unroll
-        for (int jj = 0; jj < PPW; ++jj) {
-            const int pc = jj * NW + wave, rho = (pc & 3) * 8 + lrow;
-            voff[jj] = rho * (C * 4) + (pc >> 2) * 128 + ((slot ^ ((rho >> 1) & 7)) << 4);
-        }
-    }
+    for (int jj = 0; jj < PPW; ++jj) voff[jj] = swin_w_piece_off(jj * NW + wave, lane, C);
 #if defined(__HIP_DEVICE_COMPILE__)
     typedef __attribute__((address_space(3))) void *lds_ptr;
     const auto rsw = __builtin_amdgcn_make_buffer_rsrc((void *)w, 0, (unsigned)(N * C * 4), 0x00020000);
@@ -1046,15 +1073,9 @@ __global__ __launch_bounds__(NW * 64, CG <= 4 ? 4 : 2) void swin_lnqkv_x3_kernel
     __builtin_amdgcn_s_waitcnt(0x0F70);
     const int pr = pi_row(r);
     char *orow = qkv + tok * ((size_t)N * 4);
-    int sc = 0, si = 2;
+    int sc = 0, si = NSTAGE - 1;
     for (int j = 0; j < NF; ++j) {
-        if (j + 1 < NF)
-            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PPW) : "memory");
-        else
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
+        swin_ring_top<PPW>(j + 1 < NF);
         if (j + 2 < NF) OCM_QKV_DMA(j + 2, si);
         const char *Ws = smem + sc * STAGE;
         f32x16 S;
@@ -1068,6 +1089,8 @@ __global__ __launch_bounds__(NW * 64, CG <= 4 ? 4 : 2) void swin_lnqkv_x3_kernel
             S = mfma32x3(ah, al, xh[sI], xl[sI], S);
         }
         // register e of lane half h = feature 32 j + key_of_reg(e, h): two runs of eight -> two 16-byte pieces per half
+        // own copy: through swin_bias_run<GELU> the C = 192 GELU kernel goes from 168 to 170 registers (accumulator offset 168 -> 172)
+        // and the C = 128 kernels' vmcnt wait sequence changes
 #pragma unroll
         for (int s2 = 0; s2 < 2; ++s2) {
             const float *bp = bs + 32 * j + 16 * s2 + 8 * h;
@@ -1094,8 +1117,7 @@ __global__ __launch_bounds__(NW * 64, CG <= 4 ? 4 : 2) void swin_lnqkv_x3_kernel
                 *(bf16x8 *)(p + 64) = pl;
             }
         }
-        sc = sc == NSTAGE - 1 ? 0 : sc + 1;
-        si = si == NSTAGE - 1 ? 0 : si + 1;
+        swin_ring_next<NSTAGE>(sc, si);
     }
 #undef OCM_QKV_DMA
 }
@@ -1109,7 +1131,7 @@ hipError_t launch_swin_lnlinear(int prec, const float *x, const float *g, const 
     if (!swin_lnqkv_fused_supported(prec, C) || T == 0 || T > 0x7fffffffu || N <= 0 || N % 32 || N > 4096) return hipErrorInvalidValue;
     constexpr int NW = 4;
     const dim3 grid((unsigned)((T + NW * 32 - 1) / (NW * 32))), block(NW * 64);
-    const int lds = 3 * (C / 32 * 4096) + N * 4;
+    const int lds = 3 * swin_w_chunk(C) + N * 4;  // the ring | the bias
     auto kern = C == 96    ? (gelu ? swin_lnqkv_x3_kernel<3, NW, true> : swin_lnqkv_x3_kernel<3, NW, false>)
                 : C == 128 ? (gelu ? swin_lnqkv_x3_kernel<4, NW, true> : swin_lnqkv_x3_kernel<4, NW, false>)
                            : (gelu ? swin_lnqkv_x3_kernel<6, NW, true> : swin_lnqkv_x3_kernel<6, NW, false>);
@@ -1136,7 +1158,7 @@ hipError_t launch_swin_mlp(int prec, float *x, const float *g, const float *be, 
     constexpr int NW96 = 4, NS96 = 2, NW128 = 8, NS128 = 3;
     const int nw = C == 96 ? NW96 : NW128, nst = C == 96 ? NS96 : NS128;
     const dim3 grid((unsigned)((T + nw * 32 - 1) / (nw * 32))), block(nw * 64);
-    const int lds = nst * (C / 32 * 4096 + C * 128) + hidden * 4;
+    const int lds = nst * (swin_w_chunk(C) + C * 128) + hidden * 4;  // stages of (W1 chunk | W2 column group) | b1
     auto kern = C == 96 ? swin_mlp_x3_kernel<3, 12, NW96, NS96> : swin_mlp_x3_kernel<4, 16, NW128, NS128>;
     static OptinMask optin[2];
     if (hipError_t e = lds_optin((const void *)kern, lds, optin[C == 96 ? 0 : 1]); e != hipSuccess) return e;
@@ -1159,13 +1181,14 @@ hipError_t launch_swin_mlp(int prec, float *x, const float *g, const float *be, 
 //     wavefronts, one counted vmcnt wait and one barrier per step:
 //       q: accumulator registers + bias, split -> ARE the B fragments of the score product (never leave registers);
 //       k, v: + bias, split -> the window's K image (64 keys x 128 B) and row-major V images (hi, lo) in LDS, padding keys 0;
-//       o: scores / softmax / context exactly as swin_wattn_x3_kernel (same operands, same order: the context pairs have
-//          the same bits as the unfused path's), V^T read from LDS with its rows in pi order, so that the normalised context
+//       o: scores / softmax / context as swin_wattn_x3_kernel (same operands, same order; the P split and the pair stores are
+//          the steps it calls, x3_split_p and swin_store_ctx_pairs), with FUSE_PROJ V^T read from LDS with its rows in pi
+//          order, so that the normalised context
 //          registers ARE the B fragments of y^T (C x 32 tokens) += Wo[:, head] . ctx^T;
 //   * epilogue: + bias + x, fp32, in place (a window's tokens belong to no other window: no other wavefront reads them).
 // FUSE_PROJ false (C = 192: the x fragments take 96 registers, a second set of 96 for y^T does not fit beside them): three
-// chunks per head, the fourth step only waits for the K / V images; the context leaves as pairs (swin_wattn_x3_kernel's
-// stores, V^T rows in natural order) for the o_proj GEMM. Eight wavefronts = four windows per workgroup there.
+// chunks per head, the fourth step only waits for the K / V images; the context leaves as pairs (swin_store_ctx_pairs, V^T
+// rows in natural order) for the o_proj GEMM. Eight wavefronts = four windows per workgroup there.
 // ------------------------------------------------------------------------------------------
 template <int CG, int WS, int NW, bool FUSE_PROJ>
 __global__ __launch_bounds__(NW * 64, 2) void swin_attn_block_x3_kernel(float *__restrict__ x, const float *__restrict__ gam,
@@ -1174,8 +1197,8 @@ __global__ __launch_bounds__(NW * 64, 2) void swin_attn_block_x3_kernel(float *_
                                                                     const float *__restrict__ bo,
                                                                     const float *__restrict__ bias_perm, char *__restrict__ ctx,
                                                                     WinGeom g, int total, float scale2, float eps) {
-    constexpr int C = CG * 32, HEADS = CG, NWIN = NW / 2, CH = CG * 4096, NSTAGE = 3, PIECES = 4 * CG, PPW = PIECES / NW;
-    constexpr int NS = 2 * CG, KPH = FUSE_PROJ ? 4 : 3, NCH = KPH * HEADS, KV = 64 * 128 + 2 * 32 * 128 + 64;
+    constexpr int C = CG * 32, HEADS = CG, NWIN = NW / 2, CH = swin_w_chunk(C), NSTAGE = 3, PIECES = 4 * CG, PPW = PIECES / NW;
+    constexpr int NS = 2 * CG, KPH = FUSE_PROJ ? 4 : 3, NCH = KPH * HEADS, KV = SWIN_KV;
     static_assert(PIECES % NW == 0, "the wavefronts share the pieces of a chunk evenly");
     extern __shared__ __attribute__((aligned(1024))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -1183,15 +1206,14 @@ __global__ __launch_bounds__(NW * 64, 2) void swin_attn_block_x3_kernel(float *_
     const int r = lane & 31, h = lane >> 5;
     const int win = wave >> 1, qt = wave & 1;
     char *Ks = smem + NSTAGE * CH + win * KV;  // K: 64 keys x 128 B (chunks 0..3 hi, 4..7 lo, lds_off swizzle)
-    char *Vh = Ks + 64 * 128, *Vl = Vh + 32 * 128;  // V hi / lo: [64 keys][32 dims] row-major, 64-byte rows
-    unsigned char *Rg = (unsigned char *)(Vl + 32 * 128);
+    char *Vh = Ks + SWIN_K_IMG, *Vl = Vh + SWIN_V_IMG;  // V hi / lo: [64 keys][32 dims] row-major, 64-byte rows
+    unsigned char *Rg = (unsigned char *)(Vl + SWIN_V_IMG);
     float *bs = (float *)(smem + NSTAGE * CH + NWIN * KV);  // bq | bk | bv | bo
 
     int wid = blockIdx.x * NWIN + win;
     const bool wlive = wid < total;  // an odd window count leaves the last workgroup one idle pair (it keeps the barriers)
     wid = min(wid, total - 1);
-    const int wlin = wid % g.nW, b = wid / g.nW;
-    const int wy = wlin / g.nWx, wx = wlin - wy * g.nWx;
+    const auto [head0, b, wy, wx] = win_decode(g, wid, 1);  // (head0 = 0: the id of a window)
     const int ws = WS ? WS : g.ws;
     const int A = ws * ws;
     const int p = qt * 32 + r;  // window position = key index of this lane's token
@@ -1201,20 +1223,14 @@ __global__ __launch_bounds__(NW * 64, 2) void swin_attn_block_x3_kernel(float *_
     for (int i = tid; i < 3 * C; i += NW * 64) bs[i] = bqkv[i];
     if (FUSE_PROJ)
         for (int i = tid; i < C; i += NW * 64) bs[3 * C + i] = bo[i];
-    const bool masked = g.shift > 0 && (wy == g.H / ws - 1 || wx == g.nWx - 1);  // wave-uniform
+    const bool masked = win_masked(g, ws, wy, wx);
     if (masked && qt == 0) Rg[lane] = (unsigned char)(lane < A ? win_region(g, ws, wy, wx, lane) : 0);
 
     int voffA[PPW], voffB[PPW];
-    {
-        const int lrow = lane >> 3, slot = lane & 7;
 #pragma unroll
-        for (int jj = 0; jj < PPW; ++jj) {
-            const int pc = jj * NW + wave;
-            const int rho = (pc & 3) * 8 + lrow;  // q / k / v chunk: image pc >> 2 = k group, rows (pc & 3) * 8 .. + 7
-            voffA[jj] = rho * (C * 4) + (pc >> 2) * 128 + ((slot ^ ((rho >> 1) & 7)) << 4);
-            const int c = pc * 8 + lrow;  // o_proj chunk: rows pc * 8 .. + 7 of the C outputs, the head's k group
-            voffB[jj] = c * (C * 4) + ((slot ^ ((c >> 1) & 7)) << 4);
-        }
+    for (int jj = 0; jj < PPW; ++jj) {
+        voffA[jj] = swin_w_piece_off(jj * NW + wave, lane, C);   // q / k / v chunk
+        voffB[jj] = swin_w2_piece_off(jj * NW + wave, lane, C);  // o_proj chunk: the head's k group of all C rows of Wo
     }
 #if defined(__HIP_DEVICE_COMPILE__)
     typedef __attribute__((address_space(3))) void *lds_ptr;
@@ -1281,24 +1297,8 @@ __global__ __launch_bounds__(NW * 64, 2) void swin_attn_block_x3_kernel(float *_
         for (int e = 0; e < 16; ++e) Y[mf][e] = 0.f;
     const int pr = pi_row(r);
     int sc = 0, si = NSTAGE - 1;
-    // top of step j: own pieces of chunk j have landed (chunk j + 1 may still be on its way), everybody's have after the
-    // barrier, and everybody is past the stage that chunk j + 2 goes into
-    // (EXTRA: vector-memory loads issued between chunk j's DMA and chunk j + 1's, or after both — the head's eight bias loads)
-#define OCM_AB_TOP(j, EXTRA)                                                           \
-    do {                                                                               \
-        if ((j) + 1 < NCH)                                                             \
-            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PPW + (EXTRA)) : "memory");       \
-        else                                                                           \
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                           \
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                             \
-        __builtin_amdgcn_s_barrier();                                                  \
-        asm volatile("" ::: "memory");                                                 \
-    } while (0)
-#define OCM_AB_NEXT()                              \
-    do {                                           \
-        sc = sc == NSTAGE - 1 ? 0 : sc + 1;        \
-        si = si == NSTAGE - 1 ? 0 : si + 1;        \
-    } while (0)
+    // ring steps: chunk j + 1 may still be on its way at the top of step j, with PPW pieces and — for the q and k steps — the
+    // head's eight bias loads, which are issued between chunk j's DMA and chunk j + 1's or after both
     // 32 output features of the chunk in stage sc for the wave's 32 tokens: register e of lane half h = feature key_of_reg(e, h)
     auto project = [&](f32x16 &S) {
         const char *Wst = smem + sc * CH;
@@ -1311,18 +1311,6 @@ __global__ __launch_bounds__(NW * 64, 2) void swin_attn_block_x3_kernel(float *_
             const bf16x8 al = *(const bf16x8 *)(img + lds_off(pr, 4 + (sI & 1) * 2 + h));
             S = mfma32x3(ah, al, xh[sI], xl[sI], S);
         }
-    };
-    // registers 8 s2 .. 8 s2 + 7 (features 16 s2 + 8 h .. + 7) + bias, as a pair of fragments
-    auto biased_pair = [&](const f32x16 &S, const float *bvec, int s2, bf16x8 &ph, bf16x8 &pl) {
-        const float *bp = bvec + 16 * s2 + 8 * h;
-        const f32x4 c0 = *(const f32x4 *)bp, c1 = *(const f32x4 *)(bp + 4);
-        f32x4 u0, u1;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            u0[e] = S[8 * s2 + e] + c0[e];
-            u1[e] = S[8 * s2 + 4 + e] + c1[e];
-        }
-        split8(u0, u1, ph, pl);
     };
     const bf16x8 zero8 = {(bf16)0.f, (bf16)0.f, (bf16)0.f, (bf16)0.f, (bf16)0.f, (bf16)0.f, (bf16)0.f, (bf16)0.f};
 
@@ -1340,44 +1328,41 @@ __global__ __launch_bounds__(NW * 64, 2) void swin_attn_block_x3_kernel(float *_
                 for (int e4 = 0; e4 < 4; ++e4) bv[sub][e4] = *(const f32x4 *)(bq + (sub * 4 + e4) * 256);
         }
         // ---- q
-        OCM_AB_TOP(j0, 8);
+        swin_ring_top<PPW + 8>(j0 + 1 < NCH);
         OCM_AB_DMA(j0 + 2, si);
         project(S);
 #pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2) biased_pair(S, bs + head * 32, s2, qh[s2], ql[s2]);
-        OCM_AB_NEXT();
+        for (int s2 = 0; s2 < 2; ++s2) swin_bias_run<false>(S, bs + head * 32, s2, h, qh[s2], ql[s2]);
+        swin_ring_next<NSTAGE>(sc, si);
         // ---- k -> the window's K image, row p
-        OCM_AB_TOP(j0 + 1, 8);
+        swin_ring_top<PPW + 8>(j0 + 2 < NCH);
         if (j0 + 3 < NCH) OCM_AB_DMA(j0 + 3, si);
         project(S);
 #pragma unroll
         for (int s2 = 0; s2 < 2; ++s2) {
             bf16x8 ph, pl;
-            biased_pair(S, bs + C + head * 32, s2, ph, pl);
+            swin_bias_run<false>(S, bs + C + head * 32, s2, h, ph, pl);
             *(bf16x8 *)(Ks + lds_off(p, 2 * s2 + h)) = valid ? ph : zero8;
             *(bf16x8 *)(Ks + lds_off(p, 4 + 2 * s2 + h)) = valid ? pl : zero8;
         }
-        OCM_AB_NEXT();
+        swin_ring_next<NSTAGE>(sc, si);
         // ---- v -> the window's V images, row p
-        OCM_AB_TOP(j0 + 2, 0);
+        swin_ring_top<PPW>(j0 + 3 < NCH);
         if (j0 + 4 < NCH) OCM_AB_DMA(j0 + 4, si);  // FUSE_PROJ: the next head's q chunk; otherwise its k chunk
         project(S);
 #pragma unroll
         for (int s2 = 0; s2 < 2; ++s2) {
             bf16x8 ph, pl;
-            biased_pair(S, bs + 2 * C + head * 32, s2, ph, pl);
+            swin_bias_run<false>(S, bs + 2 * C + head * 32, s2, h, ph, pl);
             *(bf16x8 *)(Vh + p * 64 + (2 * s2 + h) * 16) = valid ? ph : zero8;
             *(bf16x8 *)(Vl + p * 64 + (2 * s2 + h) * 16) = valid ? pl : zero8;
         }
-        OCM_AB_NEXT();
+        swin_ring_next<NSTAGE>(sc, si);
         // ---- scores, softmax, context (swin_wattn_x3_kernel for this wave's query tile), then y^T += Wo[:, head] . ctx^T
-        if constexpr (FUSE_PROJ) {
-            OCM_AB_TOP(j0 + 3, 0);
-        } else {  // no chunk of its own: only the K / V images have to be complete
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
-        }
+        if constexpr (FUSE_PROJ)
+            swin_ring_top<PPW>(j0 + 4 < NCH);
+        else  // no chunk of its own: only the K / V images have to be complete
+            swin_ring_barrier();
         f32x16 S2[2];
 #pragma unroll
         for (int sub = 0; sub < 2; ++sub) {
@@ -1430,13 +1415,7 @@ __global__ __launch_bounds__(NW * 64, 2) void swin_attn_block_x3_kernel(float *_
 #pragma unroll
             for (int s2 = 0; s2 < 2; ++s2) {
                 bf16x8 ph, pl;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const float pv = S2[sub][8 * s2 + e];
-                    const bf16 t = (bf16)pv;
-                    ph[e] = t;
-                    pl[e] = (bf16)(pv - (float)t);
-                }
+                x3_split_p(S2[sub], s2, ph, pl);
                 // V^T rows in pi order: lane 4 q + pp of a 16-lane group addresses key row q, dims 4 swap(pp) .. + 3, so that
                 // column slot i of the group receives dim pi_row(i) and accumulator register e of lane half h holds dim
                 // key_of_reg(e, h): registers 8 s .. 8 s + 7 are the B fragment (k = 16 s + 8 h ..) of the o_proj product
@@ -1446,22 +1425,7 @@ __global__ __launch_bounds__(NW * 64, 2) void swin_attn_block_x3_kernel(float *_
                 O = mfma32x3(vh, vl, ph, pl, O);
             }
         if constexpr (!FUSE_PROJ) {
-            // lane (r, h) holds dims {8 gq + 4 h + e} in fp32: the pair halves go out as four 8-byte pieces per half
-            if (valid && wlive) {
-                const float inv = 1.0f / l;
-                char *dst = ctx + tok * ((size_t)C * 4) + head * 128;
-#pragma unroll
-                for (int gq = 0; gq < 4; ++gq) {
-                    f32x4 o;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) o[e] = O[4 * gq + e] * inv;
-                    bf16x4 oh, ol;
-                    split4(o, oh, ol);
-                    char *pd = dst + (8 * gq + 4 * h) * 2;
-                    *(bf16x4 *)pd = oh;
-                    *(bf16x4 *)(pd + 64) = ol;
-                }
-            }
+            if (valid && wlive) swin_store_ctx_pairs(O, l, ctx + tok * ((size_t)C * 4) + head * 128, h);
         } else {
             const float inv = 1.0f / l;
             const char *Wos = smem + sc * CH;
@@ -1483,25 +1447,11 @@ __global__ __launch_bounds__(NW * 64, 2) void swin_attn_block_x3_kernel(float *_
                 }
             }
         }
-        if constexpr (FUSE_PROJ) OCM_AB_NEXT();
+        if constexpr (FUSE_PROJ) swin_ring_next<NSTAGE>(sc, si);
     }
 #undef OCM_AB_DMA
-#undef OCM_AB_TOP
-#undef OCM_AB_NEXT
-    if (!FUSE_PROJ || !valid || !wlive) return;
-    // y^T: lane (r, h) register 4 gq + e of fragment mf = channel 32 mf + 8 gq + 4 h + e of the lane's token
-    float *xo = x + tok * C;
-#pragma unroll
-    for (int mf = 0; mf < CG; ++mf)
-#pragma unroll
-        for (int gq = 0; gq < 4; ++gq) {
-            const int c = 32 * mf + 8 * gq + 4 * h;
-            const f32x4 old = *(const f32x4 *)(xo + c), bb = *(const f32x4 *)(bs + 3 * C + c);
-            f32x4 o;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) o[e] = Y[mf][4 * gq + e] + bb[e] + old[e];
-            *(f32x4 *)(xo + c) = o;
-        }
+    if constexpr (FUSE_PROJ)
+        if (valid && wlive) swin_resid_store<CG>(Y, bs + 3 * C, x + tok * C, h);
 }
 
 // proj_fused: the whole half in one kernel (C = 96); otherwise (C = 192) the kernel stops at the context pairs
@@ -1515,7 +1465,7 @@ static hipError_t launch_swin_attn_block_t(float *x, const float *g, const float
                                            const void *wo, const float *bo, const float *bias_perm, void *ctx, const WinGeom &gm,
                                            long total, float eps, hipStream_t s) {
     constexpr int C = CG * 32, NWIN = NW / 2;
-    constexpr int lds = 3 * CG * 4096 + NWIN * (64 * 128 + 2 * 32 * 128 + 64) + 4 * C * 4;
+    constexpr int lds = 3 * swin_w_chunk(C) + NWIN * SWIN_KV + 4 * C * 4;  // the ring | K / V images per window | bq bk bv bo
     static_assert(lds <= 160 * 1024, "LDS");
     const float scale2 = 0.17677669529663687f * 1.4426950408889634f;  // 32^-0.5 (SwinAttention.scaling :408) in the log2 domain
     const dim3 grid((unsigned)((total + NWIN - 1) / NWIN)), block(NW * 64);

@@ -14,6 +14,7 @@
 #include "../../include/ocm_swin.h"
 #include "host_common.h"
 #include "launch.h"
+#include "swin_geom.h"
 
 #define fail ocm_fail
 
@@ -23,28 +24,6 @@ constexpr int WB_A = 49;      // positions of the largest window (7 x 7)
 constexpr int WB_LD = 33;     // LDS row of one 32-wide head, padded: a lane-strided row read hits 32 different banks
 constexpr int WB_CHUNK = 64;  // windows per first-level chunk of the table-gradient sum
 
-struct WbGeom {
-    int H, W, ws, shift, nWx, nW, heads;
-};
-
-// token of position p of window (b, wy, wx): the window tiles the grid rolled by -shift, so its source is (+shift) mod size
-// (the map of the forward's win_token, kernels_swin.hip)
-__device__ __forceinline__ int64_t wb_token(const WbGeom &g, int b, int wy, int wx, int p) {
-    const int py = p / g.ws, px = p - py * g.ws;
-    int y = wy * g.ws + py + g.shift, x = wx * g.ws + px + g.shift;
-    if (y >= g.H) y -= g.H;
-    if (x >= g.W) x -= g.W;
-    return ((int64_t)b * g.H + y) * g.W + x;
-}
-
-// region id of SwinLayer.get_attn_mask for position p of the window, in the shifted frame
-__device__ __forceinline__ int wb_region(const WbGeom &g, int wy, int wx, int p) {
-    const int py = p / g.ws, px = p - py * g.ws;
-    const int ys = wy * g.ws + py, xs = wx * g.ws + px;
-    const int ry = (ys >= g.H - g.ws) + (ys >= g.H - g.shift), rx = (xs >= g.W - g.ws) + (xs >= g.W - g.shift);
-    return ry * 3 + rx;
-}
-
 // One wavefront (= workgroup) per (image, window, head); lane i owns query i in the first pass and key i in the second.
 //   pass 1 (query rows): S_i. = q_i K^T scale + bias + mask (-100, transformers' additive mask), P_i. = softmax,
 //                        o_i = P_i. V, delta_i = dO_i . o_i, dS_ij = P_ij (dO_i . v_j - delta_i), dQ_i = scale sum_j dS_ij k_j
@@ -53,20 +32,19 @@ __device__ __forceinline__ int wb_region(const WbGeom &g, int wy, int wx, int p)
 // Every sum runs in position order. q, k, v, dO of the window and P, dS live in LDS (44 KB); all products are fp32 FMAs.
 __global__ __launch_bounds__(64) void swin_wattn_bwd_kernel(const float *__restrict__ qkv, const float *__restrict__ dctx,
                                                             const float *__restrict__ table, float *__restrict__ dqkv,
-                                                            float *__restrict__ part, WbGeom g, float scale) {
+                                                            float *__restrict__ part, WinGeom g, float scale) {
     __shared__ float Qs[WB_A * WB_LD], Ks[WB_A * WB_LD], Vs[WB_A * WB_LD], Gs[WB_A * WB_LD];
     __shared__ float Ps[WB_A * WB_A], Ds[WB_A * WB_A];
-    __shared__ int64_t Tok[64];
+    __shared__ size_t Tok[64];
     __shared__ int Rg[64];
     const int lane = threadIdx.x;
     const int id = blockIdx.x;
-    const int head = id % g.heads, wlin = (id / g.heads) % g.nW, b = id / (g.heads * g.nW);
-    const int wy = wlin / g.nWx, wx = wlin - wy * g.nWx;
+    const auto [head, b, wy, wx] = win_decode(g, id, g.heads);
     const int ws = g.ws, A = ws * ws, AP = A | 1, C = g.heads * 32, ld = 3 * C, nb = 2 * ws - 1;
     const bool masked = g.shift > 0;
     if (lane < A) {
-        Tok[lane] = wb_token(g, b, wy, wx, lane);
-        Rg[lane] = masked ? wb_region(g, wy, wx, lane) : 0;
+        Tok[lane] = win_token(g, ws, b, wy, wx, lane);
+        Rg[lane] = masked ? win_region(g, ws, wy, wx, lane) : 0;
     }
     __syncthreads();
     for (int idx = lane; idx < A * 32; idx += 64) {
@@ -79,15 +57,14 @@ __global__ __launch_bounds__(64) void swin_wattn_bwd_kernel(const float *__restr
     }
     __syncthreads();
     if (lane < A) {
-        const int i = lane, yi = i / ws, xi = i - yi * ws;
+        const int i = lane;
         float *prow = Ps + i * AP, *drow = Ds + i * AP;
         float mx = -INFINITY;
         for (int j = 0; j < A; ++j) {
             float s = 0.f;
 #pragma unroll
             for (int d = 0; d < 32; ++d) s = fmaf(Qs[i * WB_LD + d], Ks[j * WB_LD + d], s);
-            const int yj = j / ws, xj = j - yj * ws;
-            s = s * scale + table[((yi - yj + ws - 1) * nb + (xi - xj + ws - 1)) * g.heads + head];
+            s = s * scale + table[rel_bias_index(ws, g.heads, i, j, head)];
             if (masked && Rg[j] != Rg[i]) s += -100.0f;
             prow[j] = s;
             mx = fmaxf(mx, s);
@@ -150,7 +127,7 @@ __global__ __launch_bounds__(64) void swin_wattn_bwd_kernel(const float *__restr
         }
     }
     const int nbb = nb * nb;
-    float *prt = part + ((size_t)b * g.nW + wlin) * nbb * g.heads + head;
+    float *prt = part + ((size_t)b * g.nW + wy * g.nWx + wx) * nbb * g.heads + head;
     for (int bin = lane; bin < nbb; bin += 64) {
         const int ry = bin / nb - (ws - 1), rx = bin % nb - (ws - 1);  // yi - yj, xi - xj
         float s = 0.f;
@@ -282,7 +259,7 @@ extern "C" int ocm_op_swin_window_attention_backward(const float *qkv, const flo
     if (workspace_bytes < need)
         return fail(OCM_EINVAL, "window attention backward workspace: %zu bytes given, %zu needed", workspace_bytes, need);
     const hipStream_t s = (hipStream_t)stream;
-    const WbGeom g{height, width, window, shift, width / window, (height / window) * (width / window), heads};
+    const WinGeom g{height, width, window, shift, width / window, (height / window) * (width / window), heads};
     const int64_t nwin = (int64_t)batch * g.nW, total = nwin * heads;
     const int cols = (2 * window - 1) * (2 * window - 1) * heads;
     const int64_t R = (nwin + WB_CHUNK - 1) / WB_CHUNK;

@@ -13,6 +13,11 @@
 
 #define fail ocm_fail
 
+// ABI precision -> the launchers' operand index (0 bf16, 1 fp32, 2 split-bf16); -1 for anything else
+static int prec_index(int32_t precision) {
+    return precision == OCM_PREC_FP32 ? 1 : precision == OCM_PREC_BF16X3 ? 2 : precision == OCM_PREC_BF16 ? 0 : -1;
+}
+
 namespace {
 
 enum SlotKind {
@@ -113,7 +118,7 @@ extern "C" int ocm_swin_create(const ocm_swin_config *cfg, ocm_swin_t **out) {
 
     ocm_swin *h = new ocm_swin();
     h->cfg = *cfg;
-    h->prec = cfg->precision == OCM_PREC_FP32 ? 1 : cfg->precision == OCM_PREC_BF16X3 ? 2 : 0;
+    h->prec = prec_index(cfg->precision);
     h->esz = h->prec ? 4 : 2;       // split-bf16 pairs are 4 bytes per element too
     h->kstep = h->prec ? 32 : 64;   // and their K step is one 128-byte group of 32
     const int ws = cfg->window_size, A = ws * ws;
@@ -466,7 +471,7 @@ extern "C" int ocm_swin_set_option(ocm_swin_t *h, int32_t option, int32_t value)
 extern "C" int ocm_op_swin_lnqkv(int32_t precision, const float *x, const float *gamma, const float *beta, const void *w,
                                  const float *bias, void *qkv, int64_t tokens, int32_t channels, float eps, void *stream) {
     if (!x || !gamma || !beta || !w || !bias || !qkv) return fail(OCM_EINVAL, "null argument");
-    const int pc = precision == OCM_PREC_FP32 ? 1 : precision == OCM_PREC_BF16X3 ? 2 : precision == OCM_PREC_BF16 ? 0 : -1;
+    const int pc = prec_index(precision);
     if (pc < 0) return fail(OCM_EINVAL, "bad precision");
     if (tokens <= 0 || tokens > 0x7fffffffLL) return fail(OCM_EINVAL, "bad token count %lld", (long long)tokens);
     if (!swin_lnqkv_fused_supported(pc, channels))
@@ -480,7 +485,7 @@ extern "C" int ocm_op_swin_mlp(int32_t precision, float *x, const float *gamma, 
                                const float *b1, const void *w2, const float *b2, int64_t tokens, int32_t channels,
                                int32_t hidden, float eps, void *stream) {
     if (!x || !gamma || !beta || !w1 || !b1 || !w2 || !b2) return fail(OCM_EINVAL, "null argument");
-    const int pc = precision == OCM_PREC_FP32 ? 1 : precision == OCM_PREC_BF16X3 ? 2 : precision == OCM_PREC_BF16 ? 0 : -1;
+    const int pc = prec_index(precision);
     if (pc < 0) return fail(OCM_EINVAL, "bad precision");
     if (tokens <= 0 || tokens > 0x7fffffffLL) return fail(OCM_EINVAL, "bad token count %lld", (long long)tokens);
     if (!swin_mlp_fused_supported(pc, channels, hidden))
@@ -495,7 +500,7 @@ extern "C" int ocm_op_swin_attn_block(int32_t precision, float *x, const float *
                                       int32_t batch, int32_t height, int32_t width, int32_t window, int32_t shift, int32_t heads,
                                       float eps, void *stream) {
     if (!x || !gamma || !beta || !wqkv || !bqkv || !wo || !bo || !rel_table || !scratch) return fail(OCM_EINVAL, "null argument");
-    const int pc = precision == OCM_PREC_FP32 ? 1 : precision == OCM_PREC_BF16X3 ? 2 : precision == OCM_PREC_BF16 ? 0 : -1;
+    const int pc = prec_index(precision);
     if (pc < 0) return fail(OCM_EINVAL, "bad precision");
     if (window < 2 || window > 7 || height <= 0 || width <= 0 || height % window || width % window || batch <= 0 || heads <= 0 ||
         shift < 0 || shift >= window)
@@ -519,7 +524,7 @@ extern "C" int ocm_op_swin_attn_block(int32_t precision, float *x, const float *
 extern "C" int ocm_op_swin_merge_ln(int32_t precision, const float *x, const float *gamma, const float *beta, void *y,
                                    int32_t batch, int32_t height, int32_t width, int32_t channels, int32_t ldy, void *stream) {
     if (!x || !gamma || !beta || !y) return fail(OCM_EINVAL, "null argument");
-    const int pc = precision == OCM_PREC_FP32 ? 1 : precision == OCM_PREC_BF16X3 ? 2 : precision == OCM_PREC_BF16 ? 0 : -1;
+    const int pc = prec_index(precision);
     if (pc < 0) return fail(OCM_EINVAL, "bad precision");
     if (batch <= 0 || height <= 0 || width <= 0 || channels <= 0 || channels % 32 || channels > 512 || ldy < 4 * channels ||
         ldy % (pc ? 32 : 64))
@@ -545,7 +550,7 @@ extern "C" int ocm_op_swin_window_attention(int32_t precision, const void *qkv, 
     hipStream_t s = (hipStream_t)stream;
     float *perm = scratch, *dense = scratch + (size_t)heads * 4096;
     HIP_TRY(launch_swin_bias_perm(rel_table, perm, dense, heads, window, s));
-    HIP_TRY(launch_swin_window_attention(precision == OCM_PREC_FP32 ? 1 : precision == OCM_PREC_BF16X3 ? 2 : 0, qkv, ld, ctx, ldc, perm, dense, batch, height,
-                                         width, window, shift, heads, s));
+    HIP_TRY(launch_swin_window_attention(prec_index(precision), qkv, ld, ctx, ldc, perm, dense, batch, height, width, window,
+                                         shift, heads, s));
     return OCM_OK;
 }

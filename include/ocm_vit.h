@@ -276,7 +276,8 @@ int ocm_op_attention_probs_hd(int32_t precision, const void *q, const void *k, c
                               int32_t batch, int32_t n_tokens, int32_t heads, int32_t head_dim, float scale, void *stream);
 
 /* Attention for heads of ANY width (head_dim a multiple of 4, up to 512; at most 8192 tokens; heads * head_dim a multiple of 32
- * for a split-bf16 ctx) on the fp32 tensor
+ * for a split-bf16 ctx; batch * heads at most 65535, the launch's grid y, which holds for an engine handle with such heads
+ * too) on the fp32 tensor
  * qkv_f32 [3][B][H][N][head_dim] that ocm_op_qkv_proj_hd writes: plain fp32 FMAs, one wavefront per query row — what an engine
  * handle runs for head widths the MFMA kernels are not built for, and what the free-standing Attention module
  * (dino/vision_transformer.py:66-90 accepts any dim / num_heads) calls for them. ctx (optional): [B][N][H*head_dim] in the

@@ -872,6 +872,8 @@ extern "C" int ocm_op_attention_generic(int32_t precision, const float *qkv_f32,
     if (head_dim % 4 || head_dim > 512 || n_tokens > 8192 || (pc == 2 && (heads * head_dim) % 32))
         return fail(OCM_EINVAL, "generic attention: head_dim %d must be a multiple of 4 up to 512, at most 8192 tokens, and "
                                 "heads * head_dim a multiple of 32 for a split-bf16 context", head_dim);
+    // one (image, head) pair per grid y
+    if ((int64_t)batch * heads > 65535) return fail(OCM_EINVAL, "batch * heads = %lld > 65535", (long long)batch * heads);
     HIP_TRY(launch_attention_generic(pc, qkv_f32, ctx, attn, nullptr, 0, nullptr, batch, n_tokens, heads, head_dim, scale,
                                      (hipStream_t)stream));
     return OCM_OK;

@@ -1518,6 +1518,8 @@ __global__ __launch_bounds__(256) void attn_generic_kernel(const float *__restri
         const float *kp = K + (size_t)key * hd;
         float acc = 0.f;
         for (int d = 0; d < hd; d += 4) {
+            // qs is only 4-byte aligned for waves 1-3 when (hd + N) % 4 != 0: this relies on the unaligned LDS access mode
+            // (every residue runs in tests/test_attention_generic_gpu.py::test_token_counts)
             const f32x4 kv = *(const f32x4 *)(kp + d), qv = *(const f32x4 *)(qs + d);
             acc = fmaf(qv[0], kv[0], acc);
             acc = fmaf(qv[1], kv[1], acc);
@@ -1572,6 +1574,7 @@ hipError_t launch_attention_generic(int prec, const float *qkv, void *ctx, float
                                     hipStream_t s) {
     if (head_dim % 4 || head_dim > 512 || n_tokens > 8192) return hipErrorInvalidValue;
     if (prec == 2 && (heads * head_dim) % 32) return hipErrorInvalidValue;
+    if ((int64_t)batch * heads > 65535) return hipErrorInvalidValue;  // grid y
     const bool all = ctx || attn;
     const int nq = all ? n_tokens : n_rows;
     if (nq <= 0) return hipSuccess;

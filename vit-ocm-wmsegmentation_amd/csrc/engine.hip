@@ -420,9 +420,9 @@ static int run_attention(const ocm_vit *h, const Workspace &w, int batch, int n,
     if (out_rows && !out_attn) { PROF(OCM_K_PROBS, s); HIP_TRY(launch_attention_rows(pc, w.q, w.k, query_rows, n_rows, out_rows, batch, n, np, H, scale, s, h->hd)); }
     if (attn_only && !out_attn) return OCM_OK;
     { PROF(OCM_K_ATTN, s); HIP_TRY(launch_attention(pc, w.q, w.k, w.vt, attn_only ? nullptr : w.ctx, out_attn ? w.lse : nullptr, batch, n, np, H, scale, s, h->hd, w.kpart, w.kpart_bytes)); }
-    if (out_attn) {
-        { PROF(OCM_K_PROBS, s); HIP_TRY(launch_attention_probs(pc, w.q, w.k, w.lse, out_attn, batch, n, np, H, scale, s, h->hd)); }
-        if (out_rows) { PROF(OCM_K_PROBS, s); HIP_TRY(launch_rows_from_probs(out_attn, query_rows, n_rows, out_rows, batch, n, H, s)); }
+    if (out_attn) {  // with the selected rows as a slice of them (short lists: written by the same launch)
+        PROF(OCM_K_PROBS, s);
+        HIP_TRY(launch_attention_probs(pc, w.q, w.k, w.lse, out_attn, batch, n, np, H, scale, s, h->hd, query_rows, n_rows, out_rows));
     }
     return OCM_OK;
 }

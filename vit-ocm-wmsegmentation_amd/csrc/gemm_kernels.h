@@ -857,59 +857,95 @@ struct EpiVt {
     __device__ __forceinline__ void run(const float *C, int m0, int n0, const f32x2 *rowtab, const f32x2 *coltab) const {
         constexpr int BM = Cfg::BM, BN = Cfg::BN, NT = Cfg::NT;
         const int rem0 = n0 - 2 * D;
-        // Split pairs, one tile per call (and any tile that lies inside one image at an aligned offset): a lane owns EIGHT
-        // consecutive tokens of one feature row — two 16-byte stores (hi, lo) instead of sixteen 2-byte ones; the ragged last
-        // piece of the sequence goes element by element.
+        // Split pairs: the store unit is an aligned group of the DESTINATION — eight tokens t .. t + 7 of one image with
+        // t % 8 == 0, all of them inside this tile — which one lane writes as two 16-byte stores (hi, lo) instead of sixteen
+        // 2-byte ones. A tile crosses image boundaries at arbitrary columns (N = 197: m0 = 128 tm mod 197), so a group starts
+        // at any column of the LDS image; what is left over — at most seven tokens in front of the tile's first group and
+        // at most seven behind the last group of every image segment — goes element by element. Same fp32 operations per
+        // value as the token-per-lane form below. Padding columns t >= ntok are never written.
         if constexpr (Elem<E>::MODE == 2 && NT >= BM / 8) {
-            // chosen per tile (workgroup-uniform): all its rows in one image, starting at a multiple of eight tokens. Other
-            // tiles keep the token-per-lane form below, whose element stores are contiguous across the wavefront.
-            const int b0 = m0 / ntok, t0 = m0 - b0 * ntok;
-            if (vt && (t0 & 7) == 0 && t0 + min(BM, M - m0) <= ntok) {
-                constexpr int GPR = BM / 8;  // token groups per feature row
-                for (int q = threadIdx.x; q < BN * GPR; q += NT) {
-                    const int row = q / GPR, g = q - row * GPR, m = m0 + g * 8;
-                    if (m >= M) continue;
-                    const int b = m / ntok, t = m - b * ntok;
-                    const int rem = rem0 + row;
-                    const int head = hd == 64 ? rem >> 6 : rem / hd, d = rem - head * hd;
-                    f32x4 v0 = *(const f32x4 *)(C + row * BM + g * 8), v1 = *(const f32x4 *)(C + row * BM + g * 8 + 4);
-                    if (ln.stats) {
-                        const f32x2 cd = coltab[row];
+            if (vt) {
+                const int cols = min(BM, M - m0);  // token columns of this tile
+                const int b0 = m0 / ntok, t0 = m0 - b0 * ntok;
+                const int G = ntok >> 3;  // whole groups per image
+                // the tile's groups in order: linear index L = b G + t / 8 from the first group at or behind column 0.
+                // Consecutive lanes take consecutive groups of one feature row; a lane keeps its group for the whole tile
+                // (image, token, LDS column, the LayerNorm pairs of its eight tokens: computed once) and walks the feature rows
+                constexpr int GPR = BM / 8, GSTEP = NT / GPR;
+                static_assert(NT % GPR == 0, "a lane keeps one token group");
+                const int L = (G ? b0 * G + min((t0 + 7) >> 3, G) : 0) + (int)threadIdx.x % GPR;
+                const int gb = G ? L / G : 0, gt = (L - gb * G) * 8, c = gb * ntok + gt - m0;
+                if (G && c + 8 <= cols) {
+                    f32x2 mr[8];
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            const f32x2 r0 = rowtab[g * 8 + e], r1 = rowtab[g * 8 + 4 + e];
-                            v0[e] = fmaf(r0[1], fmaf(-r0[0], cd[0], v0[e]), cd[1]);
-                            v1[e] = fmaf(r1[1], fmaf(-r1[0], cd[0], v1[e]), cd[1]);
+                    for (int e = 0; e < 8; ++e) mr[e] = ln.stats ? rowtab[c + e] : f32x2{0.f, 1.f};
+                    // columns c .. c + 7 from 16-byte-aligned reads: twelve floats from c - (c & 3), shifted by c & 3
+                    // (the third read stays inside the row: c + 8 <= BM and c % 4 != 0 give c - (c & 3) + 12 <= BM)
+                    const int a = c & 3;
+                    const bool s1 = a & 1, s2 = a & 2;
+                    const float *p0 = C + (c - a);
+                    const int third = a ? 8 : 4;
+                    char *dst = (char *)vt + sp_off(gt);
+                    for (int row = threadIdx.x / GPR; row < BN; row += GSTEP) {
+                        const float *p = p0 + row * BM;
+                        const f32x4 x0 = *(const f32x4 *)p, x1 = *(const f32x4 *)(p + 4), x2 = *(const f32x4 *)(p + third);
+                        // by one (named registers: an indexed array of them went to scratch) ...
+                        const float f0 = s1 ? x0[1] : x0[0], f1 = s1 ? x0[2] : x0[1], f2 = s1 ? x0[3] : x0[2];
+                        const float f3 = s1 ? x1[0] : x0[3], f4 = s1 ? x1[1] : x1[0], f5 = s1 ? x1[2] : x1[1];
+                        const float f6 = s1 ? x1[3] : x1[2], f7 = s1 ? x2[0] : x1[3], f8 = s1 ? x2[1] : x2[0];
+                        const float f9 = s1 ? x2[2] : x2[1];
+                        // ... and by two
+                        f32x4 v0 = {s2 ? f2 : f0, s2 ? f3 : f1, s2 ? f4 : f2, s2 ? f5 : f3};
+                        f32x4 v1 = {s2 ? f6 : f4, s2 ? f7 : f5, s2 ? f8 : f6, s2 ? f9 : f7};
+                        if (ln.stats) {
+                            const f32x2 cd = coltab[row];
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) {
+                                v0[e] = fmaf(mr[e][1], fmaf(-mr[e][0], cd[0], v0[e]), cd[1]);
+                                v1[e] = fmaf(mr[4 + e][1], fmaf(-mr[4 + e][0], cd[0], v1[e]), cd[1]);
+                            }
                         }
-                    }
-                    char *rowp = (char *)vt + ((int64_t)(b * H + head) * hd + d) * npad * 4;
-                    if ((t & 7) == 0 && t + 8 <= ntok && m + 8 <= M) {
+                        const int rem = rem0 + row;
+                        const int head = hd == 64 ? rem >> 6 : rem / hd, d = rem - head * hd;
+                        char *rowp = dst + ((int64_t)(gb * H + head) * hd + d) * npad * 4;
                         bf16x8 hi, lo;
                         split8(v0, v1, hi, lo);
-                        *(bf16x8 *)(rowp + sp_off(t)) = hi;
-                        *(bf16x8 *)(rowp + sp_off(t) + 64) = lo;
+                        *(bf16x8 *)rowp = hi;
+                        *(bf16x8 *)(rowp + 64) = lo;
                         if (qkv32) {
-                            float *o = qkv32 + ((((int64_t)2 * B + b) * H + head) * ntok + t) * hd + d;
+                            float *o = qkv32 + ((((int64_t)2 * B + gb) * H + head) * ntok + gt) * hd + d;
 #pragma unroll
                             for (int e = 0; e < 4; ++e) {
                                 o[(int64_t)e * hd] = v0[e];
                                 o[(int64_t)(4 + e) * hd] = v1[e];
                             }
                         }
-                    } else {
-                        int bb = b, tt = t;
-#pragma unroll
-                        for (int e = 0; e < 8; ++e) {
-                            if (m + e < M) {
-                                const float v = e < 4 ? v0[e & 3] : v1[e & 3];
-                                store_act1((E *)nullptr, (char *)vt + ((int64_t)(bb * H + head) * hd + d) * npad * 4, tt, v);
-                                if (qkv32) qkv32[((((int64_t)2 * B + bb) * H + head) * ntok + tt) * hd + d] = v;
-                            }
-                            if (++tt == ntok) {
-                                tt = 0;
-                                ++bb;
-                            }
+                    }
+                }
+                // the loose tokens, eight lanes per feature row and piece: piece 0 = [t0, first group) of the first image,
+                // piece 1 + s = what lies behind the last group of image segment s
+                const int nseg = (m0 + cols - 1) / ntok - b0 + 1;
+                for (int piece = 0; piece <= nseg; ++piece) {
+                    const int b = b0 + max(piece - 1, 0), ta = piece <= 1 ? t0 : 0;
+                    const int tb = min(ntok, m0 + cols - b * ntok);   // the segment is tokens [ta, tb) of image b
+                    const int hb = min((ta + 7) & ~7, tb);            // end of its leading piece
+                    const int ts = piece ? max(hb, tb & ~7) : ta, te = piece ? tb : hb;
+                    if (ts >= te) continue;  // workgroup-uniform
+                    static_assert(NT % 8 == 0, "a lane keeps one token of a piece");
+                    const int t = ts + ((int)threadIdx.x & 7);  // a lane keeps its token of the piece
+                    if (t >= te) continue;
+                    const int c = b * ntok + t - m0;
+                    const f32x2 mr = ln.stats ? rowtab[c] : f32x2{0.f, 1.f};
+                    for (int row = threadIdx.x >> 3; row < BN; row += NT / 8) {
+                        float v = C[row * BM + c];
+                        if (ln.stats) {
+                            const f32x2 cd = coltab[row];
+                            v = fmaf(mr[1], fmaf(-mr[0], cd[0], v), cd[1]);
                         }
+                        const int rem = rem0 + row;
+                        const int head = hd == 64 ? rem >> 6 : rem / hd, d = rem - head * hd;
+                        store_act1((E *)nullptr, (char *)vt + ((int64_t)(b * H + head) * hd + d) * npad * 4, t, v);
+                        if (qkv32) qkv32[((((int64_t)2 * B + b) * H + head) * ntok + t) * hd + d] = v;
                     }
                 }
                 return;

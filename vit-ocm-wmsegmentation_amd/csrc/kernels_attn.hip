@@ -1474,6 +1474,121 @@ __global__ __launch_bounds__(256) void attn_probs_x3_kernel(const char *__restri
     }
 }
 
+// Fold limit of attn_probs_x3_span_kernel: longer lists of selected rows keep rows_from_probs_kernel
+constexpr int PROBS_FOLD_ROWS = 8;
+
+// The same probabilities (the arithmetic of attn_probs_x3_kernel per 32 x 32 tile, untouched) for rows of up to 255 tokens
+// and 64-wide heads, moved differently in both directions. A workgroup owns ONE block of 32 query rows of one (b, h):
+//  * in: the block's Q rows and every key tile are 8 KiB of contiguous memory. They are fetched with contiguous 16-byte loads
+//    (eight 128-byte lines per instruction, where the fragment-shaped loads of the tile-per-wave kernel touch 32 rows) and
+//    turned into MFMA fragments through LDS regions of 32 rows at a pitch of 272 bytes (conflict-free ds_read_b128). The four
+//    waves take the key tiles w and w + 4 (N <= 255: at most eight tiles).
+//  * out: the block's rows are one contiguous span of the output (32 N floats). The waves put their values into an LDS image
+//    of that span (over the dead staging regions); after one barrier all 256 lanes stream the span with 16-byte stores. A
+//    (b, h) slab starts at a multiple of 4 bytes only, so the image is shifted by the span's offset inside its 16-byte group
+//    (LDS reads and global stores are then both aligned) and the <= 3 floats at either end go one by one.
+// `rows` (or null): rows[bh][i][j] = P[query_i][1 + j] for the queries of this block, from the same image.
+// Rows of Q / K past N - 1 (allocated padding, any contents) are read: they only reach rows / columns that are not stored.
+__global__ __launch_bounds__(256) void attn_probs_x3_span_kernel(const char *__restrict__ Q, const char *__restrict__ Kk,
+                                                                 const float *__restrict__ lse2, float *__restrict__ attn,
+                                                                 int N, int npad, float scale2,
+                                                                 const int32_t *__restrict__ query_rows, int n_rows,
+                                                                 float *__restrict__ rows) {
+    constexpr int HD = 64, NQ = HD / 16, ROWB = HD * 4, PITCH = ROWB + 16, REGION = 32 * PITCH, TILEB = 32 * ROWB;
+    __shared__ __attribute__((aligned(16))) char smem[4 * REGION];  // >= (32 * 255 + 4) floats
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int r = lane & 31, h = lane >> 5;
+    int qblk, bh;
+    xcd_remap2(qblk, bh);
+    const int q0 = qblk * 32, nq = min(32, N - q0);  // the grid has no empty block
+    const int nkt = (N + 31) >> 5;
+    const char *Qb = Q + ((int64_t)bh * npad + q0) * ROWB;
+    const char *Kb = Kk + (int64_t)bh * npad * ROWB;
+    // every global load first: 16-byte piece i of a tile is bytes 16 i .. 16 i + 15 of its 8 KiB
+    f32x4 qraw[2], kraw[2][8];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) qraw[i] = *(const f32x4 *)(Qb + (i * 256 + tid) * 16);
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+        if (wave + 4 * t < nkt) {  // wave-uniform
+#pragma unroll
+            for (int i = 0; i < 8; ++i) kraw[t][i] = *(const f32x4 *)(Kb + (int64_t)(wave + 4 * t) * TILEB + (i * 64 + lane) * 16);
+        }
+    float lr[16];
+#pragma unroll
+    for (int e = 0; e < 16; ++e) lr[e] = lse2[(int64_t)bh * N + min(q0 + acc_row32(e, h), N - 1)];
+    auto stage = [&](char *region, int piece, const f32x4 &v) {
+        *(f32x4 *)(region + (piece >> 4) * PITCH + (piece & 15) * 16) = v;
+    };
+    auto fragments = [&](const char *region, bf16x8(&hi)[NQ], bf16x8(&lo)[NQ]) {
+        const char *rp = region + r * PITCH;
+#pragma unroll
+        for (int s = 0; s < NQ; ++s) {
+            const char *p = rp + (s >> 1) * 128 + ((s & 1) * 16 + 8 * h) * 2;
+            hi[s] = *(const bf16x8 *)p;
+            lo[s] = *(const bf16x8 *)(p + 64);
+        }
+    };
+    bf16x8 qh[NQ], ql[NQ];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) stage(smem, i * 256 + tid, qraw[i]);
+    lds_barrier();
+    fragments(smem, qh, ql);
+    lds_barrier();  // region 0 becomes wave 0's
+    char *mine = smem + wave * REGION;
+    float pr[2][16];
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+        const bool have = wave + 4 * t < nkt;
+        if (have) {
+#pragma unroll
+            for (int i = 0; i < 8; ++i) stage(mine, i * 64 + lane, kraw[t][i]);
+        }
+        lds_barrier();
+        if (have) {
+            bf16x8 kh[NQ], kl[NQ];
+            fragments(mine, kh, kl);
+            f32x16 S;
+#pragma unroll
+            for (int e = 0; e < 16; ++e) S[e] = 0.f;
+#pragma unroll
+            for (int s = 0; s < NQ; ++s) S = mfma32x3(qh[s], ql[s], kh[s], kl[s], S);  // rows = queries, col (lane) = key
+#pragma unroll
+            for (int e = 0; e < 16; ++e) pr[t][e] = fast_exp2(S[e] * scale2 - lr[e]);
+        }
+        lds_barrier();  // the region is read: the next tile, then the image, may overwrite it
+    }
+    float *span = attn + ((int64_t)bh * N + q0) * N;
+    const int shift = (int)(((uintptr_t)span >> 2) & 3);
+    float *img = (float *)smem + shift;  // img[i] <-> span[i]
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+        const int key = (wave + 4 * t) * 32 + r;
+        if (key < N) {
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const int row = acc_row32(e, h);
+                if (row < nq) img[row * N + key] = pr[t][e];
+            }
+        }
+    }
+    lds_barrier();
+    const int len = nq * N;
+    const int lead = min((4 - shift) & 3, len), nvec = (len - lead) >> 2, tail = lead + 4 * nvec;
+    if (tid < lead) span[tid] = img[tid];
+    for (int i = tid; i < nvec; i += 256) *(f32x4 *)(span + lead + 4 * i) = *(const f32x4 *)(img + lead + 4 * i);
+    if (tid < len - tail) span[tail + tid] = img[tail + tid];
+    if (rows) {
+        for (int i = 0; i < n_rows; ++i) {
+            const int query = query_rows ? query_rows[i] : 0;
+            if (query < q0 || query >= q0 + nq) continue;  // workgroup-uniform
+            float *dst = rows + ((int64_t)bh * n_rows + i) * (N - 1);
+            const float *src = img + (query - q0) * N + 1;
+            for (int j = tid; j < N - 1; j += 256) dst[j] = src[j];
+        }
+    }
+}
+
 
 // ------------------------------------------------------------------------------------------
 // Heads that are not 64 channels wide (the reference's SimMIM pre-training encoder, model.py:93-103: 3 heads of 128):
@@ -1688,8 +1803,12 @@ static hipError_t launch_probs_hd(int prec, const void *q, const void *k, const 
     return hipGetLastError();
 }
 
+// `rows` (or null): also rows[b][h][i][j] = attn[b][h][query_i][1 + j] — by the span kernel itself for short lists, else by
+// rows_from_probs_kernel behind the probabilities.
 hipError_t launch_attention_probs(int prec, const void *q, const void *k, const float *lse2, float *attn, int batch,
-                                  int n_tokens, int n_pad, int heads, float scale, hipStream_t s, int head_dim) {
+                                  int n_tokens, int n_pad, int heads, float scale, hipStream_t s, int head_dim,
+                                  const int32_t *query_rows, int n_rows, float *rows) {
+    if (head_dim != 64 && head_dim != 128) return hipErrorInvalidValue;
     const int qtiles = (n_tokens + 31) / 32;
     const dim3 grid((qtiles + 3) / 4, batch * heads);
     // split-bf16 kernels: key chunks in grid.z until there are ~512 workgroups (a one-tile call is 12 .. 114 otherwise)
@@ -1697,9 +1816,23 @@ hipError_t launch_attention_probs(int prec, const void *q, const void *k, const 
     int nz = wgs >= 256 ? 1 : min(ktiles, min(16, (512 + wgs - 1) / wgs));
     if (OCM_KNOB(2) > 0) nz = min(ktiles, OCM_KNOB(2));  // development A/B
     const dim3 gridz(grid.x, grid.y, nz);
-    if (head_dim == 128) return launch_probs_hd<128>(prec, q, k, lse2, attn, n_tokens, n_pad, scale * LOG2E, grid, gridz, s);
-    if (head_dim != 64) return hipErrorInvalidValue;
-    return launch_probs_hd<64>(prec, q, k, lse2, attn, n_tokens, n_pad, scale * LOG2E, grid, gridz, s);
+    if (n_rows <= 0) rows = nullptr;
+    bool folded = false;
+    hipError_t e;
+    // split-bf16, 64-wide heads, rows of up to 255 tokens (at most two key tiles per wave, a 32-row span of the output within
+    // 32 KiB of LDS): one workgroup per span. Longer rows and 128-wide heads keep the tile-per-wave kernel and its key split.
+    if (prec == 2 && head_dim == 64 && n_tokens <= 255 && n_pad % 32 == 0 && n_pad >= n_tokens) {
+        folded = rows && n_rows <= PROBS_FOLD_ROWS;
+        attn_probs_x3_span_kernel<<<dim3(qtiles, batch * heads), dim3(256), 0, s>>>(
+            (const char *)q, (const char *)k, lse2, attn, n_tokens, n_pad, scale * LOG2E, query_rows, n_rows, folded ? rows : nullptr);
+        e = hipGetLastError();
+    } else if (head_dim == 128) {
+        e = launch_probs_hd<128>(prec, q, k, lse2, attn, n_tokens, n_pad, scale * LOG2E, grid, gridz, s);
+    } else {
+        e = launch_probs_hd<64>(prec, q, k, lse2, attn, n_tokens, n_pad, scale * LOG2E, grid, gridz, s);
+    }
+    if (e != hipSuccess || !rows || folded) return e;
+    return launch_rows_from_probs(attn, query_rows, n_rows, rows, batch, n_tokens, heads, s);
 }
 
 // ------------------------------------------------------------------------------------------

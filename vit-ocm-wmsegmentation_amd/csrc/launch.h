@@ -122,7 +122,8 @@ hipError_t launch_attention(int prec, const void *q, const void *k, const void *
 // bytes of key-slice workspace launch_attention can use at this size (0: it never splits the key range)
 size_t attention_ksplit_bytes(int prec, int batch, int n_tokens, int heads, int head_dim);
 hipError_t launch_attention_probs(int prec, const void *q, const void *k, const float *lse2, float *attn, int batch,
-                                  int n_tokens, int n_pad, int heads, float scale, hipStream_t s, int head_dim = 64);
+                                  int n_tokens, int n_pad, int heads, float scale, hipStream_t s, int head_dim = 64,
+                                  const int32_t *query_rows = nullptr, int n_rows = 0, float *rows = nullptr);
 hipError_t launch_rows_from_probs(const float *attn, const int32_t *query_rows, int n_rows, float *rows, int batch,
                                   int n_tokens, int heads, hipStream_t s);
 hipError_t launch_attention_rows(int prec, const void *q, const void *k, const int32_t *query_rows, int n_rows,

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define OCM_ABI_VERSION 16
+#define OCM_ABI_VERSION 17
 
 enum {
     OCM_OK = 0,
@@ -231,6 +231,34 @@ int ocm_linear_resid_ln_supported(int32_t D);
 int ocm_op_linear_resid_ln(int32_t precision, const void *a, const void *w, const float *bias, const float *resid,
                            float *x, const float *gamma, const float *beta, void *xn, int32_t M, int32_t D, int32_t K,
                            float eps, void *stream);
+
+/* Which kernel a GEMM-shaped operator launches for a shape: the library's own tile dispatch (csrc/gemm_plan.h), asked without
+ * launching anything. Host only: no device is touched, so it also answers on a machine without a GPU. It reports the shipped
+ * dispatch (development knobs at 0) in every build.
+ *   family     M, N, K of the GEMM                                    operators
+ *   LINEAR     M, N, K; epilogue OCM_EPI_* (4: the ReLU epilogue)     ocm_op_linear, ocm_op_linear_relu, the engines' nn.Linear layers
+ *   QKV        M = batch * n_tokens, N = 3 D, K = D (D % 64 == 0)     ocm_op_qkv_proj[_hd]
+ *   LINEAR_LD  M, N, K (bf16 / fp32 only)                             the Swin engine's strided nn.Linear
+ *   CONV       M = batch * h * w, N = O (4 O: the up-convolution),    ocm_op_conv3x3 (K = 9 C, flag CONV3X3), ocm_op_conv3x3_image (K = 27),
+ *              K = the contraction length before padding              ocm_op_upconv2x2 (K = C)
+ *   RESID_LN   M, N = D in {128, 256, 384}, K % 64 == 0               ocm_op_linear_resid_ln
+ * `epilogue` is read for LINEAR only. flags: STATS_EPILOGUE = the residual epilogue that also produces the next LayerNorm's row
+ * sums (the engine's folded-LayerNorm forward; its tiles are multiples of 64 wide), SPLITK_OFFERED = the caller holds a split-K
+ * workspace (the engine below 512 rows), CONV3X3 = the A operand comes through the 3x3 loader. Arguments the operator itself
+ * refuses return OCM_EINVAL. */
+enum { OCM_GEMM_LINEAR = 0, OCM_GEMM_QKV = 1, OCM_GEMM_LINEAR_LD = 2, OCM_GEMM_CONV = 3, OCM_GEMM_RESID_LN = 4 };
+enum { OCM_PLAN_STATS_EPILOGUE = 1, OCM_PLAN_SPLITK_OFFERED = 2, OCM_PLAN_CONV3X3 = 4 };
+typedef struct ocm_gemm_plan_info {
+    int32_t bm, bn;   /* tile rows x columns                                                        */
+    int32_t waves;    /* wavefronts per workgroup                                                   */
+    int32_t mfma16;   /* 1: v_mfma_f32_16x16x32_bf16, 0: the 32 x 32 MFMA shapes                    */
+    int32_t lds_dma;  /* main loop: 0 register-staged, 1 LDS-DMA ring                               */
+    int32_t stages;   /* LDS buffers of (bm + bn) * 128 bytes: ring depth; 2 on the register-staged loop */
+    int32_t ksteps;   /* compile-time K-step count of the kernel, 0: the run-time loop              */
+    int32_t splitk;   /* K slices, 1: none                                                          */
+} ocm_gemm_plan_info;
+int ocm_gemm_plan(int32_t family, int32_t precision, int32_t epilogue, int32_t M, int32_t N, int32_t K, uint32_t flags,
+                  ocm_gemm_plan_info *plan);
 
 /* Head-major packed projections the attention kernels consume:
  *   q, k : E [B*H][n_pad][64];  vt : E [B*H][64][n_pad],  n_pad = ocm_n_pad_prec(precision, N)

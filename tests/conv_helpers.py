@@ -18,6 +18,35 @@ TOL = {"fp32": 2e-5, "bf16x3": 2e-4, "bf16": 3e-2}
 PRECS = ("fp32", "bf16x3", "bf16")
 FILL = PATTERNS["big"]  # 0x7F7F7F7F: finite, unmistakable
 
+# The shapes of tests/test_conv_shapes_gpu.py (its docstring explains each) with the tile and K steps they dispatch; the same rows
+# are asserted without a GPU by tests/test_gemm_plan_host.py.
+# name: ((B, h, w, C, O), tile, (steps fp32 / split-bf16, steps bf16))
+CONV = {
+    "t128_c64": ((3, 105, 104, 64, 256), "128x128", (18, 9)),
+    "t128_c128": ((1, 181, 181, 128, 256), "128x128", (36, 18)),
+    "t128_c256": ((1, 181, 181, 256, 256), "128x128", (72, 36)),
+    "t128_c512": ((1, 181, 181, 512, 256), "128x128", (144, 72)),
+    "t64x128_c64": ((1, 9, 9, 64, 128), "64x128", (18, 9)),
+    "t64x128_c128": ((2, 9, 7, 128, 128), "64x128", (36, 18)),
+    "t64x128_c256": ((1, 9, 9, 256, 256), "64x128", (72, 36)),
+    "t64_c128": ((2, 5, 7, 128, 64), "64x64", (36, 18)),
+    "t64_c256": ((1, 5, 7, 256, 32), "64x64", (72, 36)),
+    "t64_c512": ((1, 5, 7, 512, 64), "64x64", (144, 72)),
+    "grid_1x1": ((3, 1, 1, 32, 32), "64x64", (9, 5)),
+    "grid_1x9": ((1, 1, 9, 64, 64), "64x64", (18, 9)),
+    "grid_6x1": ((2, 6, 1, 32, 64), "64x64", (9, 5)),
+    "c4096": ((1, 3, 3, 4096, 32), "64x64", (1152, 576)),
+    "c4064": ((1, 3, 3, 4064, 32), "64x64", (1143, 572)),
+}
+UPCONV = {
+    "up_c96": ((2, 3, 5, 96, 32), "64x64", (3, 2)),
+    "up_1x1": ((1, 1, 1, 32, 32), "64x64", (1, 1)),
+    "up_d1": ((1, 2, 2, 1024, 512), "64x64", (32, 16)),
+    "up_m70": ((2, 7, 5, 64, 32), "64x128", (2, 1)),
+    "up_n256": ((1, 9, 9, 128, 64), "64x128", (4, 2)),
+    "up_t128": ((3, 74, 74, 32, 128), "128x128", (1, 1)),
+}
+
 
 def _s():
     return torch.cuda.current_stream().cuda_stream

@@ -9,8 +9,9 @@ Branches. KROW = 32 (fp32, split-bf16 "x3") or 64 (bf16); steps = ceil(K / KROW)
     N % 128 == 0 and t128 >= 512 -> 128 x 128;  N % 128 == 0 and M > 64 -> 64 x 128;  else 64 x 64
   conv_gemm_cfg: Conv3x3Loader with 18, 36 or 72 steps -> compile-time K, the two-step prefetch ("ct"); every other depth and
     every other loader -> the runtime-K one-step pipeline ("rt").
-test_dispatch_table asserts the tile and step columns below from these formulas, test_dispatch_formulas_are_the_sources that the
-formulas are still the ones in kernels_conv.hip: a changed threshold fails there instead of moving a case to another kernel.
+test_dispatch_table asserts the tile and step columns below against the library's own decision (ocm_gemm_plan, which answers from
+the plan function conv_gemm launches by: csrc/gemm_plan.h gemm_plan_conv): a changed threshold fails there instead of moving a
+case to another kernel. tests/test_gemm_plan_host.py asserts the same rows without a GPU.
 
 ocm_op_conv3x3 (B, h, w, C, O), ReLU off and on               M      tile      t128  steps fp32, x3 / bf16   layers at 384^2, batch 8
   t128_c64    (3, 105, 104, 64, 256)                          32 760  128 x 128  512  18 ct / 9 rt           e2.conv1 (tiles span images)
@@ -51,14 +52,14 @@ ocm_op_maxpool2x2 (B, h, w, C): (1, 258, 258, 1024) has 4 260 096 lanes, past th
 ocm_op_conv1x1_planes (rows, C): 262 181 rows are past the 16 384-block cap (262 144 rows); C = 4, 32 leave sub-lanes idle, C = 128,
   192 take two and three trips of the channel loop; C = 192 runs with a null bias.
 """
+import ctypes
 import functools
-import pathlib
 
 import pytest
 import torch
 import torch.nn.functional as F
 
-from tests.conv_helpers import FILL, PRECS, TOL, _check_out, _conv_case, _gen, _rows, _run_conv3x3, _s, _slice_in, _slice_out
+from tests.conv_helpers import CONV, FILL, PRECS, TOL, UPCONV, _check_out, _conv_case, _gen, _rows, _run_conv3x3, _s, _slice_in, _slice_out
 from tests.memcheck import assert_same_bits
 from tests.unet_twin import ROUNDING
 from vit_ocm_wmsegmentation_amd import _lib
@@ -68,39 +69,15 @@ from vit_ocm_wmsegmentation_amd.engine import to_operand
 pytestmark = pytest.mark.gpu
 
 KROW = {"fp32": 32, "bf16x3": 32, "bf16": 64}  # gemm_core.h: Elem<E>::KROW
-CT_STEPS = (18, 36, 72)                        # conv_gemm_cfg: the compile-time depths of Conv3x3Loader
-SRC = pathlib.Path(__file__).resolve().parents[1] / "vit-ocm-wmsegmentation_amd" / "csrc" / "kernels_conv.hip"
+# the rows whose depth is a compile-time one ("ct" above), as (fp32 and split-bf16, bf16); every other row and the up-convolution: "rt"
+CT = {"t128_c64": (True, False), "t128_c128": (True, True), "t128_c256": (True, True), "t128_c512": (False, True),
+      "t64x128_c64": (True, False), "t64x128_c128": (True, True), "t64x128_c256": (True, True),
+      "t64_c128": (True, True), "t64_c256": (True, True), "t64_c512": (False, True), "grid_1x9": (True, False)}
 
-# name: ((B, h, w, C, O), tile, (steps fp32 / split-bf16, steps bf16)); "ct" / "rt" follows from CT_STEPS
-CONV = {
-    "t128_c64": ((3, 105, 104, 64, 256), "128x128", (18, 9)),
-    "t128_c128": ((1, 181, 181, 128, 256), "128x128", (36, 18)),
-    "t128_c256": ((1, 181, 181, 256, 256), "128x128", (72, 36)),
-    "t128_c512": ((1, 181, 181, 512, 256), "128x128", (144, 72)),
-    "t64x128_c64": ((1, 9, 9, 64, 128), "64x128", (18, 9)),
-    "t64x128_c128": ((2, 9, 7, 128, 128), "64x128", (36, 18)),
-    "t64x128_c256": ((1, 9, 9, 256, 256), "64x128", (72, 36)),
-    "t64_c128": ((2, 5, 7, 128, 64), "64x64", (36, 18)),
-    "t64_c256": ((1, 5, 7, 256, 32), "64x64", (72, 36)),
-    "t64_c512": ((1, 5, 7, 512, 64), "64x64", (144, 72)),
-    "grid_1x1": ((3, 1, 1, 32, 32), "64x64", (9, 5)),
-    "grid_1x9": ((1, 1, 9, 64, 64), "64x64", (18, 9)),
-    "grid_6x1": ((2, 6, 1, 32, 64), "64x64", (9, 5)),
-    "c4096": ((1, 3, 3, 4096, 32), "64x64", (1152, 576)),
-    "c4064": ((1, 3, 3, 4064, 32), "64x64", (1143, 572)),
-}
 CONV_BF16_ONLY = ("t64_c512",)
 CONV_PARAMS = [(c, p) for c in sorted(CONV) for p in PRECS if p == "bf16" or c not in CONV_BF16_ONLY]
 T128_TILES = {"t128_c64": 512, "t128_c128": 512, "t128_c256": 512, "t128_c512": 512, "up_t128": 516}
 
-UPCONV = {
-    "up_c96": ((2, 3, 5, 96, 32), "64x64", (3, 2)),
-    "up_1x1": ((1, 1, 1, 32, 32), "64x64", (1, 1)),
-    "up_d1": ((1, 2, 2, 1024, 512), "64x64", (32, 16)),
-    "up_m70": ((2, 7, 5, 64, 32), "64x128", (2, 1)),
-    "up_n256": ((1, 9, 9, 128, 64), "64x128", (4, 2)),
-    "up_t128": ((3, 74, 74, 32, 128), "128x128", (1, 1)),
-}
 
 # (precision, (M, N, K))
 LINEAR = [
@@ -125,49 +102,34 @@ PLANES = {
 }
 
 
-def _tile(Mr, N):
-    """conv_gemm's tile for Mr rows and N GEMM columns, and its count of 128 x 128 tiles."""
-    t128 = -(-Mr // 128) * (N // 128)
-    if N % 128 == 0 and t128 >= 512:
-        return "128x128", t128
-    if N % 128 == 0 and Mr > 64:
-        return "64x128", t128
-    return "64x64", t128
-
-
-def _steps(K, precision):
-    return -(-K // KROW[precision])
-
-
-def test_dispatch_formulas_are_the_sources():
-    src = " ".join(SRC.read_text().split())
-    for expr in ("const long t128 = (long)((M + 127) / 128) * (N / 128);",
-                 "if (N % 128 == 0 && t128 >= 512) return conv_gemm_cfg<Cfg128x128, E>(",
-                 "if (N % 128 == 0 && M > 64) return conv_gemm_cfg<Cfg64x128, E>(",
-                 "return conv_gemm_cfg<Cfg64x64, E>(",
-                 "const int steps = (Kreal + KROW - 1) / KROW,",
-                 "if constexpr (std::is_same<AL, Conv3x3Loader<E>>::value) { switch (steps) {",
-                 "return conv_gemm<E>(al, w, K, M, a.O, epi, s);",           # the 3x3 forms: N = O
-                 "return conv_gemm<E>(al, w, a.C, M, 4 * a.O, epi, s);"):     # the up-convolution: K = C, N = 4 O
-        assert expr in src, f"kernels_conv.hip no longer holds `{expr}`: re-derive this file's table"
-    for n in CT_STEPS:
-        assert f"case {n}: return launch_gemm_ks<Cfg, E, false, {n}>(" in src
-    assert src.count("return launch_gemm_ks<Cfg, E, false,") == len(CT_STEPS) + 1
+def _plan(lib, precision, Mr, N, K, loader3x3):
+    """The library's decision for a conv / up-conv GEMM: ((bm, bn), waves, LDS-DMA loop, compile-time K steps)."""
+    out = _lib.OcmGemmPlanInfo()
+    rc = lib.ocm_gemm_plan(_lib.OCM_GEMM_CONV, _lib.PRECISIONS[precision], 0, Mr, N, K, _lib.OCM_PLAN_CONV3X3 if loader3x3 else 0,
+                           ctypes.byref(out))
+    assert rc == 0, lib.ocm_last_error()
+    return "%dx%d" % (out.bm, out.bn), out.waves, out.lds_dma, out.ksteps
 
 
 @pytest.mark.parametrize("case", sorted(CONV) + sorted(UPCONV))
-def test_dispatch_table(case):
+def test_dispatch_table(lib, case):
     up = case in UPCONV
     (B, h, w, C, O), tile, steps = (UPCONV if up else CONV)[case]
-    got_tile, t128 = _tile(B * h * w, 4 * O if up else O)
-    assert got_tile == tile, f"{case}: conv_gemm runs {got_tile} tiles ({t128} of 128 x 128), the table says {tile}"
-    if tile == "128x128":
-        assert t128 == T128_TILES[case]
-    K = C if up else 9 * C
-    assert (_steps(K, "fp32"), _steps(K, "bf16x3"), _steps(K, "bf16")) == (steps[0], steps[0], steps[1])
+    Mr, N, K = B * h * w, 4 * O if up else O, C if up else 9 * C
+    t128 = -(-Mr // 128) * (N // 128)
+    want_ct = (False, False) if up else CT.get(case, (False, False))
+    for precision, st, ct in (("fp32", steps[0], want_ct[0]), ("bf16x3", steps[0], want_ct[0]), ("bf16", steps[1], want_ct[1])):
+        assert st == -(-K // KROW[precision]), f"{case} {precision}: the table's step count"
+        got_tile, waves, lds_dma, ks = _plan(lib, precision, Mr, N, K, not up)
+        assert got_tile == tile, f"{case} {precision}: the library runs {got_tile} tiles ({t128} of 128 x 128), the table says {tile}"
+        assert (waves, lds_dma) == (4, 0), f"{case} {precision}: four waves on the register-staged loop"
+        assert ks == (st if ct else 0), f"{case} {precision}: {st} steps are {'compile-time' if ct else 'run-time'} in the table, the library says {ks}"
+        if tile == "128x128":  # ... from 512 tiles of 128 x 128 on: the same width with 511 or fewer runs 64 x 128
+            assert t128 == T128_TILES[case] and t128 >= 512
+            fewer = 128 * (-(-512 // (N // 128)) - 1)
+            assert _plan(lib, precision, fewer, N, K, not up)[0] == "64x128", f"{case} {precision}: {fewer} rows"
     if case.startswith("t"):  # the compile-time-K cases: which precisions run the two-step prefetch
-        want_ct = {"c64": (True, False), "c128": (True, True), "c256": (True, True), "c512": (False, True)}[case.split("_")[1]]
-        assert (steps[0] in CT_STEPS, steps[1] in CT_STEPS) == want_ct
+        assert want_ct == {"c64": (True, False), "c128": (True, True), "c256": (True, True), "c512": (False, True)}[case.split("_")[1]]
 
 
 @pytest.mark.parametrize("case,precision", CONV_PARAMS)

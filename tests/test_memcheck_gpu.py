@@ -223,7 +223,9 @@ def run_vit_forward(lib, kind, precision, B, flagset, pattern, options=()):
             lib.ocm_vit_set_option(eng._h, opt, 0)
 
 
-# (shape, precision, batch, flag sets, options). The comments name the dispatch branch each shape reaches.
+# (shape, precision, batch, flag sets, options). The comments name the dispatch branch each shape reaches, as ocm_gemm_plan reports
+# it (csrc/gemm_plan.h; tests/test_gemm_plan_host.py asserts these rows: 197 x 384 x 1536 with a split-K workspace, 591 and 12 608
+# rows at N = 384 / 1536, 15 002 rows at D = 768).
 VIT_CASES = [
     # ViT-S/16 B = 1 (T = 197): split-K fc2 into w.part (T <= 512), the small-M DMA tiles, the folded LayerNorm (auto)
     (VITS16, "bf16x3", 1, ("feat_attn_qkv", "last_attn", "rows", "fmap_tokens_mask"), ()),
@@ -242,7 +244,7 @@ VIT_CASES = [
     # ViT-S/8 384^2 (N = 2305): the key-split attention into w.kpart at small B, streaming attention above 1024 tokens
     (VITS8, "bf16x3", 1, ("last_attn", "rows"), ()),
     (VITS8, "bf16x3", 2, ("feat_attn_qkv", "rows"), ()),
-    # ViT-B/16 384^2 B = 26 (T = 15 002): the 256 x 256 tiles
+    # ViT-B/16 384^2 B = 26 (T = 15 002): the 256 x 256 tiles on the 16 x 16 MFMA (attn.qkv, mlp.fc1; proj / fc2 have 177 of them: 128 x 128)
     (VITB16, "bf16x3", 26, ("last_attn", "fmap_tokens_mask"), ()),
     # fp32 and single bf16: other element sizes, no folded LayerNorm
     (VITS16, "fp32", 1, ("feat_attn_qkv", "rows"), ()),

@@ -87,7 +87,8 @@ def _qkv_inputs(dev, B, N, H):
     return a, w, bias
 
 
-# Single-bf16 branches of gemm_kernels.h::launch_qkv_e (M = B * N rows, D = 64 H, 3 D output columns):
+# Single-bf16 branches of the qkv projection (csrc/gemm_plan.h::gemm_plan_qkv; M = B * N rows, D = 64 H, 3 D output columns), as
+# ocm_gemm_plan reports them (tests/test_gemm_plan_host.py asserts the first two rows):
 #   (26, 577, 12)  D % 256 == 0 and big_tiles_pay (531 tiles of 256 x 256) -> qkv_kernel<Cfg256x256> (config 3's kernel)
 #   (64, 197, 6)   config 2: D = 384, 99 x 9 = 891 >= 512 tiles of 128 x 128 -> the 8-wave qkv_kernel<Cfg128x128q>, KSTEPS 6
 #   (3, 197, 6), (1, 577, 12), (2, 17, 2)  fewer than 512 tiles, D % 128 == 0 -> qkv_kernel<Cfg64x128>, ragged last row band
@@ -214,8 +215,8 @@ def refs():
     cache.clear()
 
 
-# OCM_PREC_FP32 never takes an LDS-DMA or big-tile branch: gemm_kernels.h::launch_linear_epi goes straight to its
-# register-staged tail (reg_staged:), t128 = ceil(M / 128) * ceil(N / 128):
+# OCM_PREC_FP32 never takes an LDS-DMA or big-tile branch: csrc/gemm_plan.h::gemm_plan_linear goes straight to its
+# register-staged tail (gemm_plan_reg_tail; ocm_gemm_plan reports it, tests/test_gemm_plan_host.py), t128 = ceil(M / 128) * ceil(N / 128):
 #   (12608, 1536, 384)  config 2 fc1: 1188 tiles -> gemm_kernel<Cfg128x128>, last row band 64 rows; (12609, ...) leaves ONE
 #                       row in a band of its own; (16384, 512, 384) exactly 512 tiles, every band full; (20000, 1024, 384)
 #                       1256 tiles, last band 32 rows
@@ -252,7 +253,7 @@ def test_linear_fp32(lib, dev, refs, M, N, K, epi):
     assert (out.double() - ref).abs().max().item() < 2e-5 * max(1.0, math.sqrt(K) / 8)
 
 
-# fp32 branches of gemm_kernels.h::launch_qkv_e (no LDS-DMA, no 256 x 256 tile in this mode):
+# fp32 branches of the qkv projection (csrc/gemm_plan.h::gemm_plan_qkv: no LDS-DMA, no 256 x 256 tile in this mode):
 #   (64, 197, 6)   config 2: 891 tiles of 128 x 128 -> the 8-wave qkv_kernel<Cfg128x128q>, KSTEPS 12 (D = 384)
 #   (26, 577, 12)  D = 768: 118 x 18 = 2124 tiles -> qkv_kernel<Cfg128x128q>, KSTEPS 24, ragged last row band
 #   (3, 197, 6), (2, 17, 2), (1, 577, 12)  fewer than 512 tiles, D % 128 == 0 -> qkv_kernel<Cfg64x128>

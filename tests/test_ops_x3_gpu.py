@@ -60,22 +60,26 @@ def test_layernorm_split_out(lib, dev, rows, dim):
     assert (err <= ref.abs() * 2 ** -16 + 2e-5).all(), err.max().item()  # fp32 LayerNorm, then 2^-17 pairs
 
 
-# The shapes reach every split-bf16 GEMM the BASELINE configurations dispatch (gemm_kernels.h::launch_linear_epi):
-#   (12608, 1536, 384)  config 2 fc1: 1188 tiles, N >= 1024 -> gemm_dma_kernel<128x128, eight waves>, two workgroups per CU; with an
-#                       activation output (epilogues 2 / 3) 948 tiles of 160 x 128 since round 4 (GemmCfg::HALF: a 16-row half tile
-#                       per wave row) — (12609, ...) leaves ONE valid row in the last block's half band, (20000, 1024, 384) is
-#                       125 full blocks of 160 rows
-#   (12608, 384, *)     config 2 proj / fc2: gemm_dma_kernel<128x192> on a three-stage ring
-#   (32768, 1024, 768)  config 3: 512 tiles of 256x256 -> gemm_dma_kernel<256x256>, banded epilogue
-#   (24576, 384, 1536)  config 4 fc2 (48 K steps) -> gemm_dma_kernel<128x192> as well since round 3
-#   (16384, 512, 384)   512 tiles of 128x128, N < 1024 and not a multiple of 192 -> gemm_dma_kernel<128x128, four waves>
-#                       (config 4's fc1 takes it at 48 k rows: tests/test_bench_configs_gpu.py)
-#   (1000 / 333 / 70 / 64 rows): the one-tile-per-call DMA kernels (64x128 on eight waves, 64x64 four-stage) and tails
-#   (6000, 288 / 96, 96), (5000, 576 / 192, *): Swin-T's narrow stages in split-bf16 mode -> gemm_dma_kernel<128x96> / <128x192>
+# The shapes reach every split-bf16 GEMM the BASELINE configurations dispatch. The kernel named for each is what ocm_gemm_plan
+# reports (csrc/gemm_plan.h: gemm_plan_linear); tests/test_gemm_plan_host.py asserts every row of this list, so a moved threshold
+# fails there instead of leaving a comment behind:
+#   (12608, 1536, 384)  config 2 fc1: 1188 tiles of 128 x 128, N >= 1024 -> eight waves on the 16 x 16 MFMA, two workgroups per CU;
+#                       with an activation output (epilogues 2 / 3) 948 tiles of 160 x 128 (GemmCfg::HALF: a 16-row half tile per
+#                       wave row) — (12609, ...) leaves ONE valid row in the last block's half band, (12800, ...) is 80 full
+#                       blocks of 160 rows
+#   (12608, 384, *)     config 2 proj / fc2: 128 x 192 on a three-stage LDS-DMA ring
+#   (32768, 1024, 768)  config 3: 512 tiles of 256 x 256 on the 16 x 16 MFMA, banded epilogue
+#   (20000, 1024, 384)  K = 384, N >= 1024 and 16 384 rows or more: the same 256 x 256 tile with a partial last row block (every epilogue)
+#   (24576, 384, 1536)  config 4 fc2 (48 K steps): 128 x 192 as well
+#   (16384, 512, 384)   512 tiles of 128 x 128, N < 1024 and not a multiple of 192: 128 x 128 on eight waves, 16 x 16 MFMA, in
+#                       every epilogue (config 4's fc1 takes it at 48 k rows: tests/test_bench_configs_gpu.py)
+#   (1000 / 333 / 70 / 64 rows): the one-tile-per-call LDS-DMA kernels (64 x 128 on eight waves, 64 x 64, both four-stage) and the
+#                       register-staged 64 x 64 tails
+#   (6000, 288 / 96, *), (5000, 576 / 192, *): Swin-T's narrow stages in split-bf16 mode: 128 x 96 / 128 x 192 on the LDS-DMA loop
 @pytest.mark.parametrize("M,N,K", [(1000, 384, 384), (12608, 1536, 384), (333, 384, 1536), (70, 96, 192),
                                    (12608, 384, 384), (64, 192, 64), (32768, 1024, 768), (24576, 384, 1536),
                                    (6000, 288, 96), (6000, 96, 384), (5000, 576, 192), (5000, 192, 768), (16384, 512, 384),
-                                   (12609, 1536, 384), (20000, 1024, 384)])
+                                   (12609, 1536, 384), (20000, 1024, 384), (12800, 1536, 384)])
 @pytest.mark.parametrize("epi", [0, 1, 2, 3])
 def test_linear_x3(lib, dev, M, N, K, epi):
     a = _rand((M, K), dev, 40)
@@ -100,8 +104,10 @@ def test_linear_x3(lib, dev, M, N, K, epi):
     assert (got.double() - ref).abs().max().item() < 3e-5 * max(1.0, math.sqrt(K) / 8)
 
 
-# (64, 197, 6): config 2, 891 tiles of 128x128 -> qkv_dma_kernel<Cfg128x128q> (8 waves); (26, 577, 12): ViT-B rows enough
-# for big_tiles_pay -> qkv_dma_kernel<Cfg256x256> (config 3's kernel); the others: 64x128 DMA (M <= 1024) and tails
+# (64, 197, 6): config 2, 891 tiles of 128 x 128 -> qkv_dma_kernel on eight waves and the 16 x 16 MFMA (Cfg128x128q16); (26, 577, 12):
+# ViT-B rows enough for big_tiles_pay -> qkv_dma_kernel<Cfg256x256m16> (config 3's kernel); (3, 197, 6) and (1, 577, 12): the
+# eight-wave 64 x 128 tile on a four-stage ring (M <= 4096); (5, 50, 3), (2, 17, 2): register-staged 64 x 64 (D % 128 != 0) and
+# 64 x 128 (M <= 64). As ocm_gemm_plan reports them: tests/test_gemm_plan_host.py holds the rows
 @pytest.mark.parametrize("B,N,H", [(3, 197, 6), (2, 17, 2), (1, 577, 12), (5, 50, 3), (64, 197, 6), (26, 577, 12)])
 def test_qkv_proj_x3(lib, dev, B, N, H):
     D = H * 64

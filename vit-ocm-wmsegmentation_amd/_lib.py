@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # OCM_VIT_LIB lets kernel experiments A/B two builds of the same ABI; the default is the in-tree build.
 LIB_PATH = os.environ.get("OCM_VIT_LIB") or os.path.join(_HERE, "libocm_vit.so")
 
-OCM_ABI_VERSION = 16
+OCM_ABI_VERSION = 17
 OCM_OK, OCM_EINVAL, OCM_ESTATE, OCM_EHIP, OCM_ENOMEM, OCM_ENAME = 0, 1, 2, 3, 4, 5
 
 OCM_PREC_BF16 = 0
@@ -103,6 +103,13 @@ class OcmSwinConfig(C.Structure):  # include/ocm_swin.h
     ]
 
 
+class OcmGemmPlanInfo(C.Structure):  # ocm_gemm_plan: the kernel a GEMM-shaped operator launches for a shape
+    _fields_ = [(n, C.c_int32) for n in ("bm", "bn", "waves", "mfma16", "lds_dma", "stages", "ksteps", "splitk")]
+
+
+OCM_GEMM_LINEAR, OCM_GEMM_QKV, OCM_GEMM_LINEAR_LD, OCM_GEMM_CONV, OCM_GEMM_RESID_LN = 0, 1, 2, 3, 4
+OCM_PLAN_STATS_EPILOGUE, OCM_PLAN_SPLITK_OFFERED, OCM_PLAN_CONV3X3 = 1, 2, 4
+
 # name -> (restype, argtypes); every symbol include/ocm_vit.h and include/ocm_swin.h declare
 _vp, _i32, _i64, _f32, _sz = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_size_t
 SIGNATURES = {
@@ -125,6 +132,7 @@ SIGNATURES = {
     "ocm_op_linear": (C.c_int, [_i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "ocm_linear_resid_ln_supported": (C.c_int, [_i32]),
     "ocm_op_linear_resid_ln": (C.c_int, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _f32, _vp]),
+    "ocm_gemm_plan": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _i32, C.c_uint32, C.POINTER(OcmGemmPlanInfo)]),
     "ocm_n_pad": (_i32, [_i32]),
     "ocm_op_qkv_proj": (C.c_int, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     "ocm_op_attention": (C.c_int, [_i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _f32, _vp]),

@@ -12,45 +12,38 @@
 #include <type_traits>
 #include "gemm_core.h"
 #include "launch.h"
+#include "gemm_plan.h"
 #include "dev_knobs.h"
 
 int ocm_wt_mask();  // kernels_gemm.hip
 
-// LDS-DMA ring depth of the 64 x 128 tiles that serve the one-tile-per-call forwards (M <= 1024 rows: a handful of
-// workgroups whose K loop is a chain of L2 round trips — three steps in flight instead of one)
-#ifndef OCM_SMALLM_STAGES
-#define OCM_SMALLM_STAGES 4
-#endif
-// ... and up to how many rows they are chosen: 4096 covers one ViT-S/8 window of 384^2 per call (2305 rows, 111 .. 444
-// workgroups). With FOUR waves per tile the register-staged loop was faster there (attn.qkv 18.8 against 21.8 us, mlp.fc1 16.2
-// against 17.5); with eight the LDS-DMA loop wins (the one-window forward 1.42 -> 1.28 ms)
-constexpr int OCM_SMALLM_ROWS = 4096;
-typedef GemmCfg<128, 128, 2, 2> Cfg128x128;
+// The tiles (gemm_plan.h: GEMM_TILES names each shape once; the plan functions there choose among them)
+template <GemmTile T>
+using CfgOf = GemmCfg<GEMM_TILES[T].bm, GEMM_TILES[T].bn, GEMM_TILES[T].waves_m, GEMM_TILES[T].waves_n, GEMM_TILES[T].mf16>;
+typedef CfgOf<T128x128> Cfg128x128;
 // the qkv projection runs the same tile with 8 waves (32x64 MFMA sub-tiles per wave): two waves per SIMD inside
 // one workgroup overlap its heavier scatter epilogue with the other waves' MFMAs (29.0 -> 25.8 us at ViT-S, B=64)
-typedef GemmCfg<128, 128, 2, 4> Cfg128x128q;
+typedef CfgOf<T128x128q> Cfg128x128q;
 // ... and on v_mfma_f32_16x16x32_bf16 for the split-bf16 LDS-DMA launches of that tile (gemm_core.h: GemmCfg::MF16)
-typedef GemmCfg<128, 128, 2, 4, 1> Cfg128x128q16;
-typedef GemmCfg<128, 128, 2, 2, 1> Cfg128x128m16;  // development A/B (four waves: the tile of forwards of 32 k rows and more)
+typedef CfgOf<T128x128q16> Cfg128x128q16;
+typedef CfgOf<T128x128m16> Cfg128x128m16;  // development A/B (four waves: the tile of forwards of 32 k rows and more)
 // 160 rows: two full 32-row tiles and a 16-row half tile per wave row (gemm_core.h: GemmCfg::HALF). At 12 608 rows (ViT-S/16, B = 64)
 // mlp.fc1 is 79 x 12 = 948 of these = 1.85 rounds of the 512 two-per-CU slots instead of 1 188 tiles of 128 x 128 = 2.32
-typedef GemmCfg<160, 128, 2, 4, 1> Cfg160x128q16;
-typedef GemmCfg<256, 256, 2, 4, 1> Cfg256x256m16;  // ViT-B sizes
-typedef GemmCfg<64, 128, 2, 2> Cfg64x128;
+typedef CfgOf<T160x128q16> Cfg160x128q16;
+typedef CfgOf<T256x256m16> Cfg256x256m16;  // ViT-B sizes
+typedef CfgOf<T64x128> Cfg64x128;
 // the same tile on eight wavefronts (32 x 32 each) for the one-tile-per-call forwards: with ONE workgroup per CU a lone wave per
 // SIMD waits out every LDS read before its MFMAs (850 cycles per K step for 384 of MFMA, tools/stamps_b1.py); two waves per SIMD
 // take turns
-typedef GemmCfg<64, 128, 2, 4> Cfg64x128w;
-typedef GemmCfg<64, 64, 2, 2> Cfg64x64;
-// 8 waves, one workgroup per CU: half the L2->LDS bytes per output element of 128x128. Pays off once the
-// problem has at least two full rounds of such tiles (ViT-B at 384^2, the ViT-S/8 slab windows); below
-// that the idle CUs of the last round cost more than the traffic saves, and with K = 384 (six steps) the
-// exposed prologue of a lone workgroup does (measured: ViT-S/8 slab fc1 +7 % slower, ViT-B GEMMs 13 % faster).
-typedef GemmCfg<256, 256, 2, 4> Cfg256x256;
-
-static inline bool big_tiles_pay(int M, int N, int K) {
-    return K >= 768 && N % 256 == 0 && (long)((M + 255) / 256) * (N / 256) >= 512;
-}
+typedef CfgOf<T64x128w> Cfg64x128w;
+typedef CfgOf<T64x64> Cfg64x64;
+typedef CfgOf<T256x256> Cfg256x256;  // 8 waves, one workgroup per CU (gemm_plan.h: big_tiles_pay)
+typedef CfgOf<T256x128> Cfg256x128;
+// N = 384 outputs (attn.proj, mlp.fc2) at ~12 k rows: 198 tiles, one 8-wave workgroup per CU, wave tile 32 x 96. Per K step
+// 40 KiB of operands for 1152 cycles of MFMA per SIMD, against 56 KiB for the 64 x 384 full-row tile
+typedef CfgOf<T128x192> Cfg128x192;
+// Swin's channel counts that are not multiples of 128 (96 and 288 = 3 x 96): the same 32 x 96 wave tile, four waves
+typedef CfgOf<T128x96> Cfg128x96;
 
 // Store Elem<OE>::EPW consecutive activations (taken from fp32 values) at element column `col` of the row that
 // starts at `rowp`: 8 bf16 (16 B), 4 fp32 (16 B) or 8 split pairs (16 B of hi halves + 16 B of lo halves).
@@ -347,24 +340,26 @@ static hipError_t launch_gemm_ks(const ALoad &al, const E *w, int64_t ldw, int M
     return hipGetLastError();
 }
 
-// The K extents of ViT-S/B (D and 4D, and the patch embedding) get a compile-time step count, which
-// unlocks the two-step prefetch of gemm_mainloop; any other K runs the generic one-step pipeline.
-template <class Cfg, class E, bool SWAP, class ALoad, class Epi>
-static hipError_t launch_gemm(const ALoad &al, const E *w, int64_t ldw, int M, int N, int K, const Epi &epi,
-                              hipStream_t s) {
-    if (K % Elem<E>::KROW) return hipErrorInvalidValue;
-    switch (K / Elem<E>::KROW) {
-        case 2: return launch_gemm_ks<Cfg, E, SWAP, 2>(al, w, ldw, M, N, K, epi, s);  // Swin stage 0 (K = 96 padded)
-        case 3: return launch_gemm_ks<Cfg, E, SWAP, 3>(al, w, ldw, M, N, K, epi, s);  // Swin stage 1 (K = 192 bf16, 96 fp32)
-        case 4: return launch_gemm_ks<Cfg, E, SWAP, 4>(al, w, ldw, M, N, K, epi, s);
-        case 6: return launch_gemm_ks<Cfg, E, SWAP, 6>(al, w, ldw, M, N, K, epi, s);
-        case 12: return launch_gemm_ks<Cfg, E, SWAP, 12>(al, w, ldw, M, N, K, epi, s);
-        case 24: return launch_gemm_ks<Cfg, E, SWAP, 24>(al, w, ldw, M, N, K, epi, s);
-        case 48: return launch_gemm_ks<Cfg, E, SWAP, 48>(al, w, ldw, M, N, K, epi, s);
-        case 96: return launch_gemm_ks<Cfg, E, SWAP, 96>(al, w, ldw, M, N, K, epi, s);
-        default: break;
+// Executes a plan's K-step count: calls f(std::integral_constant<int, KS>()) with KS = ksteps when `List` (gemm_plan.h) names it
+// or it is 0, the run-time loop. A count the family does not compile is an error, never another kernel.
+template <class List, int I = 0, class F>
+static hipError_t with_ksteps(int ksteps, F &&f) {
+    if constexpr (I < List::n) {
+        if (ksteps == List::v[I]) return f(std::integral_constant<int, List::v[I]>());
+        return with_ksteps<List, I + 1>(ksteps, f);
+    } else {
+        return ksteps == 0 ? f(std::integral_constant<int, 0>()) : hipErrorInvalidValue;
     }
-    return launch_gemm_ks<Cfg, E, SWAP, 0>(al, w, ldw, M, N, K, epi, s);
+}
+
+// A compile-time step count (the plan's ksteps, one of List) unlocks the two-step prefetch of gemm_mainloop; 0 runs the
+// generic one-step pipeline.
+template <class Cfg, class E, bool SWAP, class List = KsLinearReg, class ALoad, class Epi>
+static hipError_t launch_gemm(const ALoad &al, const E *w, int64_t ldw, int M, int N, int K, const Epi &epi, hipStream_t s,
+                              int ksteps) {
+    return with_ksteps<List>(ksteps, [&](auto ks) {
+        return launch_gemm_ks<Cfg, E, SWAP, decltype(ks)::value>(al, w, ldw, M, N, K, epi, s);
+    });
 }
 
 // ---- LDS-DMA staged variants (gemm_mainloop_dma) ----
@@ -381,28 +376,14 @@ static hipError_t launch_gemm_dma_ks(const E *a, int64_t lda, const E *w, int64_
     return hipGetLastError();
 }
 
-template <class Cfg, class E, int NSTAGE, class Epi>
+template <class Cfg, class E, int NSTAGE, class List = KsLinearDma, class Epi>
 static hipError_t launch_gemm_dma(const E *a, int64_t lda, const E *w, int64_t ldw, int M, int N, int K, const Epi &epi,
-                                  hipStream_t s) {
-    if (K % Elem<E>::KROW) return hipErrorInvalidValue;
-    switch (K / Elem<E>::KROW) {
-        case 6: return launch_gemm_dma_ks<Cfg, E, 6, NSTAGE, Epi>(a, lda, w, ldw, M, N, K, epi, s);
-        case 12: return launch_gemm_dma_ks<Cfg, E, 12, NSTAGE, Epi>(a, lda, w, ldw, M, N, K, epi, s);
-        case 24: return launch_gemm_dma_ks<Cfg, E, 24, NSTAGE, Epi>(a, lda, w, ldw, M, N, K, epi, s);
-        case 48: return launch_gemm_dma_ks<Cfg, E, 48, NSTAGE, Epi>(a, lda, w, ldw, M, N, K, epi, s);
-        case 96: return launch_gemm_dma_ks<Cfg, E, 96, NSTAGE, Epi>(a, lda, w, ldw, M, N, K, epi, s);  // ViT-B mlp.fc2
-        default: break;
-    }
-    return launch_gemm_dma_ks<Cfg, E, 0, NSTAGE, Epi>(a, lda, w, ldw, M, N, K, epi, s);
+                                  hipStream_t s, int ksteps) {
+    return with_ksteps<List>(ksteps, [&](auto ks) {
+        return launch_gemm_dma_ks<Cfg, E, decltype(ks)::value, NSTAGE, Epi>(a, lda, w, ldw, M, N, K, epi, s);
+    });
 }
 
-typedef GemmCfg<256, 128, 4, 2> Cfg256x128;
-// N = 384 outputs (attn.proj, mlp.fc2) at ~12 k rows: 198 tiles, one 8-wave workgroup per CU, wave tile 32 x 96. Per K step
-// 40 KiB of operands for 1152 cycles of MFMA per SIMD, against 56 KiB for the 64 x 384 full-row tile
-typedef GemmCfg<128, 192, 4, 2> Cfg128x192;
-typedef GemmCfg<128, 256, 2, 4> Cfg128x256;
-// Swin's channel counts that are not multiples of 128 (96 and 288 = 3 x 96): the same 32 x 96 wave tile, four waves
-typedef GemmCfg<128, 96, 4, 1> Cfg128x96;
 template <class Epi, class = void>
 struct epi_bn_mult {
     static constexpr int v = 1;
@@ -412,103 +393,65 @@ struct epi_bn_mult<Epi, std::void_t<decltype(Epi::BN_MULT)>> {
     static constexpr int v = Epi::BN_MULT;
 };
 
+// nn.Linear on the tile, loop and depth gemm_plan_linear chooses. Each case names a kernel family that is instantiated for this
+// element type and epilogue: LDS-DMA tiles for split-bf16 operands only, the 160-row tile for the activation-output epilogues,
+// 128 x 96 where the epilogue serves that width; a plan outside them is refused. The product switch, the two guarded keys after
+// it and the development switch must keep disjoint keys: a key moves from one to another, it is never listed twice.
 template <int MODE, class E, class Epi>
 static hipError_t launch_linear_epi(const E *a, const E *w, const Epi &epi, int M, int N, int K, hipStream_t s) {
-    RowLoader<E> al{a, K};
-    if constexpr (Elem<E>::MODE == 2) {
-#ifdef OCM_DEV
-        switch (OCM_KNOB(0)) {  // development: force a variant (tools/microbench_x3.py)
-            case -1: goto reg_staged;
-            case 1: if (N % 256 == 0) return launch_gemm_dma<Cfg256x256, E, 2>(a, K, w, K, M, N, K, epi, s); break;
-            case 4: if (N % 128 == 0) return launch_gemm_dma<Cfg128x128, E, 2>(a, K, w, K, M, N, K, epi, s); break;
-            case 6: if (N % 128 == 0) return launch_gemm_dma<Cfg256x128, E, 2>(a, K, w, K, M, N, K, epi, s); break;
-            case 7: if (N % 128 == 0) return launch_gemm_dma<Cfg64x128, E, 2>(a, K, w, K, M, N, K, epi, s); break;
-            case 8: if (N % 128 == 0) return launch_gemm_dma<Cfg64x128, E, 3>(a, K, w, K, M, N, K, epi, s); break;
-            case 9: if (N % 128 == 0) return launch_gemm_dma<Cfg64x128, E, 4>(a, K, w, K, M, N, K, epi, s); break;
-            case 10: if (N % 64 == 0) return launch_gemm_dma<Cfg64x64, E, 4>(a, K, w, K, M, N, K, epi, s); break;
-            case 11: if (N == 384) return launch_gemm_dma<Cfg128x192, E, 3>(a, K, w, K, M, N, K, epi, s); break;
-            case 12: if (N % 128 == 0) return launch_gemm_dma<Cfg128x128q, E, 2>(a, K, w, K, M, N, K, epi, s); break;  // 8 waves
-            case 13: if (N % 128 == 0) return launch_gemm_dma<Cfg128x128q16, E, 2>(a, K, w, K, M, N, K, epi, s); break;
-            case 14: if (N % 128 == 0) return launch_gemm_dma<Cfg128x128m16, E, 2>(a, K, w, K, M, N, K, epi, s); break;
-            case 19: if (N % 256 == 0 && N >= 1024 && M >= 16384) return launch_gemm_dma<Cfg256x256m16, E, 2>(a, K, w, K, M, N, K, epi, s); break;
-            case 23: if (N % 128 == 0 && M >= 4096) return launch_gemm_dma<Cfg160x128q16, E, 2>(a, K, w, K, M, N, K, epi, s); break;
-            default: break;
-        }
-#endif
-        // Split-bf16 operands, >= 512 tiles of 128x128 (fc1): LDS-DMA staging, two workgroups per CU. Inside the forward
-        // (ViT-S/16, B = 64, same box, alternating runs) fc1 62 -> 57 us; the 64x128 shapes (proj, fc2) and the qkv
-        // projection measure the same either way (their stand-alone gains of 10 % do not survive cold operands), so
-        // they stay on the register-staged loop.
-        // Few rows (the reference's one-tile-per-call loops, M = 197 .. 785): everything is L2-resident and a launch is a
-        // handful of workgroups, so the LDS-DMA loop's shorter prologue shows (stand-alone, M = 197: fc1 9.4 -> 7.9 us,
-        // fc2 23.1 -> 16.7 us on 64x64 tiles with a 4-deep ring, proj 8.3 -> 7.6 us)
-        if (M <= OCM_SMALLM_ROWS && OCM_KNOB(0) == 0) {
-            if (K >= 1024 && N % 64 == 0) return launch_gemm_dma<Cfg64x64, E, 4>(a, K, w, K, M, N, K, epi, s);
-            if (N % 128 == 0) return launch_gemm_dma<Cfg64x128w, E, OCM_SMALLM_STAGES>(a, K, w, K, M, N, K, epi, s);
-        }
-        // mlp.fc1 at K = 384 and tens of thousands of rows (the 4096^2 slab sweep: 48 k rows; Swin-T stage 2 at batch 256: 50 k):
-        // the same 256 x 256 tile although its K loop is only twelve steps (round 4, knob 0 = 19 against the 128 x 128 tile,
-        // alternating on one box: slab sweep 534.6 -> 530.6 ms, Swin-T 10.35 -> 10.27 ms; attn.qkv LOSES on it: 534.6 -> 558 ms)
-        if (K == 384 && N % 256 == 0 && N >= 1024 && M >= 16384 && OCM_KNOB(0) != 20)
-            return launch_gemm_dma<Cfg256x256m16, E, 2>(a, K, w, K, M, N, K, epi, s);
-        if (big_tiles_pay(M, N, K))  // ViT-B at 384^2: 256x256 tiles, one 8-wave workgroup per CU (fc1 1020 -> 944 us), on
-            // v_mfma_f32_16x16x32_bf16 since round 4 (B = 128, alternating runs: fc1 965 -> 870 us, fc2 903 -> 820, proj 281 -> 256)
-            return launch_gemm_dma<Cfg256x256m16, E, 2>(a, K, w, K, M, N, K, epi, s);
-        // Narrow outputs (attn.proj / mlp.fc2 of ViT-S: N = 384) with too few rows for 512 tiles of 128 x 128: 128 x 192
-        // tiles, one 8-wave workgroup per CU on a three-stage LDS-DMA ring. Per K step 40 KiB of operands for 1152 cycles
-        // of MFMA per SIMD (56 KiB for the 64 x 384 full-row tile, 64 KiB for two 64 x 128 tiles): ViT-S/16 at B = 64,
-        // in the forward, mlp.fc2 64 -> 49 us, attn.proj 28.5 -> 21.5 us against the full-row GEMM + LayerNorm kernels
-        // Past 512 tiles of 128 x 128 the choice goes by how full the last round is: at 48 405 rows (the 4096^2 slab sweep) 1137
-        // tiles of 128 x 128 are 2.2 rounds of 512 slots, 758 of 128 x 192 are 2.96 rounds of 256 (sweep 557.7 -> 551.3 ms); at
-        // 50 176 rows (Swin-T stage 2) both shapes fill 77 % of their last round and the two-per-CU tile wins (183 against 215 us).
-        if (N % 192 == 0 && N / 192 <= 2 && M >= 4096) {
-            const long rb = (M + 127) / 128, t192 = rb * (N / 192), t128 = rb * ((N + 127) / 128);
-            const double e192 = (double)t192 / (256.0 * ((t192 + 255) / 256)), e128 = (double)t128 / (512.0 * ((t128 + 511) / 512));
-            if (t128 < 512 || e192 > 1.1 * e128) return launch_gemm_dma<Cfg128x192, E, 3>(a, K, w, K, M, N, K, epi, s);
-        }
-        if (const long t128s = (long)((M + 127) / 128) * (N / 128); N % 128 == 0 && t128s >= 512) {
-            // wide outputs (mlp.fc1): the same tile on eight wavefronts, four per SIMD with two workgroups per CU (58.0 -> 56.2 us
-            // in the forward on one box, 53.0 -> 51.8 on another; the N = 384 layers lose on it: fc2 56 -> 62, proj 26 -> 27, and
-            // so does mlp.fc1 at 48 k rows: slab sweep 530 -> 533 ms)
-            // (round 4, on the 16 x 16 MFMA shape: at 48 k rows too — slab sweep 541.8 -> 538.7 ms against the four-wave tile, which
-            // on the 32 x 32 shape had been the faster one there; knob 0 = 17: the four-wave tile on the 16 x 16 shape, 542.9 ms)
-            // (round 4: narrower outputs that reach this branch — Swin-T stages 2 - 3, N = 384 / 768 at 50 k / 12 k rows — also
-            // run faster on it than on the four-wave 32 x 32-shape tile: Swin-T at batch 256 10.35 -> 10.17 ms, knob 0 = 13;
-            // knob 0 = 21 keeps the four-wave tile for them)
-            if constexpr (MODE == 2 || MODE == 3) {  // (the activation-output epilogues: any tile height)
-                // 160-row tiles when they fill the two-per-CU slots better: rounds of 512 workgroups, last one counted by its fill
-                const long t160 = (long)((M + 159) / 160) * (N / 128);
-                const double e128 = (double)t128s / (512.0 * ((t128s + 511) / 512)), e160 = (double)t160 / (512.0 * ((t160 + 511) / 512));
-                if (N >= 1024 && K == 384 && e160 > 1.1 * e128 && OCM_KNOB(0) != 22)
-                    return launch_gemm_dma<Cfg160x128q16, E, 2>(a, K, w, K, M, N, K, epi, s);
+    if (K % Elem<E>::KROW) return hipErrorInvalidValue;
+    // (the statistics epilogue, to the plan, is the one that cannot take 128 x 96: the same condition as the guard of that case below)
+    const GemmPlan p = gemm_plan_linear(Elem<E>::MODE, MODE, M, N, K, Cfg128x96::BN % epi_bn_mult<Epi>::v != 0, false, OCM_KNOB(0));
+    const int ks = p.ksteps;
+    if (p.loop == GEMM_LOOP_DMA) {
+        const int key = gemm_dma_key(p.tile, p.stages);
+        if constexpr (Elem<E>::MODE == 2) {
+            switch (key) {
+                case gemm_dma_key(T64x64, 4): return launch_gemm_dma<Cfg64x64, E, 4>(a, K, w, K, M, N, K, epi, s, ks);
+                case gemm_dma_key(T64x128w, OCM_SMALLM_STAGES): return launch_gemm_dma<Cfg64x128w, E, OCM_SMALLM_STAGES>(a, K, w, K, M, N, K, epi, s, ks);
+                case gemm_dma_key(T128x192, 3): return launch_gemm_dma<Cfg128x192, E, 3>(a, K, w, K, M, N, K, epi, s, ks);
+                case gemm_dma_key(T128x128q16, 2): return launch_gemm_dma<Cfg128x128q16, E, 2>(a, K, w, K, M, N, K, epi, s, ks);
+                case gemm_dma_key(T256x256m16, 2): return launch_gemm_dma<Cfg256x256m16, E, 2>(a, K, w, K, M, N, K, epi, s, ks);
+                case gemm_dma_key(T128x128, 2): return launch_gemm_dma<Cfg128x128, E, 2>(a, K, w, K, M, N, K, epi, s, ks);  // (knob 0 = 4 / 21; in every build)
+                default: break;
             }
-            if ((N >= 1024 || OCM_KNOB(0) != 21) && OCM_KNOB(0) != 17) return launch_gemm_dma<Cfg128x128q16, E, 2>(a, K, w, K, M, N, K, epi, s);
-            if (OCM_KNOB(0) == 17) return launch_gemm_dma<Cfg128x128m16, E, 2>(a, K, w, K, M, N, K, epi, s);
-            return launch_gemm_dma<Cfg128x128, E, 2>(a, K, w, K, M, N, K, epi, s);
-        }
-        // Swin-T's narrow stages (N = 96, 192, 288, 576 at 2e5 .. 8e5 rows): tiles that divide N exactly on the LDS-DMA
-        // loop instead of 64 x 64 register-staged tiles with a ragged last column (these GEMMs are bound by the 4-byte
-        // activations they stream, not by the matrix pipe)
-        if (N % 128 != 0 && M >= 4096) {
-            if (N % 192 == 0) return launch_gemm_dma<Cfg128x192, E, 3>(a, K, w, K, M, N, K, epi, s);
+            if constexpr (MODE == 2 || MODE == 3)
+                if (key == gemm_dma_key(T160x128q16, 2)) return launch_gemm_dma<Cfg160x128q16, E, 2>(a, K, w, K, M, N, K, epi, s, ks);
             if constexpr (Cfg128x96::BN % epi_bn_mult<Epi>::v == 0)
-                if (N % 96 == 0) return launch_gemm_dma<Cfg128x96, E, 2>(a, K, w, K, M, N, K, epi, s);
-        }
-    }
-#ifdef OCM_DEV
-    if constexpr (Elem<E>::MODE == 0) {  // development A/B: the LDS-DMA loop on single-bf16 operands (knob 0 = 4 / 7)
-        if (OCM_KNOB(0) == 4 && N % 128 == 0) return launch_gemm_dma<Cfg128x128, E, 2>(a, K, w, K, M, N, K, epi, s);
-        if (OCM_KNOB(0) == 7 && N % 128 == 0) return launch_gemm_dma<Cfg64x128, E, 2>(a, K, w, K, M, N, K, epi, s);
-    }
+                if (key == gemm_dma_key(T128x96, 2)) return launch_gemm_dma<Cfg128x96, E, 2>(a, K, w, K, M, N, K, epi, s, ks);
+#ifdef OCM_DEV  // the tiles only a forcing knob names
+            switch (key) {
+                case gemm_dma_key(T256x256, 2): return launch_gemm_dma<Cfg256x256, E, 2>(a, K, w, K, M, N, K, epi, s, ks);
+                case gemm_dma_key(T256x128, 2): return launch_gemm_dma<Cfg256x128, E, 2>(a, K, w, K, M, N, K, epi, s, ks);
+                case gemm_dma_key(T64x128, 2): return launch_gemm_dma<Cfg64x128, E, 2>(a, K, w, K, M, N, K, epi, s, ks);
+                case gemm_dma_key(T64x128, 3): return launch_gemm_dma<Cfg64x128, E, 3>(a, K, w, K, M, N, K, epi, s, ks);
+                case gemm_dma_key(T64x128, 4): return launch_gemm_dma<Cfg64x128, E, 4>(a, K, w, K, M, N, K, epi, s, ks);
+                case gemm_dma_key(T128x128q, 2): return launch_gemm_dma<Cfg128x128q, E, 2>(a, K, w, K, M, N, K, epi, s, ks);
+                case gemm_dma_key(T128x128m16, 2): return launch_gemm_dma<Cfg128x128m16, E, 2>(a, K, w, K, M, N, K, epi, s, ks);
+                case gemm_dma_key(T160x128q16, 2): return launch_gemm_dma<Cfg160x128q16, E, 2>(a, K, w, K, M, N, K, epi, s, ks);  // (knob 0 = 23: any epilogue; MODE 2 / 3 returned above)
+                default: break;
+            }
 #endif
-reg_staged:
-    if constexpr (Elem<E>::MODE == 0)
-        if (big_tiles_pay(M, N, K)) return launch_gemm<Cfg256x256, E, false>(al, w, K, M, N, K, epi, s);
-    // Tile choice: fill >= 2 workgroups per CU (256 CUs) when the problem allows it.
-    const long t128 = (long)((M + 127) / 128) * ((N + 127) / 128);
-    if (N % 128 == 0 && t128 >= 512) return launch_gemm<Cfg128x128, E, false>(al, w, K, M, N, K, epi, s);
-    if (N % 128 == 0 && M > 64) return launch_gemm<Cfg64x128, E, false>(al, w, K, M, N, K, epi, s);
-    return launch_gemm<Cfg64x64, E, false>(al, w, K, M, N, K, epi, s);
+        }
+#ifdef OCM_DEV
+        if constexpr (Elem<E>::MODE == 0) {  // development A/B: the LDS-DMA loop on single-bf16 operands (knob 0 = 4 / 7)
+            if (key == gemm_dma_key(T128x128, 2)) return launch_gemm_dma<Cfg128x128, E, 2>(a, K, w, K, M, N, K, epi, s, ks);
+            if (key == gemm_dma_key(T64x128, 2)) return launch_gemm_dma<Cfg64x128, E, 2>(a, K, w, K, M, N, K, epi, s, ks);
+        }
+#endif
+        return hipErrorInvalidValue;
+    }
+    RowLoader<E> al{a, K};
+    switch (p.tile) {
+        case T256x256:
+            if constexpr (Elem<E>::MODE == 0) return launch_gemm<Cfg256x256, E, false>(al, w, K, M, N, K, epi, s, ks);
+            break;
+        case T128x128: return launch_gemm<Cfg128x128, E, false>(al, w, K, M, N, K, epi, s, ks);
+        case T64x128: return launch_gemm<Cfg64x128, E, false>(al, w, K, M, N, K, epi, s, ks);
+        case T64x64: return launch_gemm<Cfg64x64, E, false>(al, w, K, M, N, K, epi, s, ks);
+        default: break;
+    }
+    return hipErrorInvalidValue;
 }
 
 // (external linkage: kernels_gemm_inst.hip instantiates the activation-output modes of the split-bf16 type in an object of
@@ -558,8 +501,8 @@ __global__ __launch_bounds__(Cfg::NT) void gemm_dma_splitk_kernel(const E *__res
 template <class E>
 static hipError_t launch_linear_splitk(const E *a, const E *w, const float *bias, const float *resid, float *x, int M, int N,
                                        int K, hipStream_t s, const StatsOut &so) {
-    typedef Cfg64x64 Cfg;  // (the eight-wave 64 x 128 tile halves the workgroups: 0.628 -> 0.641 ms per one-tile forward)
-    constexpr int NSTAGE = 4, KS = 12;  // K / OCM_SPLITK = 384 elements = 12 steps (ViT-S mlp.fc2); other depths: no split
+    typedef Cfg64x64 Cfg;  // the one form gemm_plan_linear offers: four-deep ring, OCM_SPLITK slices of OCM_SPLITK_STEPS steps
+    constexpr int NSTAGE = 4, KS = OCM_SPLITK_STEPS;
     constexpr int LDS = NSTAGE * (Cfg::BM + Cfg::BN) * 128;
     auto kern = gemm_dma_splitk_kernel<Cfg, E, KS, NSTAGE>;
     static OptinMask optin;
@@ -578,9 +521,10 @@ hipError_t launch_linear_e(const E *a, const E *w, const float *bias, const floa
         case 0: return launch_linear_mode<0, E>(a, w, bias, resid, out, M, N, K, s);
         case 1:
             if constexpr (Elem<E>::MODE == 2)
-                if (so.part && M <= OCM_SPLITK_MAX_ROWS && N % 64 == 0 && K == OCM_SPLITK * 12 * Elem<E>::KROW && resid &&
-                    (!so.stats || so.xs))
-                    return launch_linear_splitk<E>(a, w, bias, resid, (float *)out, M, N, K, s, so);
+                if (so.part && resid && (!so.stats || so.xs) && K % Elem<E>::KROW == 0) {  // a split-K workspace is on offer
+                    const GemmPlan p = gemm_plan_linear(2, 1, M, N, K, so.stats != nullptr, true, OCM_KNOB(0));
+                    if (p.splitk > 1) return launch_linear_splitk<E>(a, w, bias, resid, (float *)out, M, N, K, s, so);
+                }
             if (so.stats) {
                 if (N % 64) return hipErrorInvalidValue;
                 EpiResidStats<E> epi{bias, resid, (float *)out, so.xs, so.stats, M, N};
@@ -601,11 +545,16 @@ hipError_t launch_linear_e(const E *a, const E *w, const float *bias, const floa
 template <int MODE, class E>
 static hipError_t launch_linear_ld_mode(const E *a, int64_t lda, const E *w, const float *bias, const float *resid,
                                         void *out, int64_t ldo, int M, int N, int K, hipStream_t s) {
+    if (K % Elem<E>::KROW) return hipErrorInvalidValue;
     RowLoader<E> al{a, lda};
     EpiLinear<MODE, E> epi{bias, resid, out, M, N, ldo};
-    if (M >= 2048 && N > 64) return launch_gemm<Cfg128x128, E, false>(al, w, K, M, N, K, epi, s);
-    if (M > 64 && N > 64) return launch_gemm<Cfg64x128, E, false>(al, w, K, M, N, K, epi, s);
-    return launch_gemm<Cfg64x64, E, false>(al, w, K, M, N, K, epi, s);
+    const GemmPlan p = gemm_plan_linear_ld(Elem<E>::MODE, M, N, K);
+    switch (p.tile) {
+        case T128x128: return launch_gemm<Cfg128x128, E, false>(al, w, K, M, N, K, epi, s, p.ksteps);
+        case T64x128: return launch_gemm<Cfg64x128, E, false>(al, w, K, M, N, K, epi, s, p.ksteps);
+        case T64x64: return launch_gemm<Cfg64x64, E, false>(al, w, K, M, N, K, epi, s, p.ksteps);
+        default: return hipErrorInvalidValue;
+    }
 }
 
 template <class E>
@@ -712,38 +661,21 @@ struct EpiResidLN {
     }
 };
 
-// One full-row GEMM + residual + LayerNorm launch on tile configuration Cfg. `loop`: 0 = register-staged main loop,
-// 2 = two-stage LDS-DMA ring.
-template <class Cfg, class E, int D_>
-static hipError_t launch_resid_ln_cfg(int loop, const E *a, const E *w, const EpiResidLN<E, D_> &epi, int M, int K,
-                                      hipStream_t s) {
-    if (K % Elem<E>::KROW) return hipErrorInvalidValue;
-    if (loop == 2) {
-        switch (K / Elem<E>::KROW) {
-            case 12: return launch_gemm_dma_ks<Cfg, E, 12, 2>(a, K, w, K, M, D_, K, epi, s);
-            case 48: return launch_gemm_dma_ks<Cfg, E, 48, 2>(a, K, w, K, M, D_, K, epi, s);
-            default: return launch_gemm_dma_ks<Cfg, E, 0, 2>(a, K, w, K, M, D_, K, epi, s);
-        }
-    }
-    RowLoader<E> al{a, K};
-    return launch_gemm<Cfg, E, false>(al, w, K, M, D_, K, epi, s);
-}
-
+// One full-row GEMM + residual + LayerNorm launch, as gemm_plan_resid_ln says: one 8-wave workgroup per CU on the register-staged
+// loop, or the same tile on the two-stage LDS-DMA ring (the development A/B of knob 4 = 2; compiled into every build).
 template <class E, int D_>
 static hipError_t launch_resid_ln_d(const E *a, const E *w, const float *bias, const float *resid, float *x,
                                     const float *gamma, const float *beta, void *xn, int M, int K, float eps,
                                     hipStream_t s) {
     typedef GemmCfg<64, D_, 2, 4> Cfg8;  // 8 waves, wave tile 32 x D/4
+    if (K % Elem<E>::KROW) return hipErrorInvalidValue;
     EpiResidLN<E, D_> epi{bias, resid, x, gamma, beta, xn, M, eps};
     epi.wt = ((ocm_wt_mask() >> 2) & 1) | ((ocm_wt_mask() >> 4) & 2);  // mask 4: xn, mask 32: x
-#ifdef OCM_DEV
-    if constexpr (Elem<E>::MODE == 2) {
-        // development A/B (knob 4): 2 = the 8-wave tile on the two-stage LDS-DMA loop
-        if (OCM_KNOB(4) == 2) return launch_resid_ln_cfg<Cfg8, E, D_>(2, a, w, epi, M, K, s);
-    }
-#endif
-    // One 8-wave workgroup per CU on the register-staged loop (two-step prefetch of both operands)
-    return launch_resid_ln_cfg<Cfg8, E, D_>(0, a, w, epi, M, K, s);
+    const GemmPlan p = gemm_plan_resid_ln(Elem<E>::MODE, D_, K, OCM_KNOB(4));
+    if (GEMM_TILES[p.tile].bm != Cfg8::BM || GEMM_TILES[p.tile].bn != D_) return hipErrorInvalidValue;
+    if (p.loop == GEMM_LOOP_REG) return launch_gemm<Cfg8, E, false>(RowLoader<E>{a, K}, w, K, M, D_, K, epi, s, p.ksteps);
+    if (p.stages == 2) return launch_gemm_dma<Cfg8, E, 2, KsResidLnDma>(a, K, w, K, M, D_, K, epi, s, p.ksteps);
+    return hipErrorInvalidValue;
 }
 
 template <class E>
@@ -1032,13 +964,10 @@ static hipError_t launch_qkv_dma_ks(const E *a, const E *w, int M, int D, const 
 
 template <class Cfg, class E, int NSTAGE>
 static hipError_t launch_qkv_dma(const E *a, const E *w, int M, int D, const EpiQK<E> &eqk, const EpiVt<E> &ev,
-                                 hipStream_t s) {
-    switch (D / Elem<E>::KROW) {
-        case 12: return launch_qkv_dma_ks<Cfg, E, 12, NSTAGE>(a, w, M, D, eqk, ev, s);
-        case 24: return launch_qkv_dma_ks<Cfg, E, 24, NSTAGE>(a, w, M, D, eqk, ev, s);
-        default: break;
-    }
-    return launch_qkv_dma_ks<Cfg, E, 0, NSTAGE>(a, w, M, D, eqk, ev, s);
+                                 hipStream_t s, int ksteps) {
+    return with_ksteps<KsQkvDma>(ksteps, [&](auto ks) {
+        return launch_qkv_dma_ks<Cfg, E, decltype(ks)::value, NSTAGE>(a, w, M, D, eqk, ev, s);
+    });
 }
 
 template <class Cfg, class E, int KSTEPS>
@@ -1055,14 +984,10 @@ static hipError_t launch_qkv_ks(const RowLoader<E> &al, const E *w, int M, int D
 
 template <class Cfg, class E>
 static hipError_t launch_qkv_cfg(const RowLoader<E> &al, const E *w, int M, int D, const EpiQK<E> &eqk,
-                                 const EpiVt<E> &ev, hipStream_t s) {
-    switch (D / Elem<E>::KROW) {
-        case 6: return launch_qkv_ks<Cfg, E, 6>(al, w, M, D, eqk, ev, s);
-        case 12: return launch_qkv_ks<Cfg, E, 12>(al, w, M, D, eqk, ev, s);
-        case 24: return launch_qkv_ks<Cfg, E, 24>(al, w, M, D, eqk, ev, s);
-        default: break;
-    }
-    return launch_qkv_ks<Cfg, E, 0>(al, w, M, D, eqk, ev, s);
+                                 const EpiVt<E> &ev, hipStream_t s, int ksteps) {
+    return with_ksteps<KsQkvReg>(ksteps, [&](auto ks) {
+        return launch_qkv_ks<Cfg, E, decltype(ks)::value>(al, w, M, D, eqk, ev, s);
+    });
 }
 
 template <class E>
@@ -1084,39 +1009,35 @@ hipError_t launch_qkv_e(const E *a, const E *w, const float *bias, E *q, E *k, E
         if (OCM_KNOB(6) == 1) eqk.ln.stats = ev.ln.stats = nullptr;  // development timing probe (wrong results)
         if (OCM_KNOB(6) == 2) eqk.ln.nslot = ev.ln.nslot = 1;
     }
-    if constexpr (Elem<E>::MODE == 0)
-        if (D % 256 == 0 && big_tiles_pay(M, 3 * D, D)) return launch_qkv_cfg<Cfg256x256, E>(al, w, M, D, eqk, ev, s);
-    const long t128 = (long)((M + 127) / 128) * (3 * D / 128);
-    if constexpr (Elem<E>::MODE == 2) {
-        if (D % 128 == 0 && M > 64) {
-#ifdef OCM_DEV
-            switch (OCM_KNOB(3)) {  // development: force a variant (-1: the register-staged kernels below)
-                case 1: return launch_qkv_dma<Cfg128x128, E, 2>(a, w, M, D, eqk, ev, s);
-                case 2: return launch_qkv_dma<Cfg128x128q, E, 2>(a, w, M, D, eqk, ev, s);
-                case 3: return launch_qkv_dma<Cfg64x128, E, 2>(a, w, M, D, eqk, ev, s);
-                case 4: if (D % 256 == 0) return launch_qkv_dma<Cfg256x256, E, 2>(a, w, M, D, eqk, ev, s); break;
-                case 5: return launch_qkv_dma<Cfg128x128q16, E, 2>(a, w, M, D, eqk, ev, s);
-                case 6: if (D % 256 == 0) return launch_qkv_dma<Cfg256x256m16, E, 2>(a, w, M, D, eqk, ev, s); break;
+    const GemmPlan p = gemm_plan_qkv(Elem<E>::MODE, M, D, OCM_KNOB(3));
+    const int ks = p.ksteps;
+    if (p.loop == GEMM_LOOP_DMA) {
+        if constexpr (Elem<E>::MODE == 2) {
+            switch (gemm_dma_key(p.tile, p.stages)) {
+                case gemm_dma_key(T64x128w, OCM_SMALLM_STAGES): return launch_qkv_dma<Cfg64x128w, E, OCM_SMALLM_STAGES>(a, w, M, D, eqk, ev, s, ks);
+                case gemm_dma_key(T256x256m16, 2): return launch_qkv_dma<Cfg256x256m16, E, 2>(a, w, M, D, eqk, ev, s, ks);
+                case gemm_dma_key(T128x128q16, 2): return launch_qkv_dma<Cfg128x128q16, E, 2>(a, w, M, D, eqk, ev, s, ks);
+#ifdef OCM_DEV  // the tiles only a forcing knob names
+                case gemm_dma_key(T128x128, 2): return launch_qkv_dma<Cfg128x128, E, 2>(a, w, M, D, eqk, ev, s, ks);
+                case gemm_dma_key(T128x128q, 2): return launch_qkv_dma<Cfg128x128q, E, 2>(a, w, M, D, eqk, ev, s, ks);
+                case gemm_dma_key(T64x128, 2): return launch_qkv_dma<Cfg64x128, E, 2>(a, w, M, D, eqk, ev, s, ks);
+                case gemm_dma_key(T256x256, 2): return launch_qkv_dma<Cfg256x256, E, 2>(a, w, M, D, eqk, ev, s, ks);
+#endif
                 default: break;
             }
-#endif
-            if (OCM_KNOB(3) == 0) {
-                // few rows (one tile per call): the DMA loop's shorter prologue shows (B = 1 forward 1.03 -> 1.01 ms)
-                if (M <= OCM_SMALLM_ROWS) return launch_qkv_dma<Cfg64x128w, E, OCM_SMALLM_STAGES>(a, w, M, D, eqk, ev, s);
-                // ViT-B sizes: 256 x 256 tiles halve the bytes through L2 (384^2 B = 128: 755 -> 715 us per launch)
-                // (on v_mfma_f32_16x16x32_bf16 since round 4: 717 -> 670 us)
-                if (D % 256 == 0 && big_tiles_pay(M, 3 * D, D)) return launch_qkv_dma<Cfg256x256m16, E, 2>(a, w, M, D, eqk, ev, s);
-                // the 8-wave 128 x 128 tile on the LDS-DMA loop (ViT-S/16 B = 64: 46.6 -> 41.8 us per launch, +2 % end
-                // to end; ViT-B/16 384^2 B = 128: 805 -> 759 us; alternating runs on one box). The 4-wave form of the
-                // same tile (variant 1) measures like the register-staged kernel.
-                // ... on v_mfma_f32_16x16x32_bf16 (43.1 -> 41.6 us; GemmCfg::MF16)
-                if (t128 >= 512) return launch_qkv_dma<Cfg128x128q16, E, 2>(a, w, M, D, eqk, ev, s);
-            }
         }
+        return hipErrorInvalidValue;
     }
-    if (D % 128 == 0 && t128 >= 512) return launch_qkv_cfg<Cfg128x128q, E>(al, w, M, D, eqk, ev, s);
-    if (D % 128 == 0) return launch_qkv_cfg<Cfg64x128, E>(al, w, M, D, eqk, ev, s);
-    return launch_qkv_cfg<Cfg64x64, E>(al, w, M, D, eqk, ev, s);
+    switch (p.tile) {
+        case T256x256:
+            if constexpr (Elem<E>::MODE == 0) return launch_qkv_cfg<Cfg256x256, E>(al, w, M, D, eqk, ev, s, ks);
+            break;
+        case T128x128q: return launch_qkv_cfg<Cfg128x128q, E>(al, w, M, D, eqk, ev, s, ks);
+        case T64x128: return launch_qkv_cfg<Cfg64x128, E>(al, w, M, D, eqk, ev, s, ks);
+        case T64x64: return launch_qkv_cfg<Cfg64x64, E>(al, w, M, D, eqk, ev, s, ks);
+        default: break;
+    }
+    return hipErrorInvalidValue;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1274,9 +1195,11 @@ hipError_t launch_patch_e(const PatchArgs &pa, const E *w, const float *bias, co
     PatchLoader<E> al{pa.image, pa.sb, pa.sc, pa.sy, pa.origins, P, pa.wp, pa.p, pa.p * pa.p};
     EpiPatch epi{bias, pos, x, M, P, P + 1, dim, pa.mask, pa.mask_tok, so};
     // one tile per call (a dozen workgroups): eight wavefronts per tile, two per SIMD (see Cfg64x128w)
+    if (K % Elem<E>::KROW) return hipErrorInvalidValue;
+    const int ks = gemm_ct_steps<KsLinearReg>(K / Elem<E>::KROW);
     if constexpr (Elem<E>::MODE == 2)
-        if (dim % 128 == 0 && M > 64 && M <= 1024) return launch_gemm<Cfg64x128w, E, false>(al, w, K, M, dim, K, epi, s);
-    if (dim % 128 == 0 && M > 64) return launch_gemm<Cfg64x128, E, false>(al, w, K, M, dim, K, epi, s);
-    return launch_gemm<Cfg64x64, E, false>(al, w, K, M, dim, K, epi, s);
+        if (dim % 128 == 0 && M > 64 && M <= 1024) return launch_gemm<Cfg64x128w, E, false>(al, w, K, M, dim, K, epi, s, ks);
+    if (dim % 128 == 0 && M > 64) return launch_gemm<Cfg64x128, E, false>(al, w, K, M, dim, K, epi, s, ks);
+    return launch_gemm<Cfg64x64, E, false>(al, w, K, M, dim, K, epi, s, ks);
 }
 

@@ -217,31 +217,22 @@ struct EpiUpconv {
     }
 };
 
-// K steps known at compile time get gemm_mainloop's two-step prefetch: the 3x3 layers of the U-Net in fp32 / split pairs
-// (C = 64, 128, 256: 18, 36, 72 steps of 32) and their bf16 forms; any other depth runs the one-step pipeline.
-template <class Cfg, class E, class AL, class Epi>
-static hipError_t conv_gemm_cfg(const AL &al, const E *w, int Kreal, int M, int N, const Epi &epi, hipStream_t s) {
-    constexpr int KROW = Elem<E>::KROW;
-    const int steps = (Kreal + KROW - 1) / KROW, Kp = steps * KROW;  // the loaders pad the last step with zeros
-    if constexpr (std::is_same<AL, Conv3x3Loader<E>>::value) {
-        switch (steps) {
-            case 18: return launch_gemm_ks<Cfg, E, false, 18>(al, w, Kreal, M, N, Kp, epi, s);
-            case 36: return launch_gemm_ks<Cfg, E, false, 36>(al, w, Kreal, M, N, Kp, epi, s);
-            case 72: return launch_gemm_ks<Cfg, E, false, 72>(al, w, Kreal, M, N, Kp, epi, s);
-            default: break;
-        }
-    }
-    return launch_gemm_ks<Cfg, E, false, 0>(al, w, Kreal, M, N, Kp, epi, s);
-}
-
-// Tile choice by rows and output width, as the register-staged tail of launch_linear_epi: 128 x 128 once that fills two
-// workgroups per CU (>= 512 tiles), 64 x 128 for 128-multiples with more than one row tile, else 64 x 64.
+// The conv / up-conv GEMMs on the tile and depth gemm_plan_conv chooses (gemm_plan.h): tiles by rows and output width as the
+// register-staged tail of nn.Linear; the 3x3 loader's depths of the U-Net (KsConv3x3) get gemm_mainloop's two-step prefetch, any
+// other depth and every other loader the one-step pipeline. The loaders pad the last K step with zeros.
 template <class E, class AL, class Epi>
 static hipError_t conv_gemm(const AL &al, const E *w, int Kreal, int M, int N, const Epi &epi, hipStream_t s) {
-    const long t128 = (long)((M + 127) / 128) * (N / 128);
-    if (N % 128 == 0 && t128 >= 512) return conv_gemm_cfg<Cfg128x128, E>(al, w, Kreal, M, N, epi, s);
-    if (N % 128 == 0 && M > 64) return conv_gemm_cfg<Cfg64x128, E>(al, w, Kreal, M, N, epi, s);
-    return conv_gemm_cfg<Cfg64x64, E>(al, w, Kreal, M, N, epi, s);
+    constexpr bool IS3X3 = std::is_same<AL, Conv3x3Loader<E>>::value;
+    typedef std::conditional_t<IS3X3, KsConv3x3, KsNone> List;
+    constexpr int KROW = Elem<E>::KROW;
+    const int Kp = (Kreal + KROW - 1) / KROW * KROW;
+    const GemmPlan p = gemm_plan_conv(Elem<E>::MODE, M, N, Kreal, IS3X3);
+    switch (p.tile) {
+        case T128x128: return launch_gemm<Cfg128x128, E, false, List>(al, w, Kreal, M, N, Kp, epi, s, p.ksteps);
+        case T64x128: return launch_gemm<Cfg64x128, E, false, List>(al, w, Kreal, M, N, Kp, epi, s, p.ksteps);
+        case T64x64: return launch_gemm<Cfg64x64, E, false, List>(al, w, Kreal, M, N, Kp, epi, s, p.ksteps);
+        default: return hipErrorInvalidValue;
+    }
 }
 
 template <class E>

@@ -2,6 +2,7 @@
 // gemm_kernels.h, whose instantiations are compiled in kernels_gemm_inst.hip. Holds the process-wide bits: the
 // write-through store mask and, in development builds only, the kernel-variant knobs.
 #include "launch.h"
+#include "host_common.h"
 #include "dev_knobs.h"
 
 // entry templates of gemm_kernels.h (defined and explicitly instantiated in kernels_gemm_inst.hip)
@@ -82,3 +83,45 @@ hipError_t launch_patch_embed(int prec, const PatchArgs &pa, const void *w, cons
     return launch_patch_e<bf16>(pa, (const bf16 *)w, bias, pos, x, dim, s, so);
 }
 
+// ocm_gemm_plan (include/ocm_vit.h): the plan functions of gemm_plan.h behind the operators' own argument checks, knobs at 0
+extern "C" int ocm_gemm_plan(int32_t family, int32_t precision, int32_t epilogue, int32_t M, int32_t N, int32_t K,
+                             uint32_t flags, ocm_gemm_plan_info *plan) {
+    if (!plan) return ocm_fail(OCM_EINVAL, "null argument");
+    if (precision != OCM_PREC_BF16 && precision != OCM_PREC_FP32 && precision != OCM_PREC_BF16X3)
+        return ocm_fail(OCM_EINVAL, "bad precision %d", precision);
+    const int kq = gemm_krow(precision);
+    if (M <= 0 || N <= 0 || N % 32 || K <= 0) return ocm_fail(OCM_EINVAL, "bad shape M=%d N=%d K=%d (N%%32)", M, N, K);
+    if (family != OCM_GEMM_CONV && K % kq) return ocm_fail(OCM_EINVAL, "bad shape K=%d (K%%%d)", K, kq);
+    GemmPlan p;
+    switch (family) {
+        case OCM_GEMM_LINEAR:
+            if (epilogue < 0 || epilogue > 4) return ocm_fail(OCM_EINVAL, "bad epilogue %d", epilogue);
+            if ((flags & OCM_PLAN_STATS_EPILOGUE) && epilogue != OCM_EPI_BIAS_RESID_F32)
+                return ocm_fail(OCM_EINVAL, "the statistics epilogue is the residual one (epilogue %d)", epilogue);
+            p = gemm_plan_linear(precision, epilogue, M, N, K, (flags & OCM_PLAN_STATS_EPILOGUE) != 0,
+                                 (flags & OCM_PLAN_SPLITK_OFFERED) != 0, 0);
+            break;
+        case OCM_GEMM_QKV:
+            if (K % 64 || N != 3 * K) return ocm_fail(OCM_EINVAL, "qkv projection: N=%d K=%d (N = 3 K, K %% 64)", N, K);
+            p = gemm_plan_qkv(precision, M, K, 0);
+            break;
+        case OCM_GEMM_LINEAR_LD:
+            if (precision == OCM_PREC_BF16X3) return ocm_fail(OCM_EINVAL, "the strided launcher serves bf16 and fp32");
+            p = gemm_plan_linear_ld(precision, M, N, K);
+            break;
+        case OCM_GEMM_CONV:
+            if ((flags & OCM_PLAN_CONV3X3) && (K % 9 || K / 9 % 32 || K / 9 > 4096))
+                return ocm_fail(OCM_EINVAL, "3x3 convolution: K=%d (K = 9 C, C %% 32, C <= 4096)", K);
+            p = gemm_plan_conv(precision, M, N, K, (flags & OCM_PLAN_CONV3X3) != 0);
+            break;
+        case OCM_GEMM_RESID_LN:
+            if (!linear_resid_ln_supported(N)) return ocm_fail(OCM_EINVAL, "row width %d not in {128, 256, 384}", N);
+            if (K % 64) return ocm_fail(OCM_EINVAL, "bad shape K=%d (K%%64)", K);
+            p = gemm_plan_resid_ln(precision, N, K, 0);
+            break;
+        default: return ocm_fail(OCM_EINVAL, "bad family %d", family);
+    }
+    const GemmTileInfo &t = GEMM_TILES[p.tile];
+    *plan = ocm_gemm_plan_info{t.bm, t.bn, t.waves_m * t.waves_n, t.mf16, (int32_t)p.loop, p.stages, p.ksteps, p.splitk};
+    return OCM_OK;
+}

@@ -3,6 +3,7 @@
 #pragma once
 #include <atomic>
 #include "common.h"
+#include "gemm_plan.h"
 
 // hipFuncAttributeMaxDynamicSharedMemorySize is a per-device property of a kernel. Each launch site keeps one OptinMask per
 // kernel it launches (a function-local static: bit d set = done on device d) and calls lds_optin before every launch. The
@@ -69,7 +70,7 @@ struct StatsOut {
     // kernel adds them in slice order with bias and residual (and produces xs / stats). Null: never split.
     float *part = nullptr;
 };
-constexpr int OCM_SPLITK = 4, OCM_SPLITK_MAX_ROWS = 512;  // at 2305 rows (one ViT-S/8 window) the split form measures the same as the plain kernel
+// (OCM_SPLITK, OCM_SPLITK_MAX_ROWS: gemm_plan.h)
 // x = resid + bias + sum over slices of part[slice] (fixed order); optionally split pairs and row sums of x
 hipError_t launch_splitk_finish(const float *part, int slices, const float *bias, const float *resid, float *x, void *xs,
                                 float *stats, int M, int N, hipStream_t s, const StatsOut &so = StatsOut());

@@ -236,7 +236,7 @@ class SlidingWindowAttention:
         """Balanced batches (sizes differ by at most one, none above `max_batch`) whose count is chosen for the kernels
         rather than fixed. A forward is charged the rows its two MLP GEMMs (equal FLOPs, together the largest share of a
         forward) really occupy the chip for, priced by the tiles the engine dispatches in split-bf16 precision
-        (csrc/gemm_kernels.h, launch_linear_epi):
+        (csrc/gemm_plan.h, gemm_plan_linear):
           mlp.fc1 (N = 4 dim): 128 x 128 tiles, two workgroups per CU -> whole rounds of ceil(rows / 128) * (4 dim / 128)
                                tiles over 2 * CUs slots;
           mlp.fc2 (N = dim):   128 x 192 tiles, one workgroup per CU, when dim is one or two such tiles wide and either the

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define OCM_ABI_VERSION 17
+#define OCM_ABI_VERSION 18
 
 enum {
     OCM_OK = 0,
@@ -489,6 +489,39 @@ int ocm_op_bn_relu_backward(const float *dz, const float *y, const float *mean, 
  * bit exact). */
 int ocm_op_pixel_shuffle_backward(const float *grad_out, float *grad_lin, int32_t batch, int32_t hp, int32_t wp,
                                   int32_t c_out, int32_t s, void *stream);
+
+/* ---- training of build_unet (model.py:227-320; PGT.py's and unet.py's step; kernels_conv_train.hip) ----
+ * The forward runs every convolution without its ReLU (ocm_op_conv3x3 with relu = 0, or ocm_op_im2col3x3 + ocm_op_linear),
+ * ocm_op_batch_stats and ocm_op_bn_relu; the backward runs ocm_op_bn_relu_backward, ocm_op_weight_grad on an im2col operand,
+ * the data gradient as ocm_op_conv3x3 with the flipped kernel, and the operators below. Token-major fp32 rows with leading
+ * dimensions as for inference; one lane per four channels, 64-bit element indices, every output element written exactly once,
+ * no atomics. Activation pointers are 16-byte aligned, leading dimensions multiples of 4. */
+
+/* z[m][c] = max(y[m][c] * scale[c] + shift[c], 0): y dense [rows][channels], z rows ld_z floats apart. The pre-activation is the
+ * expression whose sign ocm_op_bn_relu_backward tests: an element passes that gate exactly when z > 0. channels % 4 == 0. */
+int ocm_op_bn_relu(const float *y, const float *scale, const float *shift, float *z, int64_t ld_z, int64_t rows, int32_t channels,
+                   void *stream);
+/* Backward of ocm_op_maxpool2x2 over z (the forward's input, (batch, h, w) rows): per window the scan of the forward is replayed
+ * (a later value wins when it is greater or NaN) and the position it ends on gets dpool[(b, y/2, x/2)], the other three get 0;
+ * when add is not NULL every position adds add[(b, y, x)] (the gradient a skip connection carries to the same tensor). */
+int ocm_op_maxpool2x2_backward(const float *z, int64_t ld_z, const float *dpool, int64_t ld_dp, const float *add, int64_t ld_add,
+                               float *dz, int64_t ld_dz, int32_t batch, int32_t h, int32_t w, int32_t channels, void *stream);
+/* The output gradient of ocm_op_upconv2x2 as the rows of its GEMM: g[(b, y, x)][(i*2 + j)*O + o] = dout[(b, 2y+i, 2x+j)][o], a
+ * bit-exact copy; h, w are the INPUT grid, g is dense (batch*h*w, 4 O). Then dIn = ocm_op_linear(g, W^T), dW = ocm_op_weight_grad(g,
+ * in) and dbias = its db summed over the four groups. O % 4 == 0. */
+int ocm_op_upconv2x2_gather(const float *dout, int64_t ld, float *g, int32_t batch, int32_t h, int32_t w, int32_t out_channels,
+                            void *stream);
+/* The fp32 rows ocm_op_conv3x3_image gathers: out[(b, y, x)][(ky*3 + kx)*3 + c] = image[b*stride_b + c*stride_c + (y+ky-1)*stride_y +
+ * x+kx-1], zeros outside the image and in columns 27..31; out dense (batch*h*w, 32): the x of the first layer's weight gradient. */
+int ocm_op_im2col3x3_image(const float *image, int64_t stride_b, int64_t stride_c, int64_t stride_y, float *out, int32_t batch,
+                           int32_t h, int32_t w, void *stream);
+/* Backward of ocm_op_conv1x1_planes: dlogits (B, 1, hw) contiguous; din[m][c] = dlogits[m] * w[c]; when dw is not NULL
+ * dw[c] = sum_m dlogits[m] * in[m][c]; when db is not NULL db[0] = sum_m dlogits[m]. The sums run in a fixed order through the
+ * workspace. C % 4 == 0, C <= 1024. */
+size_t ocm_conv1x1_planes_backward_workspace_bytes(int64_t rows, int32_t channels);
+int ocm_op_conv1x1_planes_backward(const float *dlogits, const float *in, int64_t ld_in, const float *w, float *din, int64_t ld_din,
+                                   float *dw, float *db, int32_t batch, int64_t hw, int32_t channels, void *workspace,
+                                   size_t workspace_bytes, void *stream);
 
 /* ---- training of the ViT encoder (SimMIM pre-training, model.py:55-83; kernels_train.hip, kernels_train_attn.hip) ----
  * The forward runs the stand-alone operators above and keeps, per block, the LayerNorm inputs, qkv_f32, lse2, the context and the

@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # OCM_VIT_LIB lets kernel experiments A/B two builds of the same ABI; the default is the in-tree build.
 LIB_PATH = os.environ.get("OCM_VIT_LIB") or os.path.join(_HERE, "libocm_vit.so")
 
-OCM_ABI_VERSION = 17
+OCM_ABI_VERSION = 18
 OCM_OK, OCM_EINVAL, OCM_ESTATE, OCM_EHIP, OCM_ENOMEM, OCM_ENAME = 0, 1, 2, 3, 4, 5
 
 OCM_PREC_BF16 = 0
@@ -207,6 +207,12 @@ SIGNATURES = {
     "ocm_op_bn_relu_im2col3x3": (C.c_int, [_i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "ocm_op_bn_relu_backward": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _sz, _vp]),
     "ocm_op_pixel_shuffle_backward": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "ocm_op_bn_relu": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp]),
+    "ocm_op_maxpool2x2_backward": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _vp]),
+    "ocm_op_upconv2x2_gather": (C.c_int, [_vp, _i64, _vp, _i32, _i32, _i32, _i32, _vp]),
+    "ocm_op_im2col3x3_image": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _i32, _i32, _i32, _vp]),
+    "ocm_conv1x1_planes_backward_workspace_bytes": (_sz, [_i64, _i32]),
+    "ocm_op_conv1x1_planes_backward": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i32, _i64, _i32, _vp, _sz, _vp]),
     "ocm_op_attention_backward": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _vp]),
     "ocm_op_attention_backward_delta": (C.c_int, [_i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "ocm_layernorm_backward_workspace_bytes": (_sz, [_i64, _i32]),

@@ -52,6 +52,11 @@ __device__ __forceinline__ bf16x8 cvt8(f32x4 lo, f32x4 hi) {
     return r;
 }
 
+// Pre-activation of a BatchNorm affine in front of a ReLU: z = max(bn_pre, 0) in the forward (ocm_op_bn_relu), the gate
+// [bn_pre > 0] in the backward (ocm_op_bn_relu_backward). One expression for both, so that an element passes the gate exactly
+// when the forward stored a positive value.
+__device__ __forceinline__ float bn_pre(float y, float scale, float shift) { return fmaf(y, scale, shift); }
+
 // ---- split-bf16 pairs (OCM_PREC_BF16X3) -------------------------------------------------------------
 // A value x is carried as two bf16 numbers hi = bf16(x), lo = bf16(x - hi): x = hi + lo up to 2^-17 |x|, and a
 // product is evaluated as hi*hi' + hi*lo' + lo*hi' on the bf16 MFMA (three instructions, fp32 accumulate; the

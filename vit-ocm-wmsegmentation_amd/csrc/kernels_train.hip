@@ -235,7 +235,7 @@ __global__ __launch_bounds__(256) void chan_reduce_kernel(const float *__restric
                 s1 = fmaf(v, xh, s1);
             } else {
                 const float yv = y[m * C + c];
-                const float u = fmaf(yv, g, hh) > 0.f ? v : 0.f;
+                const float u = bn_pre(yv, g, hh) > 0.f ? v : 0.f;
                 s0 += u;
                 s1 = fmaf(u, (yv - mu) * is, s1);
             }
@@ -291,7 +291,7 @@ __global__ __launch_bounds__(256) void bn_relu_bwd_kernel(const float *__restric
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             const float g = scale[c + e];
-            const float u = fmaf(yv[e], g, shift[c + e]) > 0.f ? d[e] : 0.f;
+            const float u = bn_pre(yv[e], g, shift[c + e]) > 0.f ? d[e] : 0.f;
             const float xh = (yv[e] - mean[c + e]) * invstd[c + e];
             o[e] = g * (u - dbeta[c + e] * inv_rows - xh * (dgamma[c + e] * inv_rows));
         }

@@ -5,7 +5,8 @@
   VisionTransformerForFinetune  model.py:110-139  trunk -> (B,C,H,W)
   LinearProbing                 model.py:142-174  encoder + one-layer (1x1 conv + PixelShuffle) decoder
   build_model / build_finetune_model / get_state_dict   model.py:85-108,176-226
-  build_unet (convolution_block, encoder_block, decoder_block)   model.py:227-320  U-Net inference on the direct 3x3 convolution
+  build_unet (convolution_block, encoder_block, decoder_block)   model.py:227-320  U-Net inference on the direct 3x3 convolution;
+                                                                 training (opt-in, enable_training) through _UNetTrain
 
 Same constructor arguments, attributes and state_dict keys. The encoders run in one engine call (the mask
 blend is fused into the patch-embedding epilogue, the (B,C,H,W) permute is a device transpose); the 1x1-conv
@@ -21,6 +22,7 @@ without a mask: finetune.py --finetune True. Every cached operand copy of a deco
 from (_cached_operand); biases are read on every call. The reference initialises mask_token with timm's trunc_normal_; here
 the package's own trunc_normal_ (dino/utils.py) with the same bounds is used.
 """
+import contextlib
 import ctypes as C
 import os
 from functools import partial
@@ -863,11 +865,274 @@ def _unet_empty(shape, device):
     return torch.empty(shape, dtype=torch.float32, device=device)
 
 
+def _rows_up2x2_t(w):
+    """(C, O, 2, 2) ConvTranspose2d kernel -> (C, 4*O): the up-convolution's data gradient dIn = g W runs as ocm_op_linear(g, W^T)
+    on the rows g of ocm_op_upconv2x2_gather."""
+    return _rows_up2x2(w).t()
+
+
+def _rows3x3_image(w, kstep):
+    """(O, 3, 3, 3) kernel of the first layer -> (O, kstep): ocm_op_conv3x3_image's 27 columns and zeros up to one K step."""
+    rows = _rows3x3(w)
+    return nn.functional.pad(rows, (0, kstep - rows.shape[1]))
+
+
+_UNET_WIDTHS = (64, 128, 256, 512)
+_IM2COL_CAP = 1 << 30  # bytes of the fp32 im2col operand one weight-gradient launch of the U-Net reads
+
+
+def _im2col_chunks(batch, rows_per_image, k, cap=_IM2COL_CAP):
+    """[(first image, images)] of the weight gradient of a 3x3 layer: its fp32 im2col operand (rows_per_image x k per image) is
+    built for whole images at a time, as many as fit under `cap` bytes and at least one. A function of the shapes alone: the
+    per-chunk gradients are added in this order, so the sum has the same bits on every run."""
+    per = max(1, cap // (rows_per_image * k * 4))
+    return [(b0, min(per, batch - b0)) for b0 in range(0, batch, per)]
+
+
+@contextlib.contextmanager
+def _phase(net, name):
+    """Device time of a part of _UNetTrain.backward for tools/bench_unet_train.py: when the module carries a `_phase_log` list,
+    (name, start event, end event) is appended to it; otherwise nothing happens."""
+    log = net.__dict__.get("_phase_log")
+    if log is None:
+        yield
+        return
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    yield
+    b.record()
+    log.append((name, a, b))
+
+
+def _unet_conv(net, prec, src, grid, C, w_op, bias, dst, O):
+    """dst (M, O) = the 3x3 pad-1 convolution of the dense rows src (M, C) with the (O, 9 C) operand + bias, no ReLU: the direct
+    kernel, or im2col + ocm_op_linear for the layer classes of _unet_composed. Serves the training forward and, with the flipped
+    kernel and a zero bias, the data gradients."""
+    lib, st, (B, h, w) = _lib.load(), _stream(), grid
+    M = B * h * w
+    if _unet_composed(prec, O):
+        cols = net._alloc((M, 9 * C * _OPERAND_DTYPE[prec].itemsize // 4), src.device)  # operand rows, in fp32-sized words
+        _lib.check(lib.ocm_op_im2col3x3(prec, _p(src), _p(cols), B, h, w, C, 0, st))
+        _lib.check(lib.ocm_op_linear(prec, _p(cols), _p(w_op), _p(bias), None, _p(dst), M, O, 9 * C, _lib.OCM_EPI_BIAS_F32, st))
+    else:
+        _lib.check(lib.ocm_op_conv3x3(prec, _p(src), C, _p(w_op), _p(bias), _p(dst), O, B, h, w, C, O, 0, st))
+
+
+def _unet_train_pass(net, x):
+    """build_unet in training mode, forward: per convolution y = conv(z_prev) + bias (no ReLU), the batch statistics of y and
+    z = max(y * scale + shift, 0) written where inference writes it. Returns (logits, everything the backward reads by name,
+    [(BatchNorm2d, batch mean, biased batch variance, values per channel)] in forward order)."""
+    lib, dev, prec = _lib.load(), x.device, _lib.PRECISIONS[net._precision]
+    B, _, H, W = x.shape
+    alloc, st, cache = net._alloc, _stream(), net._op_cache
+    f32 = dict(device=dev, dtype=torch.float32)
+    S, stats = {"x": x}, []
+
+    def layer(name, blk, which, src, grid, C, dst, ld_out):
+        cv, bn = (blk.conv1, blk.bn1) if which == 1 else (blk.conv2, blk.bn2)
+        O, M, key = cv.out_channels, B * grid[0] * grid[1], f"{name}.conv{which}"
+        y, bias = alloc((M, O), dev), _vec(cv.bias, O, dev)
+        if src is None:  # the first layer reads the image planes in place
+            kstep = 64 if prec == _lib.OCM_PREC_BF16 else 32
+            wi = _cached_operand(cache, key + ".image", cv.weight, prec, lambda: to_operand(
+                _rows3x3_image(cv.weight.detach().to(**f32), kstep).contiguous(), prec))
+            _lib.check(lib.ocm_op_conv3x3_image(prec, _p(x), x.stride(0), x.stride(1), x.stride(2), _p(wi), _p(bias), _p(y), O,
+                                                B, grid[0], grid[1], O, 0, st))
+        else:
+            _unet_conv(net, prec, src, (B, *grid), C, _weight_operand(cache, key, cv.weight, prec, dev, _rows3x3), bias, y, O)
+        mean, var = torch.empty(O, **f32), torch.empty(O, **f32)
+        nbytes = lib.ocm_channel_reduce_workspace_bytes(M, O)
+        ws = _ws(nbytes, dev)
+        _lib.check(lib.ocm_op_batch_stats(_p(y), _p(mean), _p(var), M, O, _p(ws), nbytes, st))
+        invstd = torch.rsqrt(var + bn.eps)
+        g = (bn.weight.detach().to(**f32) * invstd).contiguous()
+        h = (_vec(bn.bias, O, dev) - mean * g).contiguous()
+        _lib.check(lib.ocm_op_bn_relu(_p(y), _p(g), _p(h), dst, ld_out, M, O, st))
+        stats.append((bn, mean, var, M))
+        for k, v in (("y", y), ("mean", mean), ("invstd", invstd), ("g", g), ("h", h)):
+            S[f"{key}.{k}"] = v
+
+    encs, decs = (net.e1, net.e2, net.e3, net.e4), (net.d4, net.d3, net.d2, net.d1)
+    h, w, cur, Cin = H, W, None, 3
+    for lvl, (enc, O) in enumerate(zip(encs, _UNET_WIDTHS)):
+        name, M = f"e{lvl + 1}", B * h * w
+        t, cat, pooled = alloc((M, O), dev), alloc((M, 2 * O), dev), alloc((M // 4, O), dev)
+        layer(name + ".conv", enc.conv, 1, cur, (h, w), Cin, _p(t), O)
+        skip_ptr = cat.data_ptr() + 4 * O
+        layer(name + ".conv", enc.conv, 2, t, (h, w), O, skip_ptr, 2 * O)
+        _lib.check(lib.ocm_op_maxpool2x2(skip_ptr, 2 * O, _p(pooled), O, B, h, w, O, st))
+        S[name + ".t"], S[name + ".cat"], S[name + ".pool"] = t, cat, pooled
+        cur, Cin, h, w = pooled, O, h // 2, w // 2
+    t, z = alloc((B * h * w, 1024), dev), alloc((B * h * w, 1024), dev)
+    layer("b", net.b, 1, cur, (h, w), 512, _p(t), 1024)
+    layer("b", net.b, 2, t, (h, w), 1024, _p(z), 1024)
+    S["b.t"], S["b.z"] = t, z
+    cur, Cin = z, 1024
+    for lvl in (3, 2, 1, 0):
+        dec, O, name = decs[lvl], _UNET_WIDTHS[lvl], f"d{4 - lvl}"
+        cat = S[f"e{lvl + 1}.cat"]
+        wu = _weight_operand(cache, name + ".up", dec.up.weight, prec, dev, _rows_up2x2)
+        bu = _cached_operand(cache, name + ".up.bias", dec.up.bias, prec, lambda: _vec(dec.up.bias, O, dev))
+        _lib.check(lib.ocm_op_upconv2x2(prec, _p(cur), Cin, _p(wu), _p(bu), _p(cat), 2 * O, B, h, w, Cin, O, st))
+        h, w = 2 * h, 2 * w
+        t, z = alloc((B * h * w, O), dev), alloc((B * h * w, O), dev)
+        layer(name + ".conv", dec.conv, 1, cat, (h, w), 2 * O, _p(t), O)
+        layer(name + ".conv", dec.conv, 2, t, (h, w), O, _p(z), O)
+        S[name + ".t"], S[name + ".z"] = t, z
+        cur, Cin = z, O
+    out = torch.empty((B, 1, H, W), **f32)
+    head = net.outputs
+    wo = _cached_operand(cache, "outputs.weight", head.weight, prec,
+                         lambda: head.weight.detach().to(**f32).reshape(-1).contiguous())
+    bo = _cached_operand(cache, "outputs.bias", head.bias, prec, lambda: _vec(head.bias, 1, dev))
+    _lib.check(lib.ocm_op_conv1x1_planes(_p(cur), 64, _p(wo), _p(bo), _p(out), B, H * W, 64, st))
+    return out, S, stats
+
+
+class _UNetTrain(torch.autograd.Function):
+    """One training-mode call of build_unet: forward(meta, x, *params) -> (B, 1, H, W) logits (_unet_train_pass); backward -> the
+    parameter gradients, none for the image. It keeps y (pre-BatchNorm) and z (post-ReLU) of all 18 layers, the pooled maps and
+    the per-channel statistics: 5.3 GB at 384^2, batch 8 (counted and measured: DESIGN.md 3.24). Weight
+    gradients run ocm_op_weight_grad on an fp32 im2col operand built under _IM2COL_CAP (_im2col_chunks), data gradients as the
+    3x3 convolution with the flipped kernel; a frozen parameter's weight-gradient launches are skipped. `meta` carries the module
+    and, for the caller, the batch statistics (the running statistics are updated outside the graph)."""
+
+    @staticmethod
+    def forward(ctx, meta, x, *params):
+        out, S, meta["stats"] = _unet_train_pass(meta["net"], x)
+        ctx.meta, ctx.keys = meta, list(S)
+        ctx.save_for_backward(*S.values(), *params)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        meta, keys = ctx.meta, ctx.keys
+        net, names = meta["net"], meta["names"]
+        st_ = ctx.saved_tensors
+        S, P = dict(zip(keys, st_[:len(keys)])), dict(zip(names, st_[len(keys):]))
+        need = dict(zip(names, ctx.needs_input_grad[2:]))
+        lib, dev, prec = _lib.load(), gout.device, _lib.PRECISIONS[net._precision]
+        alloc, cache = net._alloc, net._op_cache
+        f32 = dict(device=dev, dtype=torch.float32)
+        x = S["x"]
+        B, _, H, W = x.shape
+        grads = {}
+
+        def conv_backward(key, dz, src, grid, C, want_dx):
+            """Through ReLU, BatchNorm and the convolution `key` whose input was src (M, C) (None: the image): fills the gradients
+            of the layer's parameters; returns the gradient of src when want_dx."""
+            y, mean, invstd, g, h = (S[f"{key}.{k}"] for k in ("y", "mean", "invstd", "g", "h"))
+            (M, O), st = y.shape, _stream()
+            bnkey, (hh, ww) = key[:-5] + "bn" + key[-1], grid  # "e1.conv.conv2" -> "e1.conv.bn2"
+            dy, dgam, dbet = alloc((M, O), dev), torch.empty(O, **f32), torch.empty(O, **f32)
+            nbytes = lib.ocm_channel_reduce_workspace_bytes(M, O)
+            ws = _ws(nbytes, dev)
+            _lib.check(lib.ocm_op_bn_relu_backward(_p(dz), _p(y), _p(mean), _p(invstd), _p(g), _p(h), _p(dy), _p(dgam), _p(dbet),
+                                                   M, O, _p(ws), nbytes, st))
+            if need[bnkey + ".weight"]:
+                grads[bnkey + ".weight"] = dgam
+            if need[bnkey + ".bias"]:
+                grads[bnkey + ".bias"] = dbet
+            nw, nb = need[key + ".weight"], need[key + ".bias"]
+            if nw or nb:
+                K, rpi = (32 if src is None else 9 * C), hh * ww
+                dw = db = None
+                for b0, n in _im2col_chunks(B, rpi, K):
+                    with _phase(net, "weight"):
+                        cols = alloc((n * rpi, K), dev)
+                        if src is None:
+                            _lib.check(lib.ocm_op_im2col3x3_image(_p(x[b0:]), x.stride(0), x.stride(1), x.stride(2), _p(cols), n, hh,
+                                                                  ww, st))
+                        else:
+                            _lib.check(lib.ocm_op_im2col3x3(_lib.OCM_PREC_FP32, _p(src[b0 * rpi:]), _p(cols), n, hh, ww, C, 0, st))
+                        dwi, dbi = _weight_grad(prec, dy[b0 * rpi:(b0 + n) * rpi], cols, nb)
+                        del cols
+                        dw = dwi if dw is None else dw.add_(dwi)
+                        if nb:
+                            db = dbi if db is None else db.add_(dbi)
+                if nw:
+                    grads[key + ".weight"] = dw[:, :9 * C].reshape(O, 3, 3, C).permute(0, 3, 1, 2)
+                if nb:
+                    grads[key + ".bias"] = db
+            if not want_dx:
+                return None
+            dx = alloc((M, C), dev)
+            with _phase(net, "data"):
+                _unet_conv(net, prec, dy, (B, hh, ww), O, _weight_operand(cache, key, P[key + ".weight"], prec, dev, flip_conv3x3),
+                           _zeros(cache, C, dev), dx, C)
+            return dx
+
+        with torch.cuda.device(dev):
+            st = _stream()
+            # the classifier
+            dl = gout.detach().to(torch.float32).contiguous()
+            M = B * H * W
+            dcur = alloc((M, 64), dev)
+            nw, nb = need["outputs.weight"], need["outputs.bias"]
+            dwo, dbo = (torch.empty(64, **f32) if nw else None), (torch.empty(1, **f32) if nb else None)
+            wo = _cached_operand(cache, "outputs.weight", P["outputs.weight"], prec,
+                                 lambda: P["outputs.weight"].detach().to(**f32).reshape(-1).contiguous())
+            nbytes = lib.ocm_conv1x1_planes_backward_workspace_bytes(M, 64)
+            ws = _ws(nbytes, dev)
+            _lib.check(lib.ocm_op_conv1x1_planes_backward(_p(dl), _p(S["d4.z"]), 64, _p(wo), _p(dcur), 64, _p(dwo), _p(dbo), B,
+                                                          H * W, 64, _p(ws), nbytes, st))
+            if nw:
+                grads["outputs.weight"] = dwo
+            if nb:
+                grads["outputs.bias"] = dbo
+            # the decoder, d4 .. d1: conv2, conv1 over [up | skip], the up-convolution
+            dcats = {}
+            for lvl in (0, 1, 2, 3):
+                name, O, hh, ww = f"d{4 - lvl}", _UNET_WIDTHS[lvl], H >> lvl, W >> lvl
+                dz1 = conv_backward(name + ".conv.conv2", dcur, S[name + ".t"], (hh, ww), O, True)
+                dcat = dcats[lvl] = conv_backward(name + ".conv.conv1", dz1, S[f"e{lvl + 1}.cat"], (hh, ww), 2 * O, True)
+                del dz1
+                hs, wsm, Cin = hh // 2, ww // 2, 2 * O
+                Ms = B * hs * wsm
+                g = alloc((Ms, 4 * O), dev)
+                _lib.check(lib.ocm_op_upconv2x2_gather(_p(dcat), 2 * O, _p(g), B, hs, wsm, O, st))
+                up_w = P[name + ".up.weight"]
+                if need[name + ".up.weight"] or need[name + ".up.bias"]:
+                    with _phase(net, "weight"):
+                        dw, db = _weight_grad(prec, g, S["b.z" if lvl == 3 else f"d{3 - lvl}.z"], need[name + ".up.bias"])
+                    if need[name + ".up.weight"]:
+                        grads[name + ".up.weight"] = dw.reshape(2, 2, O, Cin).permute(3, 2, 0, 1)
+                    if need[name + ".up.bias"]:
+                        grads[name + ".up.bias"] = db.reshape(4, O).sum(0)
+                dcur = alloc((Ms, Cin), dev)
+                wt = _weight_operand(cache, name + ".up", up_w, prec, dev, _rows_up2x2_t)
+                with _phase(net, "data"):
+                    _lib.check(lib.ocm_op_linear(prec, _p(to_operand(g, prec)), _p(wt), _p(_zeros(cache, Cin, dev)), None, _p(dcur),
+                                                 Ms, Cin, 4 * O, _lib.OCM_EPI_BIAS_F32, st))
+                del g
+            # the bottleneck
+            hb, wb = H >> 4, W >> 4
+            dz1 = conv_backward("b.conv2", dcur, S["b.t"], (hb, wb), 1024, True)
+            dcur = conv_backward("b.conv1", dz1, S["e4.pool"], (hb, wb), 512, True)
+            # the encoder, e4 .. e1: the pool's backward adds the skip's gradient, the right half of the level's dcat, in place
+            for lvl in (3, 2, 1, 0):
+                name, O, hh, ww = f"e{lvl + 1}", _UNET_WIDTHS[lvl], H >> lvl, W >> lvl
+                cat, dcat = S[name + ".cat"], dcats.pop(lvl)
+                dz = alloc((B * hh * ww, O), dev)
+                _lib.check(lib.ocm_op_maxpool2x2_backward(cat.data_ptr() + 4 * O, 2 * O, _p(dcur), O, dcat.data_ptr() + 4 * O, 2 * O,
+                                                          _p(dz), O, B, hh, ww, O, st))
+                del dcat
+                dz1 = conv_backward(name + ".conv.conv2", dz, S[name + ".t"], (hh, ww), O, True)
+                del dz
+                if lvl:
+                    dcur = conv_backward(name + ".conv.conv1", dz1, S[f"e{lvl}.pool"], (hh, ww), _UNET_WIDTHS[lvl - 1], True)
+                else:  # no image gradient
+                    conv_backward(name + ".conv.conv1", dz1, None, (hh, ww), 3, False)
+        return (None, None, *[_put(grads.get(n), P[n]) if need[n] else None for n in names])
+
+
 class build_unet(nn.Module):
     """model.py:280-320: the U-Net PGT.py trains on pseudo ground truth and unet.py trains supervised. Inference runs on the
     HIP path: every BatchNorm is folded, from its running statistics, into the convolution in front of it; ReLU sits in the
     convolution's epilogue (the deepest layers run as im2col + GEMM, _unet_composed); torch.cat([up, skip], 1) is two writers of one 2 O-wide buffer (the up-convolution its left half,
-    the encoder's second convolution its right half, which the max-pool reads in place). Training is not on this path."""
+    the encoder's second convolution its right half, which the max-pool reads in place). Training (PGT.py's train, unet.py) runs
+    on the HIP path for a net that has opted in with enable_training(): batch statistics in the forward, the backward through
+    _UNetTrain; any other net keeps refusing training mode."""
 
     def __init__(self):
         super().__init__()
@@ -883,6 +1148,7 @@ class build_unet(nn.Module):
         self.outputs = nn.Conv2d(64, 1, kernel_size=1, padding=0)
         self.__dict__["_precision"] = _lib.DEFAULT_PRECISION
         self.__dict__["_op_cache"] = {}
+        self.train_backward = False  # a plain attribute: not a parameter, not a buffer, not in the state_dict
         self.__dict__["_alloc"] = _unet_empty  # a test seam: the memory tests swap in an allocator of poisoned, guard-banded buffers
 
     @property
@@ -894,6 +1160,13 @@ class build_unet(nn.Module):
         if name not in _lib.PRECISIONS:
             raise ValueError(f"precision must be one of {sorted(_lib.PRECISIONS)}, got {name!r}")
         self.__dict__["_precision"] = name
+
+    def enable_training(self, flag=True):
+        """Opt this net in to (or out of) training on the HIP path: in training mode forward() then normalises with batch
+        statistics, updates the running statistics as nn.BatchNorm2d does and, with grad mode on and a parameter that requires
+        grad, builds a graph into the parameters (_UNetTrain). A net that has not opted in refuses training mode."""
+        self.train_backward = bool(flag)
+        return self
 
     def _folded(self, name, conv, bn, prec, dev, image=False):
         """(operand copy of the convolution's weight, fp32 bias) with the BatchNorm's running statistics folded in."""
@@ -915,10 +1188,13 @@ class build_unet(nn.Module):
         return w, b
 
     def forward(self, inputs):
+        if self.training and self.train_backward:
+            return self._train_forward(inputs)
         if self.training and torch.is_grad_enabled():
             raise NotImplementedError("build_unet runs inference on the HIP path; training (batch statistics, the backward of the "
                                       "convolutions, pool and up-convolution) is not implemented. A new module is in training "
-                                      "mode: call .eval() (PGT.py's evaluate / fully_test do), or wrap the call in torch.no_grad()")
+                                      "mode: call .eval() (PGT.py's evaluate / fully_test do), or wrap the call in torch.no_grad(); "
+                                      "to train on the HIP path opt in with enable_training()")
         if any(m.training for m in self.modules() if isinstance(m, nn.BatchNorm2d)):
             raise NotImplementedError("a BatchNorm2d of this build_unet is in training mode: inference is what runs on the HIP "
                                       "path (running statistics are folded into the convolutions); call .eval()")
@@ -931,6 +1207,42 @@ class build_unet(nn.Module):
         _require_hip(inputs, "input")
         with torch.no_grad(), torch.cuda.device(inputs.device):
             return self._forward(inputs.detach().to(torch.float32))
+
+    def _train_forward(self, inputs):
+        """forward() of a net that has opted in (enable_training) in training mode: what is refused, before anything is launched;
+        then the batch-statistics forward, with a graph into the parameters when grad mode is on and one of them requires grad;
+        then nn.BatchNorm2d's update of the running statistics."""
+        if not isinstance(inputs, torch.Tensor) or inputs.dim() != 4 or inputs.shape[1] != 3:
+            raise RuntimeError(f"build_unet expects a (B, 3, H, W) input, got {tuple(getattr(inputs, 'shape', ()))}")
+        B, _, H, W = inputs.shape
+        if H % 16 or W % 16 or H == 0 or W == 0 or B == 0:
+            raise RuntimeError(f"build_unet needs H and W that are multiples of 16 (four 2x2 pools, then four stride-2 "
+                               f"up-convolutions whose outputs are concatenated with the skips); got H={H}, W={W}")
+        if torch.is_grad_enabled() and inputs.requires_grad:
+            raise NotImplementedError("the training path does not produce the gradient of the input image; pass an input that "
+                                      "does not require grad")
+        if not all(m.training for m in self.modules() if isinstance(m, nn.BatchNorm2d)):
+            raise NotImplementedError("the training-mode build_unet normalises with batch statistics: a BatchNorm2d in eval mode "
+                                      "inside a training build_unet is not supported on the HIP path")
+        if B * (H // 16) * (W // 16) < 2:
+            raise ValueError(f"Expected more than 1 value per channel when training, got input size {[B, 1024, 1, 1]}")
+        _require_hip(inputs, "input")
+        x = inputs.detach().to(torch.float32)
+        if x.stride(3) != 1:
+            x = x.contiguous()
+        with torch.cuda.device(x.device):
+            if _differentiable(self):
+                named = list(self.named_parameters())
+                meta = {"net": self, "names": [n for n, _ in named]}
+                out = _UNetTrain.apply(meta, x, *[p for _, p in named])
+                stats = meta.pop("stats")
+            else:
+                with torch.no_grad():
+                    out, _, stats = _unet_train_pass(self, x)
+            for bn, mean, var, n in stats:
+                if bn.track_running_stats and bn.running_mean is not None:
+                    _update_running_stats(bn, mean, var, n)
+        return out
 
     def _forward(self, x):
         lib, dev, prec = _lib.load(), x.device, _lib.PRECISIONS[self._precision]

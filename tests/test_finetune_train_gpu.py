@@ -13,6 +13,7 @@ deviation of the product's normalised y1 from the twin's (Y1_DEVIATION, printed 
 deviates by more than any gap these geometries have: its two-layer end-to-end cases assert finite gradients only."""
 import copy
 import functools
+import gc
 from functools import partial
 
 import pytest
@@ -300,13 +301,16 @@ def test_training_forward_matches_eval_forward(dev, name, precision):
 
 # ---- (d) partial fine-tuning ----------------------------------------------------------------------------------------------------
 def _step(lp, x, y, first):
-    """One forward + backward after a warm-up step (operand caches built); (gradients, peak bytes above the resting level)."""
+    """One forward + backward after a warm-up step (operand caches built); (gradients, peak bytes above the resting level).
+    The resting level is read after a garbage collection: device memory that earlier tests left to the cycle collector would
+    count as resting, and a collection that happened to run inside the measured step would free it below that level."""
     enc = lp.encoder
     for n, p in enc.named_parameters():
         p.requires_grad_(n.startswith("norm.") or (n.startswith("blocks.") and int(n.split(".")[1]) >= first))
     peak = None
     for _ in range(2):
         lp.zero_grad(set_to_none=True)
+        gc.collect()
         torch.cuda.synchronize()
         torch.cuda.reset_peak_memory_stats()
         rest = torch.cuda.memory_allocated()

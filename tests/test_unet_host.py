@@ -1,5 +1,6 @@
 """build_unet without a GPU: the module tree and state_dict of the reference's model.py:227-320, the round trip with the test
-twin, the refusals that need no device, and the twin itself against a module-free restatement."""
+twin, the refusals that need no device, the layer description every walk of the network reads, and the twin itself against a
+module-free restatement."""
 import pytest
 import torch
 
@@ -87,6 +88,44 @@ def test_refusals_need_no_device():
     net.e2.conv.bn1.train()
     with pytest.raises(NotImplementedError, match=r"\.eval\(\)"):
         net(torch.zeros(1, 3, 32, 32))
+
+
+@pytest.mark.parametrize("H,W", [(32, 32), (48, 32)])
+def test_plan_describes_the_module_tree(H, W):
+    net = M.build_unet()
+    steps = [s for _, stage in M._unet_plan(H, W) for s in stage]
+    convs = [s for s in steps if s.op == "conv"]
+    assert [s.key for s in convs] == [f"{p}.conv{i}" for p, _, _ in BLOCKS for i in (1, 2)]  # forward order
+    assert len(convs) == 18
+    level = {"e1": 0, "e2": 1, "e3": 2, "e4": 3, "b": 4, "d1": 3, "d2": 2, "d3": 1, "d4": 0}
+    for s in convs:
+        cv, bn = net.get_submodule(s.key), net.get_submodule(s.bn)
+        assert isinstance(cv, torch.nn.Conv2d) and (s.C, s.O) == (cv.in_channels, cv.out_channels), s.key
+        assert isinstance(bn, torch.nn.BatchNorm2d) and bn.num_features == s.O, s.key
+        assert s.bn + ".running_var" in net.state_dict() and s.bn.rsplit(".", 1)[0] == s.key.rsplit(".", 1)[0]
+        lvl = level[s.key.split(".")[0]]
+        assert s.grid == (H >> lvl, W >> lvl), s.key
+        assert s.src.buf == "x" or s.src.ld == s.C, s.key  # every source of a 3x3 layer is dense
+    assert [(s.key, s.C, s.O) for s in steps if s.op == "up"] == [(p, cin, cout) for p, cin, cout in UPS]
+    assert [s.key for s in steps if s.op == "pool"] == ["e1.pool", "e2.pool", "e3.pool", "e4.pool"]
+    assert steps[-1].op == "head" and (steps[-1].key, steps[-1].C, steps[-1].src.ld) == ("outputs", 64, 64)
+    # every buffer is written by an earlier step than any step that reads it; the image is given
+    written, writers = {"x"}, {}
+    for s in steps:
+        assert s.src.buf in written, f"{s.key} reads {s.src.buf} before it is written"
+        if s.dst is not None:
+            written.add(s.dst.buf)
+            writers.setdefault(s.dst.buf, []).append(s)
+    # torch.cat([up, skip], 1): each half of a 2 O-wide buffer has exactly one writer, at columns 0 and O
+    cats = {b: w for b, w in writers.items() if b.endswith(".cat")}
+    assert sorted(cats) == ["e1.cat", "e2.cat", "e3.cat", "e4.cat"]
+    for (buf, w), O in zip(sorted(cats.items()), (64, 128, 256, 512)):
+        assert [(s.op, s.dst.col, s.dst.ld, s.O) for s in w] == [("conv", O, 2 * O, O), ("up", 0, 2 * O, O)], buf
+        readers = [(s.op, s.src.col, s.src.ld) for s in steps if s.src.buf == buf]
+        assert readers == [("pool", O, 2 * O), ("conv", 0, 2 * O)], buf
+    for buf, w in writers.items():  # every other buffer is dense and has one writer
+        if buf not in cats:
+            assert len(w) == 1 and (w[0].dst.col, w[0].dst.ld) == (0, w[0].O), buf
 
 
 def test_twin_agrees_with_the_restatement():

@@ -22,10 +22,12 @@ without a mask: finetune.py --finetune True. Every cached operand copy of a deco
 from (_cached_operand); biases are read on every call. The reference initialises mask_token with timm's trunc_normal_; here
 the package's own trunc_normal_ (dino/utils.py) with the same bounds is used.
 """
+import collections
 import contextlib
 import ctypes as C
+import operator
 import os
-from functools import partial
+from functools import lru_cache, partial
 
 import torch
 import torch.nn as nn
@@ -822,7 +824,7 @@ class _EncoderTrain(torch.autograd.Function):
 
 
 # ---- the U-Net (model.py:227-320). The nn modules hold the parameters and buffers (same tree, same state_dict keys); the
-# arithmetic of the eval-mode forward runs through kernels_conv.hip on token-major fp32 rows (build_unet.forward). ----
+# arithmetic runs through kernels_conv.hip on token-major fp32 rows: _unet_plan is the graph, _unet_walk the forward. ----
 class convolution_block(nn.Module):
     def __init__(self, in_c, out_c):
         super().__init__()
@@ -871,14 +873,56 @@ def _rows_up2x2_t(w):
     return _rows_up2x2(w).t()
 
 
-def _rows3x3_image(w, kstep):
-    """(O, 3, 3, 3) kernel of the first layer -> (O, kstep): ocm_op_conv3x3_image's 27 columns and zeros up to one K step."""
-    rows = _rows3x3(w)
-    return nn.functional.pad(rows, (0, kstep - rows.shape[1]))
+def _image_kstep(prec):
+    """Columns of the first layer's operand: ocm_op_conv3x3_image's 27, padded with zeros to one K step of the operand type."""
+    return 64 if prec == _lib.OCM_PREC_BF16 else 32
+
+
+def _image_rows(rows, prec):
+    """The (O, 27) fp32 rows (_rows3x3) of the first layer's kernel -> (O, _image_kstep(prec))."""
+    return nn.functional.pad(rows, (0, _image_kstep(prec) - rows.shape[1]))
 
 
 _UNET_WIDTHS = (64, 128, 256, 512)
 _IM2COL_CAP = 1 << 30  # bytes of the fp32 im2col operand one weight-gradient launch of the U-Net reads
+_At = collections.namedtuple("_At", "buf col ld")  # columns [col, col + width) of the fp32 rows `buf`, whose row stride is ld
+_Step = collections.namedtuple("_Step", "op key bn C O grid src dst")
+
+
+def _sub(net, key):  # nn.Module.get_submodule without its checks: this runs per layer, per call
+    return operator.attrgetter(key)(net)
+
+
+@lru_cache(maxsize=None)
+def _unet_plan(H, W):
+    """build_unet's graph, stated once for the forward walk, the backward and the operand cache: [(kind, steps)] in forward order,
+    kind "enc" (conv1, conv2, pool) x 4, "mid" (conv1, conv2), "dec" (up, conv1, conv2) x 4, "head". A step names its module
+    (`key`; a 3x3 layer also its BatchNorm2d, `bn`: state_dict prefixes), its channels C -> O, the (h, w) grid of its input rows
+    and where it reads and writes. torch.cat([up, skip], 1) is the buffer e<k>.cat: the encoder's second convolution writes its
+    right half, which the pool reads in place, the up-convolution its left half."""
+    def block(pre, lvl, src, C, O, dst):
+        t = _At(pre.split(".")[0] + ".t", 0, O)
+        return [_Step("conv", pre + ".conv1", pre + ".bn1", C, O, (H >> lvl, W >> lvl), src, t),
+                _Step("conv", pre + ".conv2", pre + ".bn2", O, O, (H >> lvl, W >> lvl), t, dst)]
+
+    plan, cur, C = [], _At("x", None, None), 3  # the image is read in place, as (B, 3, H, W) planes
+    for lvl, O in enumerate(_UNET_WIDTHS):
+        e = f"e{lvl + 1}"
+        skip, pooled = _At(e + ".cat", O, 2 * O), _At(e + ".pool", 0, O)
+        plan.append(("enc", block(e + ".conv", lvl, cur, C, O, skip)
+                     + [_Step("pool", e + ".pool", None, O, O, (H >> lvl, W >> lvl), skip, pooled)]))
+        cur, C = pooled, O
+    z = _At("b.z", 0, 2 * C)
+    plan.append(("mid", block("b", 4, cur, C, 2 * C, z)))
+    cur, C = z, 2 * C
+    for lvl, O in reversed(list(enumerate(_UNET_WIDTHS))):
+        d = f"d{4 - lvl}"
+        cat, z = _At(f"e{lvl + 1}.cat", 0, 2 * O), _At(d + ".z", 0, O)
+        plan.append(("dec", [_Step("up", d + ".up", None, C, O, (H >> (lvl + 1), W >> (lvl + 1)), cur, cat)]
+                     + block(d + ".conv", lvl, cat, 2 * O, O, z)))
+        cur, C = z, O
+    plan.append(("head", [_Step("head", "outputs", None, C, 1, (H, W), cur, None)]))
+    return tuple((kind, tuple(steps)) for kind, steps in plan)
 
 
 def _im2col_chunks(batch, rows_per_image, k, cap=_IM2COL_CAP):
@@ -904,42 +948,86 @@ def _phase(net, name):
     log.append((name, a, b))
 
 
-def _unet_conv(net, prec, src, grid, C, w_op, bias, dst, O):
-    """dst (M, O) = the 3x3 pad-1 convolution of the dense rows src (M, C) with the (O, 9 C) operand + bias, no ReLU: the direct
-    kernel, or im2col + ocm_op_linear for the layer classes of _unet_composed. Serves the training forward and, with the flipped
-    kernel and a zero bias, the data gradients."""
+def _unet_conv(net, prec, src, grid, C, w_op, bias, dst, ld_out, O, relu):
+    """Columns [0, O) of the rows at address dst (row stride ld_out) = the 3x3 pad-1 convolution of src with the (O, 9 C) operand
+    + bias, through a ReLU when `relu`. src is dense rows (M, C): the direct kernel, or im2col + GEMM for the layer classes of
+    _unet_composed (few rows, long K: the LDS-DMA GEMM measures faster); or the (B, 3, H, W) image, read in place. Serves the
+    eval forward (folded operands, ReLU), the training forward and, with the flipped kernel and a zero bias, the data gradients."""
     lib, st, (B, h, w) = _lib.load(), _stream(), grid
     M = B * h * w
-    if _unet_composed(prec, O):
+    if src.dim() == 4:
+        _lib.check(lib.ocm_op_conv3x3_image(prec, _p(src), src.stride(0), src.stride(1), src.stride(2), _p(w_op), _p(bias), dst,
+                                            ld_out, B, h, w, O, int(relu), st))
+    elif _unet_composed(prec, O):
         cols = net._alloc((M, 9 * C * _OPERAND_DTYPE[prec].itemsize // 4), src.device)  # operand rows, in fp32-sized words
         _lib.check(lib.ocm_op_im2col3x3(prec, _p(src), _p(cols), B, h, w, C, 0, st))
-        _lib.check(lib.ocm_op_linear(prec, _p(cols), _p(w_op), _p(bias), None, _p(dst), M, O, 9 * C, _lib.OCM_EPI_BIAS_F32, st))
+        if relu:
+            _lib.check(lib.ocm_op_linear_relu(prec, _p(cols), _p(w_op), _p(bias), dst, ld_out, M, O, 9 * C, st))
+        else:  # ocm_op_linear writes dense rows: ld_out == O at every call without ReLU
+            _lib.check(lib.ocm_op_linear(prec, _p(cols), _p(w_op), _p(bias), None, dst, M, O, 9 * C, _lib.OCM_EPI_BIAS_F32, st))
     else:
-        _lib.check(lib.ocm_op_conv3x3(prec, _p(src), C, _p(w_op), _p(bias), _p(dst), O, B, h, w, C, O, 0, st))
+        _lib.check(lib.ocm_op_conv3x3(prec, _p(src), C, _p(w_op), _p(bias), dst, ld_out, B, h, w, C, O, int(relu), st))
+
+
+def _head_weight(cache, w, prec, dev):
+    """The classifier's (64,) fp32 weight: one cache entry for both forwards and the backward."""
+    return _cached_operand(cache, "outputs.weight", w, prec,
+                           lambda: w.detach().to(device=dev, dtype=torch.float32).reshape(-1).contiguous())
+
+
+def _unet_walk(net, x, layer, keep):
+    """The forward of build_unet, eval and training: the steps of _unet_plan in order on token-major fp32 rows from net._alloc.
+    `layer(prec, step, B, src, dst)` runs one 3x3 layer from the tensor src to the address dst: build_unet._eval_layer, or the
+    training step of _unet_train_pass. Without `keep` (inference) a buffer is allocated in front of its first writer and only
+    the four [up | skip] buffers and the two newest dense ones (a layer's source and destination) are held; with `keep`
+    (training) a stage's buffers are allocated together and all are held. Returns (logits, {name: buffer held}, "x" the image)."""
+    lib, dev, prec, st = _lib.load(), x.device, _lib.PRECISIONS[net._precision], _stream()
+    B, _, H, W = x.shape
+    cache, bufs, dense = net._op_cache, {"x": x}, [None, None]
+    for _, stage in _unet_plan(H, W):
+        for s in stage:
+            if s.op == "head":
+                mod, out = _sub(net, s.key), torch.empty((B, 1, H, W), dtype=torch.float32, device=dev)
+                wo = _head_weight(cache, mod.weight, prec, dev)
+                bo = _cached_operand(cache, s.key + ".bias", mod.bias, prec, lambda: _vec(mod.bias, 1, dev))
+                _lib.check(lib.ocm_op_conv1x1_planes(_p(bufs[s.src.buf]), s.src.ld, _p(wo), _p(bo), _p(out), B, H * W, s.C, st))
+                return out, bufs
+            for t in (stage if keep and s.dst.buf not in bufs else (s,)):
+                if t.dst.buf not in bufs:
+                    bufs[t.dst.buf] = net._alloc((B * t.grid[0] * t.grid[1] // (4 if t.op == "pool" else 1), t.dst.ld), dev)
+                    if not keep and t.dst.ld == t.O:  # dense: the one before the last two has no reader left
+                        dense.append(t.dst.buf)
+                        bufs.pop(dense[-3], None)
+            src, dst, (h, w) = bufs[s.src.buf], bufs[s.dst.buf].data_ptr() + 4 * s.dst.col, s.grid
+            if s.op == "conv":
+                layer(prec, s, B, src, dst)
+            elif s.op == "pool":
+                _lib.check(lib.ocm_op_maxpool2x2(src.data_ptr() + 4 * s.src.col, s.src.ld, dst, s.dst.ld, B, h, w, s.O, st))
+                newest_pool = bufs[s.dst.buf]  # noqa: F841  held until the next pool, e4's until the walk returns: the peak as it was
+            else:
+                up = _sub(net, s.key)
+                wu = _weight_operand(cache, s.key, up.weight, prec, dev, _rows_up2x2)
+                bu = _cached_operand(cache, s.key + ".bias", up.bias, prec, lambda: _vec(up.bias, s.O, dev))
+                _lib.check(lib.ocm_op_upconv2x2(prec, _p(src), s.src.ld, _p(wu), _p(bu), dst, s.dst.ld, B, h, w, s.C, s.O, st))
 
 
 def _unet_train_pass(net, x):
-    """build_unet in training mode, forward: per convolution y = conv(z_prev) + bias (no ReLU), the batch statistics of y and
-    z = max(y * scale + shift, 0) written where inference writes it. Returns (logits, everything the backward reads by name,
-    [(BatchNorm2d, batch mean, biased batch variance, values per channel)] in forward order)."""
-    lib, dev, prec = _lib.load(), x.device, _lib.PRECISIONS[net._precision]
-    B, _, H, W = x.shape
-    alloc, st, cache = net._alloc, _stream(), net._op_cache
+    """build_unet in training mode, forward: _unet_walk with the training step — per convolution y = conv(z_prev) + bias (no ReLU,
+    raw operands), the batch statistics of y and z = max(y * scale + shift, 0) written where inference writes it. Returns (logits,
+    what the backward reads by name, [(BatchNorm2d, batch mean, biased batch variance, values per channel)] in forward order)."""
+    lib, dev, cache, st = _lib.load(), x.device, net._op_cache, _stream()
     f32 = dict(device=dev, dtype=torch.float32)
-    S, stats = {"x": x}, []
+    S, stats = {}, []
 
-    def layer(name, blk, which, src, grid, C, dst, ld_out):
-        cv, bn = (blk.conv1, blk.bn1) if which == 1 else (blk.conv2, blk.bn2)
-        O, M, key = cv.out_channels, B * grid[0] * grid[1], f"{name}.conv{which}"
-        y, bias = alloc((M, O), dev), _vec(cv.bias, O, dev)
-        if src is None:  # the first layer reads the image planes in place
-            kstep = 64 if prec == _lib.OCM_PREC_BF16 else 32
-            wi = _cached_operand(cache, key + ".image", cv.weight, prec, lambda: to_operand(
-                _rows3x3_image(cv.weight.detach().to(**f32), kstep).contiguous(), prec))
-            _lib.check(lib.ocm_op_conv3x3_image(prec, _p(x), x.stride(0), x.stride(1), x.stride(2), _p(wi), _p(bias), _p(y), O,
-                                                B, grid[0], grid[1], O, 0, st))
+    def layer(prec, s, B, src, dst):
+        cv, bn, O, M = _sub(net, s.key), _sub(net, s.bn), s.O, B * s.grid[0] * s.grid[1]
+        y, bias = net._alloc((M, O), dev), _vec(cv.bias, O, dev)
+        if src.dim() == 4:
+            w = _cached_operand(cache, s.key + ".image", cv.weight, prec, lambda: to_operand(
+                _image_rows(_rows3x3(cv.weight.detach().to(**f32)), prec).contiguous(), prec))
         else:
-            _unet_conv(net, prec, src, (B, *grid), C, _weight_operand(cache, key, cv.weight, prec, dev, _rows3x3), bias, y, O)
+            w = _weight_operand(cache, s.key, cv.weight, prec, dev, _rows3x3)
+        _unet_conv(net, prec, src, (B, *s.grid), s.C, w, bias, y.data_ptr(), O, O, False)
         mean, var = torch.empty(O, **f32), torch.empty(O, **f32)
         nbytes = lib.ocm_channel_reduce_workspace_bytes(M, O)
         ws = _ws(nbytes, dev)
@@ -947,54 +1035,20 @@ def _unet_train_pass(net, x):
         invstd = torch.rsqrt(var + bn.eps)
         g = (bn.weight.detach().to(**f32) * invstd).contiguous()
         h = (_vec(bn.bias, O, dev) - mean * g).contiguous()
-        _lib.check(lib.ocm_op_bn_relu(_p(y), _p(g), _p(h), dst, ld_out, M, O, st))
+        _lib.check(lib.ocm_op_bn_relu(_p(y), _p(g), _p(h), dst, s.dst.ld, M, O, st))
         stats.append((bn, mean, var, M))
-        for k, v in (("y", y), ("mean", mean), ("invstd", invstd), ("g", g), ("h", h)):
-            S[f"{key}.{k}"] = v
+        S.update({f"{s.key}.{k}": v for k, v in (("y", y), ("mean", mean), ("invstd", invstd), ("g", g), ("h", h))})
 
-    encs, decs = (net.e1, net.e2, net.e3, net.e4), (net.d4, net.d3, net.d2, net.d1)
-    h, w, cur, Cin = H, W, None, 3
-    for lvl, (enc, O) in enumerate(zip(encs, _UNET_WIDTHS)):
-        name, M = f"e{lvl + 1}", B * h * w
-        t, cat, pooled = alloc((M, O), dev), alloc((M, 2 * O), dev), alloc((M // 4, O), dev)
-        layer(name + ".conv", enc.conv, 1, cur, (h, w), Cin, _p(t), O)
-        skip_ptr = cat.data_ptr() + 4 * O
-        layer(name + ".conv", enc.conv, 2, t, (h, w), O, skip_ptr, 2 * O)
-        _lib.check(lib.ocm_op_maxpool2x2(skip_ptr, 2 * O, _p(pooled), O, B, h, w, O, st))
-        S[name + ".t"], S[name + ".cat"], S[name + ".pool"] = t, cat, pooled
-        cur, Cin, h, w = pooled, O, h // 2, w // 2
-    t, z = alloc((B * h * w, 1024), dev), alloc((B * h * w, 1024), dev)
-    layer("b", net.b, 1, cur, (h, w), 512, _p(t), 1024)
-    layer("b", net.b, 2, t, (h, w), 1024, _p(z), 1024)
-    S["b.t"], S["b.z"] = t, z
-    cur, Cin = z, 1024
-    for lvl in (3, 2, 1, 0):
-        dec, O, name = decs[lvl], _UNET_WIDTHS[lvl], f"d{4 - lvl}"
-        cat = S[f"e{lvl + 1}.cat"]
-        wu = _weight_operand(cache, name + ".up", dec.up.weight, prec, dev, _rows_up2x2)
-        bu = _cached_operand(cache, name + ".up.bias", dec.up.bias, prec, lambda: _vec(dec.up.bias, O, dev))
-        _lib.check(lib.ocm_op_upconv2x2(prec, _p(cur), Cin, _p(wu), _p(bu), _p(cat), 2 * O, B, h, w, Cin, O, st))
-        h, w = 2 * h, 2 * w
-        t, z = alloc((B * h * w, O), dev), alloc((B * h * w, O), dev)
-        layer(name + ".conv", dec.conv, 1, cat, (h, w), 2 * O, _p(t), O)
-        layer(name + ".conv", dec.conv, 2, t, (h, w), O, _p(z), O)
-        S[name + ".t"], S[name + ".z"] = t, z
-        cur, Cin = z, O
-    out = torch.empty((B, 1, H, W), **f32)
-    head = net.outputs
-    wo = _cached_operand(cache, "outputs.weight", head.weight, prec,
-                         lambda: head.weight.detach().to(**f32).reshape(-1).contiguous())
-    bo = _cached_operand(cache, "outputs.bias", head.bias, prec, lambda: _vec(head.bias, 1, dev))
-    _lib.check(lib.ocm_op_conv1x1_planes(_p(cur), 64, _p(wo), _p(bo), _p(out), B, H * W, 64, st))
-    return out, S, stats
+    out, bufs = _unet_walk(net, x, layer, True)
+    return out, {**bufs, **S}, stats
 
 
 class _UNetTrain(torch.autograd.Function):
     """One training-mode call of build_unet: forward(meta, x, *params) -> (B, 1, H, W) logits (_unet_train_pass); backward -> the
-    parameter gradients, none for the image. It keeps y (pre-BatchNorm) and z (post-ReLU) of all 18 layers, the pooled maps and
-    the per-channel statistics: 5.3 GB at 384^2, batch 8 (counted and measured: DESIGN.md 3.24). Weight
-    gradients run ocm_op_weight_grad on an fp32 im2col operand built under _IM2COL_CAP (_im2col_chunks), data gradients as the
-    3x3 convolution with the flipped kernel; a frozen parameter's weight-gradient launches are skipped. `meta` carries the module
+    parameter gradients, none for the image: the stages of _unet_plan in reverse. It keeps y (pre-BatchNorm) and z (post-ReLU) of
+    all 18 layers, the pooled maps and the per-channel statistics: 5.3 GB at 384^2, batch 8. Weight gradients
+    run ocm_op_weight_grad on an fp32 im2col operand built under _IM2COL_CAP (_im2col_chunks), data gradients as the 3x3
+    convolution with the flipped kernel; a frozen parameter's weight-gradient launches are skipped. `meta` carries the module
     and, for the caller, the batch statistics (the running statistics are updated outside the graph)."""
 
     @staticmethod
@@ -1018,24 +1072,24 @@ class _UNetTrain(torch.autograd.Function):
         B, _, H, W = x.shape
         grads = {}
 
-        def conv_backward(key, dz, src, grid, C, want_dx):
-            """Through ReLU, BatchNorm and the convolution `key` whose input was src (M, C) (None: the image): fills the gradients
-            of the layer's parameters; returns the gradient of src when want_dx."""
+        def conv_backward(s, dz, want_dx):
+            """Through ReLU, BatchNorm and the convolution of the step s: fills the gradients of the layer's parameters; returns
+            the gradient of its source rows when want_dx."""
+            key, C, (hh, ww), src = s.key, s.C, s.grid, (None if s.src.buf == "x" else S[s.src.buf])
             y, mean, invstd, g, h = (S[f"{key}.{k}"] for k in ("y", "mean", "invstd", "g", "h"))
             (M, O), st = y.shape, _stream()
-            bnkey, (hh, ww) = key[:-5] + "bn" + key[-1], grid  # "e1.conv.conv2" -> "e1.conv.bn2"
             dy, dgam, dbet = alloc((M, O), dev), torch.empty(O, **f32), torch.empty(O, **f32)
             nbytes = lib.ocm_channel_reduce_workspace_bytes(M, O)
             ws = _ws(nbytes, dev)
             _lib.check(lib.ocm_op_bn_relu_backward(_p(dz), _p(y), _p(mean), _p(invstd), _p(g), _p(h), _p(dy), _p(dgam), _p(dbet),
                                                    M, O, _p(ws), nbytes, st))
-            if need[bnkey + ".weight"]:
-                grads[bnkey + ".weight"] = dgam
-            if need[bnkey + ".bias"]:
-                grads[bnkey + ".bias"] = dbet
+            if need[s.bn + ".weight"]:
+                grads[s.bn + ".weight"] = dgam
+            if need[s.bn + ".bias"]:
+                grads[s.bn + ".bias"] = dbet
             nw, nb = need[key + ".weight"], need[key + ".bias"]
             if nw or nb:
-                K, rpi = (32 if src is None else 9 * C), hh * ww
+                K, rpi = (_image_kstep(_lib.OCM_PREC_FP32) if src is None else 9 * C), hh * ww
                 dw = db = None
                 for b0, n in _im2col_chunks(B, rpi, K):
                     with _phase(net, "weight"):
@@ -1059,80 +1113,99 @@ class _UNetTrain(torch.autograd.Function):
             dx = alloc((M, C), dev)
             with _phase(net, "data"):
                 _unet_conv(net, prec, dy, (B, hh, ww), O, _weight_operand(cache, key, P[key + ".weight"], prec, dev, flip_conv3x3),
-                           _zeros(cache, C, dev), dx, C)
+                           _zeros(cache, C, dev), dx.data_ptr(), C, C, False)
             return dx
 
         with torch.cuda.device(dev):
             st = _stream()
+            *stages, (_, (head,)) = _unet_plan(H, W)
             # the classifier
             dl = gout.detach().to(torch.float32).contiguous()
-            M = B * H * W
-            dcur = alloc((M, 64), dev)
-            nw, nb = need["outputs.weight"], need["outputs.bias"]
-            dwo, dbo = (torch.empty(64, **f32) if nw else None), (torch.empty(1, **f32) if nb else None)
-            wo = _cached_operand(cache, "outputs.weight", P["outputs.weight"], prec,
-                                 lambda: P["outputs.weight"].detach().to(**f32).reshape(-1).contiguous())
-            nbytes = lib.ocm_conv1x1_planes_backward_workspace_bytes(M, 64)
+            M, C = B * H * W, head.C
+            dcur = alloc((M, C), dev)
+            nw, nb = need[head.key + ".weight"], need[head.key + ".bias"]
+            dwo, dbo = (torch.empty(C, **f32) if nw else None), (torch.empty(1, **f32) if nb else None)
+            wo = _head_weight(cache, P[head.key + ".weight"], prec, dev)
+            nbytes = lib.ocm_conv1x1_planes_backward_workspace_bytes(M, C)
             ws = _ws(nbytes, dev)
-            _lib.check(lib.ocm_op_conv1x1_planes_backward(_p(dl), _p(S["d4.z"]), 64, _p(wo), _p(dcur), 64, _p(dwo), _p(dbo), B,
-                                                          H * W, 64, _p(ws), nbytes, st))
+            _lib.check(lib.ocm_op_conv1x1_planes_backward(_p(dl), _p(S[head.src.buf]), head.src.ld, _p(wo), _p(dcur), C, _p(dwo),
+                                                          _p(dbo), B, H * W, C, _p(ws), nbytes, st))
             if nw:
-                grads["outputs.weight"] = dwo
+                grads[head.key + ".weight"] = dwo
             if nb:
-                grads["outputs.bias"] = dbo
-            # the decoder, d4 .. d1: conv2, conv1 over [up | skip], the up-convolution
-            dcats = {}
-            for lvl in (0, 1, 2, 3):
-                name, O, hh, ww = f"d{4 - lvl}", _UNET_WIDTHS[lvl], H >> lvl, W >> lvl
-                dz1 = conv_backward(name + ".conv.conv2", dcur, S[name + ".t"], (hh, ww), O, True)
-                dcat = dcats[lvl] = conv_backward(name + ".conv.conv1", dz1, S[f"e{lvl + 1}.cat"], (hh, ww), 2 * O, True)
-                del dz1
-                hs, wsm, Cin = hh // 2, ww // 2, 2 * O
-                Ms = B * hs * wsm
-                g = alloc((Ms, 4 * O), dev)
-                _lib.check(lib.ocm_op_upconv2x2_gather(_p(dcat), 2 * O, _p(g), B, hs, wsm, O, st))
-                up_w = P[name + ".up.weight"]
-                if need[name + ".up.weight"] or need[name + ".up.bias"]:
-                    with _phase(net, "weight"):
-                        dw, db = _weight_grad(prec, g, S["b.z" if lvl == 3 else f"d{3 - lvl}.z"], need[name + ".up.bias"])
-                    if need[name + ".up.weight"]:
-                        grads[name + ".up.weight"] = dw.reshape(2, 2, O, Cin).permute(3, 2, 0, 1)
-                    if need[name + ".up.bias"]:
-                        grads[name + ".up.bias"] = db.reshape(4, O).sum(0)
-                dcur = alloc((Ms, Cin), dev)
-                wt = _weight_operand(cache, name + ".up", up_w, prec, dev, _rows_up2x2_t)
-                with _phase(net, "data"):
-                    _lib.check(lib.ocm_op_linear(prec, _p(to_operand(g, prec)), _p(wt), _p(_zeros(cache, Cin, dev)), None, _p(dcur),
-                                                 Ms, Cin, 4 * O, _lib.OCM_EPI_BIAS_F32, st))
-                del g
-            # the bottleneck
-            hb, wb = H >> 4, W >> 4
-            dz1 = conv_backward("b.conv2", dcur, S["b.t"], (hb, wb), 1024, True)
-            dcur = conv_backward("b.conv1", dz1, S["e4.pool"], (hb, wb), 512, True)
-            # the encoder, e4 .. e1: the pool's backward adds the skip's gradient, the right half of the level's dcat, in place
-            for lvl in (3, 2, 1, 0):
-                name, O, hh, ww = f"e{lvl + 1}", _UNET_WIDTHS[lvl], H >> lvl, W >> lvl
-                cat, dcat = S[name + ".cat"], dcats.pop(lvl)
-                dz = alloc((B * hh * ww, O), dev)
-                _lib.check(lib.ocm_op_maxpool2x2_backward(cat.data_ptr() + 4 * O, 2 * O, _p(dcur), O, dcat.data_ptr() + 4 * O, 2 * O,
-                                                          _p(dz), O, B, hh, ww, O, st))
-                del dcat
-                dz1 = conv_backward(name + ".conv.conv2", dz, S[name + ".t"], (hh, ww), O, True)
-                del dz
-                if lvl:
-                    dcur = conv_backward(name + ".conv.conv1", dz1, S[f"e{lvl}.pool"], (hh, ww), _UNET_WIDTHS[lvl - 1], True)
-                else:  # no image gradient
-                    conv_backward(name + ".conv.conv1", dz1, None, (hh, ww), 3, False)
+                grads[head.key + ".bias"] = dbo
+            dcats = {}  # the gradient of each [up | skip] buffer, from the decoder's first convolution to the encoder's pool
+            for kind, stage in reversed(stages):
+                if kind == "dec":  # d4 .. d1: conv2, conv1 over [up | skip], the up-convolution
+                    up, c1, c2 = stage
+                    dz1 = conv_backward(c2, dcur, True)
+                    dcat = dcats[c1.src.buf] = conv_backward(c1, dz1, True)
+                    del dz1
+                    (hs, wsm), O, Cin = up.grid, up.O, up.C
+                    Ms = B * hs * wsm
+                    g = alloc((Ms, 4 * O), dev)
+                    _lib.check(lib.ocm_op_upconv2x2_gather(_p(dcat), up.dst.ld, _p(g), B, hs, wsm, O, st))
+                    if need[up.key + ".weight"] or need[up.key + ".bias"]:
+                        with _phase(net, "weight"):
+                            dw, db = _weight_grad(prec, g, S[up.src.buf], need[up.key + ".bias"])
+                        if need[up.key + ".weight"]:
+                            grads[up.key + ".weight"] = dw.reshape(2, 2, O, Cin).permute(3, 2, 0, 1)
+                        if need[up.key + ".bias"]:
+                            grads[up.key + ".bias"] = db.reshape(4, O).sum(0)
+                    dcur = alloc((Ms, Cin), dev)
+                    wt = _weight_operand(cache, up.key, P[up.key + ".weight"], prec, dev, _rows_up2x2_t)
+                    with _phase(net, "data"):
+                        _lib.check(lib.ocm_op_linear(prec, _p(to_operand(g, prec)), _p(wt), _p(_zeros(cache, Cin, dev)), None,
+                                                     _p(dcur), Ms, Cin, 4 * O, _lib.OCM_EPI_BIAS_F32, st))
+                    del g
+                elif kind == "mid":
+                    c1, c2 = stage
+                    dz1 = conv_backward(c2, dcur, True)
+                    dcur = conv_backward(c1, dz1, True)
+                else:  # e4 .. e1: the pool's backward adds the skip's gradient, the right half of the level's dcat, in place
+                    c1, c2, pool = stage
+                    (hh, ww), O, skip = pool.grid, pool.O, pool.src
+                    cat, dcat = S[skip.buf], dcats.pop(skip.buf)
+                    dz = alloc((B * hh * ww, O), dev)
+                    _lib.check(lib.ocm_op_maxpool2x2_backward(cat.data_ptr() + 4 * skip.col, skip.ld, _p(dcur), O,
+                                                              dcat.data_ptr() + 4 * skip.col, skip.ld, _p(dz), O, B, hh, ww, O, st))
+                    del dcat
+                    dz1 = conv_backward(c2, dz, True)
+                    del dz
+                    if c1.src.buf != "x":
+                        dcur = conv_backward(c1, dz1, True)
+                    else:  # no image gradient
+                        conv_backward(c1, dz1, False)
         return (None, None, *[_put(grads.get(n), P[n]) if need[n] else None for n in names])
+
+
+def _check_unet_input(inputs):
+    """What build_unet accepts, eval or training: (B, 3, H, W) that four 2x2 pools divide. Returns (B, H, W)."""
+    if not isinstance(inputs, torch.Tensor) or inputs.dim() != 4 or inputs.shape[1] != 3:
+        raise RuntimeError(f"build_unet expects a (B, 3, H, W) input, got {tuple(getattr(inputs, 'shape', ()))}")
+    B, _, H, W = inputs.shape
+    if H % 16 or W % 16 or H == 0 or W == 0 or B == 0:
+        raise RuntimeError(f"build_unet needs H and W that are multiples of 16 (four 2x2 pools, then four stride-2 "
+                           f"up-convolutions whose outputs are concatenated with the skips); got H={H}, W={W}")
+    return B, H, W
+
+
+def _unet_image(inputs):
+    """The fp32 image on its HIP device as the first layer reads it: any batch, plane and row strides, unit pixel stride."""
+    _require_hip(inputs, "input")
+    x = inputs.detach().to(torch.float32)
+    return x if x.stride(3) == 1 else x.contiguous()
 
 
 class build_unet(nn.Module):
     """model.py:280-320: the U-Net PGT.py trains on pseudo ground truth and unet.py trains supervised. Inference runs on the
     HIP path: every BatchNorm is folded, from its running statistics, into the convolution in front of it; ReLU sits in the
-    convolution's epilogue (the deepest layers run as im2col + GEMM, _unet_composed); torch.cat([up, skip], 1) is two writers of one 2 O-wide buffer (the up-convolution its left half,
-    the encoder's second convolution its right half, which the max-pool reads in place). Training (PGT.py's train, unet.py) runs
-    on the HIP path for a net that has opted in with enable_training(): batch statistics in the forward, the backward through
-    _UNetTrain; any other net keeps refusing training mode."""
+    convolution's epilogue (the deepest layers run as im2col + GEMM, _unet_composed); torch.cat([up, skip], 1) is two writers of
+    one 2 O-wide buffer (_unet_plan). Training (PGT.py's train, unet.py) runs on the HIP path for a net that has opted in with
+    enable_training(): batch statistics in the forward, the backward through _UNetTrain; any other net keeps refusing training
+    mode. Both forwards are _unet_walk. _op_cache is keyed by a layer's state_dict prefix: inference's folded operands under
+    "<key>.folded.*", the raw operands of training and the data gradients under "<key>.<layout>" / "<key>.image" — different
+    numbers from the same weights, kept apart so that PGT.py's train() / eval() alternation within an epoch rebuilds neither."""
 
     def __init__(self):
         super().__init__()
@@ -1177,15 +1250,18 @@ class build_unet(nn.Module):
 
         def weight():
             rows = _rows3x3(conv.weight.detach().to(**f32) * gain()[:, None, None, None])
-            if image:  # 27 columns and zeros up to one K step of the operand type
-                rows = nn.functional.pad(rows, (0, (64 if prec == _lib.OCM_PREC_BF16 else 32) - rows.shape[1]))
-            return to_operand(rows.contiguous(), prec)
+            return to_operand((_image_rows(rows, prec) if image else rows).contiguous(), prec)
 
-        w = _cached_operand(self._op_cache, name + ".weight", (conv.weight, bn.weight, bn.running_var), prec, weight)
-        b = _cached_operand(self._op_cache, name + ".bias", (conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var),
+        w = _cached_operand(self._op_cache, name + ".folded.weight", (conv.weight, bn.weight, bn.running_var), prec, weight)
+        b = _cached_operand(self._op_cache, name + ".folded.bias", (conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var),
                             prec, lambda: ((conv.bias.detach().to(**f32) - bn.running_mean.detach().to(**f32)) * gain()
                                            + bn.bias.detach().to(**f32)).contiguous())
         return w, b
+
+    def _eval_layer(self, prec, s, B, src, dst):
+        """The eval step of _unet_walk: folded operands, the convolution with ReLU in its epilogue."""
+        w, b = self._folded(s.key, _sub(self, s.key), _sub(self, s.bn), prec, src.device, image=src.dim() == 4)
+        _unet_conv(self, prec, src, (B, *s.grid), s.C, w, b, dst, s.dst.ld, s.O, True)
 
     def forward(self, inputs):
         if self.training and self.train_backward:
@@ -1198,26 +1274,16 @@ class build_unet(nn.Module):
         if any(m.training for m in self.modules() if isinstance(m, nn.BatchNorm2d)):
             raise NotImplementedError("a BatchNorm2d of this build_unet is in training mode: inference is what runs on the HIP "
                                       "path (running statistics are folded into the convolutions); call .eval()")
-        if not isinstance(inputs, torch.Tensor) or inputs.dim() != 4 or inputs.shape[1] != 3:
-            raise RuntimeError(f"build_unet expects a (B, 3, H, W) input, got {tuple(getattr(inputs, 'shape', ()))}")
-        B, _, H, W = inputs.shape
-        if H % 16 or W % 16 or H == 0 or W == 0 or B == 0:
-            raise RuntimeError(f"build_unet needs H and W that are multiples of 16 (four 2x2 pools, then four stride-2 "
-                               f"up-convolutions whose outputs are concatenated with the skips); got H={H}, W={W}")
-        _require_hip(inputs, "input")
-        with torch.no_grad(), torch.cuda.device(inputs.device):
-            return self._forward(inputs.detach().to(torch.float32))
+        _check_unet_input(inputs)
+        x = _unet_image(inputs)
+        with torch.no_grad(), torch.cuda.device(x.device):
+            return _unet_walk(self, x, self._eval_layer, False)[0]
 
     def _train_forward(self, inputs):
         """forward() of a net that has opted in (enable_training) in training mode: what is refused, before anything is launched;
         then the batch-statistics forward, with a graph into the parameters when grad mode is on and one of them requires grad;
         then nn.BatchNorm2d's update of the running statistics."""
-        if not isinstance(inputs, torch.Tensor) or inputs.dim() != 4 or inputs.shape[1] != 3:
-            raise RuntimeError(f"build_unet expects a (B, 3, H, W) input, got {tuple(getattr(inputs, 'shape', ()))}")
-        B, _, H, W = inputs.shape
-        if H % 16 or W % 16 or H == 0 or W == 0 or B == 0:
-            raise RuntimeError(f"build_unet needs H and W that are multiples of 16 (four 2x2 pools, then four stride-2 "
-                               f"up-convolutions whose outputs are concatenated with the skips); got H={H}, W={W}")
+        B, H, W = _check_unet_input(inputs)
         if torch.is_grad_enabled() and inputs.requires_grad:
             raise NotImplementedError("the training path does not produce the gradient of the input image; pass an input that "
                                       "does not require grad")
@@ -1226,10 +1292,7 @@ class build_unet(nn.Module):
                                       "inside a training build_unet is not supported on the HIP path")
         if B * (H // 16) * (W // 16) < 2:
             raise ValueError(f"Expected more than 1 value per channel when training, got input size {[B, 1024, 1, 1]}")
-        _require_hip(inputs, "input")
-        x = inputs.detach().to(torch.float32)
-        if x.stride(3) != 1:
-            x = x.contiguous()
+        x = _unet_image(inputs)
         with torch.cuda.device(x.device):
             if _differentiable(self):
                 named = list(self.named_parameters())
@@ -1242,70 +1305,6 @@ class build_unet(nn.Module):
             for bn, mean, var, n in stats:
                 if bn.track_running_stats and bn.running_mean is not None:
                     _update_running_stats(bn, mean, var, n)
-        return out
-
-    def _forward(self, x):
-        lib, dev, prec = _lib.load(), x.device, _lib.PRECISIONS[self._precision]
-        B, _, H, W = x.shape
-        if x.stride(3) != 1:
-            x = x.contiguous()
-        alloc, st = self._alloc, _stream()
-
-        def conv(name, blk, which, src, ld_in, dst, ld_out, grid, C, O):
-            cv, bn = (blk.conv1, blk.bn1) if which == 1 else (blk.conv2, blk.bn2)
-            w, b = self._folded(f"{name}.conv{which}", cv, bn, prec, dev)
-            if _unet_composed(prec, O) and ld_in == C:
-                # few rows, long K: im2col + the LDS-DMA GEMM (ReLU and the output slice in its epilogue) measures faster
-                M = B * grid[0] * grid[1]
-                cols = alloc((M, 9 * C * _OPERAND_DTYPE[prec].itemsize // 4), dev)  # operand rows, in fp32-sized words
-                _lib.check(lib.ocm_op_im2col3x3(prec, src, _p(cols), B, grid[0], grid[1], C, 0, st))
-                _lib.check(lib.ocm_op_linear_relu(prec, _p(cols), _p(w), _p(b), dst, ld_out, M, O, 9 * C, st))
-                return
-            _lib.check(lib.ocm_op_conv3x3(prec, src, ld_in, _p(w), _p(b), dst, ld_out, B, grid[0], grid[1], C, O, 1, st))
-
-        widths = (64, 128, 256, 512)
-        encs, decs = (self.e1, self.e2, self.e3, self.e4), (self.d4, self.d3, self.d2, self.d1)
-        cats = []  # per level: the (M, 2 O) buffer [up | skip]
-        h, w, cur, Cin = H, W, None, 3
-        for lvl, (enc, O) in enumerate(zip(encs, widths)):
-            M = B * h * w
-            t = alloc((M, O), dev)
-            if lvl == 0:
-                wi, bi = self._folded("e1.conv1", enc.conv.conv1, enc.conv.bn1, prec, dev, image=True)
-                _lib.check(lib.ocm_op_conv3x3_image(prec, _p(x), x.stride(0), x.stride(1), x.stride(2), _p(wi), _p(bi), _p(t), O,
-                                                    B, h, w, O, 1, st))
-            else:
-                conv(f"e{lvl + 1}", enc.conv, 1, _p(cur), Cin, _p(t), O, (h, w), Cin, O)
-            cat = alloc((M, 2 * O), dev)
-            cats.append(cat)
-            skip_ptr = cat.data_ptr() + 4 * O
-            conv(f"e{lvl + 1}", enc.conv, 2, _p(t), O, skip_ptr, 2 * O, (h, w), O, O)
-            pooled = alloc((M // 4, O), dev)
-            _lib.check(lib.ocm_op_maxpool2x2(skip_ptr, 2 * O, _p(pooled), O, B, h, w, O, st))
-            cur, Cin, h, w = pooled, O, h // 2, w // 2
-        t = alloc((B * h * w, 1024), dev)
-        conv("b", self.b, 1, _p(cur), 512, _p(t), 1024, (h, w), 512, 1024)
-        cur = alloc((B * h * w, 1024), dev)
-        conv("b", self.b, 2, _p(t), 1024, _p(cur), 1024, (h, w), 1024, 1024)
-        Cin = 1024
-        for lvl in (3, 2, 1, 0):
-            dec, O, cat = decs[lvl], widths[lvl], cats[lvl]
-            name = f"d{4 - lvl}"
-            wu = _weight_operand(self._op_cache, name + ".up", dec.up.weight, prec, dev, _rows_up2x2)
-            bu = _cached_operand(self._op_cache, name + ".up.bias", dec.up.bias, prec, lambda: _vec(dec.up.bias, O, dev))
-            _lib.check(lib.ocm_op_upconv2x2(prec, _p(cur), Cin, _p(wu), _p(bu), _p(cat), 2 * O, B, h, w, Cin, O, st))
-            h, w = 2 * h, 2 * w
-            t = alloc((B * h * w, O), dev)
-            conv(name, dec.conv, 1, _p(cat), 2 * O, _p(t), O, (h, w), 2 * O, O)
-            cur = alloc((B * h * w, O), dev)
-            conv(name, dec.conv, 2, _p(t), O, _p(cur), O, (h, w), O, O)
-            Cin = O
-        out = torch.empty((B, 1, H, W), dtype=torch.float32, device=dev)
-        head = self.outputs
-        wo = _cached_operand(self._op_cache, "outputs.weight", head.weight, prec,
-                             lambda: head.weight.detach().to(device=dev, dtype=torch.float32).reshape(-1).contiguous())
-        bo = _cached_operand(self._op_cache, "outputs.bias", head.bias, prec, lambda: _vec(head.bias, 1, dev))
-        _lib.check(lib.ocm_op_conv1x1_planes(_p(cur), 64, _p(wo), _p(bo), _p(out), B, H * W, 64, st))
         return out
 
 

@@ -245,6 +245,29 @@ def bilinear_upsample(maps, scale):
     return F.interpolate(t, scale_factor=scale, mode="bilinear", align_corners=False)[:, 0].numpy()
 
 
+def bilinear_upsample_f64(maps, scale):
+    """The geometry bilinear_upsample names, written out in float64 numpy on (T, h, w) maps for an integer scale:
+    output pixel X samples the source at f = (X + 0.5) / scale - 0.5 (half-pixel centres); the taps are floor(f) and
+    floor(f) + 1, each clamped to the map (border replicate), weighted 1 - a and a with a = f - floor(f); the horizontal
+    pass comes first, the vertical pass blends its rows. Held to double F.interpolate(mode="bilinear",
+    align_corners=False) in tests/test_oracle_golden.py; the reference ocm_op_bilinear_upsample's error is measured
+    against (tests/test_post_shapes_gpu.py)."""
+    m = np.asarray(maps, dtype=np.float64)
+    _, h, w = m.shape
+
+    def taps(n):
+        f = (np.arange(n * scale, dtype=np.float64) + 0.5) / scale - 0.5
+        i0 = np.floor(f)
+        a = f - i0
+        i0 = i0.astype(np.int64)
+        return np.clip(i0, 0, n - 1), np.clip(i0 + 1, 0, n - 1), a
+
+    x0, x1, ax = taps(w)
+    y0, y1, ay = taps(h)
+    rows = m[:, :, x0] * (1.0 - ax) + m[:, :, x1] * ax
+    return rows[:, y0, :] * (1.0 - ay)[:, None] + rows[:, y1, :] * ay[:, None]
+
+
 def pil_rgb_to_l(rgb_u8):
     """PIL Image.convert("L") of an RGB uint8 array (h, w, 3): (19595 R + 38470 G + 7471 B + 0x8000) >> 16."""
     a = np.asarray(rgb_u8).astype(np.uint32)

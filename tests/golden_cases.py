@@ -57,6 +57,42 @@ def median_inputs(seed=17):
     return np.concatenate([up, noisy], 0)
 
 
+# The filter's edges (oracle/make_golden_median.py writes tests/golden/median_edges.npz, keys map<i>_size<k>): maps of height
+# or width 1, windows wider than the map (size // 2 >= h: scipy's "reflect" runs through more than one period; >= 2h at
+# (1, 1, 7) and (1, 2, 3)), the identity (size 1), eval.py's --median_filter 13 and the cap 15 with its even neighbour.
+MEDIAN_EDGE_SIZES = (1, 2, 6, 13, 14, 15)
+MEDIAN_EDGE_SHAPES = ((1, 1, 1), (1, 1, 7), (2, 5, 9), (1, 2, 3), (1, 3, 17))
+
+
+def median_edge_inputs(seed=23):
+    """One (T, h, w) float32 array per MEDIAN_EDGE_SHAPES entry: values in [0.125, 1.125) with planted ties (every third
+    element is 0.5), no NaN and no negative zero — scipy's choice among equal values of different bits is not pinned."""
+    import numpy as np
+    rng = np.random.default_rng(seed)
+    maps = []
+    for shape in MEDIAN_EDGE_SHAPES:
+        m = rng.random(shape, dtype=np.float32) + np.float32(0.125)
+        m.reshape(-1)[2::3] = 0.5
+        maps.append(m)
+    return maps
+
+
+# Post-processing geometries shared by the oracle's CPU pins (tests/test_oracle_golden.py) and the kernels' value tests
+# (tests/test_post_shapes_gpu.py). The stitchers accept stride < window <= 3 * stride; (n, window, stride):
+#   (3, 12, 4) the reference's 3:1;  (3, 12, 6) exactly two windows per pixel;  (4, 11, 5) (4, 13, 5) (5, 7, 3) (3, 10, 4)
+#   strides that do not divide the window, with two- and three-window folds;  (3, 9, 8) a one-element ramp;
+#   (2, 10, 7) window <= 2 * stride;  (1, 12, 4) a single window
+STITCH_GEOMETRIES = ((3, 12, 4), (3, 12, 6), (4, 11, 5), (3, 9, 8), (2, 10, 7), (4, 13, 5), (5, 7, 3), (1, 12, 4), (3, 10, 4))
+# uint8 slab stitcher, (H, W, stride, window); the window count per axis is len(range(0, side - 2 * stride, stride)).
+# (21, 23, 4, 12) and (21, 22, 5, 13) have windows that reach past the slab (PIL crop's zero fill), the second of them
+# at a stride that does not divide the window.
+STITCH_U8_GEOMETRIES = ((20, 20, 4, 12), (21, 23, 4, 12), (30, 28, 6, 12), (26, 26, 8, 9), (25, 27, 7, 10), (19, 19, 5, 13),
+                        (21, 22, 5, 13))
+# bilinear upsample, (T, h, w, scale): non-square maps, scales with an inexact reciprocal (3, 5), one-pixel sides, the
+# identity, and 147 456 outputs per map against the launch's 64 workgroups x 256 threads
+BILINEAR_SHAPES = ((2, 5, 7, 3), (1, 1, 9, 8), (1, 9, 1, 2), (3, 4, 6, 1), (2, 48, 48, 8), (1, 13, 31, 5))
+
+
 # model.py wrappers (SURVEY §8-f row 3): encoder geometry + decoder stride; weights / masks from synth.py.
 # img_size != 224 exercises the interpolated-position branch (model.py:38-39), 224 the native one.
 WRAPPER_CASES = {

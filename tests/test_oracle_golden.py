@@ -125,6 +125,91 @@ def test_median_filter_restatement_equals_scipy_fixture():
         assert np.array_equal(O.median_filter(x[:1], k)[0], median_filter(x[0], size=k))
 
 
+def test_median_filter_restatement_equals_scipy_edge_fixture():
+    """oracle.median_filter at the filter's edges against scipy's own outputs (tests/golden/median_edges.npz, written by
+    oracle/make_golden_median.py): maps of height / width 1, windows that reflect through more than one period of the
+    map, size 1 (the identity), eval.py's 13 and the cap 15. The same fixture holds ocm_op_median_filter
+    (tests/test_post_shapes_gpu.py), and the oracle stands in for scipy there on a map too large to store."""
+    from tests.golden_cases import MEDIAN_EDGE_SHAPES, MEDIAN_EDGE_SIZES, median_edge_inputs
+    gold = load_golden("median_edges")
+    maps = median_edge_inputs(int(gold["seed"]))
+    assert tuple(m.shape for m in maps) == MEDIAN_EDGE_SHAPES
+    assert any(k // 2 >= 2 * m.shape[1] for m in maps for k in MEDIAN_EDGE_SIZES)  # more than one period of reflection
+    for i, x in enumerate(maps):
+        assert len(np.unique(x)) < x.size or x.size == 1  # ties are planted
+        assert not np.isnan(x).any() and not np.signbit(x).any()
+        for k in MEDIAN_EDGE_SIZES:
+            want = gold[f"map{i}_size{k}"]
+            assert want.shape == x.shape and want.dtype == np.float32
+            assert np.array_equal(O.median_filter(x, k), want), (x.shape, k)
+        assert np.array_equal(gold[f"map{i}_size1"], x)
+    try:
+        from scipy.ndimage import median_filter
+    except ImportError:
+        return
+    for i, x in enumerate(maps):
+        for k in (13, 15):
+            assert np.array_equal(gold[f"map{i}_size{k}"][0], median_filter(x[0], size=k))
+
+
+def test_stitcher_restatements_accept_every_window_to_stride_ratio():
+    """concat_crops / stitched_gray_image at stride < window <= 3 * stride, not only the reference's 3:1: the geometries
+    tests/test_post_shapes_gpu.py holds the device stitchers to. A later edit of the oracle that narrows what it accepts
+    fails here, not by silently shrinking the GPU tests."""
+    from tests.golden_cases import STITCH_GEOMETRIES, STITCH_U8_GEOMETRIES
+    rng = np.random.default_rng(8)
+    for n, window, stride in STITCH_GEOMETRIES:
+        assert stride < window <= 3 * stride
+        crops = rng.random((n * n, window, window), dtype=np.float32) * 255
+        out = O.concat_crops(crops, stride, window)
+        S = window + (n - 1) * stride
+        assert out.shape == (S, S) and out.dtype == np.float32
+        # pixels only the first / the last window covers are copies of it
+        assert np.array_equal(out[:stride, :stride], crops[0][:stride, :stride])
+        assert np.array_equal(out[-stride:, -stride:], crops[-1][-stride:, -stride:])
+        # windows cut from ONE smooth map stitch back to it (every blend is a convex combination of equal values)
+        field = (np.add.outer(np.arange(S), 2 * np.arange(S)) % 64).astype(np.float32)
+        cut = np.stack([field[y:y + window, x:x + window] for y in range(0, n * stride, stride) for x in range(0, n * stride, stride)])
+        assert np.abs(O.concat_crops(cut, stride, window) - field).max() <= 64 * 2.0 ** -22
+    assert {(3 * s == w, w <= 2 * s, w == s + 1, w % s != 0) for _, w, s in STITCH_GEOMETRIES} >= {
+        (True, False, False, False), (False, True, False, False), (False, True, True, True), (False, False, False, True)}
+    for H, W, stride, window in STITCH_U8_GEOMETRIES:
+        img = rng.integers(0, 256, (H, W, 3), dtype=np.uint8)
+        n = len(range(0, H - 2 * stride, stride))
+        assert n >= 1 and n == len(range(0, W - 2 * stride, stride))
+        S = window + (n - 1) * stride
+        out = O.stitched_gray_image(img, stride, window)
+        assert out.shape == (S, S) and out.dtype == np.uint8
+        k = min(stride, H, W)
+        assert np.array_equal(out[:k, :k], O.pil_rgb_to_l(img[:k, :k]))  # the first window's own corner
+        if S > H:
+            assert not out[H:].any()  # PIL crop's zero fill below the slab
+        assert np.array_equal(O.stitched_gray_image(img[:, :, 1], stride, window),
+                              O.stitched_gray_image(np.repeat(img[:, :, 1:2], 3, 2), stride, window))
+    assert sum(w + (len(range(0, H - 2 * s, s)) - 1) * s > min(H, W) for H, W, s, w in STITCH_U8_GEOMETRIES) >= 2
+
+
+def test_bilinear_f64_restatement_equals_double_interpolate():
+    """oracle.bilinear_upsample_f64 (numpy, taps and weights written out) against torch's double-precision bilinear with
+    align_corners=False on every shape the GPU test uses. Both are float64 evaluations of one formula: they may differ by
+    a few roundings of the coordinate (<= 4 ulp of the side on either side, times the map's range per pixel) and of the
+    two blends (<= 4 ulp of max|src| on either side), so 16 * 2^-53 * (max|src| + (h + w) * (max - min)) bounds it."""
+    import torch.nn.functional as F
+    from tests.golden_cases import BILINEAR_SHAPES
+    for T, h, w, scale in BILINEAR_SHAPES:
+        rng = np.random.default_rng(100 * h + w)
+        m = (rng.standard_normal((T, h, w)) * 40 + 100).astype(np.float32)
+        got = O.bilinear_upsample_f64(m, scale)
+        want = F.interpolate(torch.from_numpy(m).double()[:, None], scale_factor=scale, mode="bilinear", align_corners=False)[:, 0]
+        assert got.shape == (T, h * scale, w * scale) and got.dtype == np.float64
+        bound = 16 * 2.0 ** -53 * (np.abs(m).max() + (h + w) * float(m.max() - m.min()))
+        assert np.abs(got - want.numpy()).max() <= bound, (T, h, w, scale)
+        if scale == 1:
+            assert np.array_equal(got, m.astype(np.float64))
+        # and the float32 oracle the older tests use is this map rounded, to float32 round-off
+        assert np.abs(O.bilinear_upsample(m, scale) - got).max() <= 2e-6 * np.abs(m).max() * (1 + h + w)
+
+
 def test_uint8_stitcher_restatement_equals_reference_fixture():
     """oracle.stitched_gray_image / concat_crops on uint8 RGB windows against the reference's own sliding_window +
     concat_crops + PIL convert (helpers.npz: stitch_u8_*)."""

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define OCM_ABI_VERSION 18
+#define OCM_ABI_VERSION 19
 
 enum {
     OCM_OK = 0,
@@ -302,6 +302,42 @@ int ocm_op_attention_hd(int32_t precision, const void *q, const void *k, const v
                         int32_t batch, int32_t n_tokens, int32_t heads, int32_t head_dim, float scale, void *stream);
 int ocm_op_attention_probs_hd(int32_t precision, const void *q, const void *k, const float *lse2, float *attn,
                               int32_t batch, int32_t n_tokens, int32_t heads, int32_t head_dim, float scale, void *stream);
+
+/* Which kernel ocm_op_attention[_hd / _ws] and an engine handle launch for a shape: the library's own dispatch (csrc/attn_plan.h),
+ * asked without launching anything. Host only: no device is touched, so it also answers on a machine without a GPU. It reports
+ * the shipped dispatch (development knobs at 0) in every build. workspace_bytes: the key-slice workspace the caller would offer
+ * (0: none, as ocm_op_attention and ocm_op_attention_hd). Arguments the operators refuse return OCM_EINVAL. */
+enum {
+    OCM_ATTN_BF16_WHOLE = 0,    /* single bf16: the whole key range of one (image, head) in LDS, N <= 256            */
+    OCM_ATTN_BF16_STREAM = 1,   /* single bf16: streaming flash kernel                                               */
+    OCM_ATTN_FP32_STREAM = 2,   /* fp32: streaming flash kernel                                                      */
+    OCM_ATTN_X3_WAVE_SPLIT = 3, /* split-bf16: one 32-query tile per workgroup, its four waves split the keys        */
+    OCM_ATTN_X3_PIPELINED = 4,  /* split-bf16: software-pipelined four-wave kernel                                   */
+    OCM_ATTN_X3_DMA = 5,        /* split-bf16: LDS-DMA ring (eight waves above 1024 tokens; four for 128-wide heads) */
+    OCM_ATTN_X3_DMA_KSPLIT = 6  /* ... with the key range cut into grid_z slices, then the merge kernel              */
+};
+typedef struct ocm_attention_plan_info {
+    int32_t kernel;   /* OCM_ATTN_*                                                                  */
+    int32_t waves;    /* wavefronts per workgroup                                                    */
+    int32_t stages;   /* LDS buffers per operand (ring depth); 1: the whole sequence resident        */
+    int32_t kslices;  /* key slices, 1: none                                                         */
+    int32_t grid_x, grid_y, grid_z;
+    int32_t lds_bytes;        /* dynamic LDS of the launch                                           */
+    uint64_t workspace_need;  /* bytes of the offered workspace the plan writes (0 without a split)  */
+} ocm_attention_plan_info;
+int ocm_attention_plan(int32_t precision, int32_t batch, int32_t n_tokens, int32_t heads, int32_t head_dim, size_t workspace_bytes,
+                       ocm_attention_plan_info *plan);
+
+/* ocm_op_attention_hd with a key-slice workspace ("ws" = workspace, not the wave-split kernel): what an engine handle does for a
+ * long sequence in few workgroups (split-bf16, 64-wide heads, more than 1024 tokens, at most 128 eight-wave workgroups). The key
+ * range is then cut into up to four slices that leave unnormalised partial results in `workspace`, and a merge kernel combines
+ * them. ocm_attention_workspace_bytes is what to offer (0: this shape never splits; also 0 for arguments the operator refuses).
+ * workspace: device memory, 16-byte aligned, or NULL; a workspace smaller than ocm_attention_plan's workspace_need is left
+ * untouched and the call runs exactly as ocm_op_attention_hd. */
+size_t ocm_attention_workspace_bytes(int32_t precision, int32_t batch, int32_t n_tokens, int32_t heads, int32_t head_dim);
+int ocm_op_attention_ws(int32_t precision, const void *q, const void *k, const void *vt, void *ctx, float *lse2, int32_t batch,
+                        int32_t n_tokens, int32_t heads, int32_t head_dim, float scale, void *workspace, size_t workspace_bytes,
+                        void *stream);
 
 /* Attention for heads of ANY width (head_dim a multiple of 4, up to 512; at most 8192 tokens; heads * head_dim a multiple of 32
  * for a split-bf16 ctx; batch * heads at most 65535, the launch's grid y, which holds for an engine handle with such heads

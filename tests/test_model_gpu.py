@@ -437,8 +437,10 @@ def test_hip_graph_replay_matches_plain_launches(dev):
 
 
 def test_key_split_attention_agrees_across_batch_sizes(dev):
-    """One ViT-S/8 window of 384^2 per call cuts the key range of its attention into four slices per workgroup (two at B = 2,
-    three at 120 workgroups) and merges them; five windows per call run unsplit. The same tiles give the same maps either way
+    """One ViT-S/8 window of 384^2 per call (60 eight-wave workgroups per attention launch) cuts the key range of its attention
+    into four slices per workgroup, two windows (120 workgroups) into two, and merges them; five windows per call run unsplit.
+    (Three slices, 65 .. 96 workgroups, are not reached here: tests/test_attention_tiles_gpu.py runs them through the operator,
+    against float64.) The same tiles give the same maps either way
     (summation order differs: fp32 rounding), and the returned matrix equals get_intermediate_feat's bit for bit."""
     from vit_ocm_wmsegmentation_amd import synth
     import vit_ocm_wmsegmentation_amd.dino.vision_transformer as vits

@@ -138,7 +138,8 @@ def _pack(lib, q, k, v, poison):
     return qp, kp, vp
 
 
-# Single-bf16 branches of kernels_attn.hip::launch_attention_bf16 (64-wide heads):
+# Single-bf16 branches of the attention dispatch (csrc/attn_plan.h, 64-wide heads), as ocm_attention_plan reports them
+# (tests/test_attn_plan_host.py asserts every row of this list):
 #   N <= 256 -> attn_small_kernel, one 8-wave workgroup per (batch, head): (1, 5, 1) one partial key tile, (1, 17, 2), (1, 33, 1)
 #               one key into the second tile, (1, 64, 1), (1, 65, 1), (2, 197, 6), (1, 256, 1) the last N it takes, and
 #               (64, 197, 6) config 2's launch: 384 workgroups, every (b, h) compared
@@ -276,7 +277,7 @@ def test_qkv_proj_fp32(lib, dev, B, N, H):
     assert (q[:, N:] == 0).all() and (vt[:, :, N:] == 0).all()
 
 
-# fp32 attention (64-wide heads) is one kernel at every N: kernels_attn.hip::launch_attention's tail, attn_fwd_f32_kernel,
+# fp32 attention (64-wide heads) is one kernel at every N (csrc/attn_plan.h; tests/test_attn_plan_host.py holds the rows): attn_fwd_f32_kernel,
 # 32 query rows per wave, four waves per workgroup, 64-key LDS tiles; attn_probs_f32_kernel / attn_rows_kernel<float> likewise.
 # The shapes reach its edges: (1, 5, 1) one partial key tile, (1, 33, 1) one key past the first 32, (1, 65, 1) into
 # the second LDS tile, (1, 1025, 1) one query row into the ninth workgroup, (64, 197, 6) config 2's 384 (batch, head)

@@ -131,6 +131,11 @@ def test_qkv_proj_x3(lib, dev, B, N, H):
     assert (from_split(vt)[:, :, N:] == 0).all()
 
 
+# Which split-bf16 attention kernel each shape runs is what ocm_attention_plan reports (csrc/attn_plan.h); tests/test_attn_plan_host.py
+# asserts every row of this list and of the two below, so a moved threshold fails there instead of moving a shape to another kernel:
+# (64, 197, 6) the software-pipelined kernel (768 workgroups), N = 2305 and 1025 the eight-wave LDS-DMA kernel, every other shape
+# the wave-split kernel (fewer than 128 workgroups). tests/test_attention_tiles_gpu.py covers the pipelined, key-split and
+# 128-wide kernels at every key-tile count.
 @pytest.mark.parametrize("B,N,H", [(2, 197, 6), (1, 17, 2), (1, 577, 3), (1, 64, 1), (1, 65, 1), (1, 2305, 2),
                                    (1, 5, 1), (1, 32, 2), (1, 33, 1), (1, 1024, 1), (1, 1025, 1),  # one tile, no padding,
                                    # one key into the second tile, the 4-wave / 8-wave switch

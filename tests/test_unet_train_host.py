@@ -1,4 +1,4 @@
-"""Training build_unet, what needs no GPU: the C ABI of the new operators (declared, bound, exported, version 18), their
+"""Training build_unet, what needs no GPU: the C ABI of the new operators (declared, bound, exported, since version 18), their
 argument checks (each returns OCM_EINVAL before anything is launched), the opt-in flag and the chunk rule of the im2col cap."""
 import os
 import re
@@ -21,8 +21,9 @@ def test_symbols_declared_bound_and_exported(lib):
         assert re.search(r"\b%s\(" % name, header), f"{name} is not declared in include/ocm_vit.h"
         assert name in _lib.SIGNATURES, f"{name} is not bound in _lib.SIGNATURES"
         assert getattr(lib, name).argtypes == _lib.SIGNATURES[name][1]
-    assert lib.ocm_abi_version() == 18 == _lib.OCM_ABI_VERSION
-    assert "#define OCM_ABI_VERSION 18" in header
+    # the operators arrived with version 18; library, binding and header name one version, whatever was added since
+    assert lib.ocm_abi_version() == _lib.OCM_ABI_VERSION >= 18
+    assert "#define OCM_ABI_VERSION %d\n" % _lib.OCM_ABI_VERSION in header
 
 
 def test_bn_relu_argument_checks(lib):

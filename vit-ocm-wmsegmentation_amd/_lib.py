@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # OCM_VIT_LIB lets kernel experiments A/B two builds of the same ABI; the default is the in-tree build.
 LIB_PATH = os.environ.get("OCM_VIT_LIB") or os.path.join(_HERE, "libocm_vit.so")
 
-OCM_ABI_VERSION = 18
+OCM_ABI_VERSION = 19
 OCM_OK, OCM_EINVAL, OCM_ESTATE, OCM_EHIP, OCM_ENOMEM, OCM_ENAME = 0, 1, 2, 3, 4, 5
 
 OCM_PREC_BF16 = 0
@@ -110,6 +110,14 @@ class OcmGemmPlanInfo(C.Structure):  # ocm_gemm_plan: the kernel a GEMM-shaped o
 OCM_GEMM_LINEAR, OCM_GEMM_QKV, OCM_GEMM_LINEAR_LD, OCM_GEMM_CONV, OCM_GEMM_RESID_LN = 0, 1, 2, 3, 4
 OCM_PLAN_STATS_EPILOGUE, OCM_PLAN_SPLITK_OFFERED, OCM_PLAN_CONV3X3 = 1, 2, 4
 
+class OcmAttentionPlanInfo(C.Structure):  # ocm_attention_plan: the kernel the attention operators launch for a shape
+    _fields_ = [(n, C.c_int32) for n in ("kernel", "waves", "stages", "kslices", "grid_x", "grid_y", "grid_z", "lds_bytes")] + [
+        ("workspace_need", C.c_uint64)]
+
+
+(OCM_ATTN_BF16_WHOLE, OCM_ATTN_BF16_STREAM, OCM_ATTN_FP32_STREAM, OCM_ATTN_X3_WAVE_SPLIT, OCM_ATTN_X3_PIPELINED, OCM_ATTN_X3_DMA,
+ OCM_ATTN_X3_DMA_KSPLIT) = range(7)
+
 # name -> (restype, argtypes); every symbol include/ocm_vit.h and include/ocm_swin.h declare
 _vp, _i32, _i64, _f32, _sz = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_size_t
 SIGNATURES = {
@@ -139,6 +147,9 @@ SIGNATURES = {
     "ocm_op_qkv_proj_hd": (C.c_int, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "ocm_op_attention_hd": (C.c_int, [_i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _vp]),
     "ocm_op_attention_probs_hd": (C.c_int, [_i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _vp]),
+    "ocm_attention_plan": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _sz, C.POINTER(OcmAttentionPlanInfo)]),
+    "ocm_attention_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32, _i32]),
+    "ocm_op_attention_ws": (C.c_int, [_i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _vp, _sz, _vp]),
     "ocm_op_attention_generic": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                            C.c_int32, C.c_float, C.c_void_p]),
     "ocm_op_attention_probs": (C.c_int, [_i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _f32, _vp]),

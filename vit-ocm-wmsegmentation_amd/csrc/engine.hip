@@ -13,6 +13,7 @@
 #include "host_common.h"
 #include "launch.h"
 #include "dev_knobs.h"
+#include "attn_plan.h"
 
 static thread_local std::string g_err;
 
@@ -827,17 +828,44 @@ extern "C" int ocm_op_qkv_proj_hd(int32_t precision, const void *a, const void *
     return op_qkv_proj(precision, a, w, bias, q, k, vt, qkv_f32, batch, n_tokens, heads, head_dim, stream);
 }
 
-static int op_attention(int32_t precision, const void *q, const void *k, const void *vt, void *ctx, float *lse2,
-                        int32_t batch, int32_t n_tokens, int32_t heads, int32_t head_dim, float scale, void *stream) {
-    int pc = 0, rc = prec_of(precision, &pc);
-    if (rc) return rc;
-    if (!q || !k || !vt || (!ctx && !lse2)) return fail(OCM_EINVAL, "null argument");
+// what every attention entry point refuses, ocm_attention_plan included
+static int attention_shape_ok(int32_t batch, int32_t n_tokens, int32_t heads, int32_t head_dim) {
     if (batch <= 0 || n_tokens <= 0 || heads <= 0) return fail(OCM_EINVAL, "bad shape");
     if (head_dim != 64 && head_dim != 128)
         return fail(OCM_EINVAL, "head_dim %d: the MFMA attention is built for 64- and 128-wide heads", head_dim);
-    HIP_TRY(launch_attention(pc, q, k, vt, ctx, lse2, batch, n_tokens, ocm_n_pad_for(pc, n_tokens), heads, scale,
-                             (hipStream_t)stream, head_dim));
     return OCM_OK;
+}
+
+static int op_attention(int32_t precision, const void *q, const void *k, const void *vt, void *ctx, float *lse2,
+                        int32_t batch, int32_t n_tokens, int32_t heads, int32_t head_dim, float scale, void *stream,
+                        void *workspace = nullptr, size_t workspace_bytes = 0) {
+    int pc = 0, rc = prec_of(precision, &pc);
+    if (rc) return rc;
+    if (!q || !k || !vt || (!ctx && !lse2)) return fail(OCM_EINVAL, "null argument");
+    if ((rc = attention_shape_ok(batch, n_tokens, heads, head_dim))) return rc;
+    if (workspace && (uintptr_t)workspace % 16) return fail(OCM_EINVAL, "workspace must be 16-byte aligned");
+    HIP_TRY(launch_attention(pc, q, k, vt, ctx, lse2, batch, n_tokens, ocm_n_pad_for(pc, n_tokens), heads, scale,
+                             (hipStream_t)stream, head_dim, (float *)workspace, workspace ? workspace_bytes : 0));
+    return OCM_OK;
+}
+
+extern "C" int ocm_attention_plan(int32_t precision, int32_t batch, int32_t n_tokens, int32_t heads, int32_t head_dim,
+                                  size_t workspace_bytes, ocm_attention_plan_info *plan) {
+    int pc = 0, rc = prec_of(precision, &pc);
+    if (rc) return rc;
+    if (!plan) return fail(OCM_EINVAL, "null argument");
+    if ((rc = attention_shape_ok(batch, n_tokens, heads, head_dim))) return rc;
+    const AttnPlan p = attn_plan(pc, batch, n_tokens, heads, head_dim, workspace_bytes, 0, 0);
+    *plan = ocm_attention_plan_info{(int32_t)p.kernel, p.waves, p.stages, p.kslices, (int32_t)p.grid_x, (int32_t)p.grid_y,
+                                    (int32_t)p.grid_z, p.lds_bytes, (uint64_t)p.workspace_need};
+    return OCM_OK;
+}
+
+extern "C" size_t ocm_attention_workspace_bytes(int32_t precision, int32_t batch, int32_t n_tokens, int32_t heads,
+                                                int32_t head_dim) {
+    int pc = 0;
+    if (prec_of(precision, &pc) || attention_shape_ok(batch, n_tokens, heads, head_dim)) return 0;
+    return attention_ksplit_bytes(pc, batch, n_tokens, heads, head_dim);
 }
 
 static int op_attention_probs(int32_t precision, const void *q, const void *k, const float *lse2, float *attn, int32_t batch,
@@ -861,6 +889,12 @@ extern "C" int ocm_op_attention_hd(int32_t precision, const void *q, const void 
                                    int32_t batch, int32_t n_tokens, int32_t heads, int32_t head_dim, float scale,
                                    void *stream) {
     return op_attention(precision, q, k, vt, ctx, lse2, batch, n_tokens, heads, head_dim, scale, stream);
+}
+
+extern "C" int ocm_op_attention_ws(int32_t precision, const void *q, const void *k, const void *vt, void *ctx, float *lse2,
+                                   int32_t batch, int32_t n_tokens, int32_t heads, int32_t head_dim, float scale,
+                                   void *workspace, size_t workspace_bytes, void *stream) {
+    return op_attention(precision, q, k, vt, ctx, lse2, batch, n_tokens, heads, head_dim, scale, stream, workspace, workspace_bytes);
 }
 
 extern "C" int ocm_op_attention_generic(int32_t precision, const float *qkv_f32, void *ctx, float *attn, int32_t batch,

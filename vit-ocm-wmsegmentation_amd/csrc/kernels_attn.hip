@@ -31,6 +31,7 @@
 #define LOG2E 1.4426950408889634f
 int ocm_wt_mask();  // kernels_gemm.hip
 #include "dev_knobs.h"
+#include "attn_plan.h"
 #define OCM_VMCNT_ATTN(n) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(n) : "memory")
 
 // Deferred running maximum of the split-bf16 flash kernels (cdna_hip_programming.md T13). The reference point m of a query row
@@ -366,18 +367,6 @@ __global__ __launch_bounds__(512, 4) void attn_small_kernel(const bf16 *__restri
                 }
         }
     }
-}
-
-static hipError_t launch_attention_bf16(const bf16 *q, const bf16 *k, const bf16 *vt, bf16 *ctx, float *lse2, int batch,
-                                        int n_tokens, int n_pad, int heads, float scale, hipStream_t s, int head_dim = 64) {
-    // 128-wide heads: the streaming kernel at every sequence length; 64-wide: the whole-sequence kernel up to 256 tokens
-    const bool small = head_dim == 64 && n_tokens <= 256;
-    auto kern = head_dim == 128 ? (ctx ? attn_fwd_kernel<true, 128> : attn_fwd_kernel<false, 128>)
-                : small         ? (ctx ? attn_small_kernel<true> : attn_small_kernel<false>)
-                                : (ctx ? attn_fwd_kernel<true> : attn_fwd_kernel<false>);
-    const dim3 grid = small ? dim3(batch * heads) : dim3(((n_tokens + 31) / 32 + 3) / 4, batch * heads);
-    kern<<<grid, dim3(small ? 512 : 256), 0, s>>>(q, k, vt, ctx, lse2, n_tokens, n_pad, heads, scale * LOG2E);
-    return hipGetLastError();
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1705,87 +1694,79 @@ hipError_t launch_attention_generic(int prec, const float *qkv, void *ctx, float
 }
 
 size_t attention_ksplit_bytes(int prec, int batch, int n_tokens, int heads, int head_dim) {
-    if (prec != 2 || head_dim != 64 || n_tokens <= 1024) return 0;
-    const int wgs = (((n_tokens + 31) / 32 + 7) / 8) * batch * heads;
-    if (wgs > 128) return 0;
-    return (size_t)4 * batch * heads * n_tokens * (64 + 4) * sizeof(float);
+    return attn_plan_workspace_bytes(prec, batch, n_tokens, heads, head_dim);
 }
 
+// Computes the plan (attn_plan.h: every threshold lives there) and executes it: one case per kernel id, each naming the
+// instantiations that id can stand for.
 hipError_t launch_attention(int prec, const void *q, const void *k, const void *vt, void *ctx, float *lse2, int batch,
                             int n_tokens, int n_pad, int heads, float scale, hipStream_t s, int head_dim, float *ksplit_ws,
                             size_t ksplit_bytes) {
     if (head_dim != 64 && head_dim != 128) return hipErrorInvalidValue;
-    if (!prec)
-        return launch_attention_bf16((const bf16 *)q, (const bf16 *)k, (const bf16 *)vt, (bf16 *)ctx, lse2, batch,
-                                     n_tokens, n_pad, heads, scale, s, head_dim);
-    const int qtiles = (n_tokens + 31) / 32;
-    const dim3 grid((qtiles + 3) / 4, batch * heads), block(256);
+    if (prec == 2 && n_pad % 32) return hipErrorInvalidValue;
+    const AttnPlan p = attn_plan(prec, batch, n_tokens, heads, head_dim, ksplit_ws ? ksplit_bytes : 0, OCM_KNOB(6), OCM_KNOB(7));
+    const dim3 grid(p.grid_x, p.grid_y, p.grid_z), block(p.waves * 64);
     const float scale2 = scale * LOG2E;
-    if (prec == 1) {
-        const float *Q = (const float *)q, *K = (const float *)k, *V = (const float *)vt;
-        if (head_dim == 128) {  // 128-wide heads: the streaming kernel on 128 KiB of dynamic LDS
-            constexpr int LDSF = 4 * 128 * 256;
-            static OptinMask optin[2];
-            auto kern = ctx ? attn_fwd_f32_kernel<true, 128> : attn_fwd_f32_kernel<false, 128>;
-            if (hipError_t e = lds_optin((const void *)kern, LDSF, optin[ctx ? 1 : 0]); e != hipSuccess) return e;
-            kern<<<grid, block, LDSF, s>>>(Q, K, V, (float *)ctx, lse2, n_tokens, n_pad, heads, scale2);
-        } else {
-            constexpr int LDSF64 = 4 * 64 * 256;  // 64 KiB: K[2] | Vt[2]
-            auto kern = ctx ? attn_fwd_f32_kernel<true> : attn_fwd_f32_kernel<false>;
-            kern<<<grid, block, LDSF64, s>>>(Q, K, V, (float *)ctx, lse2, n_tokens, n_pad, heads, scale2);
+    const char *Q = (const char *)q, *K = (const char *)k, *V = (const char *)vt;  // split pairs
+    switch (p.kernel) {
+        case ATTN_BF16_WHOLE: {
+            auto kern = ctx ? attn_small_kernel<true> : attn_small_kernel<false>;
+            kern<<<grid, block, 0, s>>>((const bf16 *)q, (const bf16 *)k, (const bf16 *)vt, (bf16 *)ctx, lse2, n_tokens, n_pad, heads,
+                                        scale2);
+            break;
         }
-        return hipGetLastError();
-    }
-    if (n_pad % 32) return hipErrorInvalidValue;
-    const char *Q = (const char *)q, *K = (const char *)k, *V = (const char *)vt;
-    if (head_dim == 128) {  // 128-wide heads (model.py:93-103): four wavefronts, two stages
-        auto kern = ctx ? attn_fwd_x3_dma_kernel<true, 4, 2, 128, 2> : attn_fwd_x3_dma_kernel<false, 4, 2, 128, 2>;
-        kern<<<grid, block, 0, s>>>(Q, K, V, (char *)ctx, lse2, n_tokens, n_pad, heads, scale2, 0, nullptr);
-        return hipGetLastError();
-    }
-    // long sequences: 8 waves per workgroup share each K / V^T tile (half the L2 -> LDS traffic per query)
-    // (the dozen workgroups of a one-tile call at N = 197 stay on four waves: eight measured 0.65 -> 0.68 ms per forward)
-    const bool wide = (n_tokens > 1024 && OCM_KNOB(7) != 1) || OCM_KNOB(7) == 2;
-    if (wide) {
-        const dim3 grid8((qtiles + 7) / 8, batch * heads), block8(512);
-        // Long sequence, few workgroups (one ViT-S/8 window per call: 60 of them, 73 key tiles each): cut the key range into
-        // up to four slices per workgroup and merge (attn_merge_x3_kernel)
-        // (the statistics-only pass of get_last_selfattention takes the same slices, so the log-sum-exp — and with it the
-        // returned probabilities — has the same bits from both entry points)
-        if (ksplit_ws && OCM_KNOB(7) == 0) {
-            const int wgs = (int)(grid8.x * grid8.y);
-            // (eight slices of 9-10 tiles measure slower than four of 18-19: 36.6 + 7.4 us against 34.3 + 5.1 us with the merge)
-            const int want = wgs <= 64 ? 4 : wgs <= 96 ? 3 : wgs <= 128 ? 2 : 1;
-            const int per = (qtiles + want - 1) / want, nslice = (qtiles + per - 1) / per;  // every slice owns >= 1 tile
-            const size_t need = (size_t)nslice * batch * heads * n_tokens * (64 + 4) * sizeof(float);
-            if (nslice > 1 && need <= ksplit_bytes) {
-                auto kern = ctx ? attn_fwd_x3_dma_kernel<true, 8, 2, 64, 3, true> : attn_fwd_x3_dma_kernel<false, 8, 2, 64, 3, true>;
-                kern<<<dim3(grid8.x, grid8.y, nslice), block8, 0, s>>>(Q, K, V, (char *)ctx, lse2, n_tokens, n_pad, heads, scale2,
-                                                                       0, ksplit_ws);
-                if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-                const int64_t rows = (int64_t)batch * heads * n_tokens;
-                attn_merge_x3_kernel<64><<<dim3((unsigned)((rows + 15) / 16)), dim3(256), 0, s>>>(
-                    ksplit_ws, nslice, (char *)ctx, lse2, batch * heads, n_tokens, heads);
-                return hipGetLastError();
+        case ATTN_BF16_STREAM: {
+            auto kern = head_dim == 128 ? (ctx ? attn_fwd_kernel<true, 128> : attn_fwd_kernel<false, 128>)
+                                        : (ctx ? attn_fwd_kernel<true> : attn_fwd_kernel<false>);
+            kern<<<grid, block, 0, s>>>((const bf16 *)q, (const bf16 *)k, (const bf16 *)vt, (bf16 *)ctx, lse2, n_tokens, n_pad, heads,
+                                        scale2);
+            break;
+        }
+        case ATTN_F32_STREAM: {
+            auto kern = head_dim == 128 ? (ctx ? attn_fwd_f32_kernel<true, 128> : attn_fwd_f32_kernel<false, 128>)
+                                        : (ctx ? attn_fwd_f32_kernel<true> : attn_fwd_f32_kernel<false>);
+            if (p.lds_bytes > 64 * 1024) {  // 128-wide heads: 128 KiB of dynamic LDS
+                static OptinMask optin[2];
+                if (hipError_t e = lds_optin((const void *)kern, p.lds_bytes, optin[ctx ? 1 : 0]); e != hipSuccess) return e;
             }
+            kern<<<grid, block, p.lds_bytes, s>>>((const float *)q, (const float *)k, (const float *)vt, (float *)ctx, lse2, n_tokens,
+                                                  n_pad, heads, scale2);
+            break;
         }
-        auto kern = ctx ? attn_fwd_x3_dma_kernel<true, 8, 2> : attn_fwd_x3_dma_kernel<false, 8, 2>;
-        kern<<<grid8, block8, 0, s>>>(Q, K, V, (char *)ctx, lse2, n_tokens, n_pad, heads, scale2, (ocm_wt_mask() >> 4) & 1,
-                                      nullptr);
-        return hipGetLastError();
+        case ATTN_X3_WS: {
+            auto kern = ctx ? attn_fwd_x3_ws_kernel<true> : attn_fwd_x3_ws_kernel<false>;
+            static OptinMask optin[2];
+            if (hipError_t e = lds_optin((const void *)kern, p.lds_bytes, optin[ctx ? 1 : 0]); e != hipSuccess) return e;
+            kern<<<grid, block, p.lds_bytes, s>>>(Q, K, V, (char *)ctx, lse2, n_tokens, n_pad, heads, scale2);
+            break;
+        }
+        case ATTN_X3_PP: {
+            auto kern = ctx ? attn_fwd_x3_pp_kernel<true> : attn_fwd_x3_pp_kernel<false>;
+            kern<<<grid, block, 0, s>>>(Q, K, V, (char *)ctx, lse2, n_tokens, n_pad, heads, scale2);
+            break;
+        }
+        case ATTN_X3_DMA:
+            if (head_dim == 128) {  // four wavefronts, two stages
+                auto kern = ctx ? attn_fwd_x3_dma_kernel<true, 4, 2, 128, 2> : attn_fwd_x3_dma_kernel<false, 4, 2, 128, 2>;
+                kern<<<grid, block, 0, s>>>(Q, K, V, (char *)ctx, lse2, n_tokens, n_pad, heads, scale2, 0, nullptr);
+            } else {  // eight wavefronts, three stages
+                auto kern = ctx ? attn_fwd_x3_dma_kernel<true, 8, 2> : attn_fwd_x3_dma_kernel<false, 8, 2>;
+                kern<<<grid, block, 0, s>>>(Q, K, V, (char *)ctx, lse2, n_tokens, n_pad, heads, scale2, (ocm_wt_mask() >> 4) & 1,
+                                            nullptr);
+            }
+            break;
+        case ATTN_X3_DMA_KSPLIT: {
+            // (the statistics-only pass of get_last_selfattention takes the same slices, so the log-sum-exp — and with it the
+            // returned probabilities — has the same bits from both entry points)
+            auto kern = ctx ? attn_fwd_x3_dma_kernel<true, 8, 2, 64, 3, true> : attn_fwd_x3_dma_kernel<false, 8, 2, 64, 3, true>;
+            kern<<<grid, block, 0, s>>>(Q, K, V, (char *)ctx, lse2, n_tokens, n_pad, heads, scale2, 0, ksplit_ws);
+            if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+            const int64_t rows = (int64_t)batch * heads * n_tokens;
+            attn_merge_x3_kernel<64><<<dim3((unsigned)((rows + 15) / 16)), dim3(256), 0, s>>>(
+                ksplit_ws, p.kslices, (char *)ctx, lse2, batch * heads, n_tokens, heads);
+            break;
+        }
     }
-    // a handful of workgroups (one tile per call): the keys of a 32-query tile split over the four waves of a workgroup;
-    // otherwise the software-pipelined kernel (knob 6 = 4: everywhere)
-    const bool split = grid.x * grid.y < 128 && OCM_KNOB(6) != 4;
-    auto kern = split ? (ctx ? attn_fwd_x3_ws_kernel<true> : attn_fwd_x3_ws_kernel<false>)
-                      : (ctx ? attn_fwd_x3_pp_kernel<true> : attn_fwd_x3_pp_kernel<false>);
-    constexpr int LDSWS = 4 * 2 * 2 * 8192;  // wave-split: four waves x two slots of K | V^T
-    if (split) {
-        static OptinMask optin[2];
-        if (hipError_t e = lds_optin((const void *)kern, LDSWS, optin[ctx ? 1 : 0]); e != hipSuccess) return e;
-    }
-    kern<<<split ? dim3(qtiles, batch * heads) : grid, block, split ? LDSWS : 0, s>>>(Q, K, V, (char *)ctx, lse2, n_tokens,
-                                                                                      n_pad, heads, scale2);
     return hipGetLastError();
 }
 

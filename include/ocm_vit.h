@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define OCM_ABI_VERSION 19
+#define OCM_ABI_VERSION 20
 
 enum {
     OCM_OK = 0,
@@ -646,6 +646,43 @@ size_t ocm_kmeans_lloyd_workspace_bytes(int32_t S, int32_t dim);
 int ocm_op_kmeans_lloyd(const float *X, int32_t S, int32_t dim, const float *centers, const int32_t *labels_old,
                         int32_t *labels, float *centers_new, double *sums, double *info, int32_t assign_only, void *workspace,
                         size_t workspace_bytes, void *stream);
+
+/* ---- region-queried attention: the query points of analyse_attention.py --region_query (:183-223; utils.py:237-281
+ * yen_threshold / morphology_cleaning, data.py:216-233 get_ROIs; kernels_morph.hip) ----
+ * Every operator works on `batch` independent (h, w) images (sides 1..32768, h * w <= 2^30: int32 pixel indices, batch <=
+ * 65535). Masks are uint8, nonzero = foreground; masks written here hold 0 / 1. Refused arguments return OCM_EINVAL (a short
+ * workspace OCM_ENOMEM) before any launch. All arithmetic is on integers: the same inputs give the same bits. */
+/* mask = (level <= img) (utils.py:242) */
+int ocm_op_mask_ge_u8(const uint8_t *img, uint8_t *mask, int64_t count, int32_t level, void *stream);
+/* 8-connected components (skimage.measure.label(connectivity=2) / scipy.ndimage.label with the 3x3 structure): labels
+ * [batch][h][w] int32, 0 on background and 1..n on foreground, numbered in raster order of each component's first pixel;
+ * counts[b] = n. Union-find on pixel indices in `labels` itself: LDS pass per ocm_label8_tile() x ocm_label8_tile() tile,
+ * tile-border pass with integer atomic minima, flatten, scan of the root flags. The workspace needs no initialisation. */
+int32_t ocm_label8_tile(void);
+size_t ocm_label8_workspace_bytes(int32_t batch, int32_t h, int32_t w);
+int ocm_op_label8(const uint8_t *mask, int32_t *labels, int32_t *counts, int32_t batch, int32_t h, int32_t w, void *workspace,
+                  size_t workspace_bytes, void *stream);
+/* Exact sums per label 1..max_regions of a label image (labels outside that range are ignored): area, sum of row and of
+ * column indices as int64 [batch][max_regions], bbox int32 [batch][max_regions][4] = (min_row, min_col, max_row + 1,
+ * max_col + 1) as skimage's regionprops gives it ((h, w, 0, 0) for a label without pixels). centroid = sum / area. */
+int ocm_op_region_stats(const int32_t *labels, int32_t batch, int32_t h, int32_t w, int32_t max_regions, int64_t *area,
+                        int64_t *sum_row, int64_t *sum_col, int32_t *bbox, void *stream);
+/* skimage.morphology.remove_small_objects(mask, min_size, connectivity=2) of a boolean mask: out = 1 on the pixels of
+ * 8-connected components of at least min_size pixels, else 0. out may be mask itself. */
+size_t ocm_remove_small_objects_workspace_bytes(int32_t batch, int32_t h, int32_t w);
+int ocm_op_remove_small_objects(const uint8_t *mask, uint8_t *out, int32_t batch, int32_t h, int32_t w, int32_t min_size,
+                                void *workspace, size_t workspace_bytes, void *stream);
+/* scipy.ndimage.binary_dilation (op 0) / binary_erosion (op 1) with a size x size footprint (size odd, 1..7; bit
+ * dy * size + dx of footprint_bits = footprint[dy][dx], centre size / 2) and border_value 0 / 1 for the pixels outside the
+ * image. skimage's binary_closing(mask, disk(2)) is dilation with border 0, then erosion with border 1. src != dst. */
+int ocm_op_binary_morph(const uint8_t *src, uint8_t *dst, int32_t batch, int32_t h, int32_t w, uint64_t footprint_bits,
+                        int32_t size, int32_t op, int32_t border_value, void *stream);
+/* analyse_attention.py:196-211 — rows (tiles, heads, n_rows, pixels) fp32 attention rows; for tile t the rows
+ * sel[offsets[t] .. offsets[t+1]) (indices into n_rows, duplicates allowed, n_sel entries in all): the head mean of each
+ * exactly as ocm_op_head_mean computes it, the maps added in that order in fp32 and divided by their number
+ * (np.mean(list_of_maps, axis=0)). maps (tiles, pixels). An empty (or out-of-range) selection writes NaN. */
+int ocm_op_query_mean(const float *rows, const int32_t *sel, const int32_t *offsets, float *maps, int32_t tiles, int32_t heads,
+                      int32_t n_rows, int32_t pixels, int32_t n_sel, void *stream);
 
 /* ---- sliding-window index math (host, integer; sw_processing.py:151-163) ---- */
 /* Number of windows per axis: len(range(0, size - 2*stride, stride)). */

@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # OCM_VIT_LIB lets kernel experiments A/B two builds of the same ABI; the default is the in-tree build.
 LIB_PATH = os.environ.get("OCM_VIT_LIB") or os.path.join(_HERE, "libocm_vit.so")
 
-OCM_ABI_VERSION = 19
+OCM_ABI_VERSION = 20
 OCM_OK, OCM_EINVAL, OCM_ESTATE, OCM_EHIP, OCM_ENOMEM, OCM_ENAME = 0, 1, 2, 3, 4, 5
 
 OCM_PREC_BF16 = 0
@@ -242,6 +242,15 @@ SIGNATURES = {
     "ocm_op_kmeans_dist": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp]),
     "ocm_kmeans_lloyd_workspace_bytes": (_sz, [_i32, _i32]),
     "ocm_op_kmeans_lloyd": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _sz, _vp]),
+    "ocm_op_mask_ge_u8": (C.c_int, [_vp, _vp, _i64, _i32, _vp]),
+    "ocm_label8_tile": (_i32, []),
+    "ocm_label8_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "ocm_op_label8": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _sz, _vp]),
+    "ocm_op_region_stats": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "ocm_remove_small_objects_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "ocm_op_remove_small_objects": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _sz, _vp]),
+    "ocm_op_binary_morph": (C.c_int, [_vp, _vp, _i32, _i32, _i32, C.c_uint64, _i32, _i32, _i32, _vp]),
+    "ocm_op_query_mean": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "ocm_sw_count": (_i32, [_i32, _i32]),
     "ocm_sw_origins": (_i32, [_i32, _i32, _i32, C.POINTER(_i32), _i32]),
     "ocm_sw_shard": (_i32, [_i32, _i32, _i32, C.POINTER(_i32), C.POINTER(_i32)]),

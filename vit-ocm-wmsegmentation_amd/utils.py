@@ -7,6 +7,11 @@ region-query index of analyse_attention.py, on device.
                       "heatmap_threshold" methods), on device
   kmeans_feature      reference utils.py:171-197 (eval.py's "k-means_feature_clustering"), clustered on device
   DiceLoss            reference utils.py:410-424 (finetune.py's loss), forward and backward on device
+  yen_threshold, get_ROIs, morphology_cleaning
+                      reference utils.py:237-281: the Yen mask, its clean-up (remove_small_objects -> binary_closing ->
+                      label) and the region centroids that analyse_attention.py --region_query queries, on device
+                      (kernels_morph.hip); label_regions / region_stats / remove_small_objects / binary_closing are
+                      the skimage pieces they are made of
 """
 import ctypes as C
 
@@ -79,6 +84,28 @@ def skimage_otsu_from_hist(hist_dev):
     mean2 = (np.cumsum((counts * centers)[::-1]) / weight2[::-1])[::-1]
     variance12 = weight1[:-1] * weight2[1:] * (mean1[:-1] - mean2[1:]) ** 2
     return int(centers[int(np.argmax(variance12))])
+
+
+def skimage_yen_from_hist(hist_dev):
+    """skimage.filters.threshold_yen (0.19.3, reference utils.py:241) from a 256-bin device histogram of a uint8 image:
+    integer bins over [min, max], pmf = counts / total, P1 = cumsum(pmf), P1_sq = cumsum(pmf^2), P2_sq = reversed
+    cumsum of pmf^2, crit = log((P1_sq[:-1] * P2_sq[1:])^-1 * (P1[:-1] * (1 - P1[:-1]))^2), the bin at its first
+    maximum; a constant image returns its value. Evaluated in float64 on the host (a 256-step scalar computation, like
+    the reference). scikit-image is not installable here: restated from its source, parity unpinned."""
+    h = hist_dev.cpu().numpy().astype(np.float64) if isinstance(hist_dev, torch.Tensor) else np.asarray(hist_dev, np.float64)
+    nz = np.nonzero(h)[0]
+    if nz.size == 0:
+        raise ValueError("empty histogram")
+    lo, hi = int(nz[0]), int(nz[-1])
+    if lo == hi:
+        return lo
+    pmf = h[lo:hi + 1] / h[lo:hi + 1].sum()
+    P1 = np.cumsum(pmf)
+    P1_sq = np.cumsum(pmf ** 2)
+    P2_sq = np.cumsum(pmf[::-1] ** 2)[::-1]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        crit = np.log(((P1_sq[:-1] * P2_sq[1:]) ** -1) * (P1[:-1] * (1.0 - P1[:-1])) ** 2)
+    return lo + int(np.argmax(crit))
 
 
 def histogram_u8(img_u8):
@@ -234,3 +261,174 @@ class DiceLoss(nn.Module):
         x = inputs.to(torch.float32).contiguous().reshape(-1)
         t = targets.detach().to(device=inputs.device, dtype=torch.float32).contiguous().reshape(-1)
         return _DiceLossFn.apply(x, t, float(smooth))
+
+
+# ---- the query points of analyse_attention.py --region_query (reference utils.py:237-281) ------------------------------------
+DISK2 = ((0, 0, 1, 0, 0), (0, 1, 1, 1, 0), (1, 1, 1, 1, 1), (0, 1, 1, 1, 0), (0, 0, 1, 0, 0))  # skimage.morphology.disk(2)
+
+
+def footprint_bits(footprint):
+    """(size, bits) of a square 0/1 footprint with an odd side <= 7: bit dy * size + dx = footprint[dy][dx]."""
+    fp = np.asarray(footprint)
+    if fp.ndim != 2 or fp.shape[0] != fp.shape[1] or fp.shape[0] % 2 == 0 or fp.shape[0] > 7:
+        raise ValueError(f"footprint must be square with an odd side <= 7, got shape {fp.shape}")
+    size = int(fp.shape[0])
+    return size, sum(1 << i for i, v in enumerate(fp.reshape(-1)) if v)
+
+
+def _mask_batch(mask, what="mask"):
+    """A bool / uint8 (H,W) or (B,H,W) HIP tensor as a contiguous uint8 (B,H,W) view (nonzero = foreground)."""
+    _require_hip(mask, what)
+    if mask.dtype not in (torch.bool, torch.uint8) or mask.dim() not in (2, 3):
+        raise ValueError(f"expected a bool or uint8 (H,W) or (B,H,W) {what}, got {mask.dtype} {tuple(mask.shape)}")
+    m = mask.contiguous()
+    m = m.view(torch.uint8) if m.dtype == torch.bool else m
+    return m.reshape((-1,) + tuple(m.shape[-2:]))
+
+
+def _like(mask, out_u8):
+    """A 0/1 uint8 (B,H,W) result in the shape of `mask`, as bool."""
+    return out_u8.view(torch.bool).reshape(mask.shape)
+
+
+def binary_morph(mask, footprint, op, border_value):
+    """scipy.ndimage.binary_dilation (op 0) / binary_erosion (op 1) of a bool mask with a square odd footprint (side <= 7)
+    and `border_value` outside the image (ocm_op_binary_morph). Returns a bool tensor of the mask's shape."""
+    m = _mask_batch(mask)
+    size, bits = footprint_bits(footprint)
+    out = torch.empty_like(m)
+    B, H, W = m.shape
+    with torch.cuda.device(m.device):
+        _lib.check(_lib.load().ocm_op_binary_morph(_p(m), _p(out), B, H, W, bits, size, int(op), int(border_value), _stream()))
+    return _like(mask, out)
+
+
+def binary_closing(mask, footprint=DISK2):
+    """skimage.morphology.binary_closing (0.19.3): binary_dilation (scipy's default border_value 0), then binary_erosion
+    with border_value=True — the image edge does not erode what the dilation grew against it."""
+    return binary_morph(binary_morph(mask, footprint, 0, 0), footprint, 1, 1)
+
+
+def remove_small_objects(mask, min_size=20):
+    """skimage.morphology.remove_small_objects(mask, min_size, connectivity=2) of a bool mask: 8-connected components
+    with fewer than min_size pixels are cleared (ocm_op_remove_small_objects)."""
+    m = _mask_batch(mask)
+    B, H, W = m.shape
+    lib = _lib.load()
+    out = torch.empty_like(m)
+    nbytes = lib.ocm_remove_small_objects_workspace_bytes(B, H, W)
+    ws = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=m.device)
+    with torch.cuda.device(m.device):
+        _lib.check(lib.ocm_op_remove_small_objects(_p(m), _p(out), B, H, W, int(min_size), _p(ws), nbytes, _stream()))
+    return _like(mask, out)
+
+
+def label_regions(mask):
+    """skimage.measure.label(mask, connectivity=2, return_num=True) on device for an (H,W) or (B,H,W) bool / uint8 mask:
+    (labels int32 of the mask's shape — 0 background, 1..n in raster order of each component's first pixel —, counts:
+    an int32 (B,) device tensor, or for an (H,W) mask a 0-dim one)."""
+    m = _mask_batch(mask)
+    B, H, W = m.shape
+    lib = _lib.load()
+    labels = torch.empty((B, H, W), dtype=torch.int32, device=m.device)
+    counts = torch.empty(B, dtype=torch.int32, device=m.device)
+    nbytes = lib.ocm_label8_workspace_bytes(B, H, W)
+    ws = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=m.device)
+    with torch.cuda.device(m.device):
+        _lib.check(lib.ocm_op_label8(_p(m), _p(labels), _p(counts), B, H, W, _p(ws), nbytes, _stream()))
+    return labels.reshape(mask.shape), (counts[0] if mask.dim() == 2 else counts)
+
+
+def region_stats(labels, max_regions):
+    """Exact integer sums of an int32 (H,W) or (B,H,W) label image for the labels 1..max_regions (ocm_op_region_stats):
+    dict(area, sum_row, sum_col: int64 (B, max_regions); bbox: int32 (B, max_regions, 4) = (min_row, min_col,
+    max_row + 1, max_col + 1)) on the device. regionprops' centroid is (sum_row / area, sum_col / area) in float64."""
+    _require_hip(labels, "labels")
+    if labels.dtype != torch.int32 or labels.dim() not in (2, 3):
+        raise ValueError(f"expected an int32 (H,W) or (B,H,W) label image, got {labels.dtype} {tuple(labels.shape)}")
+    lab = labels.contiguous().reshape((-1,) + tuple(labels.shape[-2:]))
+    B, H, W = lab.shape
+    R = max(int(max_regions), 1)
+    sums = torch.empty((3, B, R), dtype=torch.int64, device=lab.device)
+    bbox = torch.empty((B, R, 4), dtype=torch.int32, device=lab.device)
+    with torch.cuda.device(lab.device):
+        _lib.check(_lib.load().ocm_op_region_stats(_p(lab), B, H, W, R, _p(sums[0]), _p(sums[1]), _p(sums[2]), _p(bbox),
+                                                   _stream()))
+    return dict(area=sums[0], sum_row=sums[1], sum_col=sums[2], bbox=bbox)
+
+
+def yen_threshold(img, output_directory="", save=False, return_level=False):
+    """utils.py:237-248 on device. img: an (H,W) uint8 tensor, or the float (C,H,W) image tensor (turned into the PIL
+    "L" image the reference thresholds by image_to_gray_u8). Returns the bool mask `th <= img` with th =
+    skimage_yen_from_hist of the image's device histogram (and th itself with return_level=True). Saving the figure
+    (save=True) is the reference's matplotlib side effect and is not part of this path."""
+    if save:
+        raise NotImplementedError("yen_threshold(save=True) writes a figure with matplotlib in the reference; not on this path")
+    _require_hip(img, "img")
+    if img.dtype == torch.uint8:
+        if img.dim() != 2:
+            raise ValueError(f"expected an (H,W) uint8 image, got {tuple(img.shape)}")
+        img_u8 = img.contiguous()
+        hist = histogram_u8(img_u8)
+    else:
+        img_u8, hist = image_to_gray_u8(img)
+    level = skimage_yen_from_hist(hist)
+    mask = torch.empty_like(img_u8)
+    with torch.cuda.device(img_u8.device):
+        _lib.check(_lib.load().ocm_op_mask_ge_u8(_p(img_u8), _p(mask), img_u8.numel(), level, _stream()))
+    mask = mask.view(torch.bool)
+    return (mask, level) if return_level else mask
+
+
+def get_ROIs(mask):
+    """utils.py:250-254 on device: remove_small_objects(min_size=20, connectivity=2) -> binary_closing(disk(2)) -> label.
+    A bool (H,W) or (B,H,W) mask goes through the component-wise chain. A uint8 {0, 255} mask — what data.py:222-224
+    passes — gets skimage's integer-input behaviour: remove_small_objects reads the array as a label image, so the white
+    class is cleared only when it holds fewer than 20 pixels IN TOTAL, whatever their components. Returns the int32
+    label image."""
+    _require_hip(mask, "mask")
+    if mask.dtype == torch.uint8:
+        if mask.dim() != 2:
+            raise ValueError(f"a uint8 mask is one (H,W) image, got {tuple(mask.shape)}")
+        hist = histogram_u8(mask).cpu().numpy()
+        if int(hist[1:255].sum()):
+            raise ValueError("a uint8 mask must hold only 0 and 255 (data.py:222-223)")
+        if int(hist[255]) < 20:
+            return torch.zeros(mask.shape, dtype=torch.int32, device=mask.device)
+        cleaned = mask
+    else:
+        cleaned = remove_small_objects(mask, 20)
+    return label_regions(binary_closing(cleaned))[0]
+
+
+def region_centroids(labels, counts, min_area=10):
+    """regionprops of int32 (B,H,W) label images with counts[b] regions each: per image the list of (x0, y0) =
+    (centroid column, centroid row) float64 pairs of the regions with area >= min_area, in label order (utils.py:269-281)."""
+    counts = [int(c) for c in counts.reshape(-1).cpu().tolist()]
+    st = region_stats(labels, max(counts + [1]))
+    area, sr, sc = (st[k].cpu().numpy() for k in ("area", "sum_row", "sum_col"))
+    points = []
+    for b, n in enumerate(counts):
+        keep = np.nonzero(area[b, :n] >= min_area)[0]
+        a = area[b, keep].astype(np.float64)
+        points.append(list(zip((sc[b, keep] / a).tolist(), (sr[b, keep] / a).tolist())))
+    return points
+
+
+def morphology_cleaning(mask, output_directory="", save=False, as_numpy=True):
+    """utils.py:256-281 on device: the get_ROIs chain on a bool (H,W) mask, then the (x0, y0) = (centroid column,
+    centroid row) points of the regions with area >= 10 in label order — a list of float pairs as the reference returns
+    it, or with as_numpy=False a float64 (n, 2) tensor on the mask's device. The centroids are exact integer sums
+    divided in float64, which is what regionprops computes. Drawing the boxes (save=True) is the reference's matplotlib
+    side effect and is not part of this path."""
+    if save:
+        raise NotImplementedError("morphology_cleaning(save=True) draws figures with matplotlib in the reference; "
+                                  "not on this path")
+    _require_hip(mask, "mask")
+    if mask.dtype != torch.bool or mask.dim() != 2:
+        raise ValueError(f"expected a bool (H,W) mask, got {mask.dtype} {tuple(mask.shape)}")
+    labels, count = label_regions(binary_closing(remove_small_objects(mask, 20)))
+    points = region_centroids(labels[None], count.reshape(1))[0]
+    if as_numpy:
+        return points
+    return torch.tensor(points, dtype=torch.float64, device=mask.device).reshape(-1, 2)

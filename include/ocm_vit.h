@@ -684,6 +684,33 @@ int ocm_op_binary_morph(const uint8_t *src, uint8_t *dst, int32_t batch, int32_t
 int ocm_op_query_mean(const float *rows, const int32_t *sel, const int32_t *offsets, float *maps, int32_t tiles, int32_t heads,
                       int32_t n_rows, int32_t pixels, int32_t n_sel, void *stream);
 
+/* ---- Chan-Vese level sets: skimage.segmentation.chan_vese (0.19.x) as utils.py:199-225 calls it (eval.py's "chan-vese" /
+ * "chan-vese_ours" methods; kernels_levelset.hip) ----
+ * For each of `batch` independent images: image [batch][h][w] float64, already normalised as skimage does (img - min, then
+ * / max when that is not 0); phi [batch][h][w] float64, the initial level set on entry and the final one on return;
+ * mask[b][y][x] = phi > 0 (0 / 1); iters[b] = the number of iterations image b ran. The loop, all in float64:
+ *   i = 0; phivar = DBL_MAX
+ *   while phivar > tol and i < max_num_iter:
+ *     c, e, w, s, n = phi at the pixel and its x+1, x-1, y+1, y-1 neighbours (edge-replicated); eta = 1e-16
+ *     xp = e-c  xn = c-w  x0 = (e-w)/2  yp = s-c  yn = c-n  y0 = (s-n)/2
+ *     C1 = 1/sqrt(eta+xp^2+y0^2)  C2 = 1/sqrt(eta+xn^2+y0^2)  C3 = 1/sqrt(eta+x0^2+yp^2)  C4 = 1/sqrt(eta+x0^2+yn^2)
+ *     K = e C1 + w C2 + s C3 + n C4;  H = phi > 0 (the sharp Heaviside)
+ *     c1 = sum(image H) / sum(H) when sum(H) != 0, else sum(image H); c2 the same with 1 - H
+ *     D = -lambda1 (image-c1)^2 + lambda2 (image-c2)^2;  delta = 1 / (1 + phi^2)
+ *     new = (phi + dt delta (mu K + D)) / (1 + mu dt delta (C1+C2+C3+C4))
+ *     phivar = sqrt(mean((new - phi)^2)); phi = new; i += 1
+ * Every term reads the old phi. One stream-ordered launch per iteration, no host synchronisation; the images of a batch stop
+ * independently. Sums are per-workgroup partials added in a fixed order (no floating-point atomics): the same inputs give the
+ * same bits. The kernels work on ocm_chan_vese_tile() x ocm_chan_vese_tile() tiles. The workspace needs no initialisation.
+ * Refused before any launch with OCM_EINVAL (a short or null workspace: OCM_ENOMEM): batch outside 1..65535, a side outside
+ * 1..32768 or h * w > 2^30, max_num_iter outside 0..10000, a non-finite or negative mu, dt or tol, a non-finite lambda, null
+ * pointers. max_num_iter = 0 returns phi unchanged, its mask and iters = 0. */
+int32_t ocm_chan_vese_tile(void);
+size_t ocm_chan_vese_workspace_bytes(int32_t batch, int32_t h, int32_t w);
+int ocm_op_chan_vese(const double *image, double *phi, uint8_t *mask, int32_t *iters, int32_t batch, int32_t h, int32_t w,
+                     double mu, double lambda1, double lambda2, double tol, int32_t max_num_iter, double dt, void *workspace,
+                     size_t workspace_bytes, void *stream);
+
 /* ---- sliding-window index math (host, integer; sw_processing.py:151-163) ---- */
 /* Number of windows per axis: len(range(0, size - 2*stride, stride)). */
 int32_t ocm_sw_count(int32_t size, int32_t stride);

@@ -9,10 +9,11 @@ import torch
 
 from . import _lib
 from .engine import _p, _stream
-from .utils import kmeans_feature_labels, threshold
+from .utils import chan_vese_level_set, chan_vese_result_u8, image_to_gray_u8, kmeans_feature_labels, threshold
 
 METHODS = {"ours": 0, "otsu": 1, "heatmap_threshold": 2}  # index into threshold()'s (th, th2, th3)
 KMEANS_FEATURE = "k-means_feature_clustering"
+CHAN_VESE = ("chan-vese", "chan-vese_ours")  # chan_vese_segment
 
 
 def _head_mean_small(model, tiles, median_filter):
@@ -82,7 +83,8 @@ def segment_images(model, images, method="ours", median_filter=1, as_numpy=False
     of the last block's keys, upsampled to S x S, image by image (see kmeans_segment).
     Returns (masks (B,S,S) uint8 in {0,255}, average_attentions (B,S,S) fp32)."""
     if method not in METHODS and method != KMEANS_FEATURE:
-        raise ValueError(f"method {method!r} is not on this path (k-means / chan-vese stay on the host in the reference)")
+        raise ValueError(f"method {method!r} is not on this path (k-means / chan-vese stay on the host in the reference; "
+                         "chan_vese_segment runs the chan-vese methods on the device)")
     if not 1 <= int(median_filter) <= 15:
         raise ValueError("median_filter must be in 1..15")
     if method == KMEANS_FEATURE:
@@ -120,3 +122,26 @@ def kmeans_segment(model, images):
         labels = kmeans_feature_labels(X)["labels"]
         masks[b] = torch.from_numpy((labels.reshape(S, S) * 255).astype(np.uint8)).to(images.device)
     return masks
+
+
+@torch.no_grad()
+def chan_vese_segment(model, images, method="chan-vese_ours", median_filter=1, as_numpy=False):
+    """The mask eval.py scores for `method` in {"chan-vese", "chan-vese_ours"} (eval.py:182-185, utils.py:199-225) for every
+    image of a batch ((B,C,S,S), or (B,crops,C,s,s) for --crop 4 / 16): average_attention_maps once, the gray uint8 image and
+    its attention-weighted version per image, then ONE ocm_op_chan_vese call for all 2 B level sets (as the reference computes
+    both whichever method is asked for). Only the final masks leave the device.
+    Returns (masks (B,S,S) uint8 in {0,255}, average_attentions (B,S,S) fp32)."""
+    if method not in CHAN_VESE:
+        raise ValueError(f"method {method!r}: chan_vese_segment runs {CHAN_VESE}")
+    if not 1 <= int(median_filter) <= 15:
+        raise ValueError("median_filter must be in 1..15")
+    maps = average_attention_maps(model, images, median_filter)
+    gray_src = tile_crops_image(images) if images.dim() == 5 else images
+    gray = torch.stack([image_to_gray_u8(gray_src[b])[0] for b in range(gray_src.shape[0])])
+    if tuple(gray.shape) != tuple(maps.shape):
+        raise ValueError(f"images {tuple(gray.shape)} and attention maps {tuple(maps.shape)} differ in size")
+    both = torch.cat([chan_vese_result_u8(gray, maps), gray])  # [0, B): "chan-vese_ours", [B, 2B): "chan-vese"
+    B = gray.shape[0]
+    masks = chan_vese_level_set(both)[0].view(torch.uint8) * 255
+    masks = masks[:B] if method == "chan-vese_ours" else masks[B:]
+    return (masks.cpu().numpy(), maps.cpu().numpy()) if as_numpy else (masks.contiguous(), maps)

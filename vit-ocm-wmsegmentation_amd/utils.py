@@ -12,6 +12,9 @@ region-query index of analyse_attention.py, on device.
                       label) and the region centroids that analyse_attention.py --region_query queries, on device
                       (kernels_morph.hip); label_regions / region_stats / remove_small_objects / binary_closing are
                       the skimage pieces they are made of
+  chan_vese, chan_vese_level_set
+                      reference utils.py:199-225 (eval.py's "chan-vese" / "chan-vese_ours"): skimage.segmentation.chan_vese
+                      with the checkerboard start, every level set of a batch evolved on device (kernels_levelset.hip)
 """
 import ctypes as C
 
@@ -432,3 +435,92 @@ def morphology_cleaning(mask, output_directory="", save=False, as_numpy=True):
     if as_numpy:
         return points
     return torch.tensor(points, dtype=torch.float64, device=mask.device).reshape(-1, 2)
+
+
+# ---- Chan-Vese (reference utils.py:199-225; skimage.segmentation.chan_vese 0.19.x) -------------------------------------------
+def chan_vese_checkerboard(h, w, square_size=5):
+    """skimage's _cv_checkerboard: sin(pi / square_size * y)[:, None] * sin(pi / square_size * x)[None, :] in float64, computed
+    with numpy on the host so that the start holds numpy's own bits. Returns an (h, w) numpy array."""
+    sf = np.pi / square_size
+    yv = np.arange(h, dtype=np.float64).reshape(h, 1) * sf
+    xv = np.arange(w, dtype=np.float64) * sf
+    return np.sin(yv) * np.sin(xv)
+
+
+def chan_vese_normalize(images_u8):
+    """skimage's preparation of a uint8 image, per image of a (B,H,W) batch, in float64: img - min, then / max of the result
+    when that is not 0 (a constant image stays all zero). Torch's float64 subtraction and division are IEEE: numpy's bits."""
+    img = images_u8.to(torch.float64)
+    img = img - img.amin(dim=(1, 2), keepdim=True)
+    mx = img.amax(dim=(1, 2), keepdim=True)
+    return (img / torch.where(mx != 0, mx, torch.ones_like(mx))).contiguous()
+
+
+def chan_vese_level_set(images_u8, mu=0.25, lambda1=1.0, lambda2=1.0, tol=1e-3, max_num_iter=200, dt=0.5,
+                        init_level_set="checkerboard", return_phi=False):
+    """skimage.segmentation.chan_vese(image, mu, lambda1, lambda2, tol, max_num_iter, dt, init_level_set)[0] for an (H,W) or
+    (B,H,W) uint8 HIP tensor: every image is normalised as skimage does, all level sets evolve in one ocm_op_chan_vese call
+    (float64, one launch per iteration, each image stopping on its own) and nothing is synchronised with the host.
+    init_level_set: "checkerboard", or a float64 tensor of the images' shape (or (H,W), used for every image) taken as given.
+    Returns (mask bool, iters int32) — (H,W) and 0-dim for an (H,W) image, (B,H,W) and (B,) for a batch — and the final
+    float64 level set as a third element with return_phi=True."""
+    _require_hip(images_u8, "images")
+    if images_u8.dtype != torch.uint8 or images_u8.dim() not in (2, 3):
+        raise ValueError(f"expected a uint8 (H,W) or (B,H,W) image tensor, got {images_u8.dtype} {tuple(images_u8.shape)}")
+    x = images_u8.contiguous().reshape((-1,) + tuple(images_u8.shape[-2:]))
+    B, H, W = x.shape
+    dev = x.device
+    if isinstance(init_level_set, str):
+        if init_level_set != "checkerboard":
+            raise ValueError(f"init_level_set {init_level_set!r}: only \"checkerboard\" or a float64 tensor")
+        phi = torch.from_numpy(chan_vese_checkerboard(H, W)).to(dev).expand(B, H, W).contiguous()
+    else:
+        _require_hip(init_level_set, "init_level_set")
+        if init_level_set.dtype != torch.float64 or tuple(init_level_set.shape) not in ((H, W), tuple(images_u8.shape), (B, H, W)):
+            raise ValueError(f"init_level_set must be a float64 tensor of shape {(H, W)} or {tuple(images_u8.shape)}, got "
+                             f"{init_level_set.dtype} {tuple(init_level_set.shape)}")
+        phi = init_level_set.to(dev).expand(B, H, W).clone(memory_format=torch.contiguous_format)
+    image = chan_vese_normalize(x)
+    lib = _lib.load()
+    mask = torch.empty((B, H, W), dtype=torch.uint8, device=dev)
+    iters = torch.empty(B, dtype=torch.int32, device=dev)
+    nbytes = lib.ocm_chan_vese_workspace_bytes(B, H, W)
+    ws = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.ocm_op_chan_vese(_p(image), _p(phi), _p(mask), _p(iters), B, H, W, float(mu), float(lambda1),
+                                        float(lambda2), float(tol), int(max_num_iter), float(dt), _p(ws), nbytes, _stream()))
+    single = images_u8.dim() == 2
+    out = (mask.view(torch.bool).reshape(images_u8.shape), iters[0] if single else iters)
+    return out + (phi.reshape(images_u8.shape),) if return_phi else out
+
+
+def chan_vese_result_u8(img_u8, attention):
+    """utils.py:202-208: (img * attention / np.max(attention)).astype(np.uint8) — float32 products and quotients of the uint8
+    image and the float32 map, truncated — for (H,W) or (B,H,W) tensors, the maximum taken per image."""
+    a = attention.to(torch.float32)
+    mx = a.amax(dim=(-2, -1), keepdim=True)
+    return (img_u8.to(torch.float32) * a / mx).to(torch.uint8)
+
+
+def chan_vese(img, attention, output_directory="", save=False, name=None, as_numpy=True):
+    """utils.py:199-225 on device. img: the float (C,H,W) image tensor (what the reference turns into a PIL "L" image first)
+    or an (H,W) uint8 tensor; attention: (H,W) float32 heat map. Returns (res_ours, res): the Chan-Vese segmentation
+    (checkerboard start, mu 0.25, lambda 1 / 1, tol 1e-3, 200 iterations at most, dt 0.5) of the image weighted by the
+    attention and of the image itself, both level sets evolved as one batch of two — uint8 {0, 255} numpy arrays
+    (as_numpy=False keeps them on the device). The reference returns bool * 255, an int64 array of the same values. Saving
+    figures (save=True) is the reference's matplotlib side effect and is not part of this path."""
+    if save:
+        raise NotImplementedError("chan_vese(save=True) writes figures with matplotlib in the reference; not on this path")
+    _require_hip(attention, "attention")
+    if attention.dtype != torch.float32 or attention.dim() != 2:
+        raise ValueError(f"expected a float32 (H,W) attention map, got {attention.dtype} {tuple(attention.shape)}")
+    if img.dtype == torch.uint8:
+        _require_hip(img, "img")
+        img_u8 = img.contiguous()
+    else:
+        img_u8 = image_to_gray_u8(img)[0]
+    if tuple(img_u8.shape) != tuple(attention.shape):
+        raise ValueError(f"image {tuple(img_u8.shape)} and attention {tuple(attention.shape)} differ in size")
+    pair = torch.stack([chan_vese_result_u8(img_u8, attention), img_u8])
+    masks = chan_vese_level_set(pair)[0].view(torch.uint8) * 255
+    return tuple(m.cpu().numpy() for m in masks) if as_numpy else tuple(masks)

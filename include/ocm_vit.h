@@ -711,6 +711,31 @@ int ocm_op_chan_vese(const double *image, double *phi, uint8_t *mask, int32_t *i
                      double mu, double lambda1, double lambda2, double tol, int32_t max_num_iter, double dt, void *workspace,
                      size_t workspace_bytes, void *stream);
 
+/* ---- mask scores: what eval.py's validate loop reports per image (eval.py:204-221; utils.py:388-424 calculate_metrics and
+ * DiceLoss; the six-score variant of PGT.py:247-275 / finetune.py:209; kernels_score.hip) ----
+ * pred holds `batch` images of `count` elements back to back: a uint8 mask whose value is v / 255.0f (eval.py's output / 255)
+ * when pred_is_u8 != 0, else fp32 used as is; target is fp32 of the same layout. The predicted class of an element is
+ * value > 0.5f and its true class is target > 0.5f; a NaN compares false, so it is class 0.
+ *   counts[b] = {tp, fp, fn, tn}, exact
+ *   scores[b] = {jaccard tp / (tp + fp + fn), f1 2 tp / (2 tp + fp + fn), recall tp / (tp + fn), precision tp / (tp + fp),
+ *                accuracy (tp + tn) / count, auc 0.5 (tp / (tp + fn) + tn / (tn + fp)), dice_loss} in float64
+ * Each quotient is one IEEE float64 division of the integers; a zero denominator gives 0.0 (sklearn's zero_division="warn"
+ * value: an all-zero pair scores 0, 0, 0, 0, 1). auc is the ROC-AUC of the 0/1 prediction and is NaN when the target holds one
+ * class only (sklearn 1.7's value).
+ *   dice_loss = 1 - (2 sum p t + smooth) / (sum p + sum t + smooth), p = sigmoid(value) in fp32 (the sigmoid of
+ * ocm_op_dice_loss; the reference's DiceLoss applies it to eval.py's 0/1 mask as well), the three sums in float64. A NaN
+ * element makes it NaN.
+ * One pass writes per-workgroup partials into the workspace and a finishing launch per image adds them, both in a fixed order
+ * (no atomics): the same inputs give the same bits, and an image scores to the same bits alone as within a batch, wherever it
+ * starts. 16-byte loads for the images that start 16-byte aligned, element loads for the others. Nothing synchronises with the
+ * host. The workspace (16-byte aligned) needs no initialisation; its size depends on the arguments alone, grows with count up
+ * to a cap and is 0 for arguments the operator refuses.
+ * Refused before any launch with OCM_EINVAL (a short or null workspace: OCM_ENOMEM): null pointers, batch outside 1..65535,
+ * count 0 or above 2^36, a non-finite or negative smooth. */
+size_t ocm_mask_scores_workspace_bytes(int32_t batch, size_t count);
+int ocm_op_mask_scores(const void *pred, int32_t pred_is_u8, const float *target, int32_t batch, size_t count, float smooth,
+                       int64_t *counts, double *scores, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- sliding-window index math (host, integer; sw_processing.py:151-163) ---- */
 /* Number of windows per axis: len(range(0, size - 2*stride, stride)). */
 int32_t ocm_sw_count(int32_t size, int32_t stride);

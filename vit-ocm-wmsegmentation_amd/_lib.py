@@ -255,6 +255,8 @@ SIGNATURES = {
     "ocm_chan_vese_workspace_bytes": (_sz, [_i32, _i32, _i32]),
     "ocm_op_chan_vese": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, C.c_double, C.c_double, C.c_double, C.c_double, _i32,
                                    C.c_double, _vp, _sz, _vp]),
+    "ocm_mask_scores_workspace_bytes": (_sz, [_i32, _sz]),
+    "ocm_op_mask_scores": (C.c_int, [_vp, _i32, _vp, _i32, _sz, _f32, _vp, _vp, _vp, _sz, _vp]),
     "ocm_sw_count": (_i32, [_i32, _i32]),
     "ocm_sw_origins": (_i32, [_i32, _i32, _i32, C.POINTER(_i32), _i32]),
     "ocm_sw_shard": (_i32, [_i32, _i32, _i32, C.POINTER(_i32), C.POINTER(_i32)]),

@@ -36,6 +36,14 @@ __device__ __forceinline__ void lds_barrier() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
 }
 
+// p = sigmoid(x) and p (1 - p) from one exponential of -|x|: no overflow at any x, no cancellation in 1 - p. The Dice loss
+// (kernels_train.hip) and the mask scores (kernels_score.hip) share it.
+__device__ __forceinline__ void sigmoid_parts(float x, float &p, float &pq) {
+    const float e = expf(-fabsf(x)), r = 1.0f / (1.0f + e);
+    p = x >= 0.f ? r : e * r;
+    pq = e * r * r;
+}
+
 __device__ __forceinline__ f32x16 mfma32(bf16x8 a, bf16x8 b, f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
 }

@@ -437,14 +437,7 @@ __global__ __launch_bounds__(256) void token_sum_kernel(const float *__restrict_
     }
 }
 
-// ---- sigmoid Dice loss (utils.py:410-424: finetune.py's loss) ----
-// p = sigmoid(x) and p (1 - p) from one exponential of -|x|: no overflow at any x, no cancellation in 1 - p.
-__device__ __forceinline__ void sigmoid_parts(float x, float &p, float &pq) {
-    const float e = expf(-fabsf(x)), r = 1.0f / (1.0f + e);
-    p = x >= 0.f ? r : e * r;
-    pq = e * r * r;
-}
-
+// ---- sigmoid Dice loss (utils.py:410-424: finetune.py's loss); the sigmoid is sigmoid_parts (common.h) ----
 // The count is cut into G spans (a function of the count alone, every span a multiple of four elements); workgroup g sums
 // p t, p and t over span g: per thread in index order, the wave by the fixed butterfly, the four waves in wave order, and
 // writes part[k][g]. dice_finish_kernel adds the G partials of each sum (lane l takes g = l, l + 64, ..., then the same

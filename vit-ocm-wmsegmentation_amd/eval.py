@@ -9,7 +9,8 @@ import torch
 
 from . import _lib
 from .engine import _p, _stream
-from .utils import chan_vese_level_set, chan_vese_result_u8, image_to_gray_u8, kmeans_feature_labels, threshold
+from .utils import (SCORE_NAMES, chan_vese_level_set, chan_vese_result_u8, image_to_gray_u8, kmeans_feature_labels, mask_scores,
+                    threshold)
 
 METHODS = {"ours": 0, "otsu": 1, "heatmap_threshold": 2}  # index into threshold()'s (th, th2, th3)
 KMEANS_FEATURE = "k-means_feature_clustering"
@@ -145,3 +146,44 @@ def chan_vese_segment(model, images, method="chan-vese_ours", median_filter=1, a
     masks = chan_vese_level_set(both)[0].view(torch.uint8) * 255
     masks = masks[:B] if method == "chan-vese_ours" else masks[B:]
     return (masks.cpu().numpy(), maps.cpu().numpy()) if as_numpy else (masks.contiguous(), maps)
+
+
+@torch.no_grad()
+def score_images(model, images, targets, method="ours", median_filter=1):
+    """eval.py:126-221 for a batch: the mask of `method` (segment_images, or chan_vese_segment for the chan-vese methods; the
+    cv2.kmeans methods "k-means" / "k-means_ours" raise ValueError as they do there) scored against `targets` ((B,S,S) or
+    (B,1,S,S), any float, uint8 or bool dtype, classes > 0.5) by utils.mask_scores: the uint8 mask stands for output / 255.
+    Returns (scores (B,7) float64 in utils.SCORE_NAMES order, masks (B,S,S) uint8, maps (B,S,S) fp32), all on the device: the
+    scoring adds no copy and no host synchronisation to the segmentation, and only what the caller reads leaves the device."""
+    segment = chan_vese_segment if method in CHAN_VESE else segment_images
+    masks, maps = segment(model, images, method=method, median_filter=median_filter)
+    B, S = masks.shape[0], masks.shape[-1]
+    if tuple(targets.shape) not in ((B, S, S), (B, 1, S, S)):
+        raise ValueError(f"targets {tuple(targets.shape)}: expected {(B, S, S)} or {(B, 1, S, S)} for these images")
+    return mask_scores(masks, targets)[0], masks, maps
+
+
+@torch.no_grad()
+def validate(model, batches, method="ours", median_filter=1):
+    """eval.py's validate loop (:106-283) over an iterable of (images, targets) batches: every image scored by score_images,
+    the sums of the scores kept on the device and read once at the end (the only host synchronisation the scores cost).
+    Returns (acc_avg, f1_avg, loss_avg, means): the reference's three averages over all images, and a dict with the mean of each
+    of utils.SCORE_NAMES, "images" (their number) and "auc_nan_images" — the ROC-AUC is undefined for a target with one class
+    only; such images are left out of its mean (NaN when none is left) and counted here."""
+    sums = n_nan = None
+    n = 0
+    for images, targets in batches:
+        scores = score_images(model, images, targets, method, median_filter)[0]
+        nan = torch.isnan(scores[:, 5])
+        scores[:, 5] = torch.where(nan, torch.zeros_like(scores[:, 5]), scores[:, 5])
+        sums = scores.sum(0) if sums is None else sums + scores.sum(0)
+        n_nan = nan.sum() if n_nan is None else n_nan + nan.sum()
+        n += scores.shape[0]
+    if n == 0:
+        raise ValueError("validate: no batches")
+    host = torch.cat([sums, n_nan.to(torch.float64).reshape(1)]).cpu().numpy()
+    nan_images = int(host[7])
+    means = {name: float(host[k]) / n for k, name in enumerate(SCORE_NAMES)}
+    means["auc"] = float(host[5]) / (n - nan_images) if n > nan_images else float("nan")
+    means["images"], means["auc_nan_images"] = n, nan_images
+    return means["accuracy"], means["f1"], means["dice_loss"], means

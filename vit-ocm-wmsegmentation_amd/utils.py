@@ -15,6 +15,10 @@ region-query index of analyse_attention.py, on device.
   chan_vese, chan_vese_level_set
                       reference utils.py:199-225 (eval.py's "chan-vese" / "chan-vese_ours"): skimage.segmentation.chan_vese
                       with the checkerboard start, every level set of a batch evolved on device (kernels_levelset.hip)
+  mask_scores, calculate_metrics
+                      reference utils.py:388-408 (the five sklearn scores of eval.py's table), the ROC-AUC that PGT.py:247-275
+                      and finetune.py:209 add, and the per-image DiceLoss of eval.py:211, for a batch in one pass on device
+                      (kernels_score.hip)
 """
 import ctypes as C
 
@@ -524,3 +528,58 @@ def chan_vese(img, attention, output_directory="", save=False, name=None, as_num
     pair = torch.stack([chan_vese_result_u8(img_u8, attention), img_u8])
     masks = chan_vese_level_set(pair)[0].view(torch.uint8) * 255
     return tuple(m.cpu().numpy() for m in masks) if as_numpy else tuple(masks)
+
+
+# ---- the scores eval.py's validate loop reports (reference eval.py:204-221, utils.py:388-424; kernels_score.hip) --------------
+SCORE_NAMES = ("jaccard", "f1", "recall", "precision", "accuracy", "auc", "dice_loss")  # columns of mask_scores' scores
+COUNT_NAMES = ("tp", "fp", "fn", "tn")                                                 # columns of its counts
+
+
+def mask_scores(pred, target, smooth=1):
+    """Every image of a batch scored against its target in one ocm_op_mask_scores call, nothing synchronised with the host.
+    pred: (B, ...) HIP tensor, a uint8 mask whose value is v / 255 (eval.py's `output / 255`) or float32 used as is;
+    target: the same number of elements per image, uint8, bool or any float dtype (made contiguous float32). The classes are
+    value > 0.5 and target > 0.5 (NaN: class 0).
+    Returns (scores (B,7) float64 in SCORE_NAMES order, counts (B,4) int64 in COUNT_NAMES order) on the device:
+    calculate_metrics' five sklearn scores, the ROC-AUC of the 0/1 prediction (NaN when the target holds one class) and
+    DiceLoss()(value, target, smooth) per image, with float64 sums."""
+    if isinstance(pred, torch.Tensor) and isinstance(target, torch.Tensor) and (
+            pred.dim() < 1 or pred.numel() == 0 or target.numel() != pred.numel()):
+        raise ValueError(f"pred {tuple(pred.shape)} and target {tuple(target.shape)} must hold the same, non-zero number of "
+                         "elements, pred as (B, ...)")
+    _require_hip(pred, "pred")
+    _require_hip(target, "target")
+    if pred.dtype not in (torch.uint8, torch.float32):
+        raise ValueError(f"expected a uint8 or float32 (B, ...) prediction, got {pred.dtype} {tuple(pred.shape)}")
+    if not (target.is_floating_point() or target.dtype in (torch.uint8, torch.bool)):
+        raise ValueError(f"expected a float, uint8 or bool target, got {target.dtype}")
+    B = pred.shape[0]
+    count = pred.numel() // B
+    dev = pred.device
+    x = pred.detach().contiguous()
+    t = target.detach().to(device=dev, dtype=torch.float32).contiguous()
+    lib = _lib.load()
+    scores = torch.empty((B, len(SCORE_NAMES)), dtype=torch.float64, device=dev)
+    counts = torch.empty((B, len(COUNT_NAMES)), dtype=torch.int64, device=dev)
+    nbytes = lib.ocm_mask_scores_workspace_bytes(B, count)
+    ws = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.ocm_op_mask_scores(_p(x), int(x.dtype == torch.uint8), _p(t), B, count, float(smooth), _p(counts),
+                                          _p(scores), _p(ws), nbytes, _stream()))
+    return scores, counts
+
+
+def calculate_metrics(y_true, y_pred, y_score=None):
+    """utils.py:388-408, and with `y_score` the six-score variant of PGT.py:247-275 / finetune.py:209, scored on the device:
+    [jaccard, f1, recall, precision, accuracy] (+ [roc_auc of y_score > 0.5]) as np.float64, all of y_true taken as one image.
+    y_pred and y_score are values compared with 0.5 as they are (any dtype; a uint8 tensor holds 0 / 1 here, as in the
+    reference), y_true likewise. Reading the scores synchronises with the host, as the reference's sklearn calls do."""
+    def one_image(t):
+        _require_hip(t, "calculate_metrics input")
+        return t.detach().to(torch.float32).reshape(1, -1)
+
+    true = one_image(y_true)
+    out = list(mask_scores(one_image(y_pred), true)[0][0, :5].cpu().numpy())
+    if y_score is not None:
+        out.append(mask_scores(one_image(y_score), true)[0][0, 5].cpu().numpy()[()])
+    return out

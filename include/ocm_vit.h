@@ -736,6 +736,58 @@ size_t ocm_mask_scores_workspace_bytes(int32_t batch, size_t count);
 int ocm_op_mask_scores(const void *pred, int32_t pred_is_u8, const float *target, int32_t batch, size_t count, float smooth,
                        int64_t *counts, double *scores, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- pixel k-means: cv2.kmeans as utils.py:118-169 calls it (eval.py's "k-means" / "k-means_ours" methods;
+ * kernels_kmeans_px.hip) ----
+ * The reference reshapes a gray uint8 image to N = H W / 3 samples of three consecutive pixels in raster order, runs
+ * cv2.kmeans(Z, 2, None, (EPS + MAX_ITER, 10, 1.0), 10, KMEANS_RANDOM_CENTERS), paints res = np.uint8(centres)[labels] and takes
+ * its Otsu mask. Restated from OpenCV 4.x modules/core/src/kmeans.cpp for K = 2, dims = 3; parity with a live cv2 unpinned
+ * (cv2 is not installable here). A problem is one image of 3 N pixels; pixels holds `problems` of them back to back.
+ *
+ * ocm_cv_rng_uniform (host) is cv::RNG: state = (state & 0xffffffff) * 4164903690 + (state >> 32) mod 2^64, and a draw is
+ * (float)(uint32)state * 2.3283064365386963e-10f. It writes n draws and advances *state; a state of 0 stands for 0xffffffff
+ * (cv::RNG's seed 0, and a fresh process's state). cv2.kmeans draws attempts x 2 x 3 of them whatever the data are:
+ * uniforms [problems][attempts][2][3] (device) is that stream, problem after problem.
+ *
+ * The loop, float32 unless stated, every operation rounded on its own (no fused multiply-add):
+ *   lo[j], hi[j] = minimum and maximum of column j; d(x, c) = ((t0 t0 + t1 t1) + t2 t2), t = x - c
+ *   for attempt a = 0 .. attempts - 1:
+ *     c[k][j] = (u[a][k][j] * (1.f + margin * 2.f) - margin) * (hi[j] - lo[j]) + lo[j], margin = 1.f / 3
+ *     iter = 0
+ *     loop:
+ *       if iter > 0:
+ *         old = c; count[k], sum[k][j] = members and column sums of cluster k under the labels
+ *         for every k with count[k] == 0: m = the cluster with the most members; b = sum[m] * (1.f / count[m]); among the
+ *           members of m the sample with the largest d(x, b), the largest index on a tie, moves to k (its label, both counts,
+ *           both sums)
+ *         c[k][j] = sum[k][j] * (1.f / count[k]); shift = max over k of sum_j ((double)(c[k][j] - old[k][j]))^2
+ *       else shift = +inf
+ *       last = (++iter == max(max_iter, 2)) or shift <= eps * eps
+ *       if last: compactness[a] = sum_i (double)d(x_i, c[label_i]), the labels not reassigned; stop
+ *       label_i = 1 when d(x_i, c[1]) < d(x_i, c[0]), else 0 (a tie goes to 0)
+ *   best = the first attempt with the smallest compactness (an attempt replaces the best only when strictly smaller)
+ * The samples are integers 0..255, so the sums are exact integers: they are accumulated as integers and rounded to float32
+ * once. That is OpenCV's sequential float32 sum bit for bit while 255 N < 2^24 (images up to 197 379 pixels, 384 x 384
+ * included); beyond that OpenCV's own sum rounds along the way and this one stays exact. The compactness is a float64 sum in
+ * one fixed order: the same inputs give the same bits, and a problem gives the same bits alone as within a batch, wherever it
+ * starts.
+ *
+ * Outputs: labels [problems][N] (0 / 1) and centers [problems][2][3] of the best attempt; compactness and iters
+ * [problems][attempts] (iters = the value of iter when the attempt stopped); best [problems]; mask [problems][3 N] =
+ * res > level ? 255 : 0 with res[3 i + j] = (uint8)centers[label_i][j] (truncation) and level the Otsu level of res's
+ * histogram by the statements of ocm_otsu_threshold (cv2.threshold(res, 0, 255, THRESH_BINARY + THRESH_OTSU)).
+ * One workgroup runs one attempt's whole loop and a second launch finishes each problem: no atomics, no waiting between
+ * workgroups, nothing synchronises with the host. 16-byte loads and stores for the problems that start 16-byte aligned,
+ * element accesses for the others. The workspace (16-byte aligned) needs no initialisation; its size is 0 for arguments the
+ * operator refuses.
+ * Refused before any launch with OCM_EINVAL (a short or null workspace: OCM_ENOMEM): null pointers, problems outside
+ * 1..65535, samples outside 2..2^24, attempts outside 1..32, max_iter outside 1..1000, a non-finite or negative eps, a
+ * workspace that is not 16-byte aligned. */
+int ocm_cv_rng_uniform(uint64_t *state, float *out, int64_t n);
+size_t ocm_kmeans_px_workspace_bytes(int32_t problems, int64_t samples, int32_t attempts);
+int ocm_op_kmeans_px(const uint8_t *pixels, int32_t problems, int64_t samples, const float *uniforms, int32_t attempts,
+                     int32_t max_iter, double eps, uint8_t *labels, float *centers, double *compactness, int32_t *iters,
+                     int32_t *best, uint8_t *mask, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- sliding-window index math (host, integer; sw_processing.py:151-163) ---- */
 /* Number of windows per axis: len(range(0, size - 2*stride, stride)). */
 int32_t ocm_sw_count(int32_t size, int32_t stride);

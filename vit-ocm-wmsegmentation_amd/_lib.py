@@ -257,6 +257,9 @@ SIGNATURES = {
                                    C.c_double, _vp, _sz, _vp]),
     "ocm_mask_scores_workspace_bytes": (_sz, [_i32, _sz]),
     "ocm_op_mask_scores": (C.c_int, [_vp, _i32, _vp, _i32, _sz, _f32, _vp, _vp, _vp, _sz, _vp]),
+    "ocm_cv_rng_uniform": (C.c_int, [C.POINTER(C.c_uint64), _vp, _i64]),
+    "ocm_kmeans_px_workspace_bytes": (_sz, [_i32, _i64, _i32]),
+    "ocm_op_kmeans_px": (C.c_int, [_vp, _i32, _i64, _vp, _i32, _i32, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ocm_sw_count": (_i32, [_i32, _i32]),
     "ocm_sw_origins": (_i32, [_i32, _i32, _i32, C.POINTER(_i32), _i32]),
     "ocm_sw_shard": (_i32, [_i32, _i32, _i32, C.POINTER(_i32), C.POINTER(_i32)]),

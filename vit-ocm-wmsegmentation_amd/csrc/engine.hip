@@ -14,6 +14,7 @@
 #include "launch.h"
 #include "dev_knobs.h"
 #include "attn_plan.h"
+#include "otsu.h"
 
 static thread_local std::string g_err;
 
@@ -1086,33 +1087,10 @@ extern "C" int ocm_op_threshold_u8(const uint8_t *img, uint8_t *mask, int64_t co
     return OCM_OK;
 }
 
-// Otsu threshold of a 256-bin histogram (host). Restates cv2.threshold(..., THRESH_OTSU)'s
-// getThreshVal_Otsu_8u (OpenCV 4.6.0 modules/imgproc/src/thresh.cpp — an un-vendored dependency of the
-// reference, opencv-python 4.6.0.66; parity unpinned: cv2 is not installable here).
+// Otsu threshold of a 256-bin histogram (host): the statements of otsu.h, which the device shares.
 extern "C" int32_t ocm_otsu_threshold(const uint64_t *hist256, int64_t count) {
     if (!hist256 || count <= 0) return -OCM_EINVAL;
-    const double scale = 1.0 / (double)count;
-    double mu = 0;
-    for (int i = 0; i < 256; ++i) mu += i * (double)hist256[i];
-    mu *= scale;
-    double mu1 = 0, q1 = 0, max_sigma = 0;
-    int max_val = 0;
-    for (int i = 0; i < 256; ++i) {
-        const double p_i = (double)hist256[i] * scale;
-        mu1 *= q1;
-        q1 += p_i;
-        const double q2 = 1.0 - q1;
-        const double lo = q1 < q2 ? q1 : q2, hi = q1 < q2 ? q2 : q1;
-        if (lo < 1.1920928955078125e-07 || hi > 1.0 - 1.1920928955078125e-07) continue;
-        mu1 = (mu1 + i * p_i) / q1;
-        const double mu2 = (mu - q1 * mu1) / q2;
-        const double sigma = q1 * q2 * (mu1 - mu2) * (mu1 - mu2);
-        if (sigma > max_sigma) {
-            max_sigma = sigma;
-            max_val = i;
-        }
-    }
-    return max_val;
+    return ocm_otsu_level(hist256, count);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -7,14 +7,15 @@ batch goes through ONE forward and only the final masks leave the GPU.
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, utils
 from .engine import _p, _stream
-from .utils import (SCORE_NAMES, chan_vese_level_set, chan_vese_result_u8, image_to_gray_u8, kmeans_feature_labels, mask_scores,
-                    threshold)
+from .utils import (SCORE_NAMES, chan_vese_level_set, chan_vese_result_u8, image_to_gray_u8, kmeans_feature_labels, kmeans_pixels,
+                    mask_scores, threshold)
 
 METHODS = {"ours": 0, "otsu": 1, "heatmap_threshold": 2}  # index into threshold()'s (th, th2, th3)
 KMEANS_FEATURE = "k-means_feature_clustering"
 CHAN_VESE = ("chan-vese", "chan-vese_ours")  # chan_vese_segment
+KMEANS_PIXELS = ("k-means", "k-means_ours")  # kmeans_pixels_segment
 
 
 def _head_mean_small(model, tiles, median_filter):
@@ -85,7 +86,7 @@ def segment_images(model, images, method="ours", median_filter=1, as_numpy=False
     Returns (masks (B,S,S) uint8 in {0,255}, average_attentions (B,S,S) fp32)."""
     if method not in METHODS and method != KMEANS_FEATURE:
         raise ValueError(f"method {method!r} is not on this path (k-means / chan-vese stay on the host in the reference; "
-                         "chan_vese_segment runs the chan-vese methods on the device)")
+                         "chan_vese_segment runs the chan-vese methods on the device, kmeans_pixels_segment the k-means ones)")
     if not 1 <= int(median_filter) <= 15:
         raise ValueError("median_filter must be in 1..15")
     if method == KMEANS_FEATURE:
@@ -148,15 +149,60 @@ def chan_vese_segment(model, images, method="chan-vese_ours", median_filter=1, a
     return (masks.cpu().numpy(), maps.cpu().numpy()) if as_numpy else (masks.contiguous(), maps)
 
 
+def _image_side(images):
+    """(H, W) of the image a batch is segmented at: the images' own, or the tiled crops'."""
+    if images.dim() == 5:
+        r = int(round(images.shape[1] ** 0.5))
+        return r * images.shape[-2], r * images.shape[-1]
+    return images.shape[-2], images.shape[-1]
+
+
+@torch.no_grad()
+def kmeans_pixels_segment(model, images, method="k-means_ours", median_filter=1, as_numpy=False, rng_state=None):
+    """The mask eval.py scores for `method` in {"k-means", "k-means_ours"} (eval.py:178-181, utils.py:118-169) for every image
+    of a batch ((B,C,S,S), or (B,crops,C,s,s) for --crop 4 / 16): average_attention_maps once, the gray uint8 image and its
+    attention-weighted version per image, then ONE ocm_op_kmeans_px call for all 2 B problems, interleaved ours_0, image_0,
+    ours_1, ... — the reference computes both whichever method is asked for, "ours" first, and that fixes the order of
+    cv::RNG's draws. rng_state: the generator state the 2 B * 60 draws start from; None chains utils' module-level state, as
+    OpenCV's thread-local generator runs on from image to image. An image whose pixel count is no multiple of 3 raises
+    ValueError before the model is touched (numpy's reshape(-1, 3) raises there). Only the final masks leave the device.
+    Returns (masks (B,S,S) uint8 in {0,255}, average_attentions (B,S,S) fp32)."""
+    if method not in KMEANS_PIXELS:
+        raise ValueError(f"method {method!r}: kmeans_pixels_segment runs {KMEANS_PIXELS}")
+    if not 1 <= int(median_filter) <= 15:
+        raise ValueError("median_filter must be in 1..15")
+    if images.dim() not in (4, 5):
+        raise ValueError(f"expected (B,C,S,S) images or (B,crops,C,s,s) crops, got {tuple(images.shape)}")
+    H, W = _image_side(images)
+    if (H * W) % 3:
+        raise ValueError(f"cannot reshape {H} x {W} pixels into triples (numpy's reshape(-1, 3) raises as well)")
+    maps = average_attention_maps(model, images, median_filter)
+    gray_src = tile_crops_image(images) if images.dim() == 5 else images
+    gray = torch.stack([image_to_gray_u8(gray_src[b])[0] for b in range(gray_src.shape[0])])
+    if tuple(gray.shape) != tuple(maps.shape):
+        raise ValueError(f"images {tuple(gray.shape)} and attention maps {tuple(maps.shape)} differ in size")
+    B = gray.shape[0]
+    both = torch.stack([chan_vese_result_u8(gray, maps), gray], dim=1).reshape((2 * B,) + tuple(gray.shape[1:]))
+    r = kmeans_pixels(both, rng_state=utils._cv_rng_state if rng_state is None else rng_state)
+    if rng_state is None:
+        utils._cv_rng_state = r["rng_state"]
+    masks = r["mask"].reshape((B, 2) + tuple(gray.shape[1:]))[:, 0 if method == "k-means_ours" else 1]
+    return (masks.cpu().numpy(), maps.cpu().numpy()) if as_numpy else (masks.contiguous(), maps)
+
+
+def _segmenter(method):
+    return chan_vese_segment if method in CHAN_VESE else kmeans_pixels_segment if method in KMEANS_PIXELS else segment_images
+
+
 @torch.no_grad()
 def score_images(model, images, targets, method="ours", median_filter=1):
-    """eval.py:126-221 for a batch: the mask of `method` (segment_images, or chan_vese_segment for the chan-vese methods; the
-    cv2.kmeans methods "k-means" / "k-means_ours" raise ValueError as they do there) scored against `targets` ((B,S,S) or
-    (B,1,S,S), any float, uint8 or bool dtype, classes > 0.5) by utils.mask_scores: the uint8 mask stands for output / 255.
+    """eval.py:126-221 for a batch: the mask of `method` (segment_images, chan_vese_segment for the chan-vese methods,
+    kmeans_pixels_segment for the cv2.kmeans methods "k-means" / "k-means_ours", which chain utils' cv::RNG state from batch to
+    batch) scored against `targets` ((B,S,S) or (B,1,S,S), any float, uint8 or bool dtype, classes > 0.5) by utils.mask_scores:
+    the uint8 mask stands for output / 255.
     Returns (scores (B,7) float64 in utils.SCORE_NAMES order, masks (B,S,S) uint8, maps (B,S,S) fp32), all on the device: the
     scoring adds no copy and no host synchronisation to the segmentation, and only what the caller reads leaves the device."""
-    segment = chan_vese_segment if method in CHAN_VESE else segment_images
-    masks, maps = segment(model, images, method=method, median_filter=median_filter)
+    masks, maps = _segmenter(method)(model, images, method=method, median_filter=median_filter)
     B, S = masks.shape[0], masks.shape[-1]
     if tuple(targets.shape) not in ((B, S, S), (B, 1, S, S)):
         raise ValueError(f"targets {tuple(targets.shape)}: expected {(B, S, S)} or {(B, 1, S, S)} for these images")

@@ -15,6 +15,10 @@ region-query index of analyse_attention.py, on device.
   chan_vese, chan_vese_level_set
                       reference utils.py:199-225 (eval.py's "chan-vese" / "chan-vese_ours"): skimage.segmentation.chan_vese
                       with the checkerboard start, every level set of a batch evolved on device (kernels_levelset.hip)
+  kmeans, kmeans_pixels, cv_rng_uniform
+                      reference utils.py:118-169 (eval.py's "k-means" / "k-means_ours"): cv2.kmeans on the pixel triples with
+                      cv::RNG's random centres, and the Otsu mask of the painting, every problem of a batch on device
+                      (kernels_kmeans_px.hip)
   mask_scores, calculate_metrics
                       reference utils.py:388-408 (the five sklearn scores of eval.py's table), the ROC-AUC that PGT.py:247-275
                       and finetune.py:209 add, and the per-image DiceLoss of eval.py:211, for a batch in one pass on device
@@ -527,6 +531,91 @@ def chan_vese(img, attention, output_directory="", save=False, name=None, as_num
         raise ValueError(f"image {tuple(img_u8.shape)} and attention {tuple(attention.shape)} differ in size")
     pair = torch.stack([chan_vese_result_u8(img_u8, attention), img_u8])
     masks = chan_vese_level_set(pair)[0].view(torch.uint8) * 255
+    return tuple(m.cpu().numpy() for m in masks) if as_numpy else tuple(masks)
+
+
+# ---- pixel k-means (reference utils.py:118-169; cv2.kmeans of OpenCV 4.x; kernels_kmeans_px.hip) ------------------------------
+CV_RNG_START = 0xffffffff  # cv::RNG's state in a fresh process, and what its seed 0 stands for
+_cv_rng_state = CV_RNG_START  # kmeans(rng_state=None) chains it, as OpenCV's thread-local generator runs on across calls
+
+
+def cv_rng_uniform(state, n):
+    """n uniforms of cv::RNG from `state` (ocm_cv_rng_uniform; 0 stands for 0xffffffff), on the host. Returns
+    (float32 numpy array (n,), the state after them)."""
+    st = C.c_uint64(int(state) & 0xffffffffffffffff)
+    out = np.empty(int(n), np.float32)
+    _lib.check(_lib.load().ocm_cv_rng_uniform(C.byref(st), out.ctypes.data_as(C.c_void_p), int(n)))
+    return out, int(st.value)
+
+
+def kmeans_pixels(images_u8, rng_state=CV_RNG_START, attempts=10, max_iter=10, eps=1.0):
+    """cv2.kmeans(np.float32(img.reshape(-1, 3)), 2, None, (EPS + MAX_ITER, max_iter, eps), attempts, KMEANS_RANDOM_CENTERS),
+    np.uint8(centres)[labels] and its Otsu mask (utils.py:130-146) for an (H,W) or (P,H,W) uint8 HIP tensor: every image is
+    one problem of N = H W / 3 pixel triples, all of them go through one ocm_op_kmeans_px call and nothing is synchronised
+    with the host. The random centres are cv::RNG's: P * attempts * 6 uniforms drawn from `rng_state` on the host, the
+    problems consuming the stream in order. OpenCV is not installable here: restated from its source, parity unpinned.
+    Returns a dict: mask (…,H,W) uint8 {0, 255}, labels (…,N) uint8, centers (…,2,3) float32, compactness (…,attempts) float64,
+    iters (…,attempts) int32, best (…) int32 — all on the device, without the leading axis for an (H,W) image — and rng_state,
+    the state after the draws."""
+    if isinstance(images_u8, torch.Tensor) and images_u8.dim() in (2, 3) and (images_u8.shape[-1] * images_u8.shape[-2]) % 3:
+        raise ValueError(f"cannot reshape {tuple(images_u8.shape[-2:])} pixels into triples (numpy's reshape(-1, 3) raises as well)")
+    _require_hip(images_u8, "images")
+    if images_u8.dtype != torch.uint8 or images_u8.dim() not in (2, 3):
+        raise ValueError(f"expected a uint8 (H,W) or (P,H,W) image tensor, got {images_u8.dtype} {tuple(images_u8.shape)}")
+    x = images_u8.contiguous().reshape((-1,) + tuple(images_u8.shape[-2:]))
+    P, H, W = x.shape
+    N = H * W // 3
+    attempts = int(attempts)
+    if not 1 <= attempts <= 32:
+        raise ValueError(f"attempts = {attempts} (1..32)")
+    dev = x.device
+    u, state = cv_rng_uniform(rng_state, P * attempts * 6)
+    lib = _lib.load()
+    uniforms = torch.from_numpy(u).to(dev)
+    out = dict(mask=torch.empty((P, H, W), dtype=torch.uint8, device=dev), labels=torch.empty((P, N), dtype=torch.uint8, device=dev),
+               centers=torch.empty((P, 2, 3), dtype=torch.float32, device=dev),
+               compactness=torch.empty((P, attempts), dtype=torch.float64, device=dev),
+               iters=torch.empty((P, attempts), dtype=torch.int32, device=dev), best=torch.empty(P, dtype=torch.int32, device=dev))
+    nbytes = lib.ocm_kmeans_px_workspace_bytes(P, N, attempts)
+    ws = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.ocm_op_kmeans_px(_p(x), P, N, _p(uniforms), attempts, int(max_iter), float(eps), _p(out["labels"]),
+                                        _p(out["centers"]), _p(out["compactness"]), _p(out["iters"]), _p(out["best"]),
+                                        _p(out["mask"]), _p(ws), nbytes, _stream()))
+    if images_u8.dim() == 2:
+        out = {k: v[0] for k, v in out.items()}
+    out["rng_state"] = state
+    return out
+
+
+def kmeans(img, attention, output_directory="", save=False, name=None, as_numpy=True, rng_state=None):
+    """utils.py:118-169 on device. img: the float (C,H,W) image tensor (what the reference turns into a PIL "L" image first)
+    or an (H,W) uint8 tensor; attention: (H,W) float32 heat map. Returns (res_ours, res): the Otsu mask of the two-means
+    painting (cv2.kmeans on the pixel triples: 10 attempts, 10 iterations at most, eps 1.0, random centres) of the image
+    weighted by the attention and of the image itself, one call with two problems, "ours" first as the reference computes
+    them — uint8 {0, 255} numpy arrays (as_numpy=False keeps them on the device). rng_state: the cv::RNG state the 120 draws
+    start from; None chains a module-level state that starts at 0xffffffff, as OpenCV's thread-local generator does across the
+    reference's calls. Saving figures (save=True) is the reference's matplotlib side effect and is not part of this path."""
+    global _cv_rng_state
+    if save:
+        raise NotImplementedError("kmeans(save=True) writes figures with matplotlib in the reference; not on this path")
+    if (isinstance(attention, torch.Tensor) and attention.dim() == 2 and attention.numel() % 3):
+        raise ValueError(f"cannot reshape {tuple(attention.shape)} pixels into triples (numpy's reshape(-1, 3) raises as well)")
+    _require_hip(attention, "attention")
+    if attention.dtype != torch.float32 or attention.dim() != 2:
+        raise ValueError(f"expected a float32 (H,W) attention map, got {attention.dtype} {tuple(attention.shape)}")
+    if img.dtype == torch.uint8:
+        _require_hip(img, "img")
+        img_u8 = img.contiguous()
+    else:
+        img_u8 = image_to_gray_u8(img)[0]
+    if tuple(img_u8.shape) != tuple(attention.shape):
+        raise ValueError(f"image {tuple(img_u8.shape)} and attention {tuple(attention.shape)} differ in size")
+    pair = torch.stack([chan_vese_result_u8(img_u8, attention), img_u8])
+    r = kmeans_pixels(pair, rng_state=_cv_rng_state if rng_state is None else rng_state)
+    if rng_state is None:
+        _cv_rng_state = r["rng_state"]
+    masks = r["mask"]
     return tuple(m.cpu().numpy() for m in masks) if as_numpy else tuple(masks)
 
 

@@ -788,6 +788,58 @@ int ocm_op_kmeans_px(const uint8_t *pixels, int32_t problems, int64_t samples, c
                      int32_t max_iter, double eps, uint8_t *labels, float *centers, double *compactness, int32_t *iters,
                      int32_t *best, uint8_t *mask, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- Pillow's 8-bit resample: Image.resize, Image.crop(...).resize and ToTensor (sw_processing.py:217-231,
+ * analyse_attention.py:102-120, data.py:18-122 and :189-215; kernels_resample.hip) ----
+ * Restated from Pillow's libImaging (Resample.c: precompute_coeffs, normalize_coeffs_8bpc, the 8bpc passes; Geometry.c:
+ * ImagingScaleAffine for NEAREST) and pinned on the live library by tests/test_resample_host.py. The filter values are
+ * Pillow's: */
+#define OCM_RESAMPLE_NEAREST 0
+#define OCM_RESAMPLE_BILINEAR 2
+#define OCM_RESAMPLE_BICUBIC 3
+/* One axis' table (host, double arithmetic, no device): the source axis has in_size pixels, the box in0 .. in1 of it (rounded
+ * to float32, as Pillow holds a box) becomes out_size pixels.
+ *   scale = (in1 - in0) / out_size (the difference a float32), filterscale = max(scale, 1),
+ *   support = filter support * filterscale (bilinear 1, bicubic 2 with a = -0.5), ksize = (int)ceil(support) * 2 + 1
+ *   for xx in 0 .. out_size - 1: center = in0 + (xx + 0.5) * scale; xmin = max((int)(center - support + 0.5), 0);
+ *     xmax = min((int)(center + support + 0.5), in_size) - xmin; w[x] = filter((x + xmin - center + 0.5) / filterscale), summed
+ *     in index order and each divided by the sum when it is not 0; coeffs[xx][x] = (int)(+-0.5 + w[x] * 2^22), the sign of w[x];
+ *     bounds[xx] = (xmin, xmax)
+ * NEAREST is one tap of weight 2^22 (ksize 1) at ImagingScaleAffine's source index: xo = in0 + scale * 0.5, then xo += scale
+ * per pixel, truncated; an index outside the axis leaves no tap (the pixel is 0).
+ * bounds is [out_size][2], coeffs [out_size][ksize_padded] with the taps past a row's count zeroed; flip != 0 stores row xx
+ * at out_size - 1 - xx (the resized axis mirrored: RandomHorizontalFlip / RandomVerticalFlip at no cost on the device). Taps
+ * read outside the box, up to the ends of the axis, as Image.resize(box=) does; a crop (Image.crop(...).resize) is an axis of
+ * its own: in_size = the rectangle's size, in0 = 0, in1 = in_size, with the rectangle's origin given to the operator.
+ * ocm_resample_ksize returns ksize, or a negative OCM_E* code. Refused with OCM_EINVAL: an unknown filter, in_size < 1,
+ * out_size < 1, in1 <= in0, a box outside 0 .. in_size, null pointers, ksize_padded < ksize. */
+int32_t ocm_resample_ksize(int32_t filter, int32_t in_size, double in0, double in1, int32_t out_size);
+int ocm_resample_table(int32_t filter, int32_t in_size, double in0, double in1, int32_t out_size, int32_t flip,
+                       int32_t ksize_padded, int32_t *bounds, int32_t *coeffs);
+/* The two passes for a batch (device, stream-ordered, nothing synchronises with the host). Horizontal first, into a uint8
+ * intermediate in the workspace, then vertical from it — Pillow's order; the rounding between the passes is part of the result.
+ * Each pass: acc = 2^21 + sum pixel * coeff in int32, clip(acc >> 22, 0, 255).
+ * src: uint8, `batch` images of src_h x src_w pixels of `chans` (1 or 3) channels; pixel (b, y, x, c) is the byte at
+ * b stride_b + y stride_y + x stride_x + c stride_c (HWC as decoded, planar CHW, a row pitch wider than the image, a stride
+ * of 0 to repeat a plane). rects (device, [batch][4] = y0, x0, h, w; or null: the whole source) cuts image b's rectangle out
+ * first: it is a source of its own, h x w pixels, and taps stop at its edges. The x tables are for in_size = w and the y
+ * tables for in_size = h: [out][2] bounds and [out][ksize] coeffs shared by the batch (per_image 0), or one table per image,
+ * [batch][out][...], padded to a common ksize (per_image 1: RandomResizedCrop's rectangles). tmp_rows is the number of
+ * intermediate rows per image: at least the largest h (the src_h rows when rects is null).
+ * Outputs, either or both: out_u8 (batch, out_h, out_w, chans) and out_f32 (batch, chans, out_h, out_w) = (float)u8 / 255.0f,
+ * the IEEE float32 quotient (torchvision's ToTensor). Tables and rectangles are clamped on the device to the source and the
+ * intermediate before use: wrong ones give wrong pixels, never an access outside the call's memory. The workspace (16-byte
+ * aligned, ocm_resample_u8_workspace_bytes: 0 for arguments the operator refuses) needs no initialisation.
+ * Refused before any launch with OCM_EINVAL (a short or null workspace: OCM_ENOMEM): null pointers, both outputs null, batch
+ * outside 1..65535, chans other than 1 or 3, src_h outside 1..2^19, src_w outside 1..2^26, a negative stride, out_h outside
+ * 1..65535, out_w * chans outside 1..2^26, a ksize < 1, tmp_rows outside 1..2^19 or (rects null) below src_h, a workspace that
+ * is not 16-byte aligned. */
+size_t ocm_resample_u8_workspace_bytes(int32_t batch, int32_t chans, int32_t tmp_rows, int32_t out_w);
+int ocm_op_resample_u8(const uint8_t *src, int64_t stride_b, int64_t stride_y, int64_t stride_x, int64_t stride_c,
+                       int32_t batch, int32_t chans, int32_t src_h, int32_t src_w, const int32_t *rects, int32_t tmp_rows,
+                       const int32_t *xbounds, const int32_t *xcoeffs, int32_t xksize, const int32_t *ybounds,
+                       const int32_t *ycoeffs, int32_t yksize, int32_t per_image, int32_t out_h, int32_t out_w, uint8_t *out_u8,
+                       float *out_f32, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- sliding-window index math (host, integer; sw_processing.py:151-163) ---- */
 /* Number of windows per axis: len(range(0, size - 2*stride, stride)). */
 int32_t ocm_sw_count(int32_t size, int32_t stride);

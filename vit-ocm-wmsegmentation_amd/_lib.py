@@ -260,6 +260,11 @@ SIGNATURES = {
     "ocm_cv_rng_uniform": (C.c_int, [C.POINTER(C.c_uint64), _vp, _i64]),
     "ocm_kmeans_px_workspace_bytes": (_sz, [_i32, _i64, _i32]),
     "ocm_op_kmeans_px": (C.c_int, [_vp, _i32, _i64, _vp, _i32, _i32, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "ocm_resample_ksize": (_i32, [_i32, _i32, C.c_double, C.c_double, _i32]),
+    "ocm_resample_table": (C.c_int, [_i32, _i32, C.c_double, C.c_double, _i32, _i32, _i32, _vp, _vp]),
+    "ocm_resample_u8_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32]),
+    "ocm_op_resample_u8": (C.c_int, [_vp, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _i32,
+                                     _i32, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
     "ocm_sw_count": (_i32, [_i32, _i32]),
     "ocm_sw_origins": (_i32, [_i32, _i32, _i32, C.POINTER(_i32), _i32]),
     "ocm_sw_shard": (_i32, [_i32, _i32, _i32, C.POINTER(_i32), C.POINTER(_i32)]),

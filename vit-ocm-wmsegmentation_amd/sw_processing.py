@@ -60,6 +60,23 @@ def _dev_call(t):
     return torch.cuda.device(t.device)
 
 
+def prepare_slab(image_u8, image_size):
+    """sw_processing.py:217-222 and :229-231 on device: Image.open(...).convert('RGB') -> .resize(image_size), Pillow's default
+    BICUBIC for the whole slab -> ToTensor. image_u8: the decoded image as a uint8 HIP tensor, (H,W,3), or (H,W) / (H,W,1)
+    gray (convert('RGB') repeats the plane); image_size: (width, height) as Pillow takes it. Returns the (3, height, width)
+    float32 slab SlidingWindowAttention takes, bit for bit the Pillow-prepared one (utils.pil_resize)."""
+    from .utils import BICUBIC, pil_resize
+    if not isinstance(image_u8, torch.Tensor) or image_u8.dtype != torch.uint8 or image_u8.dim() not in (2, 3) or (
+            image_u8.dim() == 3 and image_u8.shape[-1] not in (1, 3)):
+        raise ValueError("prepare_slab takes one decoded image: a uint8 (H,W,3), (H,W,1) or (H,W) tensor, got "
+                         f"{getattr(image_u8, 'dtype', type(image_u8))} {tuple(getattr(image_u8, 'shape', ()))}")
+    if image_u8.dim() == 2:
+        image_u8 = image_u8[:, :, None]
+    if image_u8.shape[-1] == 1:
+        image_u8 = image_u8.expand(-1, -1, 3)  # a channel stride of 0: the plane is read three times, never copied
+    return pil_resize(image_u8, image_size, BICUBIC, to_tensor=True, layout="hwc")
+
+
 def postprocess_windows(rows, hf, wf, patch_size):
     """rows: (T, heads, n_rows, hf*wf) CLS-row maps on a HIP device. Per window, as the tile loop of
     sw_processing.py:245,253-257 does on the CPU: head mean -> (v - min) / (max - min) * 255 -> cv2.resize DOWN BY 8

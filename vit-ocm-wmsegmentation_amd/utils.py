@@ -23,6 +23,10 @@ region-query index of analyse_attention.py, on device.
                       reference utils.py:388-408 (the five sklearn scores of eval.py's table), the ROC-AUC that PGT.py:247-275
                       and finetune.py:209 add, and the per-image DiceLoss of eval.py:211, for a batch in one pass on device
                       (kernels_score.hip)
+  pil_resize, ResamplePlan, resample_table
+                      PIL.Image.resize / Image.crop(...).resize / ToTensor of uint8 images (sw_processing.py:217-231,
+                      analyse_attention.py:102-120, data.py's transforms), byte for byte, for a batch in one call on device
+                      (kernels_resample.hip); the transforms themselves are in data.py
 """
 import ctypes as C
 
@@ -672,3 +676,156 @@ def calculate_metrics(y_true, y_pred, y_score=None):
     if y_score is not None:
         out.append(mask_scores(one_image(y_score), true)[0][0, 5].cpu().numpy()[()])
     return out
+
+
+# ---- Pillow's 8-bit resample (Image.resize, Image.crop(...).resize, ToTensor; kernels_resample.hip) ---------------------------
+NEAREST, BILINEAR, BICUBIC = 0, 2, 3  # Pillow's Image.Resampling values
+
+
+def resample_ksize(resample, in_size, in0, in1, out_size):
+    """Taps per output pixel of one axis (ocm_resample_ksize, host): in_size source pixels, the box in0 .. in1 -> out_size."""
+    k = _lib.load().ocm_resample_ksize(int(resample), int(in_size), float(in0), float(in1), int(out_size))
+    if k < 0:
+        _lib.check(-k)
+    return int(k)
+
+
+def resample_table(resample, in_size, in0, in1, out_size, flip=False, ksize_padded=None):
+    """Pillow's coefficient table of one axis (ocm_resample_table, host; include/ocm_vit.h states the arithmetic): returns
+    (bounds (out_size, 2) int32 = first tap and tap count, coeffs (out_size, ksize_padded) int32 with 22 fraction bits).
+    ksize_padded defaults to the axis' own ksize; flip stores the rows in reverse order."""
+    k = resample_ksize(resample, in_size, in0, in1, out_size)
+    kp = k if ksize_padded is None else int(ksize_padded)
+    bounds = np.empty((int(out_size), 2), np.int32)
+    coeffs = np.empty((int(out_size), max(kp, 1)), np.int32)
+    _lib.check(_lib.load().ocm_resample_table(int(resample), int(in_size), float(in0), float(in1), int(out_size), int(bool(flip)), kp,
+                                              bounds.ctypes.data_as(C.c_void_p), coeffs.ctypes.data_as(C.c_void_p)))
+    return bounds, coeffs
+
+
+def _u8_image_geometry(t, layout):
+    """(B, H, W, C, (stride_b, stride_y, stride_x, stride_c), batched) of a uint8 image tensor: (H,W), (H,W,C) / (C,H,W),
+    (B,H,W,C) / (B,C,H,W). Without `layout` a last axis of 1 or 3 means interleaved ("hwc"), otherwise planar ("chw")."""
+    d = t.dim()
+    if d == 2:
+        return 1, t.shape[0], t.shape[1], 1, (0, t.stride(0), t.stride(1), 0), False
+    if layout is None:
+        layout = "hwc" if t.shape[-1] in (1, 3) else "chw"
+    if layout not in ("hwc", "chw"):
+        raise ValueError(f"layout = {layout!r} ('hwc' or 'chw')")
+    sh, st = tuple(t.shape), tuple(t.stride())
+    B, sb = (sh[0], st[0]) if d == 4 else (1, 0)
+    if layout == "hwc":
+        (H, W, Cc), (sy, sx, sc) = sh[-3:], st[-3:]
+    else:
+        (Cc, H, W), (sc, sy, sx) = sh[-3:], st[-3:]
+    return B, H, W, Cc, (sb, sy, sx, sc), d == 4
+
+
+def _per_image(value, B, what):
+    """A flag for the whole batch, or one per image -> (list of B bools, whether it was per image)."""
+    if value is None or isinstance(value, (bool, np.bool_)):
+        return [bool(value)] * B, False
+    flags = [bool(v) for v in (value.tolist() if hasattr(value, "tolist") else value)]
+    if len(flags) != B:
+        raise ValueError(f"{what}: {len(flags)} flags for {B} images")
+    return flags, True
+
+
+class ResamplePlan:
+    """Everything of a pil_resize call that depends on the geometry alone: the two axes' coefficient tables (built on the host by
+    ocm_resample_table, one upload for all of them), the crop rectangles and the sizes. A plan serves any image tensor of the
+    shape, strides and device it was made for, call after call (run). The arguments are pil_resize's."""
+
+    def __init__(self, images_u8, size, resample=BICUBIC, box=None, crop=None, hflip=None, vflip=None, layout=None):
+        if not isinstance(images_u8, torch.Tensor) or images_u8.dtype != torch.uint8 or images_u8.dim() not in (2, 3, 4):
+            raise ValueError("expected a uint8 (H,W), (H,W,C), (B,H,W,C), (C,H,W) or (B,C,H,W) image tensor, got "
+                             f"{getattr(images_u8, 'dtype', type(images_u8))} {tuple(getattr(images_u8, 'shape', ()))}")
+        if resample not in (NEAREST, BILINEAR, BICUBIC):
+            raise ValueError(f"resample = {resample!r} (NEAREST 0, BILINEAR 2, BICUBIC 3)")
+        B, H, W, Cc, strides, batched = _u8_image_geometry(images_u8, layout)
+        if Cc not in (1, 3):
+            raise ValueError(f"{Cc} channels (1 or 3)")
+        out_w, out_h = int(size[0]), int(size[1])
+        if out_w < 1 or out_h < 1:
+            raise ValueError(f"size = {tuple(size)} (width, height >= 1)")
+        hf, hf_each = _per_image(hflip, B, "hflip")
+        vf, vf_each = _per_image(vflip, B, "vflip")
+        rects, crop_each = None, False
+        if crop is not None:
+            rects = np.asarray(crop, dtype=np.int64)
+            crop_each = rects.ndim == 2
+            rects = rects if crop_each else np.broadcast_to(rects.reshape(-1, 4), (B, 4))
+            if rects.shape != (B, 4):
+                raise ValueError(f"crop: {rects.shape[0]} rectangles for {B} images")
+            if (rects[:, 0] < 0).any() or (rects[:, 1] < 0).any() or (rects[:, 2] > W).any() or (rects[:, 3] > H).any() or (
+                    rects[:, 2] <= rects[:, 0]).any() or (rects[:, 3] <= rects[:, 1]).any():
+                raise ValueError(f"crop rectangles must be non-empty and inside the {W} x {H} image")
+        per_image = crop_each or hf_each or vf_each
+        _require_hip(images_u8, "images")
+
+        def axis_tables(sizes, lo, hi, out, flips):
+            spans = [(n, 0.0 if box is None else float(box[lo]), float(n) if box is None else float(box[hi])) for n in sizes]
+            ks = [resample_ksize(resample, n, a, b, out) for n, a, b in spans]
+            tabs = [resample_table(resample, n, a, b, out, f, max(ks)) for (n, a, b), f in zip(spans, flips)]
+            return np.stack([t[0] for t in tabs]), np.stack([t[1] for t in tabs]), max(ks)
+
+        T = B if per_image else 1
+        widths = [W] * T if rects is None else [int(r[2] - r[0]) for r in rects[:T]]
+        heights = [H] * T if rects is None else [int(r[3] - r[1]) for r in rects[:T]]
+        xb, xc, self.xk = axis_tables(widths, 0, 2, out_w, hf[:T])
+        yb, yc, self.yk = axis_tables(heights, 1, 3, out_h, vf[:T])
+        parts = [xb, xc, yb, yc]
+        if rects is not None:  # (y0, x0, h, w) per image
+            parts.append(np.stack([rects[:, 1], rects[:, 0], rects[:, 3] - rects[:, 1], rects[:, 2] - rects[:, 0]], 1).astype(np.int32))
+        self.device = images_u8.device
+        self.tables = torch.from_numpy(np.concatenate([p.reshape(-1) for p in parts])).to(self.device)
+        offs = np.cumsum([0] + [p.size for p in parts])
+        self.ptr = [C.c_void_p(self.tables.data_ptr() + 4 * int(o)) for o in offs[:-1]] + [None] * (5 - len(parts))
+        self.tmp_rows = H if rects is None else int((rects[:, 3] - rects[:, 1]).max())
+        self.per_image, self.batched, self.dims = int(per_image), batched, images_u8.dim()
+        self.geometry = (tuple(images_u8.shape), tuple(images_u8.stride()))
+        self.B, self.H, self.W, self.C, self.strides, self.out_h, self.out_w = B, H, W, Cc, strides, out_h, out_w
+        self.workspace_bytes = int(_lib.load().ocm_resample_u8_workspace_bytes(B, Cc, self.tmp_rows, out_w))
+
+    def run(self, images_u8, to_tensor=False):
+        """One ocm_op_resample_u8 call on the current stream: see pil_resize for what comes back."""
+        if to_tensor not in (False, True, "both"):
+            raise ValueError(f"to_tensor = {to_tensor!r} (False, True or 'both')")
+        _require_hip(images_u8, "images")
+        if images_u8.dtype != torch.uint8 or (tuple(images_u8.shape), tuple(images_u8.stride())) != self.geometry or (
+                images_u8.device != self.device):
+            raise ValueError("the plan was made for a uint8 tensor of another shape, other strides or another device")
+        dev, B, Cc = self.device, self.B, self.C
+        want_u8, want_f32 = to_tensor in (False, "both"), to_tensor in (True, "both")
+        out_u8 = torch.empty((B, self.out_h, self.out_w, Cc), dtype=torch.uint8, device=dev) if want_u8 else None
+        out_f32 = torch.empty((B, Cc, self.out_h, self.out_w), dtype=torch.float32, device=dev) if want_f32 else None
+        ws = torch.empty(max(self.workspace_bytes, 1), dtype=torch.uint8, device=dev)
+        p = self.ptr
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().ocm_op_resample_u8(_p(images_u8), *(int(s) for s in self.strides), B, Cc, self.H, self.W, p[4],
+                                                      self.tmp_rows, p[0], p[1], self.xk, p[2], p[3], self.yk, self.per_image,
+                                                      self.out_h, self.out_w, _p(out_u8), _p(out_f32), _p(ws), self.workspace_bytes,
+                                                      _stream()))
+        if not self.batched:
+            out_u8 = None if out_u8 is None else (out_u8[0, :, :, 0] if self.dims == 2 else out_u8[0])
+            out_f32 = None if out_f32 is None else out_f32[0]
+        return (out_u8, out_f32) if to_tensor == "both" else out_f32 if to_tensor else out_u8
+
+
+def pil_resize(images_u8, size, resample=BICUBIC, box=None, crop=None, hflip=None, vflip=None, to_tensor=False, layout=None):
+    """PIL.Image.resize(size, resample, box) of every image of a uint8 HIP tensor in one ocm_op_resample_u8 call, byte for byte
+    (Pillow's integer passes, horizontal first; pinned on the live library by tests/test_resample_host.py), nothing
+    synchronised with the host. images_u8: (H,W) ("L"), (H,W,C), (B,H,W,C) or the planar (C,H,W) / (B,C,H,W), C in (1, 3),
+    read through its strides (a view with a wider row pitch is not copied); see _u8_image_geometry for `layout`.
+    size: (width, height) as Pillow takes it; resample: NEAREST, BILINEAR or BICUBIC (Pillow's default for resize).
+    box: (x0, y0, x1, y1) floats, Pillow's box= (taps read outside it). crop: (x0, y0, x1, y1) integers inside the image, or
+    one rectangle per image ((B,4)): Image.crop(rect).resize(...), taps stop at the rectangle (a box then counts inside it).
+    hflip / vflip: a flag or one per image: the resized image mirrored, as RandomHorizontalFlip / RandomVerticalFlip after
+    RandomResizedCrop do (the rows of the coefficient tables reversed: no work on the device).
+    Returns uint8 (h,w) / (h,w,C) / (B,h,w,C); with to_tensor=True float32 (C,h,w) / (B,C,h,w) = ToTensor (u8 / 255.0f);
+    with to_tensor="both" the pair (uint8, float32). The tables are built on the host for every call: ResamplePlan keeps them
+    for callers that resize one geometry again and again."""
+    if to_tensor not in (False, True, "both"):
+        raise ValueError(f"to_tensor = {to_tensor!r} (False, True or 'both')")
+    return ResamplePlan(images_u8, size, resample, box, crop, hflip, vflip, layout).run(images_u8, to_tensor)

@@ -222,6 +222,15 @@ enum {
 int ocm_op_linear(int32_t precision, const void *a, const void *w, const float *bias, const float *resid,
                   void *out, int32_t M, int32_t N, int32_t K, int32_t epilogue, void *stream);
 
+/* nn.Linear + residual with the NEXT LayerNorm's row sums (the engine's attn.proj / mlp.fc2 when that LayerNorm is folded into
+ * its consumer): x[M][N] fp32 += A · W^T + bias in place; xs[M][N] of type E = x - shift[row]; stats[M][N / 64][2] fp32 = per row
+ * (sum, sum of squares) of x - shift[row], carried by the first 64-column slot of every tile, zeros in the tile's other slots.
+ * shift[M] (or NULL: nothing is subtracted) is WRITTEN: prev_shift[row] + (sum over slots of prev_stats[row][.][0]) / N, either
+ * previous-site input may be NULL (then it counts as zero). N % 64 == 0, K as for ocm_op_linear. */
+int ocm_op_linear_stats(int32_t precision, const void *a, const void *w, const float *bias, float *x, void *xs, float *stats,
+                        float *shift, const float *prev_stats, const float *prev_shift, int32_t M, int32_t N, int32_t K,
+                        void *stream);
+
 /* nn.Linear + residual + LayerNorm in one kernel (Block.forward :107-111 with the NEXT normalisation folded in:
  *   x = resid + A[M][K] · W[D][K]^T + bias;   xn = LayerNorm(x; gamma, beta, eps) in the activation type E
  * exactly as ocm_op_linear (epilogue RESID_F32) followed by ocm_op_layernorm would produce them (bit for bit).
@@ -243,7 +252,7 @@ int ocm_op_linear_resid_ln(int32_t precision, const void *a, const void *w, cons
  *              K = the contraction length before padding              ocm_op_upconv2x2 (K = C)
  *   RESID_LN   M, N = D in {128, 256, 384}, K % 64 == 0               ocm_op_linear_resid_ln
  * `epilogue` is read for LINEAR only. flags: STATS_EPILOGUE = the residual epilogue that also produces the next LayerNorm's row
- * sums (the engine's folded-LayerNorm forward; its tiles are multiples of 64 wide), SPLITK_OFFERED = the caller holds a split-K
+ * sums (ocm_op_linear_stats and the engine's folded-LayerNorm forward; its tiles are multiples of 64 wide), SPLITK_OFFERED = the caller holds a split-K
  * workspace (the engine below 512 rows), CONV3X3 = the A operand comes through the 3x3 loader. Arguments the operator itself
  * refuses return OCM_EINVAL. */
 enum { OCM_GEMM_LINEAR = 0, OCM_GEMM_QKV = 1, OCM_GEMM_LINEAR_LD = 2, OCM_GEMM_CONV = 3, OCM_GEMM_RESID_LN = 4 };

@@ -138,6 +138,7 @@ SIGNATURES = {
     "ocm_op_merge_split": (C.c_int, [_vp, _vp, _sz, _vp]),
     "ocm_n_pad_prec": (_i32, [_i32, _i32]),
     "ocm_op_linear": (C.c_int, [_i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
+    "ocm_op_linear_stats": (C.c_int, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     "ocm_linear_resid_ln_supported": (C.c_int, [_i32]),
     "ocm_op_linear_resid_ln": (C.c_int, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _f32, _vp]),
     "ocm_gemm_plan": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _i32, C.c_uint32, C.POINTER(OcmGemmPlanInfo)]),

@@ -784,6 +784,23 @@ extern "C" int ocm_op_linear(int32_t precision, const void *a, const void *w, co
     return OCM_OK;
 }
 
+// the residual epilogue of the folded-LayerNorm forward (launch.h: StatsOut) as an operator: what the engine's attn.proj / mlp.fc2 launch
+extern "C" int ocm_op_linear_stats(int32_t precision, const void *a, const void *w, const float *bias, float *x, void *xs,
+                                   float *stats, float *shift, const float *prev_stats, const float *prev_shift, int32_t M,
+                                   int32_t N, int32_t K, void *stream) {
+    int pc = 0, rc = prec_of(precision, &pc);
+    if (rc) return rc;
+    if (!a || !w || !x || !xs || !stats) return fail(OCM_EINVAL, "null argument");
+    const int kq = pc ? 32 : 64;
+    if (M <= 0 || N <= 0 || N % 64 || K <= 0 || K % kq)
+        return fail(OCM_EINVAL, "bad shape M=%d N=%d K=%d (N%%64, K%%%d)", M, N, K, kq);
+    if (!shift && (prev_stats || prev_shift)) return fail(OCM_EINVAL, "previous-site sums or shifts without a shift output");
+    StatsOut so;
+    so.xs = xs, so.stats = stats, so.shift = shift, so.prev_stats = prev_stats, so.prev_shift = prev_shift;
+    HIP_TRY(launch_linear(pc, a, w, bias, x, x, M, N, K, OCM_EPI_BIAS_RESID_F32, (hipStream_t)stream, LnFold(), so));
+    return OCM_OK;
+}
+
 extern "C" int ocm_linear_resid_ln_supported(int32_t D) { return linear_resid_ln_supported(D) ? 1 : 0; }
 
 extern "C" int ocm_op_linear_resid_ln(int32_t precision, const void *a, const void *w, const float *bias,

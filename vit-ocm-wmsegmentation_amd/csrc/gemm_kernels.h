@@ -28,7 +28,8 @@ typedef CfgOf<T128x128q> Cfg128x128q;
 typedef CfgOf<T128x128q16> Cfg128x128q16;
 typedef CfgOf<T128x128m16> Cfg128x128m16;  // development A/B (four waves: the tile of forwards of 32 k rows and more)
 // 160 rows: two full 32-row tiles and a 16-row half tile per wave row (gemm_core.h: GemmCfg::HALF). At 12 608 rows (ViT-S/16, B = 64)
-// mlp.fc1 is 79 x 12 = 948 of these = 1.85 rounds of the 512 two-per-CU slots instead of 1 188 tiles of 128 x 128 = 2.32
+// mlp.fc1 is 79 x 12 = 948 of these = 1.85 rounds of the 512 two-per-CU slots instead of 1 188 tiles of 128 x 128 = 2.32; mlp.fc2
+// with the statistics epilogue is 79 x 3 = 237 of them, one per CU on a three-stage ring, instead of 198 tiles of 128 x 192
 typedef CfgOf<T160x128q16> Cfg160x128q16;
 typedef CfgOf<T256x256m16> Cfg256x256m16;  // ViT-B sizes
 typedef CfgOf<T64x128> Cfg64x128;
@@ -371,8 +372,12 @@ static hipError_t launch_gemm_dma_ks(const E *a, int64_t lda, const E *w, int64_
     const int tiles = ((M + Cfg::BM - 1) / Cfg::BM) * ((N + Cfg::BN - 1) / Cfg::BN);
     auto kern = gemm_dma_kernel<Cfg, E, false, KSTEPS, NSTAGE, Epi>;
     static OptinMask optin;
-    if (hipError_t e = lds_optin((const void *)kern, LDS, optin); e != hipSuccess) return e;
-    kern<<<dim3(tiles), dim3(Cfg::NT), LDS, s>>>(a, lda, w, ldw, M, N, K, epi);
+    int lds = LDS;
+#ifdef OCM_DEV  // knob 0 = 26: the two-stage 160-row mlp.fc2 asks for more than half a CU's LDS, so that workgroups cannot pair up
+    if (OCM_KNOB(0) == 26 && Cfg::HALF && NSTAGE == 2 && !Epi::ROWTAB) lds = 84 * 1024;
+#endif
+    if (hipError_t e = lds_optin((const void *)kern, lds, optin); e != hipSuccess) return e;
+    kern<<<dim3(tiles), dim3(Cfg::NT), lds, s>>>(a, lda, w, ldw, M, N, K, epi);
     return hipGetLastError();
 }
 
@@ -394,9 +399,10 @@ struct epi_bn_mult<Epi, std::void_t<decltype(Epi::BN_MULT)>> {
 };
 
 // nn.Linear on the tile, loop and depth gemm_plan_linear chooses. Each case names a kernel family that is instantiated for this
-// element type and epilogue: LDS-DMA tiles for split-bf16 operands only, the 160-row tile for the activation-output epilogues,
-// 128 x 96 where the epilogue serves that width; a plan outside them is refused. The product switch, the two guarded keys after
-// it and the development switch must keep disjoint keys: a key moves from one to another, it is never listed twice.
+// element type and epilogue: LDS-DMA tiles for split-bf16 operands only, the 160-row tile for the activation-output epilogues (two
+// stages) and the statistics epilogue (OCM_TALL_N384_STAGES), 128 x 96 where the epilogue serves that width; a plan outside them is
+// refused. The product switch, the guarded keys after it and the development switch must keep disjoint keys: a key moves from one
+// to another, it is never listed twice.
 template <int MODE, class E, class Epi>
 static hipError_t launch_linear_epi(const E *a, const E *w, const Epi &epi, int M, int N, int K, hipStream_t s) {
     if (K % Elem<E>::KROW) return hipErrorInvalidValue;
@@ -419,6 +425,14 @@ static hipError_t launch_linear_epi(const E *a, const E *w, const Epi &epi, int 
                 if (key == gemm_dma_key(T160x128q16, 2)) return launch_gemm_dma<Cfg160x128q16, E, 2>(a, K, w, K, M, N, K, epi, s, ks);
             if constexpr (Cfg128x96::BN % epi_bn_mult<Epi>::v == 0)
                 if (key == gemm_dma_key(T128x96, 2)) return launch_gemm_dma<Cfg128x96, E, 2>(a, K, w, K, M, N, K, epi, s, ks);
+            if constexpr (MODE == 1 && epi_bn_mult<Epi>::v == 64) {  // (the statistics epilogue: mlp.fc2 on one 160-row workgroup per CU)
+                if (key == gemm_dma_key(T160x128q16, OCM_TALL_N384_STAGES))
+                    return launch_gemm_dma<Cfg160x128q16, E, OCM_TALL_N384_STAGES>(a, K, w, K, M, N, K, epi, s, ks);
+#ifdef OCM_DEV  // (knob 0 = 27: the four-stage ring, which did not ship)
+                static_assert(OCM_TALL_N384_STAGES == 3, "the development key below is the depth that does not ship");
+                if (key == gemm_dma_key(T160x128q16, 4)) return launch_gemm_dma<Cfg160x128q16, E, 4>(a, K, w, K, M, N, K, epi, s, ks);
+#endif
+            }
 #ifdef OCM_DEV  // the tiles only a forcing knob names
             switch (key) {
                 case gemm_dma_key(T256x256, 2): return launch_gemm_dma<Cfg256x256, E, 2>(a, K, w, K, M, N, K, epi, s, ks);

@@ -30,7 +30,7 @@ constexpr GemmTileInfo GEMM_TILES[GEMM_TILE_COUNT] = {
     {128, 128, 2, 4, 1, 2}, // T128x128q16
     {128, 128, 2, 2, 1, 2}, // T128x128m16
     {128, 192, 4, 2, 0, 3}, // T128x192
-    {160, 128, 2, 4, 1, 2}, // T160x128q16
+    {160, 128, 2, 4, 1, 4}, // T160x128q16: two stages under the two-per-CU mlp.fc1, three under the one-per-CU mlp.fc2 (knob 0 = 27: four)
     {256, 128, 4, 2, 0, 2}, // T256x128
     {256, 256, 2, 4, 0, 2}, // T256x256
     {256, 256, 2, 4, 1, 2}, // T256x256m16
@@ -103,6 +103,9 @@ constexpr int OCM_SMALLM_ROWS = 4096;
 // Split-K (launch.h: StatsOut::part): slices, and up to how many rows (at 2305 rows, one ViT-S/8 window, the split form measures
 // the same as the plain kernel). The kernel is built for slices of 12 steps: K = 4 x 384 (ViT-S mlp.fc2); other depths: no split
 constexpr int OCM_SPLITK = 4, OCM_SPLITK_MAX_ROWS = 512, OCM_SPLITK_STEPS = 12;
+// Ring depth of the 160 x 128 tile where it runs ONE workgroup per CU (mlp.fc2, below): 3 x 36 KiB = 108 KiB, two K steps in
+// flight and no room for a second workgroup on the CU (four stages, 144 KiB, measured slower: knob 0 = 27)
+constexpr int OCM_TALL_N384_STAGES = 3;
 
 // 256 x 256 tiles: 8 waves, one workgroup per CU: half the L2->LDS bytes per output element of 128x128. Pays off once the
 // problem has at least two full rounds of such tiles (ViT-B at 384^2, the ViT-S/8 slab windows); below
@@ -138,9 +141,10 @@ constexpr GemmPlan gemm_plan_reg_tail(int M, int N, int steps) {
 // statistics-producing residual epilogue (EpiResidStats, BN_MULT = 64: tile widths that are multiples of 64 only).
 // splitk_offered: the caller holds a split-K workspace and what the finishing kernel needs (a residual; pairs with the sums).
 // knob: development knob 0 (tools/microbench_x3.py, tools/stamps_x3.py, tools/ab_bench.sh, tools/ab_swin.sh); 0 ships.
-//   force a variant where its shape guard holds:  1, 4, 6 .. 14, 19, 23 (split-bf16), 4, 7 (single bf16), -1 (register-staged)
-//   leave a branch out:  20 (256 x 256 at K = 384), 22 (160-row tiles), 17 / 21 (the eight-wave 16 x 16-shape 128 x 128 tile:
-//   17 its four-wave form, 21 the four-wave 32 x 32-shape tile below N = 1024); any non-zero value: the few-row branch
+//   force a variant where its shape guard holds:  1, 4, 6 .. 14, 19, 23, 25 .. 28 (split-bf16), 4, 7 (single bf16), -1 (register-staged)
+//   leave a branch out:  20 (256 x 256 at K = 384), 22 (160-row tiles of mlp.fc1), 24 (160-row tiles of mlp.fc2), 17 / 21 (the
+//   eight-wave 16 x 16-shape 128 x 128 tile: 17 its four-wave form, 21 the four-wave 32 x 32-shape tile below N = 1024); any non-zero
+//   value: the few-row branch
 inline GemmPlan gemm_plan_linear(int prec, int epilogue, int M, int N, int K, bool stats_epilogue, bool splitk_offered, int knob) {
     const int steps = K / gemm_krow(prec);
     if (prec == 2 && epilogue == 1 && splitk_offered && M <= OCM_SPLITK_MAX_ROWS && N % 64 == 0 && steps == OCM_SPLITK * OCM_SPLITK_STEPS)
@@ -164,6 +168,12 @@ inline GemmPlan gemm_plan_linear(int prec, int epilogue, int M, int N, int K, bo
             case 14: if (N % 128 == 0) return dma(T128x128m16, 2); break;
             case 19: if (N % 256 == 0 && N >= 1024 && M >= 16384) return dma(T256x256m16, 2); break;
             case 23: if (N % 128 == 0 && M >= 4096) return dma(T160x128q16, 2); break;
+            // the 160-row tile for mlp.fc2 alone (N = 384, K >= 768) by ring depth: 25 = three stages, 27 = four, 28 = two, 26 = two
+            // with the LDS request padded past half a CU (launch_gemm_dma_ks), so that only one workgroup fits per CU
+            case 25: if (N == 384 && steps >= 24 && M > OCM_SMALLM_ROWS) return dma(T160x128q16, 3); break;
+            case 26:
+            case 28: if (N == 384 && steps >= 24 && M > OCM_SMALLM_ROWS) return dma(T160x128q16, 2); break;
+            case 27: if (N == 384 && steps >= 24 && M > OCM_SMALLM_ROWS) return dma(T160x128q16, 4); break;
             default: break;
         }
         // Split-bf16 operands, >= 512 tiles of 128x128 (fc1): LDS-DMA staging, two workgroups per CU. Inside the forward
@@ -185,6 +195,21 @@ inline GemmPlan gemm_plan_linear(int prec, int epilogue, int M, int N, int K, bo
         // round 4 (B = 128, alternating runs: fc1 965 -> 870 us, fc2 903 -> 820, proj 281 -> 256)
         if (big_tiles_pay(M, N, K)) return dma(T256x256m16, 2);
         const long rb = (M + 127) / 128, t128 = rb * (N / 128);  // (t128: where N is a multiple of 128)
+        // mlp.fc2 of ViT-S (N = 384, K >= 768: 24 K steps and more) in a single round of workgroups: 160 x 128 tiles on a
+        // THREE-stage ring when they put the launch on at least 10 % more CUs than 128 x 192 tiles would — at 12 608 rows
+        // (ViT-S/16, B = 64) 79 x 3 = 237 workgroups of 0.83 x the MFMA work per K step instead of 99 x 2 = 198. Both tilings
+        // must be one round (<= 256 workgroups: up to 13 600 rows); 108 KiB of LDS keep a second workgroup off the CU.
+        // In the forward, alternating on one box (knob 0 = 24 keeps 128 x 192; 28 / 26 / 25 / 27 the ring depths): fc2 55.2 us
+        // on 128 x 192 -> 61.8 on two stages, 61.9 on two stages with the LDS request padded to one workgroup per CU, 52.1 on
+        // three, 53.9 on four (another box: 52.1 -> 62.6 / 61.4 / 49.6 / 50.8): the ring depth, not workgroups pairing up, was
+        // what the two-stage trial of round 4 lost. Libraries alternating, twelve rounds: 2.230 -> 2.200 ms per step.
+        // Rows (bench.py --batch 21 / 32 / 69 = 4 137 / 6 304 / 13 593 rows): fc2 43.6 -> 42.0, 46.0 -> 43.3, 57.3 -> 55.3 us,
+        // so the rule starts where the few-row branch ends. Only the statistics-producing residual epilogue (the engine's
+        // fc2) was measured and is covered; attn.proj (12 steps) stays on 128 x 192.
+        if (N == 384 && steps >= 24 && epilogue == 1 && stats_epilogue && M > OCM_SMALLM_ROWS && knob != 24) {
+            const long t160 = (long)((M + 159) / 160) * 3, t192 = rb * 2;
+            if (t160 <= 256 && t192 <= 256 && 10 * t160 >= 11 * t192) return dma(T160x128q16, OCM_TALL_N384_STAGES);
+        }
         // Narrow outputs (attn.proj / mlp.fc2 of ViT-S: N = 384) with too few rows for 512 tiles of 128 x 128: 128 x 192
         // tiles, one 8-wave workgroup per CU on a three-stage LDS-DMA ring. Per K step 40 KiB of operands for 1152 cycles
         // of MFMA per SIMD (56 KiB for the 64 x 384 full-row tile, 64 KiB for two 64 x 128 tiles): ViT-S/16 at B = 64,

@@ -849,6 +849,59 @@ int ocm_op_resample_u8(const uint8_t *src, int64_t stride_b, int64_t stride_y, i
                        const int32_t *ycoeffs, int32_t yksize, int32_t per_image, int32_t out_h, int32_t out_w, uint8_t *out_u8,
                        float *out_f32, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- the optimizer step, the gradient norm and its clipping (optimizer.py, utils.py:363 get_grad_norm, mim.py's and train.py's
+ * clip_grad_norm_; kernels_optim.hip) ----
+ * fp32 tensors, many per call: the host array `tensors` describes them, the operator cuts it into launches whose table of
+ * pointers travels in the kernel arguments (no device copy of it, no allocation, nothing synchronises with the host). A
+ * descriptor's pointers are device addresses of `count` contiguous floats each, 4-byte aligned; 16-byte loads and stores are
+ * used for a tensor whose pointers are all 16-byte aligned, element accesses otherwise, and nothing past `count` elements is
+ * touched. count == 0 is legal (its pointers are not looked at). An operator looks only at the pointers it uses; the others may
+ * be null. */
+typedef struct OcmOptimTensor {
+    void *param; /* updated in place by the step */
+    void *grad;  /* read by the step and the norm, scaled in place by the scale */
+    void *m;     /* Adam / AdamW: exp_avg; SGD: momentum_buffer (unused with momentum == 0) */
+    void *v;     /* Adam / AdamW: exp_avg_sq; SGD: unused */
+    int64_t count;
+} OcmOptimTensor;
+#define OCM_OPTIM_ADAMW 0
+#define OCM_OPTIM_ADAM 1
+#define OCM_OPTIM_SGD 2
+/* The values of one step, in double as torch's Python holds them; the operator forms the factors (1 - lr weight_decay,
+ * 1 - beta1, 1 - beta2, 1 - dampening) in double and rounds each to float32 once. The caller forms the two that depend on the
+ * step count: step_size = lr / (1 - beta1^step) and bias_correction2_sqrt = sqrt(1 - beta2^step).
+ * The rules are torch's single-tensor ones, every operation rounded on its own:
+ *   AdamW  p = p (1 - lr wd); m = m + (1 - beta1)(g - m); v = v beta2 + ((1 - beta2) g) g;
+ *          p = p + (-step_size)(m / (sqrt(v) / bias_correction2_sqrt + eps))
+ *   Adam   the same without the first statement and with g' = g + wd p for g (wd != 0; grad itself is not written)
+ *   SGD    g' = g + wd p (wd != 0); with momentum != 0: m = g' when first_step, else m = m momentum + (1 - dampening) g';
+ *          g' = g' + momentum m when nesterov, else m; then p = p + (-lr) g' */
+typedef struct OcmOptimHyper {
+    int32_t rule;       /* OCM_OPTIM_* */
+    int32_t nesterov;   /* SGD */
+    int32_t first_step; /* SGD: the momentum buffers hold nothing yet and are written from g' */
+    int32_t reserved;
+    double lr, beta1, beta2, eps, weight_decay, step_size, bias_correction2_sqrt, momentum, dampening;
+} OcmOptimHyper;
+/* The tensors one launch takes and the elements one workgroup takes (a multiple of 4). */
+void ocm_optim_limits(int32_t *max_tensors, int32_t *chunk_elems);
+/* One step of every tensor of the table under one set of values. Refused before any launch with OCM_EINVAL: a null table or
+ * null hyper-parameters, n < 0, an unknown rule, non-finite values (bias_correction2_sqrt <= 0 for the Adam rules), a count
+ * outside 0..2^36, a null or misaligned pointer the rule uses in a descriptor with count > 0. */
+int ocm_op_optim_step(const OcmOptimTensor *tensors, int32_t n, const OcmOptimHyper *hyper, void *stream);
+/* The 2-norm of all gradients of the table. One workgroup per chunk writes the float64 sum of the squares (each square formed in
+ * float64) to the workspace, a last workgroup adds them: *sumsq = the total (float64), *norm = (float)sqrt(total), *coef =
+ * min(max_norm / (norm + 1e-6f), 1) in float32 as torch.nn.utils.clip_grad_norm_ forms it (a NaN norm gives NaN, an infinite one
+ * 0). All three are device addresses. Every sum has one fixed order and there are no atomics: equal gradients give equal bits on
+ * every call, aligned or not. The workspace (8-byte aligned) needs no initialisation; its size depends on the counts alone and
+ * is 0 for a table the operator refuses. Refused with OCM_EINVAL: as above (only grad is looked at), null outputs, a null, short
+ * or misaligned workspace. */
+size_t ocm_grad_norm_workspace_bytes(const OcmOptimTensor *tensors, int32_t n);
+int ocm_op_grad_norm(const OcmOptimTensor *tensors, int32_t n, double max_norm, double *sumsq, float *norm, float *coef,
+                     void *workspace, size_t workspace_bytes, void *stream);
+/* grad = grad * *coef for every gradient of the table, the coefficient read from device memory by the kernel. */
+int ocm_op_grad_scale(const OcmOptimTensor *tensors, int32_t n, const float *coef, void *stream);
+
 /* ---- sliding-window index math (host, integer; sw_processing.py:151-163) ---- */
 /* Number of windows per axis: len(range(0, size - 2*stride, stride)). */
 int32_t ocm_sw_count(int32_t size, int32_t stride);

@@ -24,6 +24,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import vit_ocm_wmsegmentation_amd  # noqa: E402,F401
 from vit_ocm_wmsegmentation_amd import _lib  # noqa: E402
 from vit_ocm_wmsegmentation_amd import model as M  # noqa: E402
+from vit_ocm_wmsegmentation_amd import optimizer as OPT  # noqa: E402
 from vit_ocm_wmsegmentation_amd import utils as U  # noqa: E402
 
 
@@ -86,6 +87,8 @@ def main():
     ap.add_argument("--depth", type=int, default=12)
     ap.add_argument("--precision", default="bf16x3", choices=sorted(_lib.PRECISIONS))
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--optimizer", default="torch", choices=["torch", "hip"],
+                    help="the HIP step's optimizer: torch.optim (default) or optimizer.py's multi-tensor kernels")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     B, S, p, D, H = args.batch, args.img, 8, 384, 6
@@ -96,7 +99,7 @@ def main():
     lp = M.LinearProbing(enc, p, layer_num=2).to(dev).train()
     enc.set_precision(args.precision)
     loss_fn = U.DiceLoss()
-    opt = torch.optim.Adam(lp.parameters(), lr=1e-4)
+    opt = (OPT.Adam if args.optimizer == "hip" else torch.optim.Adam)(lp.parameters(), lr=1e-4)
     twin = EagerTwin(D, args.depth, H, p, S).to(dev).train()
     opt_t = torch.optim.Adam(twin.parameters(), lr=1e-4)
     x = torch.rand(B, 3, S, S, device=dev) * 0.3

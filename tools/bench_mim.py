@@ -24,6 +24,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import vit_ocm_wmsegmentation_amd  # noqa: E402,F401
 from vit_ocm_wmsegmentation_amd import _lib  # noqa: E402
 from vit_ocm_wmsegmentation_amd import model as M  # noqa: E402
+from vit_ocm_wmsegmentation_amd import optimizer as OPT  # noqa: E402
 
 
 class EagerTwin(nn.Module):
@@ -83,6 +84,8 @@ def main():
     ap.add_argument("--depth", type=int, default=4)
     ap.add_argument("--precision", default="bf16x3", choices=sorted(_lib.PRECISIONS))
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--optimizer", default="torch", choices=["torch", "hip"],
+                    help="the HIP step's optimizer: torch.optim (default) or optimizer.py's multi-tensor kernels")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     B, S, p, D, H = args.batch, args.img, 8, 384, 3
@@ -91,7 +94,7 @@ def main():
                                        qkv_bias=True, norm_layer=partial(nn.LayerNorm, eps=1e-6), interpolate_encoding=True)
     mim = M.MIM(enc, p).to(dev).train()
     enc.set_precision(args.precision)
-    opt = torch.optim.AdamW(mim.parameters(), lr=1e-4, weight_decay=0.05)
+    opt = (OPT.AdamW if args.optimizer == "hip" else torch.optim.AdamW)(mim.parameters(), lr=1e-4, weight_decay=0.05)
     twin = EagerTwin(D, args.depth, H, p, S).to(dev).train()
     opt_t = torch.optim.AdamW(twin.parameters(), lr=1e-4, weight_decay=0.05)
     x = torch.rand(B, 3, S, S, device=dev) * 0.3

@@ -5,7 +5,7 @@ under torch autograd with the same weights, timed in alternation with the HIP st
 the training forward keeps per image. The split by kernel class comes from a kernel trace of this tool
 (rocprofv3 --kernel-trace --stats).
 
-  python tools/bench_swin_train.py [--batch 8] [--precision bf16] [--reps 5]
+  python tools/bench_swin_train.py [--batch 8] [--precision bf16] [--reps 5] [--optimizer hip]
 """
 import argparse
 import json
@@ -21,6 +21,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import vit_ocm_wmsegmentation_amd  # noqa: E402,F401
 from oracle import swin_oracle as SO  # noqa: E402
 from vit_ocm_wmsegmentation_amd import _lib, synth  # noqa: E402
+from vit_ocm_wmsegmentation_amd import optimizer as OPT  # noqa: E402
 from vit_ocm_wmsegmentation_amd import swin as SW  # noqa: E402
 
 
@@ -38,6 +39,8 @@ def main():
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--precision", default="bf16", choices=sorted(_lib.PRECISIONS))
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--optimizer", default="torch", choices=["torch", "hip"],
+                    help="the HIP step's optimizer: torch.optim (default) or optimizer.py's multi-tensor kernels")
     args = ap.parse_args()
     dev, B = torch.device("cuda:0"), args.batch
     cfg = dict(synth.SWIN_TINY)
@@ -45,7 +48,7 @@ def main():
     m = SW.SwinForImageClassification(SW.SwinConfig(num_labels=5))
     m.load_state_dict(sd)
     m = m.to(dev).set_precision(args.precision).train().requires_grad_(True)
-    opt = torch.optim.AdamW(m.parameters(), lr=5e-5)
+    opt = (OPT.AdamW if args.optimizer == "hip" else torch.optim.AdamW)(m.parameters(), lr=5e-5)
     prm = {k: v.to(dev).requires_grad_(True) for k, v in sd.items()}
     opt_t = torch.optim.AdamW(list(prm.values()), lr=5e-5)
     torch.manual_seed(0)

@@ -20,6 +20,7 @@ sys.path.insert(0, ROOT)
 from tests.unet_twin import UNetTwin  # noqa: E402  (the eager twin: F.conv2d, F.batch_norm, F.max_pool2d, F.conv_transpose2d)
 from vit_ocm_wmsegmentation_amd import _lib  # noqa: E402
 from vit_ocm_wmsegmentation_amd import model as M  # noqa: E402
+from vit_ocm_wmsegmentation_amd import optimizer as OPT  # noqa: E402
 
 
 def dice_loss(pred, target, smooth=1.0):
@@ -60,6 +61,8 @@ def main():
     ap.add_argument("--img", type=int, default=384)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--precisions", default="fp32,bf16x3,bf16")
+    ap.add_argument("--optimizer", default="torch", choices=["torch", "hip"],
+                    help="the HIP step's optimizer: torch.optim (default) or optimizer.py's multi-tensor kernels")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
@@ -71,7 +74,7 @@ def main():
     for precision in args.precisions.split(","):
         net = M.build_unet().to(dev).train().enable_training()
         net.precision = precision
-        opt = torch.optim.Adam(net.parameters(), lr=1e-4)
+        opt = (OPT.Adam if args.optimizer == "hip" else torch.optim.Adam)(net.parameters(), lr=1e-4)
         log = net.__dict__["_phase_log"] = []
         for _ in range(2):  # warm-up: operand copies, LDS opt-in, allocator
             _step(net, opt, x, y, log)

@@ -115,6 +115,18 @@ class OcmAttentionPlanInfo(C.Structure):  # ocm_attention_plan: the kernel the a
         ("workspace_need", C.c_uint64)]
 
 
+class OcmOptimTensor(C.Structure):  # one tensor of an optimizer / gradient-norm call: device addresses and the element count
+    _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("count", C.c_int64)]
+
+
+class OcmOptimHyper(C.Structure):  # ocm_op_optim_step: the values of one step, in double as torch's Python holds them
+    _fields_ = [(n, C.c_int32) for n in ("rule", "nesterov", "first_step", "reserved")] + [
+        (n, C.c_double) for n in ("lr", "beta1", "beta2", "eps", "weight_decay", "step_size", "bias_correction2_sqrt",
+                                  "momentum", "dampening")]
+
+
+OCM_OPTIM_ADAMW, OCM_OPTIM_ADAM, OCM_OPTIM_SGD = 0, 1, 2
+
 (OCM_ATTN_BF16_WHOLE, OCM_ATTN_BF16_STREAM, OCM_ATTN_FP32_STREAM, OCM_ATTN_X3_WAVE_SPLIT, OCM_ATTN_X3_PIPELINED, OCM_ATTN_X3_DMA,
  OCM_ATTN_X3_DMA_KSPLIT) = range(7)
 
@@ -266,6 +278,11 @@ SIGNATURES = {
     "ocm_resample_u8_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32]),
     "ocm_op_resample_u8": (C.c_int, [_vp, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _i32,
                                      _i32, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "ocm_optim_limits": (None, [C.POINTER(_i32), C.POINTER(_i32)]),
+    "ocm_op_optim_step": (C.c_int, [_vp, _i32, C.POINTER(OcmOptimHyper), _vp]),
+    "ocm_grad_norm_workspace_bytes": (_sz, [_vp, _i32]),
+    "ocm_op_grad_norm": (C.c_int, [_vp, _i32, C.c_double, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "ocm_op_grad_scale": (C.c_int, [_vp, _i32, _vp, _vp]),
     "ocm_sw_count": (_i32, [_i32, _i32]),
     "ocm_sw_origins": (_i32, [_i32, _i32, _i32, C.POINTER(_i32), _i32]),
     "ocm_sw_shard": (_i32, [_i32, _i32, _i32, C.POINTER(_i32), C.POINTER(_i32)]),

@@ -27,6 +27,10 @@ region-query index of analyse_attention.py, on device.
                       PIL.Image.resize / Image.crop(...).resize / ToTensor of uint8 images (sw_processing.py:217-231,
                       analyse_attention.py:102-120, data.py's transforms), byte for byte, for a batch in one call on device
                       (kernels_resample.hip); the transforms themselves are in data.py
+  clip_grad_norm_, grad_norm, get_grad_norm
+                      torch.nn.utils.clip_grad_norm_ (mim.py, train.py) and reference utils.py:363-373, the 2-norm of every
+                      gradient in one multi-tensor pass with float64 sums and the scaling by a coefficient that never leaves
+                      the device (kernels_optim.hip); the optimizers themselves are in optimizer.py
 """
 import ctypes as C
 
@@ -36,6 +40,7 @@ import torch.nn as nn
 
 from . import _lib
 from .engine import _p, _require_hip, _stream
+from .optimizer import _check_tensor, _table
 
 
 def compute_attention(attentions, query, w_featmap, h_featmap, patch_size):
@@ -829,3 +834,68 @@ def pil_resize(images_u8, size, resample=BICUBIC, box=None, crop=None, hflip=Non
     if to_tensor not in (False, True, "both"):
         raise ValueError(f"to_tensor = {to_tensor!r} (False, True or 'both')")
     return ResamplePlan(images_u8, size, resample, box, crop, hflip, vflip, layout).run(images_u8, to_tensor)
+
+
+# ---- the gradient norm and its clipping (torch.nn.utils.clip_grad_norm_, reference utils.py:363-373; kernels_optim.hip) -----------
+def _grad_norm_launch(parameters, max_norm, norm_type, scale, error_if_nonfinite=False):
+    """ocm_op_grad_norm (and, with `scale`, ocm_op_grad_scale) over the gradients of `parameters`, which may be a tensor or any
+    iterable (it is walked once); returns the norm as a 0-dim float32 tensor on the gradients' device. Nothing synchronises with
+    the host unless `error_if_nonfinite` asks for the norm between the two launches."""
+    if float(norm_type) != 2.0:
+        raise ValueError(f"norm_type = {norm_type}: the HIP path computes the 2-norm only")
+    if isinstance(parameters, torch.Tensor):
+        parameters = [parameters]
+    params = [p for p in parameters if p.grad is not None]
+    if not params:
+        return torch.tensor(0.0)  # what torch returns for no gradients
+    device, grads = None, []
+    for p in params:
+        g = p.grad
+        device = _check_tensor(g, "a gradient", device)
+        if not g.is_contiguous():
+            g = g.contiguous()
+            if scale:
+                p.grad = g  # scaled in place below: the parameter keeps the copy
+        grads.append(g)  # a copy that is only read lives until the launches are queued; the allocator is stream-ordered
+    zeros = [0] * len(grads)
+    table = _table((zeros, [g.data_ptr() for g in grads], zeros, zeros, [g.numel() for g in grads]))
+    lib = _lib.load()
+    tab, n = table.ctypes.data, table.shape[0]
+    nbytes = lib.ocm_grad_norm_workspace_bytes(tab, n)
+    if not nbytes:
+        raise ValueError("a gradient holds more than 2^36 elements")
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=device)
+    out = torch.empty(4, dtype=torch.float32, device=device)  # [sum of squares: float64][norm][coefficient]
+    base = out.data_ptr()
+    with torch.cuda.device(device):
+        stream = _stream()
+        _lib.check(lib.ocm_op_grad_norm(tab, n, float(max_norm), base, base + 8, base + 12, _p(ws), nbytes, stream))
+        if error_if_nonfinite and not bool(torch.isfinite(out[2])):
+            raise RuntimeError(f"The total norm of order {float(norm_type)} for gradients from `parameters` is non-finite, so it "
+                               "cannot be clipped. To disable this error and scale the gradients by the non-finite norm anyway, "
+                               "set `error_if_nonfinite=False`")
+        if scale:
+            _lib.check(lib.ocm_op_grad_scale(tab, n, base + 12, stream))
+            torch.autograd.graph.increment_version(grads)
+    return out[2]
+
+
+def clip_grad_norm_(parameters, max_norm, norm_type=2.0, error_if_nonfinite=False, foreach=None):
+    """torch.nn.utils.clip_grad_norm_ for fp32 gradients on one HIP device: every gradient is multiplied in place by
+    clamp(max_norm / (norm + 1e-6), max=1), formed on the device in float32 as torch forms it (a NaN or infinite norm does what
+    torch's does). `parameters` is a tensor or any iterable of tensors, a generator such as model.parameters() included. Returns
+    the norm before clipping, a 0-dim float32 device tensor, without synchronising; `error_if_nonfinite` reads it back once, before
+    anything is scaled, as torch's does. A non-contiguous gradient is replaced by a contiguous copy and that is scaled. The norm
+    is the float32 rounding of a float64 sum of squares: the same bits on every call. `foreach` is accepted and ignored."""
+    return _grad_norm_launch(parameters, max_norm, norm_type, scale=True, error_if_nonfinite=error_if_nonfinite)
+
+
+def grad_norm(parameters, norm_type=2.0):
+    """The 2-norm of all gradients of `parameters` as clip_grad_norm_ returns it, the gradients left as they are (the norm of a
+    non-contiguous gradient is taken on a temporary contiguous copy)."""
+    return _grad_norm_launch(parameters, float("inf"), norm_type, scale=False)
+
+
+def get_grad_norm(parameters, norm_type=2):
+    """reference utils.py:363-373 as a Python float: one synchronisation instead of one .item() per parameter."""
+    return float(grad_norm(parameters, norm_type))

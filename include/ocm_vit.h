@@ -693,6 +693,29 @@ int ocm_op_binary_morph(const uint8_t *src, uint8_t *dst, int32_t batch, int32_t
 int ocm_op_query_mean(const float *rows, const int32_t *sel, const int32_t *offsets, float *maps, int32_t tiles, int32_t heads,
                       int32_t n_rows, int32_t pixels, int32_t n_sel, void *stream);
 
+/* ---- ROI-guided SimMIM masks: mim.py --roi_masking (data.py:211-233, SimMIMTransform.__call__; kernels_roi.hip) ----
+ * The two ends of the per-image chain threshold -> get_ROIs -> resize(order=0) -> mask * rois; the closing and the labelling
+ * between them are ocm_op_binary_morph (twice) and ocm_op_label8 on the whole batch. Same conventions as the block above. */
+/* binary = ToPILImage()(img).convert('L') > level: `batch` float32 images of `chans` (1 or 3) dense (h, w) planes, images
+ * stride_b and planes stride_c elements apart; L is ocm_op_image_to_gray_u8's arithmetic bit for bit (mul(255) truncated, PIL's
+ * integer RGB -> L weights; one plane is its own grey image). mask [batch][h][w] = 0 / 1; white[b] = the number of white pixels of
+ * image b, an exact integer (the operator zeroes it itself, in stream order). level 0..255. */
+int ocm_op_roi_threshold(const float *images, int64_t stride_b, int64_t stride_c, int32_t chans, int32_t batch, int32_t h,
+                         int32_t w, int32_t level, uint8_t *mask, int32_t *white, void *stream);
+/* labels [batch][h][w] int32 (ocm_op_label8 of the closed mask); row_idx [gh] / col_idx [gw] int32 device tables: grid cell (i, j)
+ * samples labels[b][row_idx[i]][col_idx[j]] — scipy.ndimage.zoom(order=0, mode='mirror', grid_mode=True), which is what
+ * skimage.transform.resize(order=0, anti_aliasing=False) calls; an entry outside the image reads as background. For image b:
+ *   roi(i, j) = white[b] >= min_size && (label & 255) != 0
+ *               (remove_small_objects reads the uint8 {0, 255} image as a label image: the white class goes as a whole, and only
+ *               when it holds fewer than min_size pixels in total; rois.astype(np.uint8) of a float64 label wraps modulo 256)
+ *   new(i, j) = masks[b][i][j] != 0 && roi(i, j)
+ *   out[b] = new and used[b] = 1 when any cell of new is set, else out[b] = (masks[b] != 0) and used[b] = 0.
+ * masks / out: [batch][gh][gw] elements of mask_bytes bytes (1: uint8 or bool, 8: int64), out holds 0 / 1; masks != out.
+ * One workgroup per image. */
+int ocm_op_roi_apply(const int32_t *labels, const int32_t *row_idx, const int32_t *col_idx, const int32_t *white,
+                     int32_t min_size, const void *masks, int32_t mask_bytes, void *out, uint8_t *used, int32_t batch, int32_t h,
+                     int32_t w, int32_t gh, int32_t gw, void *stream);
+
 /* ---- Chan-Vese level sets: skimage.segmentation.chan_vese (0.19.x) as utils.py:199-225 calls it (eval.py's "chan-vese" /
  * "chan-vese_ours" methods; kernels_levelset.hip) ----
  * For each of `batch` independent images: image [batch][h][w] float64, already normalised as skimage does (img - min, then

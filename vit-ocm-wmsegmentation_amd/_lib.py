@@ -264,6 +264,8 @@ SIGNATURES = {
     "ocm_op_remove_small_objects": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _sz, _vp]),
     "ocm_op_binary_morph": (C.c_int, [_vp, _vp, _i32, _i32, _i32, C.c_uint64, _i32, _i32, _i32, _vp]),
     "ocm_op_query_mean": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "ocm_op_roi_threshold": (C.c_int, [_vp, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "ocm_op_roi_apply": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "ocm_chan_vese_tile": (_i32, []),
     "ocm_chan_vese_workspace_bytes": (_sz, [_i32, _i32, _i32]),
     "ocm_op_chan_vese": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, C.c_double, C.c_double, C.c_double, C.c_double, _i32,

@@ -10,17 +10,32 @@ ocm_op_resample_u8 call per batch (utils.pil_resize, kernels_resample.hip), byte
   random_resized_crop_params torchvision's RandomResizedCrop.get_params on a torch.Generator
   simmim_images              data.py:189-198 (SimMIMTransform.transform_img): RandomResizedCrop, two random flips, ToTensor
   MaskGenerator              data.py:163-186, restated as is (a few integers per image: numpy on the host)
+  roi_mask                   data.py:216-233 (SimMIMTransform.__call__ with --roi_masking): the random masks of a batch kept only
+                             on tissue — grey level > 10, get_ROIs, resize(order=0) onto the patch grid, mask * rois unless that
+                             is empty — in five operator calls per batch (kernels_roi.hip, kernels_morph.hip)
+  SimMIMTransform            data.py:189-253 for a batch: simmim_images, the MaskGenerator draws and, with args.roi_masking,
+                             roi_mask -> (img, mask), what MIM.forward takes
 
 Decoding files stays on the host. torchvision is not installed here: random_resized_crop_params restates its get_params from
-the source, and the parity of its random stream with a live torchvision is unpinned. The ROI masking of SimMIMTransform
-(data.py:216-233) resizes with skimage's resize(order=0), which is not installed either, and stays out.
+the source, and the parity of its random stream with a live torchvision is unpinned.
+
+To switch build_loader_simmim (data.py:271-280) over: let the dataset return the decoded uint8 (H,W,3) tile as it is (no
+transform in the workers), collate with default_collate, and in the training loop call
+    transform = SimMIMTransform(args)                  # once
+    img, mask = transform(batch_u8.to(device))         # per step; mim(img, mask) as before
+scikit-image is not installed here either, so the parity of roi_mask with skimage itself is unpinned; what is pinned on live
+libraries (tests/test_roi_mask_host.py) is what skimage 0.19.3 calls and what the chain is made of: scipy.ndimage.zoom(order=0,
+mode='mirror', grid_mode=True) for resize(order=0, anti_aliasing=False), scipy.ndimage's dilation, erosion and label, Pillow's
+convert('L'), torch's mul(255).byte() and numpy's float64 -> uint8 cast.
 """
+import functools
 import math
 
 import numpy as np
 import torch
 
-from . import utils
+from . import _lib, utils
+from .engine import _p, _require_hip, _stream
 from .utils import BICUBIC, BILINEAR, NEAREST  # noqa: F401
 
 
@@ -149,3 +164,92 @@ class MaskGenerator:
         mask[mask_idx] = 1
         mask = mask.reshape((self.rand_size, self.rand_size))
         return mask.repeat(self.scale, axis=0).repeat(self.scale, axis=1)
+
+
+@functools.lru_cache(maxsize=16)
+def _roi_tables(h, w, gh, gw, device):
+    """utils.roi_sample_index of both axes as one int32 device tensor (rows, then columns): one upload per geometry and device."""
+    return torch.from_numpy(np.concatenate([utils.roi_sample_index(h, gh), utils.roi_sample_index(w, gw)])).to(device)
+
+
+def roi_mask(images, masks, level=10, min_size=20):
+    """The ROI step of SimMIMTransform.__call__ (data.py:216-233) for a batch, nothing copied to the host. Per image:
+      binary = 255 where ToPILImage()(img).convert('L') > level, else 0 (uint8)
+      rois   = get_ROIs(binary): remove_small_objects -> binary_closing(disk(2)) -> label (8-connected)
+      rois   = resize(rois, mask.shape, order=0, anti_aliasing=False, preserve_range=True).astype(np.uint8) != 0
+      mask   = mask * rois, unless that is empty: then the mask stays as it was
+    Two quirks of the reference are kept (utils.get_ROIs documents the first). remove_small_objects reads the uint8 image as a
+    label image, so the white class is cleared as a whole, and only when it holds fewer than min_size pixels IN TOTAL — its
+    components do not matter. And the uint8 cast of the float64 label image wraps modulo 256 (numpy on x86-64: 256.0 -> 0,
+    257.0 -> 1, no warning), so a sampled label that is a multiple of 256 counts as background: (label & 255) != 0.
+    images: float32 (B,C,S1,S2) on the HIP device, C in (1, 3), read through its image and channel strides (a batch slice is
+    not copied). masks: (B,gh,gw) int64 / uint8 / bool on the same device. Returns (new_masks of the dtype and shape of masks,
+    holding 0 / 1; used: bool (B,), whether image b got mask * rois). The sampling is utils.roi_sample_index."""
+    _require_hip(images, "images")
+    _require_hip(masks, "masks")
+    if images.dim() != 4 or images.dtype != torch.float32 or images.shape[1] not in (1, 3):
+        raise ValueError(f"expected float32 (B,C,H,W) images with C in (1,3), got {images.dtype} {tuple(images.shape)}")
+    if masks.dim() != 3 or masks.dtype not in (torch.int64, torch.uint8, torch.bool) or masks.shape[0] != images.shape[0]:
+        raise ValueError(f"expected int64 / uint8 / bool (B,gh,gw) masks for {images.shape[0]} images, got {masks.dtype} "
+                         f"{tuple(masks.shape)}")
+    if masks.device != images.device:
+        raise ValueError(f"images on {images.device}, masks on {masks.device}: one device per call")
+    B, Cc, h, w = images.shape
+    gh, gw = int(masks.shape[1]), int(masks.shape[2])
+    if B < 1 or gh < 1 or gw < 1 or h < 1 or w < 1:
+        raise ValueError(f"empty batch, image or grid: images {tuple(images.shape)}, masks {tuple(masks.shape)}")
+    if images.stride(3) != 1 or images.stride(2) != w or (Cc == 3 and images.stride(1) < h * w) or (
+            B > 1 and images.stride(0) < h * w):
+        images = images.contiguous()
+    dev, lib = images.device, _lib.load()
+    m = masks.contiguous()
+    binary = torch.empty((B, h, w), dtype=torch.uint8, device=dev)
+    grown = torch.empty_like(binary)
+    white = torch.empty(B, dtype=torch.int32, device=dev)
+    labels = torch.empty((B, h, w), dtype=torch.int32, device=dev)
+    counts = torch.empty(B, dtype=torch.int32, device=dev)
+    nbytes = lib.ocm_label8_workspace_bytes(B, h, w)
+    ws = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
+    tables = _roi_tables(h, w, gh, gw, dev)
+    out = torch.empty_like(m)
+    used = torch.empty(B, dtype=torch.bool, device=dev)
+    size, bits = utils.footprint_bits(utils.DISK2)
+    with torch.cuda.device(dev):
+        s = _stream()
+        _lib.check(lib.ocm_op_roi_threshold(_p(images), int(images.stride(0)), int(images.stride(1)), Cc, B, h, w, int(level),
+                                            _p(binary), _p(white), s))
+        _lib.check(lib.ocm_op_binary_morph(_p(binary), _p(grown), B, h, w, bits, size, 0, 0, s))
+        _lib.check(lib.ocm_op_binary_morph(_p(grown), _p(binary), B, h, w, bits, size, 1, 1, s))  # binary: now the closed mask
+        _lib.check(lib.ocm_op_label8(_p(binary), _p(labels), _p(counts), B, h, w, _p(ws), nbytes, s))
+        _lib.check(lib.ocm_op_roi_apply(_p(labels), _p(tables), tables.data_ptr() + 4 * gh, _p(white), int(min_size), _p(m),
+                                        m.element_size(), _p(out), _p(used), B, h, w, gh, gw, s))
+    return out, used
+
+
+class SimMIMTransform:
+    """data.py:189-253 for a batch of decoded tiles. args carries what the reference reads: DATA.IMG_SIZE, DATA.MASK_PATCH_SIZE,
+    DATA.MASK_RATIO, MODEL.PATCH_SIZE and roi_masking. The cv2.imwrite calls of the reference (:234-250, debug PNGs to a fixed
+    path) are not part of this."""
+
+    def __init__(self, args):
+        self.roi_masking = args.roi_masking
+        self.image_size = args.DATA.IMG_SIZE
+        self.mask_generator = MaskGenerator(
+            input_size=args.DATA.IMG_SIZE,
+            mask_patch_size=args.DATA.MASK_PATCH_SIZE,
+            model_patch_size=args.MODEL.PATCH_SIZE,
+            mask_ratio=args.DATA.MASK_RATIO,
+        )
+
+    def __call__(self, images_u8, generator=None):
+        """uint8 (B,H,W,3) on the HIP device -> (img float32 (B,3,S,S) = simmim_images, mask int64 (B,G,G) on the device, G =
+        IMG_SIZE / MODEL.PATCH_SIZE). The masks are drawn image after image by MaskGenerator from numpy's global stream (the
+        crops and flips from `generator`, torch's stream: the two do not interleave); with roi_masking they go through
+        roi_mask on the device."""
+        _require_hip(images_u8, "images")
+        img = simmim_images(images_u8, self.image_size, generator)
+        draws = np.stack([self.mask_generator() for _ in range(img.shape[0])]).astype(np.int64)
+        mask = torch.from_numpy(draws).to(img.device)
+        if self.roi_masking:
+            mask = roi_mask(img, mask)[0]
+        return img, mask

@@ -421,6 +421,20 @@ def get_ROIs(mask):
     return label_regions(binary_closing(cleaned))[0]
 
 
+def roi_sample_index(in_size, out_size):
+    """The source index of every output cell of skimage.transform.resize(order=0, anti_aliasing=False) along one axis (0.19.3:
+    scipy.ndimage.zoom(order=0, mode='mirror', grid_mode=True)), an int32 (out_size,) numpy array, on the host. With z =
+    in_size / out_size as a double, idx(i) = clamp(floor(((i + 0.5) * z - 0.5) + 0.5), 0, in_size - 1): the coordinate first,
+    then the rounding of order 0, in two steps as scipy takes them — the shorter floor((i + 0.5) * in_size / out_size) lands on
+    another pixel for some pairs, (30, 11) and (52, 23) among them."""
+    in_size, out_size = int(in_size), int(out_size)
+    if in_size < 1 or out_size < 1:
+        raise ValueError(f"roi_sample_index({in_size}, {out_size}): both sizes must be at least 1")
+    z = np.float64(in_size) / np.float64(out_size)
+    coord = (np.arange(out_size, dtype=np.float64) + 0.5) * z - 0.5
+    return np.clip(np.floor(coord + 0.5), 0, in_size - 1).astype(np.int32)
+
+
 def region_centroids(labels, counts, min_area=10):
     """regionprops of int32 (B,H,W) label images with counts[b] regions each: per image the list of (x0, y0) =
     (centroid column, centroid row) float64 pairs of the regions with area >= min_area, in label order (utils.py:269-281)."""

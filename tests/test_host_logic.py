@@ -212,6 +212,7 @@ def test_engine_parameter_slots_follow_replaced_parameters():
     more than the call's launches); a Parameter object replaced afterwards is still what the next signature sees."""
     import torch.nn as nn
     import vit_ocm_wmsegmentation_amd.dino.vision_transformer as vits
+    from vit_ocm_wmsegmentation_amd.engine import signature
     m = vits.vit_tiny(patch_size=16, num_classes=0)
     named = dict(m._named_engine_params())
     want = {n for n, _ in m.named_parameters() if not n.startswith(("pos_embed", "head."))}
@@ -222,10 +223,10 @@ def test_engine_parameter_slots_follow_replaced_parameters():
     assert again["blocks.1.attn.qkv.weight"] is m.blocks[1].attn.qkv.weight and again["blocks.1.attn.qkv.weight"] is not old
     with torch.no_grad():
         m.blocks[0].mlp.fc1.bias.add_(1.0)  # in-place update: same object, new version -> a different signature
-    sig0 = tuple((p.data_ptr(), p._version) for _, p in m._named_engine_params())
+    sig0 = signature(p for _, p in m._named_engine_params())
     with torch.no_grad():
         m.blocks[0].mlp.fc1.bias.add_(1.0)
-    assert sig0 != tuple((p.data_ptr(), p._version) for _, p in m._named_engine_params())
+    assert sig0 != signature(p for _, p in m._named_engine_params())
     import pickle
     m2 = pickle.loads(pickle.dumps(m))  # the cached slots hold module references: they are not part of the pickled state
     assert set(dict(m2._named_engine_params())) == want

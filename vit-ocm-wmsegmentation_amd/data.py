@@ -35,7 +35,7 @@ import numpy as np
 import torch
 
 from . import _lib, utils
-from .engine import _p, _require_hip, _stream
+from .engine import _p, _require_hip, _stream, _ws
 from .utils import BICUBIC, BILINEAR, NEAREST  # noqa: F401
 
 
@@ -209,7 +209,7 @@ def roi_mask(images, masks, level=10, min_size=20):
     labels = torch.empty((B, h, w), dtype=torch.int32, device=dev)
     counts = torch.empty(B, dtype=torch.int32, device=dev)
     nbytes = lib.ocm_label8_workspace_bytes(B, h, w)
-    ws = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
+    ws = _ws(nbytes, dev)
     tables = _roi_tables(h, w, gh, gw, dev)
     out = torch.empty_like(m)
     used = torch.empty(B, dtype=torch.bool, device=dev)

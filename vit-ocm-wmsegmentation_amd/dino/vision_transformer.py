@@ -22,29 +22,15 @@ import torch
 import torch.nn as nn
 
 from .. import _lib
-from ..engine import Engine, _p, _require_hip, _stream, to_operand
+from ..engine import OPERAND_DTYPE, Engine, SourceCache, _f32c, _p, _require_hip, _stream, signature, to_operand
 from .utils import trunc_normal_
 
 
-def _f32c(t):
-    return t.detach().to(torch.float32).contiguous()
-
-
-class _OperandCache:
-    """Operand copy (engine.to_operand: bf16 / fp32 / split-bf16 pairs) of an fp32 matrix parameter for the stand-alone
-    operator paths, rebuilt when the parameter or the precision changes."""
-
-    def __init__(self):
-        self.key, self.val = None, None
-
-    def get(self, param, prec):
-        key = (param.data_ptr(), param._version, param.device, prec)
-        if key != self.key:
-            self.key, self.val = key, to_operand(_f32c(param), prec)
-        return self.val
-
-
-_ACT_DTYPE = {_lib.OCM_PREC_BF16: torch.bfloat16, _lib.OCM_PREC_FP32: torch.float32, _lib.OCM_PREC_BF16X3: torch.int32}
+def _weight_operand(mod, child, prec):
+    """Operand copy (engine.to_operand: bf16 / fp32 / split-bf16 pairs) of the weight of mod's nn.Linear `child` for the
+    stand-alone operator paths, rebuilt when the parameter, its device or the precision changes (engine.SourceCache)."""
+    w = getattr(mod, child).weight
+    return mod._w.get(child, (w,), lambda: to_operand(_f32c(w), prec), (w.device, prec))
 
 
 def _module_prec(mod):
@@ -84,7 +70,7 @@ class Mlp(nn.Module):
         self.act = act_layer()
         self.fc2 = nn.Linear(hidden_features or in_features, out_features or in_features)
         self.drop = nn.Dropout(drop)
-        self._w = (_OperandCache(), _OperandCache())
+        self._w = SourceCache()
 
     def forward(self, x):
         """Free-standing use (outside a VisionTransformer): the stand-alone operators in this module's `precision`
@@ -96,11 +82,11 @@ class Mlp(nn.Module):
         rows, hid, out_f = x32.shape[0], self.fc1.out_features, self.fc2.out_features
         with torch.cuda.device(x32.device):
             a = to_operand(x32, pc)
-            h = torch.empty((rows, hid), dtype=_ACT_DTYPE[pc], device=x32.device)
-            _lib.check(lib.ocm_op_linear(pc, _p(a), _p(self._w[0].get(self.fc1.weight, pc)), _p(_bias_or_zeros(self.fc1)), None,
+            h = torch.empty((rows, hid), dtype=OPERAND_DTYPE[pc], device=x32.device)
+            _lib.check(lib.ocm_op_linear(pc, _p(a), _p(_weight_operand(self, "fc1", pc)), _p(_bias_or_zeros(self.fc1)), None,
                                          _p(h), rows, hid, shape[-1], _lib.OCM_EPI_BIAS_GELU_BF16, _stream()))
             y = torch.empty((rows, out_f), dtype=torch.float32, device=x32.device)
-            _lib.check(lib.ocm_op_linear(pc, _p(h), _p(self._w[1].get(self.fc2.weight, pc)), _p(_bias_or_zeros(self.fc2)), None,
+            _lib.check(lib.ocm_op_linear(pc, _p(h), _p(_weight_operand(self, "fc2", pc)), _p(_bias_or_zeros(self.fc2)), None,
                                          _p(y), rows, out_f, hid, _lib.OCM_EPI_BIAS_F32, _stream()))
         return y.reshape(*shape[:-1], out_f)
 
@@ -116,7 +102,7 @@ class Attention(nn.Module):
         self.attn_drop = nn.Dropout(attn_drop)
         self.proj = nn.Linear(dim, dim)
         self.proj_drop = nn.Dropout(proj_drop)
-        self._w = (_OperandCache(), _OperandCache())
+        self._w = SourceCache()
 
     def forward(self, x, return_qkv=False):
         """Free-standing use (outside a VisionTransformer): the stand-alone operators in this module's `precision`
@@ -136,13 +122,13 @@ class Attention(nn.Module):
         # reference accepts every dim / num_heads, :66-90) the generic fp32 kernel on the fp32 qkv tensor
         mfma = hd in (64, 128)
         x32 = _f32c(x).reshape(B * N, Cd)
-        dev, npad, adt = x32.device, lib.ocm_n_pad_prec(pc, N), _ACT_DTYPE[pc]
+        dev, npad, adt = x32.device, lib.ocm_n_pad_prec(pc, N), OPERAND_DTYPE[pc]
         with torch.cuda.device(dev):
             a = to_operand(x32, pc)
             qkv = torch.empty((3, B, H, N, hd), dtype=torch.float32, device=dev)
             ctx = torch.empty((B * N, Cd), dtype=adt, device=dev)
             attn = torch.empty((B, H, N, N), dtype=torch.float32, device=dev)
-            wq, bq = _p(self._w[0].get(self.qkv.weight, pc)), _p(_bias_or_zeros(self.qkv))
+            wq, bq = _p(_weight_operand(self, "qkv", pc)), _p(_bias_or_zeros(self.qkv))
             if mfma:
                 q = torch.empty((B * H, npad, hd), dtype=adt, device=dev)
                 k = torch.empty_like(q)
@@ -157,7 +143,7 @@ class Attention(nn.Module):
                 _lib.check(lib.ocm_op_qkv_proj_hd(pc, _p(a), wq, bq, None, None, None, _p(qkv), B, N, H, hd, _stream()))
                 _lib.check(lib.ocm_op_attention_generic(pc, _p(qkv), _p(ctx), _p(attn), B, N, H, hd, float(self.scale), _stream()))
             y = torch.empty((B * N, Cd), dtype=torch.float32, device=dev)
-            _lib.check(lib.ocm_op_linear(pc, _p(ctx), _p(self._w[1].get(self.proj.weight, pc)), _p(_bias_or_zeros(self.proj)),
+            _lib.check(lib.ocm_op_linear(pc, _p(ctx), _p(_weight_operand(self, "proj", pc)), _p(_bias_or_zeros(self.proj)),
                                          None, _p(y), B * N, Cd, Cd, _lib.OCM_EPI_BIAS_F32, _stream()))
         return y.reshape(B, N, Cd), attn, qkv
 
@@ -246,8 +232,8 @@ class VisionTransformer(nn.Module):
                            num_heads=num_heads, mlp_hidden=int(embed_dim * mlp_ratio), ln_eps=float(self.norm.eps),
                            qk_scale=float(qk_scale or (embed_dim // num_heads) ** -0.5))
         self._drop_any = max(drop_rate, attn_drop_rate, drop_path_rate) > 0
-        self.__dict__["_engines"] = {}
-        self.__dict__["_pos_cache"] = {}
+        self.__dict__["_engines"] = SourceCache()  # device -> Engine, made from _named_engine_params()
+        self.__dict__["_pos_cache"] = SourceCache()  # "pos" -> the table of the latest (shape, device), made from pos_embed
         self.__dict__["_gray_fold"] = False
         self.__dict__["_precision"] = _lib.DEFAULT_PRECISION
         for i, blk in enumerate(self.blocks):
@@ -267,7 +253,7 @@ class VisionTransformer(nn.Module):
 
     def __getstate__(self):
         st = self.__dict__.copy()
-        st["_engines"], st["_pos_cache"] = {}, {}
+        st["_engines"], st["_pos_cache"] = SourceCache(), SourceCache()  # (a shallow copy would share them otherwise)
         st.pop("_auto_graphs", None)
         st.pop("_param_slots", None)
         st.pop("_auto_seen", None)
@@ -282,7 +268,7 @@ class VisionTransformer(nn.Module):
         if self.patch_embed.proj.in_channels != 3 and on:
             raise ValueError("grayscale fold applies to a 3-channel patch embedding")
         self.__dict__["_gray_fold"] = bool(on)
-        self.__dict__["_engines"] = {}
+        self.__dict__["_engines"] = SourceCache()
         return self
 
     def set_precision(self, precision):
@@ -303,11 +289,11 @@ class VisionTransformer(nn.Module):
             raise ValueError(f"precision must be one of {sorted(_lib.PRECISIONS)}, got {precision!r}")
         if precision != self._precision:
             self.__dict__["_precision"] = precision
-            self.__dict__["_engines"] = {}
+            self.__dict__["_engines"] = SourceCache()
         return self
 
-    def _named_engine_params(self):
-        """(name, parameter) of everything the engine holds a copy of. The (owning module, key) pairs are resolved once —
+    def _named_engine_params(self, names=True):
+        """(name, parameter) of everything the engine holds a copy of (the parameters alone without `names`). The (owning module, key) pairs are resolved once —
         walking the module tree with named_parameters() costs more than a one-tile forward's launches — and the parameters
         are then read from the modules' own dicts, so a replaced Parameter object is still seen. A replaced SUB-MODULE
         (`blk.attn.qkv = nn.Linear(...)`, a swapped Block, a LoRA / quantisation wrapper) is seen too: the cache keeps the
@@ -326,23 +312,26 @@ class VisionTransformer(nn.Module):
                 slots.append((self.get_submodule(prefix) if prefix else self, key, n))
             edges = [(mod._modules, cn, child) for _, mod in self.named_modules() for cn, child in mod._modules.items()]
             cached = self.__dict__["_param_slots"] = (slots, edges)
+        if not names:  # what every forward compares: no pairs built
+            return [p for mod, key, _ in cached[0] if (p := mod._parameters.get(key)) is not None]
         return [(n, p) for mod, key, n in cached[0] if (p := mod._parameters.get(key)) is not None]
 
     def _engine(self, device):
         if self.training and self._drop_any:
             raise NotImplementedError("dropout / drop-path > 0 in training mode is outside the inference hot path")
+        params = self._named_engine_params(names=False)
+        sig = signature(params)
+        eng = self._engines.hit(device, sig)
+        if eng is not None:
+            return eng
         named = self._named_engine_params()
-        sig = tuple((p.data_ptr(), p._version) for _, p in named)
-        ent = self._engines.get(device)
-        if ent is not None and ent[1] == sig:
-            return ent[0]
-        for _, p in named:
+        for p in params:
             if p.device != device:
                 raise RuntimeError(f"parameters are on {p.device} but the input is on {device}; call model.to(device)")
         hy = dict(self._hyper)
         if self._gray_fold:
             hy["in_chans"] = 1
-        eng = ent[0] if ent is not None else Engine(device=device, precision=_lib.PRECISIONS[self._precision], **hy)
+        eng = self._engines.peek(device) or Engine(device=device, precision=_lib.PRECISIONS[self._precision], **hy)
         have, keep = set(), []
         for name, p in named:
             eng.set_param(name, p, keep)
@@ -358,18 +347,14 @@ class VisionTransformer(nn.Module):
         if self.patch_embed.proj.bias is None:
             eng.set_param("patch_embed.proj.bias", torch.zeros(self.embed_dim, device=device), keep)
         eng.flush(keep)  # one synchronisation per load, not one per parameter
-        self._engines[device] = (eng, sig)
+        self._engines.put(device, sig, None, params, eng)
         self.__dict__["_engine_epoch"] = self.__dict__.get("_engine_epoch", 0) + 1  # captured launch sequences are stale now
         return eng
 
     def _pos_for(self, npatch, w, h, device):
         """(N, D) fp32 positional table for a w x h pixel tile, on `device`, cached per shape."""
-        key = (npatch, w, h, device, self.pos_embed.data_ptr(), self.pos_embed._version)
-        pos = self._pos_cache.get(key)
-        if pos is None:
-            pos = self._interpolated_pos(npatch, w, h)[0].to(device=device, dtype=torch.float32).contiguous()
-            self.__dict__["_pos_cache"] = {key: pos}
-        return pos
+        return self._pos_cache.get("pos", (self.pos_embed,), lambda: self._interpolated_pos(npatch, w, h)[0].to(
+            device=device, dtype=torch.float32).contiguous(), (npatch, w, h, device))
 
     def _interpolated_pos(self, npatch, w, h, pos=None):
         """reference interpolate_pos_encoding (:176-196), evaluated once per tile shape on the host
@@ -481,8 +466,9 @@ class VisionTransformer(nn.Module):
                         return None
                 finally:
                     self.__dict__["_graph_suspended"] = False
-                # everything the captured launches point at stays alive with the capture
-                ent = cache[key] = (graph, xs, out, (eng, list(eng._ws.values()), dict(self._pos_cache), qr))
+                # everything the captured launches point at (and pos_embed's storage, which the key names) stays alive with it
+                keep = (eng, list(eng._ws.values()), self._pos_cache.peek("pos"), self.pos_embed.detach(), qr)
+                ent = cache[key] = (graph, xs, out, keep)
             graph, xs, out, _ = ent
             xs.copy_(x)
             graph.replay()
@@ -601,8 +587,8 @@ class GraphedCall:
         finally:
             m.__dict__["_graph_suspended"] = False
         eng = m._engine(x.device)
-        # everything the captured launches point at stays alive with the capture, whatever the engine caches next
-        keep = (eng, list(eng._ws.values()), dict(m._pos_cache))
+        # everything the captured launches point at (and pos_embed's storage, which the key names) stays alive with the capture
+        keep = (eng, list(eng._ws.values()), m._pos_cache.peek("pos"), m.pos_embed.detach())
         self._cap = (self._key(x), graph, xs, out, keep)  # the warm-up may have (re)built the engine entry
 
     @torch.no_grad()

@@ -29,12 +29,58 @@ def _p(t):
     return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
 
+def _f32c(t):
+    return t.detach().to(torch.float32).contiguous()
+
+
+def _ws(nbytes, dev):
+    return torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)  # at least a byte: a workspace has an address
+
+
+OPERAND_DTYPE = {_lib.OCM_PREC_BF16: torch.bfloat16, _lib.OCM_PREC_FP32: torch.float32, _lib.OCM_PREC_BF16X3: torch.int32}
+
+
+def signature(tensors):
+    return tuple((t.data_ptr(), t._version) for t in tensors)
+
+
+class SourceCache:
+    """Copies derived from parameters and buffers (GEMM operands, folded weights, an uploaded engine, the position table), one
+    per name, valid while signature(sources) and the site's `extra` (precision, device, shape) are what they were when the copy
+    was made. An entry holds a detach() alias of every source, which pins its storage (the Parameter would not do: `p.data =
+    new` frees the storage under a live object): no other tensor can get a pinned address, so an equal signature means the same
+    memory, not written through an op autograd sees. The price: a replaced parameter's memory stays allocated until the next
+    lookup of its entries (a miss replaces an entry and lets the pins go). Copies and pickles are empty."""
+
+    def __init__(self):
+        self._ent = {}  # name -> (signature, extra, value, pins)
+
+    def __reduce__(self):
+        return type(self), ()
+
+    def peek(self, name):  # the value under `name` whatever it was made from, or None: a rebuild may reuse its predecessor
+        return self._ent.get(name, (None, None, None))[2]
+
+    def hit(self, name, sig, extra=None):  # the value, or None
+        ent = self._ent.get(name, (None, None, None))
+        return ent[2] if ent[0] == sig and ent[1] == extra else None
+
+    def put(self, name, sig, extra, srcs, value):  # sig = signature(srcs), as hit() was asked
+        self._ent[name] = (sig, extra, value, tuple(t.detach() for t in srcs))
+        return value
+
+    def get(self, name, srcs, make, extra=None):
+        sig = signature(srcs)
+        value = self.hit(name, sig, extra)
+        return self.put(name, sig, extra, srcs, make()) if value is None else value
+
+
 def to_operand(x32, precision):
     """fp32 HIP tensor -> the contraction kernels' operand type for `precision` (an _lib.OCM_PREC_* value):
     bf16 tensor, the fp32 tensor itself, or split-bf16 pairs (an int32 tensor of the same shape: 4 bytes per
     element, every 32 consecutive elements of the last axis stored as [32 x hi | 32 x lo])."""
     _require_hip(x32, "operand")
-    x32 = x32.detach().to(torch.float32).contiguous()
+    x32 = _f32c(x32)
     if precision == _lib.OCM_PREC_FP32:
         return x32
     lib = _lib.load()
@@ -262,7 +308,7 @@ class Engine:
 
     def final_norm(self, x):
         _require_hip(x, "x")
-        xc = x.detach().to(torch.float32).contiguous()
+        xc = _f32c(x)
         y = torch.empty_like(xc)
         with torch.cuda.device(self.device):
             check(self.lib.ocm_vit_final_norm(self._h, _p(xc), _p(y), xc.numel() // self.D, _stream()))

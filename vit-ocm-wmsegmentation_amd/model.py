@@ -35,7 +35,7 @@ import torch.nn as nn
 from . import _lib
 from .dino.utils import trunc_normal_
 from .dino.vision_transformer import VisionTransformer
-from .engine import _p, _require_hip, _stream, to_operand
+from .engine import OPERAND_DTYPE as _OPERAND_DTYPE, SourceCache, _p, _require_hip, _stream, _ws, to_operand
 
 
 class _FmapEncoder(VisionTransformer):
@@ -134,7 +134,7 @@ class MIM(nn.Module):
         self.encoder, self.encoder_stride = encoder, encoder_stride
         self.decoder = _pixel_shuffle_head(encoder.num_features, encoder_stride, 3)
         self.in_chans, self.patch_size = 3, 8
-        self.__dict__["_dec_cache"] = {}
+        self.__dict__["_dec_cache"] = SourceCache()
 
     def forward(self, x, mask):
         if _differentiable(self):  # training mode, grad mode on, something to train: the HIP backward (_EncoderTrain)
@@ -188,7 +188,7 @@ class LinearProbing(nn.Module):
         self.two_layer_decoder = nn.Sequential(
             nn.Conv2d(feats, 4 * s2, kernel_size=3, padding=1), nn.BatchNorm2d(4 * s2), nn.ReLU(inplace=True),
             nn.Conv2d(4 * s2, s2, kernel_size=3, padding=1), nn.PixelShuffle(encoder_stride))
-        self.__dict__["_dec_cache"] = {}
+        self.__dict__["_dec_cache"] = SourceCache()
 
     def _two_layer(self, tokens):
         """two_layer_decoder (model.py:154-166) in eval mode on the HIP path, token-major: im2col(3x3) + MFMA GEMM with
@@ -249,9 +249,6 @@ class LinearProbing(nn.Module):
 
 # ---- the decoders' pieces. Token-major rows m = (image, y, x), M = B*hp*wp; s = stride, mid = 4 s^2. Training (finetune.py,
 # mim.py) runs the forward with batch statistics and the backward through kernels_train.hip. ----
-_OPERAND_DTYPE = {_lib.OCM_PREC_BF16: torch.bfloat16, _lib.OCM_PREC_FP32: torch.float32, _lib.OCM_PREC_BF16X3: torch.int32}
-
-
 def _rows1x1(w):
     """(O, C, 1, 1) kernel -> the (O, C) weight of ocm_op_linear over the token rows."""
     return w.reshape(w.shape[0], -1)
@@ -272,10 +269,6 @@ def flip_conv3x3(w):
     (ky*3 + kx)*O + o holds w[o][c][2-ky][2-kx]. im2col3x3(dY) @ flip_conv3x3(w)^T equals conv2d_input(dY, w) with padding
     1 (the transposed convolution is the convolution with the flipped, channel-transposed kernel)."""
     return w.flip(2, 3).permute(1, 2, 3, 0).reshape(w.shape[1], -1)
-
-
-def _ws(nbytes, dev):
-    return torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
 
 
 def _put(t, like):
@@ -311,17 +304,8 @@ def _pixel_shuffle_backward(g, M, s, hp, wp):
 
 
 def _cached_operand(cache, name, srcs, prec, make):
-    """What make() builds from `srcs` (a parameter, or a tuple of parameters and buffers), rebuilt when one of them is replaced
-    or updated in place: the key is every source's own (data_ptr, _version), and the precision."""
-    if isinstance(srcs, tuple):
-        key = (*((t.data_ptr(), t._version) for t in srcs), prec)
-    else:
-        key = (srcs.data_ptr(), srcs._version, prec)
-    hit = cache.get(name)
-    if hit is None or hit[0] != key:
-        hit = (key, make())
-        cache[name] = hit
-    return hit[1]
+    """What make() builds from `srcs` (a parameter, or a tuple of parameters and buffers) in `prec`: engine.SourceCache."""
+    return cache.get(name, srcs if isinstance(srcs, tuple) else (srcs,), make, prec)
 
 
 def _weight_operand(cache, name, w, prec, dev, layout):
@@ -332,10 +316,7 @@ def _weight_operand(cache, name, w, prec, dev, layout):
 
 def _zeros(cache, n, dev):
     """The all-zero fp32 bias of a GEMM that adds none: one vector per length."""
-    z = cache.get(("zeros", n))
-    if z is None or z.device != dev:
-        z = cache[("zeros", n)] = torch.zeros(n, device=dev, dtype=torch.float32)
-    return z
+    return cache.get(("zeros", n), (), lambda: torch.zeros(n, device=dev, dtype=torch.float32), dev)
 
 
 def _im2col3x3(prec, x, grid, C, relu=False, affine=None):
@@ -654,7 +635,7 @@ class _EncoderTrain(torch.autograd.Function):
         f32 = dict(device=dev, dtype=torch.float32)
         adt = _OPERAND_DTYPE[prec]
         kind = _LN_KIND[prec]
-        cache = enc.__dict__.setdefault("_train_cache", {})
+        cache = enc.__dict__.setdefault("_train_cache", SourceCache())
 
         def op(name):
             w = P[name]
@@ -716,19 +697,14 @@ class _EncoderTrain(torch.autograd.Function):
         params = dict(zip(names, st[2 + 6 * nb:]))
         lib, dev = _lib.load(), gout.device
         f32 = dict(device=dev, dtype=torch.float32)
-        cache = enc.__dict__.setdefault("_train_cache", {})
+        cache = enc.__dict__.setdefault("_train_cache", SourceCache())
         grads = {}
 
         def op_t(name):  # operand copy of W^T: the data gradient dX = dY W runs as ocm_op_linear(dY, W^T)
             w = params[name]
             return _cached_operand(cache, name + ".T", w, prec, lambda: to_operand(w.detach().to(**f32).t().contiguous(), prec))
 
-        zeros = {}
-
-        def zero(n):
-            if n not in zeros:
-                zeros[n] = torch.zeros(n, **f32)
-            return zeros[n]
+        zero = partial(_zeros, cache, dev=dev)  # the zero biases of the data-gradient GEMMs
 
         def wgrad(dy, xin, wname, bname):
             if need.get(wname) or need.get(bname):
@@ -1220,7 +1196,7 @@ class build_unet(nn.Module):
         self.d4 = decoder_block(128, 64)
         self.outputs = nn.Conv2d(64, 1, kernel_size=1, padding=0)
         self.__dict__["_precision"] = _lib.DEFAULT_PRECISION
-        self.__dict__["_op_cache"] = {}
+        self.__dict__["_op_cache"] = SourceCache()
         self.train_backward = False  # a plain attribute: not a parameter, not a buffer, not in the state_dict
         self.__dict__["_alloc"] = _unet_empty  # a test seam: the memory tests swap in an allocator of poisoned, guard-banded buffers
 

@@ -9,8 +9,8 @@ is one multi-tensor launch of kernels_optim.hip per (param group, step count) in
                       floats as torch forms them. fp32 parameters on one HIP device only; there is no CPU or eager fall-back.
 
 step() launches on the current stream of the parameters' device, allocates nothing after the first step, never reads the device
-back, and afterwards raises every stepped parameter's version counter: the operand caches and engines of this package key on
-(data_ptr, _version), and a raw kernel write is invisible to autograd's own counting. The `step` entries of the state are 0-dim
+back, and afterwards raises every stepped parameter's version counter: the operand caches and engines of this package (engine.SourceCache)
+compare (data_ptr, _version), and a raw kernel write is invisible to autograd's own counting. The `step` entries of the state are 0-dim
 views of CPU tensors shared by many parameters (read and raised in one operation each); a loaded state's own `step` tensors are
 replaced by such views of the same value at the first step() after load_state_dict().
 """

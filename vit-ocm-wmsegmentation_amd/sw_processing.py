@@ -16,6 +16,7 @@ import torch
 import torch.distributed as dist
 
 from . import _lib
+from .engine import _p, _stream
 
 
 def window_count(size, stride=128):
@@ -96,15 +97,14 @@ def postprocess_windows(rows, hf, wf, patch_size):
     lib = _lib.load()
     small = torch.empty((T, hf, wf), dtype=torch.float32, device=rows.device)
     big = torch.empty((T, hf * rep * scale, wf * rep * scale), dtype=torch.float32, device=rows.device)
-    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    st = _stream()
     with _dev_call(rows):
-        _lib.check(lib.ocm_op_tile_postprocess(C.c_void_p(rows.data_ptr()), C.c_void_p(small.data_ptr()), T, H, nr, P, st))
+        _lib.check(lib.ocm_op_tile_postprocess(_p(rows), _p(small), T, H, nr, P, st))
         if rep > 1:  # pure index replication (the block values the //8 resize lands on)
             blocks = torch.empty((T, hf * rep, wf * rep), dtype=torch.float32, device=rows.device)
-            _lib.check(lib.ocm_op_nearest_upsample(C.c_void_p(small.data_ptr()), C.c_void_p(blocks.data_ptr()), T, hf, wf, rep, st))
+            _lib.check(lib.ocm_op_nearest_upsample(_p(small), _p(blocks), T, hf, wf, rep, st))
             small = blocks
-        _lib.check(lib.ocm_op_bilinear_upsample(C.c_void_p(small.data_ptr()), C.c_void_p(big.data_ptr()), T, hf * rep,
-                                                wf * rep, scale, st))
+        _lib.check(lib.ocm_op_bilinear_upsample(_p(small), _p(big), T, hf * rep, wf * rep, scale, st))
     return big
 
 
@@ -121,9 +121,7 @@ def stitch_windows(crops, stride, window):
     ramp = torch.from_numpy(np.linspace(1, 0, window - stride)).to(crops.device)  # float64, as the reference builds it
     out = torch.empty((S, S), dtype=torch.float32, device=crops.device)
     with _dev_call(crops):
-        _lib.check(_lib.load().ocm_op_stitch(C.c_void_p(crops.data_ptr()), C.c_void_p(out.data_ptr()),
-                                             C.c_void_p(ramp.data_ptr()), n, window, stride,
-                                             C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        _lib.check(_lib.load().ocm_op_stitch(_p(crops), _p(out), _p(ramp), n, window, stride, _stream()))
     return out
 
 
@@ -145,9 +143,8 @@ def stitched_gray_image(slab, stride, window):
     hist = torch.empty(256, dtype=torch.int64, device=slab.device)
     with _dev_call(slab):
         _lib.check(_lib.load().ocm_op_stitch_image_u8(
-            C.c_void_p(slab.data_ptr()), int(slab.stride(0)), int(slab.stride(1)), int(slab.shape[0]), int(slab.shape[1]),
-            int(slab.shape[2]), C.c_void_p(out.data_ptr()), C.c_void_p(ramp.data_ptr()), n, window, stride,
-            C.c_void_p(hist.data_ptr()), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+            _p(slab), int(slab.stride(0)), int(slab.stride(1)), int(slab.shape[0]), int(slab.shape[1]),
+            int(slab.shape[2]), _p(out), _p(ramp), n, window, stride, _p(hist), _stream()))
     return out, hist
 
 
@@ -172,13 +169,12 @@ def threshold(img_u8, heat, hist_img=None, as_numpy=False):
     scratch = torch.empty(2048, dtype=torch.uint8, device=dev)
     h_res = torch.empty(256, dtype=torch.int64, device=dev)
     h_att = torch.empty(256, dtype=torch.int64, device=dev)
-    vp = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
     with _dev_call(heat):
-        st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        _lib.check(lib.ocm_op_weighted_u8(vp(heat), vp(img_u8), n, vp(scratch), vp(res), vp(att), vp(h_res), vp(h_att), st))
+        st = _stream()
+        _lib.check(lib.ocm_op_weighted_u8(_p(heat), _p(img_u8), n, _p(scratch), _p(res), _p(att), _p(h_res), _p(h_att), st))
         levels = (_otsu_from_hist(h_res, n), skimage_otsu_from_hist(hist_img), _otsu_from_hist(h_att, n))
         for k, src in enumerate((res, img_u8, att)):
-            _lib.check(lib.ocm_op_threshold_u8(vp(src), vp(masks[k]), n, levels[k], st))
+            _lib.check(lib.ocm_op_threshold_u8(_p(src), _p(masks[k]), n, levels[k], st))
     out = dict(th=masks[0], th2=masks[1], th3=masks[2], result=res, attention=att, levels=levels)
     if as_numpy:
         out = {k: (v.cpu().numpy() if torch.is_tensor(v) else v) for k, v in out.items()}
@@ -197,15 +193,14 @@ def otsu_heatmap_mask(heat):
     mask = torch.empty(heat.shape, dtype=torch.uint8, device=dev)
     scratch = torch.empty(2048, dtype=torch.uint8, device=dev)
     hist = torch.empty(256, dtype=torch.int64, device=dev)
-    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    st = _stream()
     with _dev_call(heat):
-        _lib.check(lib.ocm_op_normalize_u8(C.c_void_p(heat.data_ptr()), n, C.c_void_p(scratch.data_ptr()),
-                                           C.c_void_p(img.data_ptr()), C.c_void_p(hist.data_ptr()), st))
+        _lib.check(lib.ocm_op_normalize_u8(_p(heat), n, _p(scratch), _p(img), _p(hist), st))
         h = hist.cpu().numpy().astype(np.uint64)  # 2 KiB D2H: the level is a 256-step scalar loop
         level = int(lib.ocm_otsu_threshold(h.ctypes.data_as(C.POINTER(C.c_uint64)), n))
         if level < 0:
             raise ValueError("ocm_otsu_threshold failed")
-        _lib.check(lib.ocm_op_threshold_u8(C.c_void_p(img.data_ptr()), C.c_void_p(mask.data_ptr()), n, level, st))
+        _lib.check(lib.ocm_op_threshold_u8(_p(img), _p(mask), n, level, st))
     return img, mask, level
 
 

@@ -17,8 +17,8 @@ import torch.nn.functional as F
 
 from . import _lib
 from .dino.utils import trunc_normal_
-from .engine import _p, _require_hip, _stream, from_split, to_operand
-from .model import _OPERAND_DTYPE, _differentiable, _linear, _ln, _ln_backward, _weight_grad, _ws
+from .engine import OPERAND_DTYPE, SourceCache, _p, _require_hip, _stream, _ws, from_split, signature, to_operand
+from .model import _differentiable, _linear, _ln, _ln_backward, _weight_grad
 
 
 class SwinConfig:
@@ -104,7 +104,7 @@ class SwinForImageClassification(nn.Module):
             self._names[flat] = key
         self._register_state_dict_hook(self._rename_out)
         self._register_load_state_dict_pre_hook(self._rename_in)
-        self.__dict__["_engine"] = None
+        self.__dict__["_engine_cache"] = SourceCache()  # "engine" -> dict(h, ws), made from every parameter, per device
         self.__dict__["_precision"] = "bf16"
 
     # ---- transformers key names in and out ----------------------------------------------------
@@ -128,11 +128,15 @@ class SwinForImageClassification(nn.Module):
             self._drop_engine()
         return self
 
+    @property
+    def _engine(self):  # the engine entry of the latest inference forward, or None
+        return self._engine_cache.peek("engine")
+
     def _drop_engine(self):
-        eng = self.__dict__.get("_engine")
+        eng = self._engine
         if eng is not None:
             _lib.load().ocm_swin_destroy(eng["h"])
-        self.__dict__["_engine"] = None
+        self.__dict__["_engine_cache"] = SourceCache()
 
     def __del__(self):
         try:
@@ -141,10 +145,10 @@ class SwinForImageClassification(nn.Module):
             pass
 
     def _get_engine(self, device):
-        params = [(self._names[n], p) for n, p in self.named_parameters()]
-        sig = (device, tuple((p.data_ptr(), p._version) for _, p in params))
-        eng = self.__dict__.get("_engine")
-        if eng is not None and eng["sig"] == sig:
+        params = list(self.parameters())
+        sig = signature(params)
+        eng = self._engine_cache.hit("engine", sig, device)
+        if eng is not None:
             return eng
         self._drop_engine()
         lib, c = _lib.load(), self.config
@@ -157,16 +161,14 @@ class SwinForImageClassification(nn.Module):
         h = C.c_void_p(0)
         with torch.cuda.device(device):
             _lib.check(lib.ocm_swin_create(C.byref(cfg), C.byref(h)))
-            for key, p in params:
+            for flat, p in self.named_parameters():
                 if p.device != device:
                     lib.ocm_swin_destroy(h)
                     raise RuntimeError(f"parameters are on {p.device} but the input is on {device}; call model.to(device)")
                 t = p.detach().to(torch.float32).contiguous()
-                _lib.check(lib.ocm_swin_set_param(h, key.encode(), _p(t), t.numel(), _stream()))
+                _lib.check(lib.ocm_swin_set_param(h, self._names[flat].encode(), _p(t), t.numel(), _stream()))
             torch.cuda.current_stream().synchronize()
-        eng = dict(h=h, sig=sig, ws={})
-        self.__dict__["_engine"] = eng
-        return eng
+        return self._engine_cache.put("engine", sig, device, params, dict(h=h, ws={}))
 
     def forward(self, pixel_values=None, labels=None, output_hidden_states=False, **unused):
         _require_hip(pixel_values, "pixel_values")
@@ -280,19 +282,11 @@ def _operand(t32, prec):
 
 class _Weights:
     """Operand copies of weight matrices ([N][K] and the transposes the data gradients read), K zero-padded to the operand's
-    K step, cached in the module per (data_ptr, _version) of the parameters they are made from: an optimizer step or
-    load_state_dict makes new copies, an unchanged parameter is not repacked."""
+    K step, cached in the module under the parameters they are made from and the precision (engine.SourceCache): an optimizer
+    step or load_state_dict makes new copies, an unchanged parameter is not repacked."""
 
     def __init__(self, model, P, prec):
-        self.cache, self.P, self.prec = model.__dict__.setdefault("_train_cache", {}), P, prec
-
-    def _get(self, tag, keys, make):
-        sig = (self.prec,) + tuple((self.P[k].data_ptr(), self.P[k]._version) for k in keys)
-        hit = self.cache.get(tag)
-        if hit is None or hit[0] != sig:
-            hit = (sig, make())
-            self.cache[tag] = hit
-        return hit[1]
+        self.cache, self.P, self.prec = model.__dict__.setdefault("_train_cache", SourceCache()), P, prec
 
     def _mat(self, keys, rows):
         w = torch.cat([self.P[k].detach().float().reshape(self.P[k].shape[0], -1) for k in keys])
@@ -300,11 +294,12 @@ class _Weights:
 
     def w(self, *keys, rows=None):
         """cat(keys) as [N][K] (rows zero-padded up to `rows`)."""
-        return self._get(keys, keys, lambda: _operand(self._mat(keys, rows), self.prec))
+        return self.cache.get(keys, [self.P[k] for k in keys], lambda: _operand(self._mat(keys, rows), self.prec), self.prec)
 
     def wt(self, *keys, rows=None):
         """The transpose [K][N] of w(*keys, rows=rows): the data gradient dX = dY W runs as a linear with W^T."""
-        return self._get(("T",) + keys, keys, lambda: _operand(self._mat(keys, rows).t().contiguous(), self.prec))
+        return self.cache.get(("T",) + keys, [self.P[k] for k in keys],
+                              lambda: _operand(self._mat(keys, rows).t().contiguous(), self.prec), self.prec)
 
 
 def _ctx_f32(cx, C, prec):
@@ -333,7 +328,7 @@ class _SwinTrain(torch.autograd.Function):
         lib, dev = _lib.load(), x.device
         prec = _lib.PRECISIONS[model._precision]
         f32 = dict(device=dev, dtype=torch.float32)
-        adt = _OPERAND_DTYPE[prec]
+        adt = OPERAND_DTYPE[prec]
         W = _Weights(model, P, prec)
         eps, F32 = float(c.layer_norm_eps), _lib.OCM_LN_F32
         B, Cin, S = x.shape[0], c.num_channels, c.image_size

@@ -39,7 +39,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .engine import _p, _require_hip, _stream
+from .engine import _p, _require_hip, _stream, _ws
 from .optimizer import _check_tensor, _table
 
 
@@ -243,7 +243,7 @@ class _DiceLossFn(torch.autograd.Function):
         loss = torch.empty((), dtype=torch.float32, device=dev)
         sums = torch.empty(3, dtype=torch.float32, device=dev)
         nbytes = lib.ocm_dice_loss_workspace_bytes(n)
-        ws = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
+        ws = _ws(nbytes, dev)
         with torch.cuda.device(dev):
             _lib.check(lib.ocm_op_dice_loss(_p(logits), _p(targets), _p(loss), _p(sums), n, smooth, _p(ws), nbytes, _stream()))
         ctx.smooth = smooth
@@ -337,7 +337,7 @@ def remove_small_objects(mask, min_size=20):
     lib = _lib.load()
     out = torch.empty_like(m)
     nbytes = lib.ocm_remove_small_objects_workspace_bytes(B, H, W)
-    ws = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=m.device)
+    ws = _ws(nbytes, m.device)
     with torch.cuda.device(m.device):
         _lib.check(lib.ocm_op_remove_small_objects(_p(m), _p(out), B, H, W, int(min_size), _p(ws), nbytes, _stream()))
     return _like(mask, out)
@@ -353,7 +353,7 @@ def label_regions(mask):
     labels = torch.empty((B, H, W), dtype=torch.int32, device=m.device)
     counts = torch.empty(B, dtype=torch.int32, device=m.device)
     nbytes = lib.ocm_label8_workspace_bytes(B, H, W)
-    ws = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=m.device)
+    ws = _ws(nbytes, m.device)
     with torch.cuda.device(m.device):
         _lib.check(lib.ocm_op_label8(_p(m), _p(labels), _p(counts), B, H, W, _p(ws), nbytes, _stream()))
     return labels.reshape(mask.shape), (counts[0] if mask.dim() == 2 else counts)
@@ -516,7 +516,7 @@ def chan_vese_level_set(images_u8, mu=0.25, lambda1=1.0, lambda2=1.0, tol=1e-3, 
     mask = torch.empty((B, H, W), dtype=torch.uint8, device=dev)
     iters = torch.empty(B, dtype=torch.int32, device=dev)
     nbytes = lib.ocm_chan_vese_workspace_bytes(B, H, W)
-    ws = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
+    ws = _ws(nbytes, dev)
     with torch.cuda.device(dev):
         _lib.check(lib.ocm_op_chan_vese(_p(image), _p(phi), _p(mask), _p(iters), B, H, W, float(mu), float(lambda1),
                                         float(lambda2), float(tol), int(max_num_iter), float(dt), _p(ws), nbytes, _stream()))
@@ -600,7 +600,7 @@ def kmeans_pixels(images_u8, rng_state=CV_RNG_START, attempts=10, max_iter=10, e
                compactness=torch.empty((P, attempts), dtype=torch.float64, device=dev),
                iters=torch.empty((P, attempts), dtype=torch.int32, device=dev), best=torch.empty(P, dtype=torch.int32, device=dev))
     nbytes = lib.ocm_kmeans_px_workspace_bytes(P, N, attempts)
-    ws = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
+    ws = _ws(nbytes, dev)
     with torch.cuda.device(dev):
         _lib.check(lib.ocm_op_kmeans_px(_p(x), P, N, _p(uniforms), attempts, int(max_iter), float(eps), _p(out["labels"]),
                                         _p(out["centers"]), _p(out["compactness"]), _p(out["iters"]), _p(out["best"]),
@@ -674,7 +674,7 @@ def mask_scores(pred, target, smooth=1):
     scores = torch.empty((B, len(SCORE_NAMES)), dtype=torch.float64, device=dev)
     counts = torch.empty((B, len(COUNT_NAMES)), dtype=torch.int64, device=dev)
     nbytes = lib.ocm_mask_scores_workspace_bytes(B, count)
-    ws = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
+    ws = _ws(nbytes, dev)
     with torch.cuda.device(dev):
         _lib.check(lib.ocm_op_mask_scores(_p(x), int(x.dtype == torch.uint8), _p(t), B, count, float(smooth), _p(counts),
                                           _p(scores), _p(ws), nbytes, _stream()))
@@ -819,7 +819,7 @@ class ResamplePlan:
         want_u8, want_f32 = to_tensor in (False, "both"), to_tensor in (True, "both")
         out_u8 = torch.empty((B, self.out_h, self.out_w, Cc), dtype=torch.uint8, device=dev) if want_u8 else None
         out_f32 = torch.empty((B, Cc, self.out_h, self.out_w), dtype=torch.float32, device=dev) if want_f32 else None
-        ws = torch.empty(max(self.workspace_bytes, 1), dtype=torch.uint8, device=dev)
+        ws = _ws(self.workspace_bytes, dev)
         p = self.ptr
         with torch.cuda.device(dev):
             _lib.check(_lib.load().ocm_op_resample_u8(_p(images_u8), *(int(s) for s in self.strides), B, Cc, self.H, self.W, p[4],

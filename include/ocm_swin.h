@@ -27,12 +27,17 @@ typedef struct ocm_swin_config {
     int32_t depths[4];    /* (2, 2, 6, 2)                                                             */
     int32_t num_heads[4]; /* (3, 6, 12, 24): channels / heads must be 32                              */
     int32_t window_size;  /* 7                                                                        */
-    int32_t num_labels;   /* classifier outputs (5 in the reference)                                  */
+    int32_t num_labels;   /* classifier outputs (5 in the reference), positive unless a backbone      */
     float mlp_ratio;      /* 4.0                                                                      */
     float ln_eps;         /* 1e-5                                                                     */
     int32_t precision;    /* OCM_PREC_BF16 / OCM_PREC_FP32 / OCM_PREC_BF16X3 (ocm_vit.h)              */
-    int32_t reserved;
+    int32_t reserved;     /* flag bits: 0, or OCM_SWIN_CFG_BACKBONE                                   */
 } ocm_swin_config;
+
+/* reserved = OCM_SWIN_CFG_BACKBONE: transformers' SwinModel, a backbone without classifier. num_labels is ignored (0 labels),
+ * no classifier.* parameter exists or is waited for by ocm_swin_params_ready, and `logits` of the forward may be null.
+ * (Without the flag num_labels = 0 stays an error, as before.) */
+enum { OCM_SWIN_CFG_BACKBONE = 1 };
 
 typedef struct ocm_swin ocm_swin_t;
 
@@ -58,6 +63,44 @@ size_t ocm_swin_workspace_bytes(const ocm_swin_t *h, int32_t batch);
  * (B, L_last, C_last) = last_hidden_state after the final LayerNorm. */
 int ocm_swin_forward(ocm_swin_t *h, const float *pixel_values, int32_t batch, float *logits, float *pooled,
                      float *last_hidden, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---- the backbone outputs (transformers' SwinModel / SwinEncoder with output_hidden_states / output_attentions) ----
+ * Every member of ocm_swin_outputs is optional: a null pointer skips that output. All buffers are fp32 device memory the
+ * caller owns, sized by ocm_swin_output_shape, the attention buffers 16-byte aligned.
+ *   hidden[i], i in [0, num_stages]: token-major (B, L_i, C_i). [0] is the embeddings output, [s + 1] stage s's output AFTER
+ *     its patch merging, the last entry the last stage's output BEFORE the final LayerNorm (transformers' hidden_states).
+ *     They are copies of the residual stream at the stage boundaries: asking for them changes nothing that is computed.
+ *   reshaped[i]: the same values as (B, C_i, H_i, W_i) = hidden[i].transpose(1, 2).reshape(...) (reshaped_hidden_states).
+ *   attentions: a HOST array of sum(depths) device pointers in global layer order (stage 0's blocks first), or null.
+ *     attentions[l] receives layer l's softmax(q k^T / sqrt(32) + bias + shift mask) as (B * nW, heads, ws^2, ws^2), windows of
+ *     the rolled grid in window_partition order, nW counted on the grid PADDED to the window (as transformers returns it with
+ *     attn_implementation="eager"; one entry per layer, not per stage). A layer whose map is requested runs LayerNorm ->
+ *     q | k | v GEMM -> window attention -> o_proj (the chain of OCM_SWIN_OPT_FUSE_MLP = 0 and of the padded geometries)
+ *     followed by ocm_op_swin_window_probs on the q | k | v rows. So does every layer BEFORE the last requested one, so that
+ *     a map holds the same bits whichever other maps are asked for; the layers after it stay on their fused kernels. In
+ *     fp32 and bf16 that is the chain the plain call runs (same bits); in split-bf16 logits / pooled / last_hidden then
+ *     agree with the plain call to fp32 rounding, as OCM_SWIN_OPT_FUSE_MLP = 0 does. ocm_swin_workspace_bytes covers both
+ *     chains (the q | k | v and LayerNorm buffers are sized for every stage, fused or not). */
+typedef struct ocm_swin_outputs {
+    float *hidden[5];
+    float *reshaped[5];
+    float *const *attentions;
+} ocm_swin_outputs;
+
+/* ocm_swin_forward with the backbone outputs: `outputs` null (or all of its members null) is ocm_swin_forward, bit for bit.
+ * On a backbone (OCM_SWIN_CFG_BACKBONE) logits may be null and is not written. ocm_swin_forward is this call with null. */
+int ocm_swin_forward_ex(ocm_swin_t *h, const float *pixel_values, int32_t batch, float *logits, float *pooled,
+                        float *last_hidden, const ocm_swin_outputs *outputs, void *workspace, size_t workspace_bytes,
+                        void *stream);
+
+/* Shape of an output of ocm_swin_forward_ex for a configuration and batch: a host function, no device is touched (the
+ * configuration is checked as ocm_swin_create checks it). kind OCM_SWIN_OUT_HIDDEN: index in [0, num_stages] -> dims
+ * (B, L, C, 1); OCM_SWIN_OUT_RESHAPED: (B, C, H, W); OCM_SWIN_OUT_ATTENTION: index = global layer -> (B * nW, heads, ws^2, ws^2)
+ * with nW = ceil(grid / ws)^2 (the padded grid; an odd grid is halved upwards by the patch merging). The window is
+ * window_size in every stage (a grid smaller than the window is refused); where the grid equals the window the odd layers
+ * run without a shift, which changes values, not shapes. */
+enum { OCM_SWIN_OUT_HIDDEN = 0, OCM_SWIN_OUT_RESHAPED = 1, OCM_SWIN_OUT_ATTENTION = 2 };
+int ocm_swin_output_shape(const ocm_swin_config *cfg, int32_t batch, int32_t kind, int32_t index, int64_t dims[4]);
 
 /* Per-handle dispatch options. OCM_SWIN_OPT_FUSE_MLP (default 1): in split-bf16 precision the layers of the narrow stages
  * (96 or 128 channels) run their MLP half as ONE kernel (ocm_op_swin_mlp), those of up to 192 channels layernorm_before +
@@ -99,6 +142,22 @@ int ocm_op_swin_attn_block(int32_t precision, float *x, const float *gamma, cons
 int ocm_op_swin_window_attention(int32_t precision, const void *qkv, int32_t ld, void *ctx, int32_t ldc,
                                  const float *rel_table, float *scratch, int32_t batch, int32_t height, int32_t width,
                                  int32_t window, int32_t shift, int32_t heads, void *stream);
+
+/* The probabilities of those windows as an output (transformers' per-layer `attentions`): the arguments and argument domain of
+ * ocm_op_swin_window_attention (qkv rows with ld >= 3 * 32 * heads in whole 16-byte pieces, rel_table, the same scratch, all
+ * three precisions), and probs (batch * nW, heads, ws^2, ws^2) fp32, 16-byte aligned = softmax(q k^T / sqrt(32) + bias + shift
+ * mask), windows of the grid rolled by -shift in window_partition order, tokens row-major inside a window. Scores are computed
+ * from the element format as the attention kernel of that precision computes them (bf16 and pairs on MFMA, three instructions
+ * per product for pairs; fp32 by FMAs), the softmax is fp32; the -100 mask is additive as in transformers (masked entries are
+ * ~4e-44 or 0). One workgroup per (window, head) stages its block in LDS and writes it linearly; no atomics and a fixed
+ * summation order: reruns give the same bits. */
+int ocm_op_swin_window_probs(int32_t precision, const void *qkv, int32_t ld, float *probs, const float *rel_table,
+                             float *scratch, int32_t batch, int32_t height, int32_t width, int32_t window, int32_t shift,
+                             int32_t heads, void *stream);
+
+/* x (batch, tokens, channels) fp32 token-major -> out (batch, channels, tokens): hidden.transpose(1, 2), i.e. the
+ * (B, C, H, W) feature map of a stage (32 x 32 LDS tiles, coalesced on both sides; any positive sizes, batch <= 65535). */
+int ocm_op_swin_tokens_to_nchw(const float *x, float *out, int32_t batch, int32_t tokens, int32_t channels, void *stream);
 
 /* The LayerNorm of SwinPatchMerging (modeling_swin.py:309-326, before the reduction): x (batch, height, width, channels) fp32;
  * y (batch * ceil(height / 2) * ceil(width / 2), ldy) operand rows in the precision's element format (fp32, bf16 or split pairs)

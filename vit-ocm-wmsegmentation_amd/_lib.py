@@ -17,6 +17,8 @@ OCM_PREC_BF16 = 0
 OCM_PREC_FP32 = 1
 OCM_PREC_BF16X3 = 2
 OCM_SWIN_OPT_FUSE_MLP = 0
+OCM_SWIN_CFG_BACKBONE = 1  # ocm_swin_config.reserved: no classifier (transformers' SwinModel)
+OCM_SWIN_OUT_HIDDEN, OCM_SWIN_OUT_RESHAPED, OCM_SWIN_OUT_ATTENTION = 0, 1, 2  # ocm_swin_output_shape kinds
 PRECISIONS = {"bf16": OCM_PREC_BF16, "fp32": OCM_PREC_FP32, "bf16x3": OCM_PREC_BF16X3}
 DEFAULT_PRECISION = "bf16x3"  # holds the north star's 1e-3 on every golden weight set with an unsaturated softmax
 OCM_LN_F32, OCM_LN_BF16, OCM_LN_SPLIT = 0, 1, 2
@@ -103,6 +105,10 @@ class OcmSwinConfig(C.Structure):  # include/ocm_swin.h
     ]
 
 
+class OcmSwinOutputs(C.Structure):  # ocm_swin_forward_ex: optional device buffers; attentions is a host array of sum(depths) pointers
+    _fields_ = [("hidden", C.c_void_p * 5), ("reshaped", C.c_void_p * 5), ("attentions", C.POINTER(C.c_void_p))]
+
+
 class OcmGemmPlanInfo(C.Structure):  # ocm_gemm_plan: the kernel a GEMM-shaped operator launches for a shape
     _fields_ = [(n, C.c_int32) for n in ("bm", "bn", "waves", "mfma16", "lds_dma", "stages", "ksteps", "splitk")]
 
@@ -183,7 +189,13 @@ SIGNATURES = {
     "ocm_swin_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int32]),
     "ocm_swin_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_size_t, C.c_void_p]),
+    "ocm_swin_forward_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.POINTER(OcmSwinOutputs), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "ocm_swin_output_shape": (C.c_int, [C.POINTER(OcmSwinConfig), C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
     "ocm_swin_set_option": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
+    "ocm_op_swin_window_probs": (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                           C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "ocm_op_swin_tokens_to_nchw": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "ocm_op_swin_lnqkv": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_int64, C.c_int32, C.c_float, C.c_void_p]),
     "ocm_op_swin_mlp": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -10,6 +10,8 @@
 //                          softmax, P v, window reverse, shift back — one wavefront per (window, head), K and V^T
 //                          of the window staged in LDS, both contractions on MFMA   (SwinLayer.forward :529-574)
 //   swin_wattn_f32_kernel  the same in plain fp32 FMAs (OCM_PREC_FP32)
+//   swin_wprobs_kernel     the softmax of those windows as an output (transformers' `attentions`)
+//   swin_tokens_to_nchw_kernel  (B, L, C) -> (B, C, H, W) through an LDS tile (reshaped_hidden_states)
 //   swin_pool_head_kernel  final LayerNorm + mean over tokens + classifier       (SwinModel :887-892, :1052)
 #include "launch.h"
 #include "swin_geom.h"
@@ -843,6 +845,256 @@ hipError_t launch_swin_window_attention(int prec, const void *qkv, int ld, void 
     else
         swin_wattn_kernel<0><<<dim3(blocks), dim3(256), 0, s>>>((const bf16 *)qkv, ld, (bf16 *)ctx, ldc, bias_perm, g,
                                                                  (int)total, scale * 1.4426950408889634f);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------
+// attention probabilities of one SwinLayer as an OUTPUT (transformers' `attentions`, SwinSelfAttention :529-563):
+//     P (B * nW, heads, ws^2, ws^2) fp32 = softmax(q k^T / sqrt(32) + relative-position bias + shift mask)
+// in window_partition order of the rolled grid, tokens row-major inside a window — the work id of win_decode, so the
+// ws^4 block of a (window, head) pair is one contiguous piece of the output. One single-wavefront workgroup per pair
+// computes the scores the way the attention kernel of its precision does (bf16 / split pairs: S^T = K.Q^T on MFMA with the K
+// rows in pi order and the permuted bias table; fp32: FMAs in channel order and the dense table), runs the softmax in fp32
+// (fixed order, no atomics), stages the block in LDS as [query][key] and writes it with linear stores: scalars up to the
+// first 16-byte boundary of the output, 16-byte vectors, scalars for the tail (ws^4 is odd for odd windows).
+// The additive -100 mask is transformers': masked entries come out as exp(-100) ~ 4e-44 or 0, nothing is special-cased.
+// ------------------------------------------------------------------------------------------
+// the staged block Ps[n] -> out[0 .. n), out = probs + first (probs is 16-byte aligned); one wavefront
+__device__ __forceinline__ void swin_wprobs_store(const float *Ps, float *__restrict__ probs, size_t first, int n, int lane) {
+    float *out = probs + first;
+    int lead = (int)((4 - (first & 3)) & 3);
+    if (lead > n) lead = n;
+    if (lane < lead) out[lane] = Ps[lane];
+    const int nvec = (n - lead) >> 2;
+    for (int v = lane; v < nvec; v += 64) {
+        const int e = lead + 4 * v;
+        *(f32x4 *)(out + e) = f32x4{Ps[e], Ps[e + 1], Ps[e + 2], Ps[e + 3]};
+    }
+    const int tail = lead + 4 * nvec;
+    if (tail + lane < n) out[tail + lane] = Ps[tail + lane];
+}
+
+// bf16 (PREC 0) and split pairs (PREC 2): the score and softmax steps of swin_wattn_kernel / swin_wattn_x3_kernel
+template <int PREC, int WS>
+__global__ __launch_bounds__(64) void swin_wprobs_mfma_kernel(const char *__restrict__ qkv, int ld, float *__restrict__ probs,
+                                                              const float *__restrict__ bias_perm, WinGeom g, float scale2) {
+    constexpr int ESZ = PREC == 0 ? 2 : 4;      // bytes per element (pairs: 4)
+    constexpr int NCH = PREC == 0 ? 4 : 8;      // 16-byte chunks of a head's K row (pairs: 4 x hi | 4 x lo)
+    // the K image (64 keys x NCH chunks) and, once both query tiles' scores sit in registers, the staged block share one buffer:
+    // 9.6 KiB per workgroup instead of 17.6, twice as many resident workgroups
+    constexpr int K_BYTES = 64 * NCH * 16, P_BYTES = (49 * 49 + 3) * 4;
+    __shared__ __attribute__((aligned(16))) char smem[K_BYTES > P_BYTES ? K_BYTES : P_BYTES];
+    __shared__ unsigned char Rg[64];
+    char *Ks = smem;
+    float *Ps = (float *)smem;
+    const int lane = threadIdx.x;
+    const int r = lane & 31, h = lane >> 5;
+    const int id = blockIdx.x;
+    const auto [head, b, wy, wx] = win_decode(g, id, g.heads);
+    const int ws = WS ? WS : g.ws;
+    const int A = ws * ws, C = g.heads * 32;
+    const size_t ldb = (size_t)ld * ESZ;
+    const char *base = qkv + (size_t)head * 32 * ESZ;
+    // K rows of the window -> LDS (padding keys: exact zeros), Q fragments of both query tiles -> registers
+#pragma unroll
+    for (int i = 0; i < NCH; ++i) {
+        const int idx = lane + 64 * i, key = idx / NCH, ch = idx % NCH;
+        bf16x8 kreg;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) kreg[e] = (bf16)0.f;
+        if (key < A) kreg = *(const bf16x8 *)(base + win_token(g, ws, b, wy, wx, key) * ldb + (size_t)C * ESZ + ch * 16);
+        if constexpr (PREC == 0)
+            *(bf16x8 *)(Ks + key * 64 + ((ch ^ ((key >> 2) & 3)) << 4)) = kreg;  // the chunk swizzle of swin_wattn_kernel
+        else
+            *(bf16x8 *)(Ks + lds_off(key, ch)) = kreg;
+    }
+    bf16x8 qh[2][2], ql[2][2];
+#pragma unroll
+    for (int qt = 0; qt < 2; ++qt) {
+        const char *qrow = base + win_token(g, ws, b, wy, wx, min(qt * 32 + r, A - 1)) * ldb;
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            qh[qt][s] = *(const bf16x8 *)(qrow + (16 * s + 8 * h) * 2);
+            if constexpr (PREC == 2) ql[qt][s] = *(const bf16x8 *)(qrow + (16 * s + 8 * h) * 2 + 64);
+        }
+    }
+    const bool masked = win_masked(g, ws, wy, wx);
+    if (masked) Rg[lane] = (unsigned char)(lane < A ? win_region(g, ws, wy, wx, lane) : 0);
+    const int pr = pi_row(r);
+    const float *bp = bias_perm + (size_t)head * 2 * 64 * 32 + lane * 4;
+    __syncthreads();
+    f32x16 Sq[2][2];  // raw scores of both query tiles (a second tile exists for windows of more than 32 positions)
+#pragma unroll
+    for (int qt = 0; qt < 2; ++qt)
+#pragma unroll
+        for (int sub = 0; sub < 2; ++sub) {
+#pragma unroll
+            for (int e = 0; e < 16; ++e) Sq[qt][sub][e] = 0.f;
+            if (qt * 32 >= A) continue;
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                if constexpr (PREC == 0) {
+                    const bf16x8 a = *(const bf16x8 *)(Ks + (sub * 32 + pr) * 64 + (((2 * s + h) ^ ((pr >> 2) & 3)) << 4));
+                    Sq[qt][sub] = mfma32(a, qh[qt][s], Sq[qt][sub]);
+                } else {
+                    const bf16x8 kh = *(const bf16x8 *)(Ks + lds_off(sub * 32 + pr, 2 * s + h));
+                    const bf16x8 kl = *(const bf16x8 *)(Ks + lds_off(sub * 32 + pr, 4 + 2 * s + h));
+                    Sq[qt][sub] = mfma32x3(kh, kl, qh[qt][s], ql[qt][s], Sq[qt][sub]);
+                }
+            }
+        }
+    __syncthreads();  // every K fragment has been read: the buffer now receives the block
+#pragma unroll
+    for (int qt = 0; qt < 2; ++qt) {
+        if (qt * 32 >= A) break;
+        const int qi = qt * 32 + r;
+        f32x16(&S)[2] = Sq[qt];
+        float mx = -INFINITY;
+        const int myreg = masked ? Rg[min(qi, A - 1)] : 0;
+#pragma unroll
+        for (int sub = 0; sub < 2; ++sub)
+#pragma unroll
+            for (int e4 = 0; e4 < 4; ++e4) {
+                const f32x4 bv = *(const f32x4 *)(bp + qt * 64 * 32 + (sub * 4 + e4) * 256);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    float v = fmaf(S[sub][e4 * 4 + e], scale2, bv[e]);  // log2 domain; padding keys carry -1e30
+                    if (masked) {
+                        const int j = sub * 32 + key_of_reg(e4 * 4 + e, h);
+                        if (j < A && Rg[j] != myreg) v += -100.0f * 1.4426950408889634f;
+                    }
+                    S[sub][e4 * 4 + e] = v;
+                    mx = fmaxf(mx, v);
+                }
+            }
+        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+        float l = 0.f;
+#pragma unroll
+        for (int sub = 0; sub < 2; ++sub)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const float p = fast_exp2(S[sub][e] - mx);
+                S[sub][e] = p;
+                l += p;
+            }
+        l += __shfl_xor(l, 32, 64);
+        const float inv = 1.0f / l;
+        if (qi < A) {
+            float *prow = Ps + qi * A;
+#pragma unroll
+            for (int sub = 0; sub < 2; ++sub)
+#pragma unroll
+                for (int e = 0; e < 16; ++e) {
+                    const int j = sub * 32 + key_of_reg(e, h);
+                    if (j < A) prow[j] = S[sub][e] * inv;
+                }
+        }
+    }
+    __syncthreads();
+    swin_wprobs_store(Ps, probs, (size_t)id * (A * A), A * A, lane);
+}
+
+// fp32: lane = query, K rows broadcast from LDS, the score FMAs of swin_wattn_f32_kernel
+__global__ __launch_bounds__(64) void swin_wprobs_f32_kernel(const float *__restrict__ qkv, int ld, float *__restrict__ probs,
+                                                             const float *__restrict__ bias_dense, WinGeom g, float scale) {
+    __shared__ __attribute__((aligned(16))) float Ks[49 * 32];
+    __shared__ __attribute__((aligned(16))) float Ps[49 * 49 + 3];
+    const int lane = threadIdx.x;
+    const int id = blockIdx.x;
+    const auto [head, b, wy, wx] = win_decode(g, id, g.heads);
+    const int ws = g.ws;
+    const int A = ws * ws, C = g.heads * 32;
+    const float *base = qkv + head * 32;
+    for (int idx = lane; idx < A * 8; idx += 64) {
+        const int key = idx >> 3, ch = idx & 7;
+        *(f32x4 *)(Ks + key * 32 + ch * 4) = *(const f32x4 *)(base + win_token(g, ws, b, wy, wx, key) * (size_t)ld + C + ch * 4);
+    }
+    __syncthreads();
+    if (lane < A) {
+        const float *qrow = base + win_token(g, ws, b, wy, wx, lane) * (size_t)ld;
+        float q[32];
+#pragma unroll
+        for (int d = 0; d < 32; d += 4) {
+            const f32x4 t = *(const f32x4 *)(qrow + d);
+            q[d] = t[0]; q[d + 1] = t[1]; q[d + 2] = t[2]; q[d + 3] = t[3];
+        }
+        const bool masked = g.shift > 0;
+        const int myreg = masked ? win_region(g, ws, wy, wx, lane) : 0;
+        const float *brow = bias_dense + ((size_t)head * A + lane) * A;
+        float *prow = Ps + lane * A;
+        float mx = -INFINITY;
+        for (int j = 0; j < A; ++j) {
+            float d0 = 0.f;
+#pragma unroll
+            for (int d = 0; d < 32; ++d) d0 = fmaf(q[d], Ks[j * 32 + d], d0);
+            float sc = d0 * scale + brow[j];
+            if (masked && win_region(g, ws, wy, wx, j) != myreg) sc += -100.0f;
+            prow[j] = sc;
+            mx = fmaxf(mx, sc);
+        }
+        float l = 0.f;
+        for (int j = 0; j < A; ++j) {
+            const float p = __expf(prow[j] - mx);
+            prow[j] = p;
+            l += p;
+        }
+        const float inv = 1.0f / l;
+        for (int j = 0; j < A; ++j) prow[j] *= inv;
+    }
+    __syncthreads();
+    swin_wprobs_store(Ps, probs, (size_t)id * (A * A), A * A, lane);
+}
+
+hipError_t launch_swin_window_probs(int prec, const void *qkv, int ld, float *probs, const float *bias_perm,
+                                    const float *bias_dense, int batch, int H, int W, int ws, int shift, int heads, hipStream_t s) {
+    if (ws < 2 || ws > 7 || H % ws || W % ws || ld < 3 * heads * 32 || ((uintptr_t)probs & 15)) return hipErrorInvalidValue;
+    if (prec == 2 ? ld % 32 : prec == 0 ? ld % 8 : ld % 4) return hipErrorInvalidValue;  // 16-byte loads of q and k
+    WinGeom g{H, W, ws, shift, W / ws, (H / ws) * (W / ws), heads};
+    const long total = (long)batch * g.nW * heads;
+    if (total <= 0 || total > 0x7fffffffL) return hipErrorInvalidValue;
+    const float scale = 0.17677669529663687f, scale2 = scale * 1.4426950408889634f;  // 32^-0.5 (and in the log2 domain)
+    const dim3 grid((unsigned)total), block(64);
+    const char *q = (const char *)qkv;
+    if (prec == 1)
+        swin_wprobs_f32_kernel<<<grid, block, 0, s>>>((const float *)qkv, ld, probs, bias_dense, g, scale);
+    else if (prec == 2 && ws == 7)
+        swin_wprobs_mfma_kernel<2, 7><<<grid, block, 0, s>>>(q, ld, probs, bias_perm, g, scale2);
+    else if (prec == 2)
+        swin_wprobs_mfma_kernel<2, 0><<<grid, block, 0, s>>>(q, ld, probs, bias_perm, g, scale2);
+    else if (ws == 7)
+        swin_wprobs_mfma_kernel<0, 7><<<grid, block, 0, s>>>(q, ld, probs, bias_perm, g, scale2);
+    else
+        swin_wprobs_mfma_kernel<0, 0><<<grid, block, 0, s>>>(q, ld, probs, bias_perm, g, scale2);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------
+// token-major (B, L, C) fp32 -> (B, C, L): transformers' reshaped_hidden_states, hidden.transpose(1, 2).reshape(B, C, H, W).
+// 32 x 32 tiles through LDS (33-float rows), so that the reads run along C and the writes along L. (tokens_to_fmap_kernel of
+// kernels_misc.hip is the ViT encoders' version: it drops the class token and takes whole 32-channel groups only.)
+// ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void swin_tokens_to_nchw_kernel(const float *__restrict__ x, float *__restrict__ out, int L,
+                                                                  int C) {
+    __shared__ float tile[32][33];
+    const int b = blockIdx.z, t0 = blockIdx.x * 32, c0 = blockIdx.y * 32;
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;  // 32 x 8
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int t = t0 + ty + 8 * i, c = c0 + tx;
+        if (t < L && c < C) tile[ty + 8 * i][tx] = x[((size_t)b * L + t) * C + c];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int c = c0 + ty + 8 * i, t = t0 + tx;
+        if (t < L && c < C) out[((size_t)b * C + c) * L + t] = tile[tx][ty + 8 * i];
+    }
+}
+
+hipError_t launch_swin_tokens_to_nchw(const float *x, float *out, int batch, int L, int C, hipStream_t s) {
+    if (batch <= 0 || batch > 65535 || L <= 0 || C <= 0 || (C + 31) / 32 > 65535) return hipErrorInvalidValue;
+    const dim3 grid((L + 31) / 32, (C + 31) / 32, batch);
+    swin_tokens_to_nchw_kernel<<<grid, dim3(256), 0, s>>>(x, out, L, C);
     return hipGetLastError();
 }
 

@@ -180,6 +180,11 @@ hipError_t launch_swin_bias_perm(const float *table, float *perm, float *dense, 
 hipError_t launch_swin_window_attention(int prec, const void *qkv, int ld, void *ctx, int ldc, const float *bias_perm,
                                         const float *bias_dense, int batch, int H, int W, int ws, int shift, int heads,
                                         hipStream_t s);
+// the softmax of the same windows as an output: probs (batch * nW, heads, ws^2, ws^2) fp32, 16-byte aligned; ld >= 3 * 32 * heads
+hipError_t launch_swin_window_probs(int prec, const void *qkv, int ld, float *probs, const float *bias_perm,
+                                    const float *bias_dense, int batch, int H, int W, int ws, int shift, int heads, hipStream_t s);
+// x (batch, L, C) fp32 -> out (batch, C, L): reshaped_hidden_states
+hipError_t launch_swin_tokens_to_nchw(const float *x, float *out, int batch, int L, int C, hipStream_t s);
 // layernorm_before + q | k | v projection of a narrow-stage SwinLayer in one kernel (split-bf16, C = 96 / 128)
 bool swin_lnqkv_fused_supported(int prec, int C);
 hipError_t launch_swin_lnqkv(int prec, const float *x, const float *g, const float *be, const void *w, const float *bias,

@@ -63,6 +63,7 @@ struct ocm_swin {
     char *arena = nullptr;
     size_t arena_bytes = 0;
     bool fuse_mlp = true;  // ocm_swin_set_option(OCM_SWIN_OPT_FUSE_MLP)
+    int labels = 0;        // classifier outputs; 0 for a backbone (OCM_SWIN_CFG_BACKBONE)
 
     size_t reserve(size_t bytes) {
         const size_t off = arena_bytes;
@@ -87,8 +88,8 @@ struct ocm_swin {
     int chans(int s) const { return cfg.embed_dim << s; }
 };
 
-extern "C" int ocm_swin_create(const ocm_swin_config *cfg, ocm_swin_t **out) {
-    if (!cfg || !out) return fail(OCM_EINVAL, "ocm_swin_create: null argument");
+// what ocm_swin_create accepts (ocm_swin_output_shape answers for the same configurations)
+static int swin_check_config(const ocm_swin_config *cfg) {
     if (cfg->patch_size != 4) return fail(OCM_EINVAL, "patch_size %d: only 4 is built", cfg->patch_size);
     if (cfg->num_channels != 1 && cfg->num_channels != 3) return fail(OCM_EINVAL, "num_channels must be 1 or 3");
     if (cfg->window_size < 2 || cfg->window_size > 7)
@@ -96,7 +97,8 @@ extern "C" int ocm_swin_create(const ocm_swin_config *cfg, ocm_swin_t **out) {
     if (cfg->num_stages < 1 || cfg->num_stages > 4) return fail(OCM_EINVAL, "num_stages %d must be in [1,4]", cfg->num_stages);
     if (cfg->embed_dim <= 0 || cfg->embed_dim % 32 || cfg->embed_dim > 128)
         return fail(OCM_EINVAL, "embed_dim %d must be a multiple of 32, <= 128", cfg->embed_dim);
-    if (cfg->num_labels <= 0) return fail(OCM_EINVAL, "num_labels must be positive");
+    if (cfg->reserved & ~OCM_SWIN_CFG_BACKBONE) return fail(OCM_EINVAL, "unknown bits in reserved: %d", cfg->reserved);
+    if (!(cfg->reserved & OCM_SWIN_CFG_BACKBONE) && cfg->num_labels <= 0) return fail(OCM_EINVAL, "num_labels must be positive");
     if (cfg->precision != OCM_PREC_BF16 && cfg->precision != OCM_PREC_FP32 && cfg->precision != OCM_PREC_BF16X3)
         return fail(OCM_EINVAL, "bad precision");
     int grid = cfg->image_size / 4;
@@ -115,6 +117,12 @@ extern "C" int ocm_swin_create(const ocm_swin_config *cfg, ocm_swin_t **out) {
     }
     const int M4 = (int)(cfg->mlp_ratio * cfg->embed_dim);
     if (M4 <= 0 || M4 % 32) return fail(OCM_EINVAL, "mlp_ratio * embed_dim must be a multiple of 32");
+    return OCM_OK;
+}
+
+extern "C" int ocm_swin_create(const ocm_swin_config *cfg, ocm_swin_t **out) {
+    if (!cfg || !out) return fail(OCM_EINVAL, "ocm_swin_create: null argument");
+    if (int rc = swin_check_config(cfg)) return rc;
 
     ocm_swin *h = new ocm_swin();
     h->cfg = *cfg;
@@ -176,8 +184,12 @@ extern "C" int ocm_swin_create(const ocm_swin_config *cfg, ocm_swin_t **out) {
     const int Cl = h->chans(cfg->num_stages - 1);
     h->fin_g = h->add_f32("swin.layernorm.weight", Cl);
     h->fin_b = h->add_f32("swin.layernorm.bias", Cl);
-    h->cls_w = h->add_f32("classifier.weight", (size_t)cfg->num_labels * Cl);
-    h->cls_b = h->add_f32("classifier.bias", cfg->num_labels);
+    h->cls_w = h->cls_b = 0;
+    h->labels = (cfg->reserved & OCM_SWIN_CFG_BACKBONE) ? 0 : cfg->num_labels;
+    if (h->labels > 0) {  // a backbone has no classifier parameters
+        h->cls_w = h->add_f32("classifier.weight", (size_t)cfg->num_labels * Cl);
+        h->cls_b = h->add_f32("classifier.bias", cfg->num_labels);
+    }
     if (h->arena_bytes > ((size_t)1 << 31)) {
         delete h;
         return fail(OCM_EINVAL, "parameter arena too large");
@@ -303,9 +315,25 @@ extern "C" size_t ocm_swin_workspace_bytes(const ocm_swin_t *h, int32_t batch) {
     return carve_swin(h, batch, nullptr).bytes;
 }
 
+namespace {
+// hidden_states / reshaped_hidden_states entry `i`: copies of the residual stream x (batch, L, C) at a stage boundary
+int swin_emit_hidden(const ocm_swin_outputs *o, int i, const float *x, int batch, int L, int C, hipStream_t s) {
+    if (!o) return OCM_OK;
+    if (o->hidden[i]) HIP_TRY(hipMemcpyAsync(o->hidden[i], x, (size_t)batch * L * C * 4, hipMemcpyDeviceToDevice, s));
+    if (o->reshaped[i]) HIP_TRY(launch_swin_tokens_to_nchw(x, o->reshaped[i], batch, L, C, s));
+    return OCM_OK;
+}
+}  // namespace
+
 extern "C" int ocm_swin_forward(ocm_swin_t *h, const float *pixel_values, int32_t batch, float *logits, float *pooled,
                                 float *last_hidden, void *workspace, size_t workspace_bytes, void *stream) {
-    if (!h || !pixel_values || !logits) return fail(OCM_EINVAL, "null argument");
+    return ocm_swin_forward_ex(h, pixel_values, batch, logits, pooled, last_hidden, nullptr, workspace, workspace_bytes, stream);
+}
+
+extern "C" int ocm_swin_forward_ex(ocm_swin_t *h, const float *pixel_values, int32_t batch, float *logits, float *pooled,
+                                   float *last_hidden, const ocm_swin_outputs *outs, void *workspace, size_t workspace_bytes,
+                                   void *stream) {
+    if (!h || !pixel_values || (!logits && h->labels > 0)) return fail(OCM_EINVAL, "null argument");
     if (batch <= 0) return fail(OCM_EINVAL, "batch %d must be positive", batch);
     int rc = ocm_swin_params_ready(h);
     if (rc) return rc;
@@ -324,6 +352,18 @@ extern "C" int ocm_swin_forward(ocm_swin_t *h, const float *pixel_values, int32_
                                   h->ptr<float>(h->emb_be), w.x, batch, c.num_channels, c.image_size, c.embed_dim, 1e-5f, s));
     }
     float *x = w.x, *xo = w.x2;
+    if (int rc2 = swin_emit_hidden(outs, 0, x, batch, H * H, c.embed_dim, s)) return rc2;
+    int layer = 0;  // global layer index: the slot of outs->attentions
+    // A requested attention map needs the q | k | v rows, so that layer's attention half runs unfused — and so does every
+    // layer BEFORE the last requested one: a map is then the same bits whichever other maps are asked for (a fused half in front
+    // of it would move its input by fp32 rounding). Layers after the last requested one stay on their fused kernels.
+    int last_req = -1;
+    if (outs && outs->attentions) {
+        int n_layers = 0;
+        for (int st = 0; st < c.num_stages; ++st) n_layers += c.depths[st];
+        for (int l = 0; l < n_layers; ++l)
+            if (outs->attentions[l]) last_req = l;
+    }
     for (int st = 0; st < c.num_stages; ++st) {
         const int C = h->chans(st), heads = c.num_heads[st], M = (int)(c.mlp_ratio * C);
         const int Kc = h->Kp(C), Km = h->Kp(M);
@@ -331,8 +371,11 @@ extern "C" int ocm_swin_forward(ocm_swin_t *h, const float *pixel_values, int32_
         if (T > 0x7fffffff) return fail(OCM_EINVAL, "too many tokens");
         if (Kc != C) HIP_TRY(hipMemsetAsync(w.ctx, 0, T * Kc * h->esz, s));  // K padding of the o_proj operand stays zero
         if (Km != M) HIP_TRY(hipMemsetAsync(w.hid, 0, T * Km * h->esz, s));
-        for (size_t b = 0; b < h->stages[st].layers.size(); ++b) {
+        for (size_t b = 0; b < h->stages[st].layers.size(); ++b, ++layer) {
             const LayerP &lp = h->stages[st].layers[b];
+            float *const probs = outs && outs->attentions ? outs->attentions[layer] : nullptr;
+            if (probs && ((uintptr_t)probs & 15)) return fail(OCM_EINVAL, "attentions[%d] must be 16-byte aligned", layer);
+            const bool fuse_attn = h->fuse_mlp && layer > last_req;
             const int shift = (b % 2 == 1 && H > ws) ? ws / 2 : 0;  // set_shift_and_window_size :576-582
             const int Hp = round_up(H, ws);
             if (Hp != H) {
@@ -356,6 +399,11 @@ extern "C" int ocm_swin_forward(ocm_swin_t *h, const float *pixel_values, int32_
                     HIP_TRY(launch_swin_window_attention(pc, w.qkv, 3 * C, w.ctx, Kc, h->ptr<float>(lp.bias_perm),
                                                          h->ptr<float>(lp.bias_dense), batch, Hp, Hp, ws, shift, heads, s));
                 }
+                if (probs) {  // the windows of the padded grid, as transformers returns them
+                    PROF(OCM_K_PROBS, s);
+                    HIP_TRY(launch_swin_window_probs(pc, w.qkv, 3 * C, probs, h->ptr<float>(lp.bias_perm),
+                                                     h->ptr<float>(lp.bias_dense), batch, Hp, Hp, ws, shift, heads, s));
+                }
                 {
                     PROF(OCM_K_PROJ, s);
                     HIP_TRY(swin_linear(pc, w.ctx, Kc, h->ptr<char>(lp.wo), h->ptr<float>(lp.bo), nullptr, w.yp, C, (int)Tp, C, Kc,
@@ -366,7 +414,7 @@ extern "C" int ocm_swin_forward(ocm_swin_t *h, const float *pixel_values, int32_
             // kernel classes for ocm_prof_begin / ocm_prof_end (tools/bench_swin.py): LayerNorm kernels -> layernorm; the q|k|v
             // projection (fused with layernorm_before or not) -> qkv_gemm; window attention -> attention; attention.output.dense
             // and the patch-merging reduction -> proj_gemm; mlp.fc1 (and the fused LayerNorm + MLP kernel) -> fc1_gemm; mlp.fc2 -> fc2_gemm
-            if (h->fuse_mlp && swin_attn_block_fused_supported(pc, C, heads, ws)) {
+            if (fuse_attn && swin_attn_block_fused_supported(pc, C, heads, ws)) {
                 // stages 0 and 1: layernorm_before, q | k | v and window attention in ONE kernel — no q | k | v tensor exists; at
                 // 96 channels also o_proj and the residual (x read twice, written once), at 192 the context pairs go to the
                 // o_proj GEMM (profiled under the attention class)
@@ -382,7 +430,7 @@ extern "C" int ocm_swin_forward(ocm_swin_t *h, const float *pixel_values, int32_
                                              OCM_EPI_BIAS_RESID_F32, s));
                 }
             } else {
-            if (h->fuse_mlp && swin_lnqkv_fused_supported(pc, C)) {  // narrow stages: no normalised copy of x in HBM
+            if (fuse_attn && swin_lnqkv_fused_supported(pc, C)) {  // narrow stages: no normalised copy of x in HBM
                 PROF(OCM_K_QKV, s);
                 HIP_TRY(launch_swin_lnqkv(pc, x, h->ptr<float>(lp.ln1_g), h->ptr<float>(lp.ln1_b), h->ptr<char>(lp.wqkv),
                                           h->ptr<float>(lp.bqkv), w.qkv, T, C, eps, s));
@@ -400,6 +448,11 @@ extern "C" int ocm_swin_forward(ocm_swin_t *h, const float *pixel_values, int32_
                 PROF(OCM_K_ATTN, s);
                 HIP_TRY(launch_swin_window_attention(pc, w.qkv, 3 * C, w.ctx, Kc, h->ptr<float>(lp.bias_perm),
                                                      h->ptr<float>(lp.bias_dense), batch, H, H, ws, shift, heads, s));
+            }
+            if (probs) {
+                PROF(OCM_K_PROBS, s);
+                HIP_TRY(launch_swin_window_probs(pc, w.qkv, 3 * C, probs, h->ptr<float>(lp.bias_perm),
+                                                 h->ptr<float>(lp.bias_dense), batch, H, H, ws, shift, heads, s));
             }
             {
                 PROF(OCM_K_PROJ, s);
@@ -451,13 +504,45 @@ extern "C" int ocm_swin_forward(ocm_swin_t *h, const float *pixel_values, int32_
             xo = t;
             H = Hn;
         }
+        // hidden_states[st + 1]: the stage's output after its patch merging (the last stage: before the final LayerNorm)
+        if (int rc2 = swin_emit_hidden(outs, st + 1, x, batch, H * H, st + 1 < c.num_stages ? 2 * C : C, s)) return rc2;
     }
     const int Cl = h->chans(c.num_stages - 1);
     PROF(OCM_K_LN, s);
     HIP_TRY(launch_swin_pool_head(x, h->ptr<float>(h->fin_g), h->ptr<float>(h->fin_b), h->ptr<float>(h->cls_w),
-                                  h->ptr<float>(h->cls_b), logits, pooled, last_hidden, batch, H * H, Cl, c.num_labels, eps,
-                                  s));
+                                  h->ptr<float>(h->cls_b), logits, pooled, last_hidden, batch, H * H, Cl, h->labels, eps, s));
     return OCM_OK;
+}
+
+extern "C" int ocm_swin_output_shape(const ocm_swin_config *cfg, int32_t batch, int32_t kind, int32_t index, int64_t dims[4]) {
+    if (!cfg || !dims) return fail(OCM_EINVAL, "ocm_swin_output_shape: null argument");
+    if (int rc = swin_check_config(cfg)) return rc;
+    if (batch <= 0) return fail(OCM_EINVAL, "batch %d must be positive", batch);
+    const int ws = cfg->window_size;
+    int H = cfg->image_size / 4, layer = 0;
+    if (kind == OCM_SWIN_OUT_HIDDEN || kind == OCM_SWIN_OUT_RESHAPED) {
+        if (index < 0 || index > cfg->num_stages) return fail(OCM_EINVAL, "hidden state %d of %d", index, cfg->num_stages + 1);
+        // entry i > 0 follows stage i - 1 and its patch merging (none after the last stage)
+        const int merges = index < cfg->num_stages ? index : cfg->num_stages - 1;
+        for (int m = 0; m < merges; ++m) H = (H + 1) / 2;
+        const int64_t C = (int64_t)cfg->embed_dim << merges;
+        if (kind == OCM_SWIN_OUT_HIDDEN)
+            dims[0] = batch, dims[1] = (int64_t)H * H, dims[2] = C, dims[3] = 1;
+        else
+            dims[0] = batch, dims[1] = C, dims[2] = H, dims[3] = H;
+        return OCM_OK;
+    }
+    if (kind != OCM_SWIN_OUT_ATTENTION) return fail(OCM_EINVAL, "unknown output kind %d", kind);
+    for (int st = 0; st < cfg->num_stages; ++st) {
+        if (index >= layer && index < layer + cfg->depths[st]) {
+            const int64_t nw = (H + ws - 1) / ws;  // windows per side of the grid padded to the window
+            dims[0] = batch * nw * nw, dims[1] = cfg->num_heads[st], dims[2] = dims[3] = ws * ws;
+            return OCM_OK;
+        }
+        layer += cfg->depths[st];
+        H = (H + 1) / 2;
+    }
+    return fail(OCM_EINVAL, "attention layer %d of %d", index, layer);
 }
 
 extern "C" int ocm_swin_set_option(ocm_swin_t *h, int32_t option, int32_t value) {
@@ -533,6 +618,38 @@ extern "C" int ocm_op_swin_merge_ln(int32_t precision, const float *x, const flo
     const int64_t T4 = (int64_t)batch * ((height + 1) / 2) * ((width + 1) / 2);
     if ((int64_t)batch * height * width > 0x7fffffffLL) return fail(OCM_EINVAL, "too many tokens");
     HIP_TRY(launch_swin_ln(pc, x, gamma, beta, y, (size_t)T4, 4 * channels, ldy, 1e-5f, true, height, width, (hipStream_t)stream));
+    return OCM_OK;
+}
+
+extern "C" int ocm_op_swin_window_probs(int32_t precision, const void *qkv, int32_t ld, float *probs, const float *rel_table,
+                                        float *scratch, int32_t batch, int32_t height, int32_t width, int32_t window,
+                                        int32_t shift, int32_t heads, void *stream) {
+    if (!qkv || !probs || !rel_table || !scratch) return fail(OCM_EINVAL, "null argument");
+    if (precision != OCM_PREC_BF16 && precision != OCM_PREC_FP32 && precision != OCM_PREC_BF16X3)
+        return fail(OCM_EINVAL, "bad precision");
+    if (window < 2 || window > 7 || height <= 0 || width <= 0 || height % window || width % window || batch <= 0 || heads <= 0 ||
+        shift < 0 || shift >= window)
+        return fail(OCM_EINVAL, "bad window geometry");
+    if (ld < 3 * 32 * heads || ld % (precision == OCM_PREC_BF16X3 ? 32 : precision == OCM_PREC_BF16 ? 8 : 4))
+        return fail(OCM_EINVAL, "ld %d: rows hold q | k | v of %d heads in whole 16-byte pieces (split-bf16: groups of 32 elements)",
+                    ld, heads);
+    if ((uintptr_t)probs & 15) return fail(OCM_EINVAL, "probs must be 16-byte aligned");
+    if ((int64_t)batch * (height / window) * (width / window) * heads > 0x7fffffffLL || (int64_t)batch * height * width > 0x7fffffffLL)
+        return fail(OCM_EINVAL, "too many windows");
+    hipStream_t s = (hipStream_t)stream;
+    float *perm = scratch, *dense = scratch + (size_t)heads * 4096;  // the layout ocm_op_swin_window_attention leaves
+    HIP_TRY(launch_swin_bias_perm(rel_table, perm, dense, heads, window, s));
+    HIP_TRY(launch_swin_window_probs(prec_index(precision), qkv, ld, probs, perm, dense, batch, height, width, window, shift,
+                                     heads, s));
+    return OCM_OK;
+}
+
+extern "C" int ocm_op_swin_tokens_to_nchw(const float *x, float *out, int32_t batch, int32_t tokens, int32_t channels,
+                                          void *stream) {
+    if (!x || !out) return fail(OCM_EINVAL, "null argument");
+    if (batch <= 0 || batch > 65535 || tokens <= 0 || channels <= 0 || channels > 65535 * 32)
+        return fail(OCM_EINVAL, "bad shape (batch %d, %d tokens, %d channels)", batch, tokens, channels);
+    HIP_TRY(launch_swin_tokens_to_nchw(x, out, batch, tokens, channels, (hipStream_t)stream));
     return OCM_OK;
 }
 

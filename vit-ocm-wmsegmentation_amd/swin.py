@@ -3,6 +3,12 @@
 `load_state_dict`), `model(pixel_values=..., labels=...)` -> object with `.loss`, `.logits` (and `.pooler_output`, optionally
 `.last_hidden_state`). The arithmetic runs in libocm_vit.so (include/ocm_swin.h); there is no CPU fallback.
 
+As a backbone: `output_hidden_states=True` adds transformers' `hidden_states` / `reshaped_hidden_states` (the per-stage
+feature maps), `output_attentions=True` the window-softmax of every layer (`attentions`, one entry per LAYER: transformers
+5.x returns the last block of each stage only, and only with attn_implementation="eager" — take
+`attentions[cumsum(depths) - 1]` for those). `SwinModel` is the model without the classifier, and
+`SwinForImageClassification.swin` the same view over a (fine-tuned) classifier's own parameters and engine.
+
 Inference runs the engine (ocm_swin_forward). Training — train.py's Trainer loop — runs when the module is in training mode,
 grad mode is on and a parameter requires grad (the parameters are created with requires_grad=False: opt in with
 `model.requires_grad_(True)`): the stand-alone operators under one autograd Function (_SwinTrain) whose backward is HIP
@@ -44,11 +50,26 @@ class SwinConfig:
 
 
 class SwinOutput(types.SimpleNamespace):
-    """What `forward` returns: the attributes loss, logits, pooler_output, last_hidden_state, and, as transformers'
-    ModelOutput does for a Trainer's compute_loss, out["loss"] and out[0] (the non-None of loss, logits, in that order)."""
+    """What `forward` returns: the attributes loss, logits, pooler_output, last_hidden_state, hidden_states,
+    reshaped_hidden_states, attentions (tuples, or None when not asked for), and, as transformers' ModelOutput does for a
+    Trainer's compute_loss, out["loss"] and out[0] (the non-None of loss, logits, in that order)."""
 
     def to_tuple(self):
         return tuple(v for v in (self.loss, self.logits) if v is not None)
+
+    def __getitem__(self, key):
+        if isinstance(key, str):
+            return getattr(self, key)
+        return self.to_tuple()[key]
+
+
+class SwinModelOutput(types.SimpleNamespace):
+    """What SwinModel.forward returns: last_hidden_state, pooler_output (None without the pooling layer), hidden_states,
+    reshaped_hidden_states, attentions; out["name"] and out[i] over the non-None of them in that order."""
+
+    def to_tuple(self):
+        return tuple(v for v in (self.last_hidden_state, self.pooler_output, self.hidden_states,
+                                 self.reshaped_hidden_states, self.attentions) if v is not None)
 
     def __getitem__(self, key):
         if isinstance(key, str):
@@ -84,21 +105,87 @@ def _param_shapes(cfg):
                                   window_size=cfg.window_size, mlp_ratio=cfg.mlp_ratio, num_labels=cfg.num_labels))
 
 
-class SwinForImageClassification(nn.Module):
-    """Parameters are registered flat under their transformers state_dict keys, so `state_dict()` /
-    `load_state_dict()` interoperate with transformers checkpoints key for key."""
+def _layer_list(config, output_attentions):
+    """The global layer indices whose attention map is wanted: False / None -> none, True -> every layer, or an iterable of
+    layer indices (an extension: the layers after the last of them stay on their fused kernels; the other entries of
+    `attentions` are None)."""
+    n = sum(config.depths)
+    if output_attentions is None or output_attentions is False:
+        return []
+    if output_attentions is True:
+        return list(range(n))
+    layers = sorted({int(i) for i in output_attentions})
+    if layers and not 0 <= layers[0] <= layers[-1] < n:
+        raise ValueError(f"output_attentions names layers {layers}; the model has layers 0 .. {n - 1}")
+    return layers
 
-    def __init__(self, config):
-        super().__init__()
-        self.config = config
-        self.num_labels = config.num_labels
+
+def _engine_run(eng, config, pixel_values, want_last, want_hidden, layers):
+    """One inference forward through an engine entry (ocm_swin_forward_ex) -> dict(logits, pooled, last_hidden, hidden_states,
+    reshaped_hidden_states, attentions). Shapes come from ocm_swin_output_shape."""
+    lib = _lib.load()
+    x = pixel_values.detach().to(torch.float32).contiguous()
+    dev, B = x.device, x.shape[0]
+    f32 = dict(dtype=torch.float32, device=dev)
+    n_hidden, n_layers = config.num_layers + 1, sum(config.depths)
+
+    def shape(kind, index):
+        dims = (C.c_int64 * 4)()
+        _lib.check(lib.ocm_swin_output_shape(C.byref(eng["cfg"]), B, kind, index, dims))
+        return tuple(dims)
+
+    _, L, Cl, _ = shape(_lib.OCM_SWIN_OUT_HIDDEN, config.num_layers)
+    logits = torch.empty((B, eng["labels"]), **f32) if eng["labels"] else None
+    pooled = torch.empty((B, Cl), **f32)
+    hidden = torch.empty((B, L, Cl), **f32) if want_last else None
+    outs, hs, rs, at = None, None, None, None
+    if want_hidden or layers:
+        outs = _lib.OcmSwinOutputs()
+        if want_hidden:
+            hs = tuple(torch.empty(shape(_lib.OCM_SWIN_OUT_HIDDEN, i)[:3], **f32) for i in range(n_hidden))
+            rs = tuple(torch.empty(shape(_lib.OCM_SWIN_OUT_RESHAPED, i), **f32) for i in range(n_hidden))
+            for i in range(n_hidden):
+                outs.hidden[i], outs.reshaped[i] = hs[i].data_ptr(), rs[i].data_ptr()
+        if layers:
+            ptrs = (C.c_void_p * n_layers)()
+            at = [None] * n_layers
+            for i in layers:
+                at[i] = torch.empty(shape(_lib.OCM_SWIN_OUT_ATTENTION, i), **f32)
+                ptrs[i] = at[i].data_ptr()
+            outs.attentions = C.cast(ptrs, C.POINTER(C.c_void_p))
+            at = tuple(at)
+    ws = eng["ws"].get(B)
+    if ws is None:
+        nbytes = lib.ocm_swin_workspace_bytes(eng["h"], B)
+        ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
+        eng["ws"] = {B: ws}
+    off = (-ws.data_ptr()) % 256
+    with torch.cuda.device(dev):
+        _lib.check(lib.ocm_swin_forward_ex(eng["h"], _p(x), B, _p(logits), _p(pooled), _p(hidden),
+                                           C.byref(outs) if outs is not None else None,
+                                           C.c_void_p(ws.data_ptr() + off), ws.numel() - off, _stream()))
+    return dict(logits=logits, pooled=pooled, last_hidden=hidden, hidden_states=hs, reshaped_hidden_states=rs, attentions=at)
+
+
+class _SwinBase(nn.Module):
+    """Parameters registered flat under their transformers state_dict keys (so `state_dict()` / `load_state_dict()`
+    interoperate with transformers checkpoints key for key), the precision switch and the engine made from them.
+    `_engine_prefix` + key is the engine's parameter name, `_engine_labels` its classifier width (0: a backbone)."""
+
+    _engine_prefix = ""
+
+    def _register(self, shapes=None, params=None):
+        """Create the parameters of `shapes` (key -> shape, transformers' initialisation), or adopt `params` (key -> Parameter)."""
         self._names = {}
-        for key, shape in _param_shapes(config).items():
-            p = nn.Parameter(torch.zeros(shape), requires_grad=False)
-            if "norm" in key and key.endswith("weight"):
-                nn.init.ones_(p)
-            elif key.endswith("weight") or key.endswith("relative_position_bias_table"):
-                trunc_normal_(p, std=.02)
+        for key in (shapes if params is None else params):
+            if params is None:
+                p = nn.Parameter(torch.zeros(shapes[key]), requires_grad=False)
+                if "norm" in key and key.endswith("weight"):
+                    nn.init.ones_(p)
+                elif key.endswith("weight") or key.endswith("relative_position_bias_table"):
+                    trunc_normal_(p, std=.02)
+            else:
+                p = params[key]
             flat = key.replace(".", "__")
             self.register_parameter(flat, p)
             self._names[flat] = key
@@ -152,10 +239,12 @@ class SwinForImageClassification(nn.Module):
             return eng
         self._drop_engine()
         lib, c = _lib.load(), self.config
+        labels = self._engine_labels
         cfg = _lib.OcmSwinConfig(image_size=c.image_size, patch_size=c.patch_size, num_channels=c.num_channels,
                                  embed_dim=c.embed_dim, num_stages=c.num_layers, window_size=c.window_size,
-                                 num_labels=c.num_labels, mlp_ratio=c.mlp_ratio, ln_eps=c.layer_norm_eps,
-                                 precision=_lib.PRECISIONS[self._precision], reserved=0)
+                                 num_labels=labels, mlp_ratio=c.mlp_ratio, ln_eps=c.layer_norm_eps,
+                                 precision=_lib.PRECISIONS[self._precision],
+                                 reserved=0 if labels else _lib.OCM_SWIN_CFG_BACKBONE)
         for i in range(c.num_layers):
             cfg.depths[i], cfg.num_heads[i] = c.depths[i], c.num_heads[i]
         h = C.c_void_p(0)
@@ -166,20 +255,61 @@ class SwinForImageClassification(nn.Module):
                     lib.ocm_swin_destroy(h)
                     raise RuntimeError(f"parameters are on {p.device} but the input is on {device}; call model.to(device)")
                 t = p.detach().to(torch.float32).contiguous()
-                _lib.check(lib.ocm_swin_set_param(h, self._names[flat].encode(), _p(t), t.numel(), _stream()))
+                name = self._engine_prefix + self._names[flat]
+                _lib.check(lib.ocm_swin_set_param(h, name.encode(), _p(t), t.numel(), _stream()))
             torch.cuda.current_stream().synchronize()
-        return self._engine_cache.put("engine", sig, device, params, dict(h=h, ws={}))
+        return self._engine_cache.put("engine", sig, device, params, dict(h=h, ws={}, cfg=cfg, labels=labels))
 
-    def forward(self, pixel_values=None, labels=None, output_hidden_states=False, **unused):
+    def _check_pixels(self, pixel_values):
         _require_hip(pixel_values, "pixel_values")
         c = self.config
         if pixel_values.dim() != 4 or tuple(pixel_values.shape[1:]) != (c.num_channels, c.image_size, c.image_size):
             raise ValueError(f"expected (B, {c.num_channels}, {c.image_size}, {c.image_size}) pixel_values, got "
                              f"{tuple(pixel_values.shape)}")
+
+
+class SwinForImageClassification(_SwinBase):
+    """transformers' SwinForImageClassification: the classifier on the pooled output of the backbone (`.swin`).
+
+    forward(pixel_values, labels=None, output_hidden_states=False, output_attentions=False):
+      * output_hidden_states=True: `last_hidden_state` (the final LayerNorm's output, this path's own attribute), and in
+        inference `hidden_states` (num_stages + 1 token-major tensors: the embeddings output, every stage's output after its
+        patch merging, the last one before the final LayerNorm) and `reshaped_hidden_states` (the same as (B, C, H, W)).
+      * output_attentions=True (or an iterable of global layer indices): `attentions`, a tuple with one
+        (B * nW, heads, ws^2, ws^2) tensor per layer (None for a layer not asked for), nW counted on the padded grid. The
+        layers up to the last one asked for run their attention half unfused (a map does not depend on which other maps
+        are asked for); in split-bf16 the other outputs then agree with the plain call to fp32 rounding, in fp32 and bf16
+        bit for bit.
+      * in training mode (module.train(), grad mode on, a parameter requiring grad) the attention maps are not built:
+        output_attentions raises NotImplementedError, and hidden_states / reshaped_hidden_states are None (the training
+        forward keeps what its backward needs, not the stage outputs); last_hidden_state is returned as before."""
+
+    def __init__(self, config):
+        super().__init__()
+        self.config = config
+        self.num_labels = config.num_labels
+        self._register(shapes=_param_shapes(config))
+
+    @property
+    def _engine_labels(self):
+        return self.config.num_labels
+
+    @property
+    def swin(self):
+        """The backbone as a SwinModel over this module's own Parameter objects and engine (no second packed copy of the
+        weights): `model.swin(pixel_values, output_hidden_states=True)` after fine-tuning the classifier. The view is built on
+        access and is not a submodule: state_dict(), parameters() and named_parameters() of the classifier do not see it."""
+        return SwinModel._view_of(self)
+
+    def forward(self, pixel_values=None, labels=None, output_hidden_states=False, output_attentions=False, **unused):
+        self._check_pixels(pixel_values)
         if _differentiable(self):
+            if _layer_list(self.config, output_attentions):
+                raise NotImplementedError("attention maps are built in inference only: call model.eval() (or run under "
+                                          "torch.no_grad()) to get `attentions`")
             return self._train_forward(pixel_values, labels, output_hidden_states)
         with torch.no_grad():
-            return self._infer(pixel_values, labels, output_hidden_states)
+            return self._infer(pixel_values, labels, output_hidden_states, _layer_list(self.config, output_attentions))
 
     # ---- training ----------------------------------------------------------------------------------------------------------
     def _check_trainable(self, x, labels):
@@ -233,34 +363,79 @@ class SwinForImageClassification(nn.Module):
         if labels is not None:
             loss = nn.functional.cross_entropy(logits, labels.to(dev))
         hidden = meta["hidden"] if output_hidden_states else None  # the final LayerNorm's output, without a graph
-        return SwinOutput(loss=loss, logits=logits, pooler_output=pooled, last_hidden_state=hidden)
+        return SwinOutput(loss=loss, logits=logits, pooler_output=pooled, last_hidden_state=hidden, hidden_states=None,
+                          reshaped_hidden_states=None, attentions=None)
 
     # ---- inference ---------------------------------------------------------------------------------------------------------
-    def _infer(self, pixel_values, labels, output_hidden_states):
-        c = self.config
-        x = pixel_values.detach().to(torch.float32).contiguous()
-        dev, B = x.device, x.shape[0]
-        eng, lib = self._get_engine(dev), _lib.load()
-        side = c.image_size // c.patch_size
-        for _ in range(c.num_layers - 1):  # SwinPatchMerging.maybe_pad: an odd grid is padded to an even one before it is halved
-            side = (side + 1) // 2
-        L = side * side
-        logits = torch.empty((B, c.num_labels), dtype=torch.float32, device=dev)
-        pooled = torch.empty((B, c.hidden_size), dtype=torch.float32, device=dev)
-        hidden = torch.empty((B, L, c.hidden_size), dtype=torch.float32, device=dev) if output_hidden_states else None
-        ws = eng["ws"].get(B)
-        if ws is None:
-            nbytes = lib.ocm_swin_workspace_bytes(eng["h"], B)
-            ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
-            eng["ws"] = {B: ws}
-        off = (-ws.data_ptr()) % 256
-        with torch.cuda.device(dev):
-            _lib.check(lib.ocm_swin_forward(eng["h"], _p(x), B, _p(logits), _p(pooled), _p(hidden) if hidden is not None else None,
-                                            C.c_void_p(ws.data_ptr() + off), ws.numel() - off, _stream()))
+    def _infer(self, pixel_values, labels, output_hidden_states, layers=()):
+        r = _engine_run(self._get_engine(pixel_values.device), self.config, pixel_values, output_hidden_states,
+                        output_hidden_states, list(layers))
         loss = None
         if labels is not None:
-            loss = nn.functional.cross_entropy(logits, labels.to(dev))
-        return SwinOutput(loss=loss, logits=logits, pooler_output=pooled, last_hidden_state=hidden)
+            loss = nn.functional.cross_entropy(r["logits"], labels.to(pixel_values.device))
+        return SwinOutput(loss=loss, logits=r["logits"], pooler_output=r["pooled"], last_hidden_state=r["last_hidden"],
+                          hidden_states=r["hidden_states"], reshaped_hidden_states=r["reshaped_hidden_states"],
+                          attentions=r["attentions"])
+
+
+class SwinModel(_SwinBase):
+    """transformers' SwinModel: the backbone without the classifier, inference only. Parameters are registered under
+    transformers' SwinModel keys (the classifier model's keys without the `swin.` prefix and without classifier.*).
+
+    forward(pixel_values, output_hidden_states=False, output_attentions=False) -> SwinModelOutput(last_hidden_state,
+    pooler_output (None when add_pooling_layer=False), hidden_states, reshaped_hidden_states, attentions), the three
+    tuples as SwinForImageClassification.forward describes them. Not built (NotImplementedError): use_mask_token=True, a
+    bool_masked_pos, interpolate_pos_encoding=True, and training (training mode with a parameter that requires grad)."""
+
+    _engine_prefix = "swin."
+    _engine_labels = 0
+
+    def __init__(self, config, add_pooling_layer=True, use_mask_token=False):
+        super().__init__()
+        if use_mask_token:
+            raise NotImplementedError("use_mask_token=True (SwinForMaskedImageModeling's mask token) is not built")
+        self.config = config
+        self.add_pooling_layer = add_pooling_layer
+        self.__dict__["_owner"] = None
+        self._register(shapes={k[len("swin."):]: v for k, v in _param_shapes(config).items() if k.startswith("swin.")})
+
+    @classmethod
+    def _view_of(cls, owner):
+        """A SwinModel over the `swin.*` Parameter objects of a SwinForImageClassification, running through its engine."""
+        self = cls.__new__(cls)
+        nn.Module.__init__(self)
+        self.config, self.add_pooling_layer = owner.config, True
+        self.__dict__["_owner"] = owner
+        self._register(params={owner._names[flat][len("swin."):]: p for flat, p in owner.named_parameters()
+                               if owner._names[flat].startswith("swin.")})
+        self.__dict__["_precision"] = owner._precision
+        self.training = owner.training
+        return self
+
+    def set_precision(self, precision):
+        if self._owner is not None:  # one engine, the owner's
+            self._owner.set_precision(precision)
+            self.__dict__["_precision"] = self._owner._precision
+            return self
+        return super().set_precision(precision)
+
+    def forward(self, pixel_values=None, bool_masked_pos=None, output_hidden_states=False, output_attentions=False,
+                interpolate_pos_encoding=False, **unused):
+        if bool_masked_pos is not None:
+            raise NotImplementedError("bool_masked_pos (masked image modelling) is not built")
+        if interpolate_pos_encoding:
+            raise NotImplementedError("interpolate_pos_encoding=True is not built: pixel_values must be config.image_size wide")
+        self._check_pixels(pixel_values)
+        if _differentiable(self):
+            raise NotImplementedError("SwinModel is inference only: call .eval(), run under torch.no_grad(), or train "
+                                      "through SwinForImageClassification")
+        layers = _layer_list(self.config, output_attentions)
+        with torch.no_grad():
+            eng = (self._owner if self._owner is not None else self)._get_engine(pixel_values.device)
+            r = _engine_run(eng, self.config, pixel_values, True, output_hidden_states, layers)
+        return SwinModelOutput(last_hidden_state=r["last_hidden"], pooler_output=r["pooled"] if self.add_pooling_layer else None,
+                               hidden_states=r["hidden_states"], reshaped_hidden_states=r["reshaped_hidden_states"],
+                               attentions=r["attentions"])
 
 
 # ---- training: SwinForImageClassification as stand-alone operators under one autograd Function. Token-major rows

@@ -193,6 +193,26 @@ int ocm_op_swin_merge_gather(const float *x, float *y, int32_t batch, int32_t he
 int ocm_op_swin_merge_scatter(const float *dy, float *dx, int32_t batch, int32_t height, int32_t width, int32_t channels,
                               void *stream);
 
+/* ---- the padded geometries in training (SwinLayer.maybe_pad, SwinPatchMerging.maybe_pad). Byte-moving and bit exact: 16-byte
+ * accesses (every pointer 16-byte aligned), one writer per output element, every output byte written. ----
+ * ocm_op_swin_pad_rows: rows of row_bytes bytes (a positive multiple of 16) in any element format (fp32, bf16, split pairs),
+ * src (batch, height, width, row) -> dst (batch, height_pad, width_pad, row), zeros at the positions right of and below the grid
+ * (the kernel the engine runs on its padded geometries). ocm_op_swin_crop_rows: the inverse, src (batch, height_pad, width_pad,
+ * row) -> dst (batch, height, width, row); each is the other's backward. height_pad >= height, width_pad >= width. */
+int ocm_op_swin_pad_rows(const void *src, void *dst, int32_t batch, int32_t height, int32_t width, int32_t height_pad,
+                         int32_t width_pad, size_t row_bytes, void *stream);
+int ocm_op_swin_crop_rows(const void *src, void *dst, int32_t batch, int32_t height, int32_t width, int32_t height_pad,
+                          int32_t width_pad, size_t row_bytes, void *stream);
+
+/* ocm_op_swin_merge_gather / _scatter for any positive sides, channels a multiple of 4: y (batch * ceil(height / 2) *
+ * ceil(width / 2), 4 * channels) = x0 | x1 | x2 | x3 with zeros where the 2 x 2 neighbourhood leaves the grid (an odd side is
+ * padded by one zero row / column); the scatter is its transpose: every element of dx (batch, height, width, channels) is
+ * written, and what dy holds at the appended positions is dropped. On even sides both give the bits of the pair above. */
+int ocm_op_swin_merge_gather_pad(const float *x, float *y, int32_t batch, int32_t height, int32_t width, int32_t channels,
+                                 void *stream);
+int ocm_op_swin_merge_scatter_pad(const float *dy, float *dx, int32_t batch, int32_t height, int32_t width, int32_t channels,
+                                  void *stream);
+
 /* The pooled head: pooled (batch, channels) = the token mean of x (batch, tokens, channels) fp32, tokens summed in order;
  * its backward dx (batch, tokens, channels) = dpooled / tokens broadcast over the tokens. */
 int ocm_op_swin_pool(const float *x, float *pooled, int32_t batch, int32_t tokens, int32_t channels, void *stream);

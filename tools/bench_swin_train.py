@@ -1,11 +1,12 @@
-"""Time one train.py fine-tuning step of SwinForImageClassification on the HIP path: Swin-T at 224^2, 5 labels, AdamW (lr 5e-5),
-drop_path_rate 0.1. Reports per phase (training forward, which repacks the weights an optimizer step changed; backward; AdamW;
+"""Time one train.py fine-tuning step of SwinForImageClassification on the HIP path: Swin-T at 224^2 (or --image-size: 384 is the
+project's tile, whose grids 96 / 48 / 24 / 12 are padded to the windows of 7: the tool then turns enable_padded_training on and
+prints the padded / real token counts per stage), 5 labels, AdamW (lr 5e-5), drop_path_rate 0.1. Reports per phase (training forward, which repacks the weights an optimizer step changed; backward; AdamW;
 `step` is their sum) and, as a yardstick, an fp32 eager twin on the same GPU: the oracle's functions (oracle/swin_oracle.py)
 under torch autograd with the same weights, timed in alternation with the HIP step in one process. Also reports the activations
 the training forward keeps per image. The split by kernel class comes from a kernel trace of this tool
 (rocprofv3 --kernel-trace --stats).
 
-  python tools/bench_swin_train.py [--batch 8] [--precision bf16] [--reps 5] [--optimizer hip]
+  python tools/bench_swin_train.py [--batch 8] [--precision bf16] [--reps 5] [--optimizer hip] [--image-size 384] [--no-twin]
 """
 import argparse
 import json
@@ -41,18 +42,32 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--optimizer", default="torch", choices=["torch", "hip"],
                     help="the HIP step's optimizer: torch.optim (default) or optimizer.py's multi-tensor kernels")
+    ap.add_argument("--image-size", type=int, default=224, help="square input side, a multiple of the patch size 4")
+    ap.add_argument("--no-twin", action="store_true", help="skip the fp32 eager twin (for a kernel trace of the HIP step alone)")
     args = ap.parse_args()
-    dev, B = torch.device("cuda:0"), args.batch
-    cfg = dict(synth.SWIN_TINY)
+    dev, B, S = torch.device("cuda:0"), args.batch, args.image_size
+    cfg = dict(synth.SWIN_TINY, image_size=S)
     sd = synth.synth_swin_state_dict(cfg, seed=3)
-    m = SW.SwinForImageClassification(SW.SwinConfig(num_labels=5))
+    m = SW.SwinForImageClassification(SW.SwinConfig(image_size=S, num_labels=5))
     m.load_state_dict(sd)
     m = m.to(dev).set_precision(args.precision).train().requires_grad_(True)
+    tokens, side, ws = [], S // cfg["patch_size"], cfg["window_size"]
+    for s in range(len(cfg["depths"])):  # per stage: the grid, and the grid padded to the window the attention runs on
+        pad = -(-side // ws) * ws
+        tokens.append(dict(stage=s, grid=side, padded_grid=pad, real=side * side, padded=pad * pad,
+                           ratio=round(pad * pad / (side * side), 2), odd_merge=bool(side % 2 and s + 1 < len(cfg["depths"]))))
+        side = (side + 1) // 2
+    needs_padding = any(t["padded"] != t["real"] or t["odd_merge"] for t in tokens)
+    if needs_padding:
+        m.enable_padded_training()
+    for t in tokens:
+        print(f"stage {t['stage']}: grid {t['grid']}^2 = {t['real']} tokens, padded {t['padded_grid']}^2 = {t['padded']} "
+              f"({t['ratio']:.2f}x){', odd merge' if t['odd_merge'] else ''}")
     opt = (OPT.AdamW if args.optimizer == "hip" else torch.optim.AdamW)(m.parameters(), lr=5e-5)
     prm = {k: v.to(dev).requires_grad_(True) for k, v in sd.items()}
     opt_t = torch.optim.AdamW(list(prm.values()), lr=5e-5)
     torch.manual_seed(0)
-    x = torch.rand(B, 3, 224, 224, device=dev) * 0.3
+    x = torch.rand(B, 3, S, S, device=dev) * 0.3
     y = torch.randint(0, 5, (B,), device=dev)
 
     def hip_step():
@@ -63,6 +78,8 @@ def main():
         return tf, tb, to
 
     def twin_step():
+        if args.no_twin:
+            return float("nan")
         opt_t.zero_grad(set_to_none=True)
         t0 = time.perf_counter()
         with torch.device(dev):  # the oracle builds its index tables and shift masks on the default device
@@ -83,7 +100,8 @@ def main():
         rows["step"].append(tf + tb + to)
         rows["twin"].append(twin_step())
     med = {k: sorted(v)[len(v) // 2] for k, v in rows.items()}
-    res = dict(box=socket.gethostname(), gpu=torch.cuda.get_device_name(0), batch=B, precision=args.precision,
+    res = dict(box=socket.gethostname(), gpu=torch.cuda.get_device_name(0), batch=B, precision=args.precision, image_size=S,
+               padded_training=needs_padding, padded_over_real_tokens=[t["ratio"] for t in tokens],
                ms={k: round(v, 2) for k, v in med.items()}, speedup_vs_eager=round(med["twin"] / med["step"], 2),
                kept_mib_per_image=round(m.__dict__["_train_kept_bytes"] / B / 2 ** 20, 1), reps=args.reps)
     print(json.dumps(res))

@@ -213,6 +213,10 @@ SIGNATURES = {
                                                         _vp]),
     "ocm_op_swin_merge_gather": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "ocm_op_swin_merge_scatter": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp]),
+    "ocm_op_swin_pad_rows": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _sz, _vp]),
+    "ocm_op_swin_crop_rows": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _sz, _vp]),
+    "ocm_op_swin_merge_gather_pad": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp]),
+    "ocm_op_swin_merge_scatter_pad": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "ocm_op_swin_pool": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp]),
     "ocm_op_swin_pool_backward": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp]),
     "ocm_op_swin_drop_path": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),

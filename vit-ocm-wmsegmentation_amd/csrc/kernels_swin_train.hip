@@ -8,6 +8,10 @@
 //   swin_colsum_kernel         fixed-order column sums: the per-window bin partials -> the table gradient, in two levels
 //   swin_merge_gather_kernel   SwinPatchMerging's 2 x 2 gather (x0 | x1 | x2 | x3) as fp32 rows: the merging LayerNorm's input
 //   swin_merge_scatter_kernel  its inverse in gather form (a permutation: bit exact)
+//   swin_crop_rows_kernel      the padded geometries: rows of a grid padded to the window back to the grid (the pad is the
+//                              engine's swin_pad_rows_kernel), 16-byte pieces in any element format
+//   swin_merge_gather_pad_kernel / _scatter_pad  the gather for any sides (an odd side gets a zero row / column) and its
+//                              transpose, 16-byte pieces
 //   swin_pool_kernel / _bwd    the token mean of the final LayerNorm's output and its broadcast backward
 //   swin_drop_path_kernel      residual + per-image-scaled branch (SwinDropPath), and the branch's gradient
 // No atomics anywhere: every sum has one order fixed by the shapes, so reruns give the same bits.
@@ -210,6 +214,51 @@ __global__ __launch_bounds__(256) void swin_drop_path_kernel(const float *x, con
     }
 }
 
+// SwinLayer.maybe_pad's inverse: rows (B, Hp, Wp, row) -> (B, H, W, row) in 16-byte pieces (the pad itself is kernels_swin.hip's
+// swin_pad_rows_kernel, which the engine runs too)
+__global__ __launch_bounds__(256) void swin_crop_rows_kernel(const f32x4 *__restrict__ src, f32x4 *__restrict__ dst, int H, int W,
+                                                             int Hp, int Wp, int chunks, size_t total) {
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+        const size_t row = i / chunks;
+        const int c = (int)(i - row * chunks);
+        const size_t b = row / ((size_t)H * W);
+        const int rem = (int)(row - b * H * W), y = rem / W, xx = rem - y * W;
+        dst[i] = src[((b * Hp + y) * Wp + xx) * (size_t)chunks + c];
+    }
+}
+
+// swin_merge_gather_kernel for any sides (SwinPatchMerging.maybe_pad: an odd side gets one zero row / column), in 16-byte
+// pieces: C4 = C / 4 pieces per channel row, zeros where the 2 x 2 neighbourhood leaves the grid
+__global__ __launch_bounds__(256) void swin_merge_gather_pad_kernel(const f32x4 *__restrict__ x, f32x4 *__restrict__ y, int H,
+                                                                    int W, int C4, size_t total) {
+    const int H2 = (H + 1) / 2, W2 = (W + 1) / 2, K4 = 4 * C4;
+    for (size_t n = (size_t)blockIdx.x * 256 + threadIdx.x; n < total; n += (size_t)gridDim.x * 256) {
+        const int k = (int)(n % K4);
+        const size_t t = n / K4;
+        const int j = (int)(t % W2), i = (int)((t / W2) % H2);
+        const size_t b = t / ((size_t)W2 * H2);
+        const int q = k / C4, c = k - q * C4;
+        const int yy = 2 * i + (q & 1), xx = 2 * j + (q >> 1);
+        f32x4 v = {0.f, 0.f, 0.f, 0.f};
+        if (yy < H && xx < W) v = x[((b * H + yy) * W + xx) * (size_t)C4 + c];
+        y[n] = v;
+    }
+}
+
+// its transpose in gather form: every dx element has exactly one source; what dy holds at the appended row / column is not read
+__global__ __launch_bounds__(256) void swin_merge_scatter_pad_kernel(const f32x4 *__restrict__ dy, f32x4 *__restrict__ dx, int H,
+                                                                     int W, int C4, size_t total) {
+    const int H2 = (H + 1) / 2, W2 = (W + 1) / 2;
+    for (size_t n = (size_t)blockIdx.x * 256 + threadIdx.x; n < total; n += (size_t)gridDim.x * 256) {
+        const int c = (int)(n % C4);
+        const size_t t = n / C4;
+        const int xx = (int)(t % W), yy = (int)((t / W) % H);
+        const size_t b = t / ((size_t)W * H);
+        const int q = (xx & 1) * 2 + (yy & 1);
+        dx[n] = dy[((b * H2 + yy / 2) * W2 + xx / 2) * (size_t)(4 * C4) + q * C4 + c];
+    }
+}
+
 unsigned grid_for(size_t work) {
     const size_t g = (work + 255) / 256;
     return (unsigned)(g < 1 ? 1 : g > 8192 ? 8192 : g);
@@ -234,6 +283,29 @@ int merge_ok(int batch, int height, int width, int channels) {
     if (batch <= 0 || height <= 0 || width <= 0 || height % 2 || width % 2 || channels <= 0)
         return fail(OCM_EINVAL, "bad patch-merging geometry (batch %d, %d x %d, %d channels): even sides only", batch, height,
                     width, channels);
+    return OCM_OK;
+}
+
+bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
+
+int rows_ok(const void *src, const void *dst, int batch, int height, int width, int height_pad, int width_pad,
+            size_t row_bytes) {
+    if (!src || !dst) return fail(OCM_EINVAL, "null argument");
+    if (batch <= 0 || height <= 0 || width <= 0 || height_pad < height || width_pad < width || row_bytes == 0 ||
+        row_bytes % 16 || row_bytes > 0x7fffffffu)
+        return fail(OCM_EINVAL, "bad padded-row geometry (batch %d, %d x %d in %d x %d, rows of %zu bytes: a positive multiple "
+                    "of 16)", batch, height, width, height_pad, width_pad, row_bytes);
+    if ((int64_t)height_pad * width_pad > 0x7fffffffLL) return fail(OCM_EINVAL, "too many positions per image");
+    if (!aligned16(src) || !aligned16(dst)) return fail(OCM_EINVAL, "rows must be 16-byte aligned");
+    return OCM_OK;
+}
+
+int merge_pad_ok(const void *a, const void *b, int batch, int height, int width, int channels) {
+    if (!a || !b) return fail(OCM_EINVAL, "null argument");
+    if (batch <= 0 || height <= 0 || width <= 0 || channels <= 0 || channels % 4)
+        return fail(OCM_EINVAL, "bad patch-merging geometry (batch %d, %d x %d, %d channels): positive sides, channels a "
+                    "multiple of 4", batch, height, width, channels);
+    if (!aligned16(a) || !aligned16(b)) return fail(OCM_EINVAL, "rows must be 16-byte aligned");
     return OCM_OK;
 }
 
@@ -292,6 +364,44 @@ extern "C" int ocm_op_swin_merge_scatter(const float *dy, float *dx, int32_t bat
     const size_t total = (size_t)batch * height * width * channels;
     swin_merge_scatter_kernel<<<dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream>>>(dy, dx, height, width, channels,
                                                                                             total);
+    HIP_TRY(hipGetLastError());
+    return OCM_OK;
+}
+
+extern "C" int ocm_op_swin_pad_rows(const void *src, void *dst, int32_t batch, int32_t height, int32_t width, int32_t height_pad,
+                                    int32_t width_pad, size_t row_bytes, void *stream) {
+    if (int rc = rows_ok(src, dst, batch, height, width, height_pad, width_pad, row_bytes)) return rc;
+    HIP_TRY(launch_swin_pad_rows(src, dst, batch, height, width, height_pad, width_pad, row_bytes, (hipStream_t)stream));
+    return OCM_OK;
+}
+
+extern "C" int ocm_op_swin_crop_rows(const void *src, void *dst, int32_t batch, int32_t height, int32_t width,
+                                     int32_t height_pad, int32_t width_pad, size_t row_bytes, void *stream) {
+    if (int rc = rows_ok(src, dst, batch, height, width, height_pad, width_pad, row_bytes)) return rc;
+    const int chunks = (int)(row_bytes / 16);
+    const size_t total = (size_t)batch * height * width * chunks;
+    swin_crop_rows_kernel<<<dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream>>>(
+        (const f32x4 *)src, (f32x4 *)dst, height, width, height_pad, width_pad, chunks, total);
+    HIP_TRY(hipGetLastError());
+    return OCM_OK;
+}
+
+extern "C" int ocm_op_swin_merge_gather_pad(const float *x, float *y, int32_t batch, int32_t height, int32_t width,
+                                            int32_t channels, void *stream) {
+    if (int rc = merge_pad_ok(x, y, batch, height, width, channels)) return rc;
+    const size_t total = (size_t)batch * ((height + 1) / 2) * ((width + 1) / 2) * channels;  // 4 * (channels / 4) pieces a row
+    swin_merge_gather_pad_kernel<<<dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream>>>(
+        (const f32x4 *)x, (f32x4 *)y, height, width, channels / 4, total);
+    HIP_TRY(hipGetLastError());
+    return OCM_OK;
+}
+
+extern "C" int ocm_op_swin_merge_scatter_pad(const float *dy, float *dx, int32_t batch, int32_t height, int32_t width,
+                                             int32_t channels, void *stream) {
+    if (int rc = merge_pad_ok(dy, dx, batch, height, width, channels)) return rc;
+    const size_t total = (size_t)batch * height * width * (channels / 4);
+    swin_merge_scatter_pad_kernel<<<dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream>>>(
+        (const f32x4 *)dy, (f32x4 *)dx, height, width, channels / 4, total);
     HIP_TRY(hipGetLastError());
     return OCM_OK;
 }

@@ -312,6 +312,14 @@ class SwinForImageClassification(_SwinBase):
             return self._infer(pixel_values, labels, output_hidden_states, _layer_list(self.config, output_attentions))
 
     # ---- training ----------------------------------------------------------------------------------------------------------
+    def enable_padded_training(self, on=True):
+        """Opt in to training on the geometries that need transformers' padding paths: a stage grid that is not a multiple of
+        the window (SwinLayer.maybe_pad: Swin-T on a 384^2 tile has grids 96 / 48 / 24 / 12 for windows of 7) or an odd grid
+        before a patch merging. A per-module setting, not part of the state_dict; geometries without padding launch what
+        they launch without it. Returns self."""
+        self.__dict__["_padded_training"] = bool(on)
+        return self
+
     def _check_trainable(self, x, labels):
         """What the training path refuses, before anything is launched."""
         c = self.config
@@ -325,19 +333,25 @@ class SwinForImageClassification(_SwinBase):
         if c.patch_size != 4 or not 2 <= c.window_size <= 7:
             raise NotImplementedError("training is built for patch_size 4 and windows of 2 to 7")
         side = c.image_size // c.patch_size
+        padded = self.__dict__.get("_padded_training", False)
+        hint = "; model.enable_padded_training() trains through transformers' padding paths"
         for s in range(c.num_layers):
             if c.embed_dim * 2 ** s != 32 * c.num_heads[s] or c.embed_dim % 32 or c.embed_dim > 128:
                 raise NotImplementedError(f"stage {s}: training is built for 32-wide heads and embed_dim a multiple of 32 "
                                           "up to 128")
-            if side < c.window_size or side % c.window_size:
+            if padded and side < c.window_size:
+                raise NotImplementedError(f"stage {s}: its {side} x {side} grid is smaller than window_size {c.window_size}; "
+                                          "neither training nor inference is built for that")
+            if not padded and (side < c.window_size or side % c.window_size):
                 raise NotImplementedError(f"stage {s}: its {side} x {side} grid is not a multiple of window_size "
                                           f"{c.window_size}; training is built for geometries without transformers' padding "
-                                          "paths (every stage grid a multiple of the window, even before each merge)")
+                                          "paths (every stage grid a multiple of the window, even before each merge)" + hint)
             if s + 1 < c.num_layers:
-                if side % 2:
+                if side % 2 and not padded:
                     raise NotImplementedError(f"stage {s}: the odd {side} x {side} grid would be padded before the patch "
-                                              "merging; training is built for geometries without transformers' padding paths")
-                side //= 2
+                                              "merging; training is built for geometries without transformers' padding paths"
+                                              + hint)
+                side = (side + 1) // 2
         if labels is not None:
             if c.num_labels < 2:
                 raise ValueError(f"training with labels is built for single-label classification with num_labels >= 2 (got "
@@ -455,6 +469,20 @@ def _operand(t32, prec):
     return to_operand(_pad_cols(t32, _kpad(t32.shape[1], prec)), prec)
 
 
+def _pad_rows(lib, src, B, H, Hp):
+    """Rows (B * H * H, n) of any element type -> (B * Hp * Hp, n): SwinLayer.maybe_pad, zeros right of and below the grid."""
+    dst = torch.empty((B * Hp * Hp, src.shape[1]), dtype=src.dtype, device=src.device)
+    _lib.check(lib.ocm_op_swin_pad_rows(_p(src), _p(dst), B, H, H, Hp, Hp, src.shape[1] * src.element_size(), _stream()))
+    return dst
+
+
+def _crop_rows(lib, src, B, H, Hp):
+    """The inverse: rows (B * Hp * Hp, n) -> the (B * H * H, n) at the real positions."""
+    dst = torch.empty((B * H * H, src.shape[1]), dtype=src.dtype, device=src.device)
+    _lib.check(lib.ocm_op_swin_crop_rows(_p(src), _p(dst), B, H, H, Hp, Hp, src.shape[1] * src.element_size(), _stream()))
+    return dst
+
+
 class _Weights:
     """Operand copies of weight matrices ([N][K] and the transposes the data gradients read), K zero-padded to the operand's
     K step, cached in the module under the parameters they are made from and the precision (engine.SourceCache): an optimizer
@@ -490,7 +518,9 @@ class _SwinTrain(torch.autograd.Function):
     """SwinForImageClassification in training mode: forward(meta, pixel_values, *params) -> (logits, pooled); backward ->
     parameter gradients (the image gets none). The forward runs the stand-alone operators in the module's precision (not the
     engine, not the fused Swin kernels): patch unfold + GEMM + LayerNorm, per layer LayerNorm -> q | k | v GEMM (fp32) ->
-    window attention -> o_proj (+ drop path) -> LayerNorm -> fc1 (fp32 pre-activation) -> GELU -> fc2, the merging LayerNorm +
+    window attention (on the grid padded to the window where enable_padded_training applies: operand rows zero-padded before
+    the projection, the context cropped after the attention) -> o_proj (+ drop path) -> LayerNorm -> fc1 (fp32
+    pre-activation) -> GELU -> fc2, the merging LayerNorm +
     reduction, the final LayerNorm, token mean and classifier (rows zero-padded to a multiple of 32). Kept per layer: the two
     LayerNorm inputs, the fp32 q | k | v, the context in operand form and the fp32 fc1 pre-activation; per merge its input;
     LayerNorm statistics and outputs are recomputed in the backward."""
@@ -524,20 +554,28 @@ class _SwinTrain(torch.autograd.Function):
         for s in range(c.num_layers):
             heads, M, ws = c.num_heads[s], int(c.mlp_ratio * C), c.window_size
             T, Kc, Km = B * H * H, _kpad(C, prec), _kpad(M, prec)
+            Hp = -(-H // ws) * ws  # the grid padded to the window (enable_padded_training); Hp = H elsewhere
+            Tp = B * Hp * Hp
             for b in range(c.depths[s]):
                 pre = f"swin.encoder.layers.{s}.blocks.{b}."
                 a = pre + "attention."
                 shift = ws // 2 if b % 2 and H > ws else 0  # set_shift_and_window_size: no shift when the grid is the window
                 xn = _ln(lib, t, P[pre + "layernorm_before.weight"], P[pre + "layernorm_before.bias"], F32, T, C, eps,
                          torch.float32)
-                qkv = _linear(lib, prec, _operand(xn, prec), W.w(a + "q_proj.weight", a + "k_proj.weight", a + "v_proj.weight"),
-                              torch.cat([P[a + n + "_proj.bias"] for n in "qkv"]), None, T, 3 * C, Kc)
+                xo = _operand(xn, prec)
                 del xn
-                cx = torch.zeros((T, Kc), dtype=adt, device=dev)
+                if Hp != H:  # SwinLayer.maybe_pad: zero rows after layernorm_before; their q | k | v is the projection bias
+                    xo = _pad_rows(lib, xo, B, H, Hp)
+                qkv = _linear(lib, prec, xo, W.w(a + "q_proj.weight", a + "k_proj.weight", a + "v_proj.weight"),
+                              torch.cat([P[a + n + "_proj.bias"] for n in "qkv"]), None, Tp, 3 * C, Kc)
+                del xo
+                cx = torch.zeros((Tp, Kc), dtype=adt, device=dev)
                 scratch = torch.empty(heads * (4096 + ws ** 4), **f32)
                 table = P[a + "relative_position_bias.relative_position_bias_table"]
                 _lib.check(lib.ocm_op_swin_window_attention(prec, _p(to_operand(qkv, prec)), 3 * C, _p(cx), Kc, _p(table),
-                                                            _p(scratch), B, H, H, ws, shift, heads, _stream()))
+                                                            _p(scratch), B, Hp, Hp, ws, shift, heads, _stream()))
+                if Hp != H:  # the padded positions' context is dropped; o_proj is row-wise and runs on the real rows
+                    cx = _crop_rows(lib, cx, B, H, Hp)
                 wo, bo = W.w(a + "o_proj.weight"), P[a + "o_proj.bias"]
                 scale = None
                 if masks[li] is None:
@@ -569,14 +607,15 @@ class _SwinTrain(torch.autograd.Function):
                 t, li = x2, li + 1
             if s + 1 < c.num_layers:  # SwinPatchMerging: gather + LayerNorm(4C) in one kernel, then the reduction
                 dn = f"swin.encoder.layers.{s}.downsample."
-                T4, K4 = B * (H // 2) ** 2, _kpad(4 * C, prec)
+                H2 = (H + 1) // 2  # SwinPatchMerging.maybe_pad: an odd grid gets a zero row and column (in the kernel)
+                T4, K4 = B * H2 * H2, _kpad(4 * C, prec)
                 y = torch.empty((T4, K4), dtype=adt, device=dev)
                 _lib.check(lib.ocm_op_swin_merge_ln(prec, _p(t), _p(P[dn + "norm.weight"]), _p(P[dn + "norm.bias"]), _p(y), B,
                                                     H, H, C, K4, _stream()))
                 keep.append(t)
                 t = _linear(lib, prec, y, W.w(dn + "reduction.weight"), torch.zeros(2 * C, **f32), None, T4, 2 * C, K4)
                 del y
-                H, C = H // 2, 2 * C
+                H, C = H2, 2 * C
         # head: final LayerNorm, token mean, classifier
         L, nl = H * H, c.num_labels
         NLp = -(-nl // 32) * 32
@@ -642,7 +681,7 @@ class _SwinTrain(torch.autograd.Function):
             geo += [(s, b, H, C) for b in range(c.depths[s])]
             if s + 1 < c.num_layers:
                 geo.append((s, None, H, C))
-                H, C = H // 2, 2 * C
+                H, C = (H + 1) // 2, 2 * C
         L, nl = H * H, c.num_labels
         NLp = -(-nl // 32) * 32
         tL, pooled = keep[-2], keep[-1]
@@ -672,7 +711,8 @@ class _SwinTrain(torch.autograd.Function):
                 if kind == "merge":
                     ki -= 1
                     xin = keep[ki]
-                    T4, C2 = B * (H // 2) ** 2, 2 * C
+                    T4, C2 = B * ((H + 1) // 2) ** 2, 2 * C
+                    odd = "_pad" if H % 2 else ""  # the gather / scatter that append the zero row and column
                     if need[pre + "reduction.weight"]:
                         y32 = torch.empty((T4, 4 * C), **f32)
                         _lib.check(lib.ocm_op_swin_merge_ln(_lib.OCM_PREC_FP32, _p(xin), _p(P[pre + "norm.weight"]),
@@ -682,18 +722,20 @@ class _SwinTrain(torch.autograd.Function):
                     dy = _linear(lib, prec, _operand(dx, prec), W.wt(pre + "reduction.weight"), torch.zeros(4 * C, **f32), None,
                                  T4, 4 * C, _kpad(C2, prec))
                     gth = torch.empty((T4, 4 * C), **f32)
-                    _lib.check(lib.ocm_op_swin_merge_gather(_p(xin), _p(gth), B, H, H, C, _stream()))
+                    _lib.check(getattr(lib, "ocm_op_swin_merge_gather" + odd)(_p(xin), _p(gth), B, H, H, C, _stream()))
                     dg4, dg, db = _ln_backward(lib, dy, gth, P[pre + "norm.weight"], None, T4, 4 * C, 1e-5)
                     lngrads(pre + "norm.", dg, db)
                     del dy, gth
                     dx = torch.empty((T, C), **f32)
-                    _lib.check(lib.ocm_op_swin_merge_scatter(_p(dg4), _p(dx), B, H, H, C, _stream()))
+                    _lib.check(getattr(lib, "ocm_op_swin_merge_scatter" + odd)(_p(dg4), _p(dx), B, H, H, C, _stream()))
                     continue
                 # a SwinLayer: x1 = t + drop_path(o_proj(attn(LN1(t)))), x2 = x1 + fc2(gelu(fc1(LN2(x1))))
                 ki -= 6
                 t, qkv, cx, x1, hpre, scale = keep[ki:ki + 6]
                 heads, M, ws = c.num_heads[s], int(c.mlp_ratio * C), c.window_size
                 shift = ws // 2 if b % 2 and H > ws else 0
+                Hp = -(-H // ws) * ws
+                Tp = B * Hp * Hp
                 a = pre + "attention."
                 dh = _linear(lib, prec, _operand(dx, prec), W.wt(pre + "mlp.fc2.weight"), torch.zeros(M, **f32), None, T, M,
                              _kpad(C, prec))
@@ -721,13 +763,15 @@ class _SwinTrain(torch.autograd.Function):
                 dctx = _linear(lib, prec, _operand(dbr, prec), W.wt(a + "o_proj.weight"), torch.zeros(C, **f32), None, T, C,
                                _kpad(C, prec))
                 del dbr
+                if Hp != H:  # the crop's gradient: zeros at the padded positions
+                    dctx = _pad_rows(lib, dctx, B, H, Hp)
                 tkey = a + "relative_position_bias.relative_position_bias_table"
-                dqkv = torch.empty((T, 3 * C), **f32)
+                dqkv = torch.empty((Tp, 3 * C), **f32)
                 dtab = torch.empty(P[tkey].shape, **f32)
-                nbytes = lib.ocm_swin_window_attention_backward_workspace_bytes(B, H, H, ws, heads)
+                nbytes = lib.ocm_swin_window_attention_backward_workspace_bytes(B, Hp, Hp, ws, heads)
                 wsb = _ws(nbytes, dev)
                 _lib.check(lib.ocm_op_swin_window_attention_backward(_p(qkv), _p(dctx), _p(P[tkey]), _p(dqkv), _p(dtab), B,
-                                                                     H, H, ws, shift, heads, _p(wsb), nbytes, _stream()))
+                                                                     Hp, Hp, ws, shift, heads, _p(wsb), nbytes, _stream()))
                 if need[tkey]:
                     grads[tkey] = dtab
                 del dctx, wsb
@@ -735,6 +779,8 @@ class _SwinTrain(torch.autograd.Function):
                 pk = [a + n + "_proj." for n in "qkv"]
                 if any(need[k + "weight"] or need[k + "bias"] for k in pk):
                     xn1 = _ln(lib, t, g1, P[pre + "layernorm_before.bias"], _lib.OCM_LN_F32, T, C, eps, torch.float32)
+                    if Hp != H:  # the padded rows' input is zero (nothing for the weights), their dq | dk | dv reaches the biases
+                        xn1 = _pad_rows(lib, xn1, B, H, Hp)
                     dw, dbq = _weight_grad(prec, dqkv, xn1, True)
                     for i, k in enumerate(pk):
                         if need[k + "weight"]:
@@ -742,6 +788,8 @@ class _SwinTrain(torch.autograd.Function):
                         if need[k + "bias"]:
                             grads[k + "bias"] = dbq[i * C:(i + 1) * C]
                     del xn1
+                if Hp != H:  # the padding's gradient: the real positions' rows
+                    dqkv = _crop_rows(lib, dqkv, B, H, Hp)
                 dxn1 = _linear(lib, prec, _operand(dqkv, prec), W.wt(*[k + "weight" for k in pk]), torch.zeros(C, **f32), None,
                                T, C, _kpad(3 * C, prec))
                 del dqkv

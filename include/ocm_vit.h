@@ -242,8 +242,8 @@ int ocm_op_linear_resid_ln(int32_t precision, const void *a, const void *w, cons
                            float eps, void *stream);
 
 /* Which kernel a GEMM-shaped operator launches for a shape: the library's own tile dispatch (csrc/gemm_plan.h), asked without
- * launching anything. Host only: no device is touched, so it also answers on a machine without a GPU. It reports the shipped
- * dispatch (development knobs at 0) in every build.
+ * launching anything. Host only: no device is touched, so it also answers on a machine without a GPU. It makes the very call
+ * the launchers make (a plan is a function of the shape alone).
  *   family     M, N, K of the GEMM                                    operators
  *   LINEAR     M, N, K; epilogue OCM_EPI_* (4: the ReLU epilogue)     ocm_op_linear, ocm_op_linear_relu, the engines' nn.Linear layers
  *   QKV        M = batch * n_tokens, N = 3 D, K = D (D % 64 == 0)     ocm_op_qkv_proj[_hd]
@@ -313,8 +313,8 @@ int ocm_op_attention_probs_hd(int32_t precision, const void *q, const void *k, c
                               int32_t batch, int32_t n_tokens, int32_t heads, int32_t head_dim, float scale, void *stream);
 
 /* Which kernel ocm_op_attention[_hd / _ws] and an engine handle launch for a shape: the library's own dispatch (csrc/attn_plan.h),
- * asked without launching anything. Host only: no device is touched, so it also answers on a machine without a GPU. It reports
- * the shipped dispatch (development knobs at 0) in every build. workspace_bytes: the key-slice workspace the caller would offer
+ * asked without launching anything. Host only: no device is touched, so it also answers on a machine without a GPU. It makes
+ * the very call the launcher makes. workspace_bytes: the key-slice workspace the caller would offer
  * (0: none, as ocm_op_attention and ocm_op_attention_hd). Arguments the operators refuse return OCM_EINVAL. */
 enum {
     OCM_ATTN_BF16_WHOLE = 0,    /* single bf16: the whole key range of one (image, head) in LDS, N <= 256            */

@@ -1,6 +1,7 @@
 #!/bin/bash
-# Development: in-forward A/B of whole library builds (e.g. `make -C vit-ocm-wmsegmentation_amd/csrc abl15` against the
-# product library). Usage: tools/ab_libs.sh vit-ocm-wmsegmentation_amd/libocm_vit.so exp_libs/abl15.so [--slab]
+# Development: in-forward A/B of whole library builds (e.g. the library of another commit, built with
+# `make -C vit-ocm-wmsegmentation_amd/csrc OUT=...`, against the in-tree one).
+# Usage: tools/ab_libs.sh vit-ocm-wmsegmentation_amd/libocm_vit.so exp_libs/other.so [--slab]
 # Alternates the libraries twice on one box; prints ms/step and the per-class kernel times (or the slab sweep time).
 SLAB=0; LIBS=()
 for a in "$@"; do if [ "$a" = "--slab" ]; then SLAB=1; else LIBS+=("$a"); fi; done

@@ -19,7 +19,7 @@ static void fail(const char *what, int prec, int bh, int n, int hd, size_t ws, c
 }
 
 static AttnPlan check(int prec, int batch, int n, int heads, int hd, size_t ws, size_t reported) {
-    const AttnPlan p = attn_plan(prec, batch, n, heads, hd, ws, 0, 0);
+    const AttnPlan p = attn_plan(prec, batch, n, heads, hd, ws);
     const int bh = batch * heads, qtiles = attn_qtiles(n);
     ++g_plans;
     if (p.kslices < 1 || p.grid_z != (unsigned)p.kslices) fail("nslice >= 1", prec, bh, n, hd, ws, p);

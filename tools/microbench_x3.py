@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
-"""Development tool (GPU box): times the split-bf16 (and bf16) nn.Linear kernel variants selectable through
-ocm_debug_knob(0, v) at the bench shapes (ViT-S/16, B=64: M = 12608) and checks every variant against variant 0.
-    python tools/microbench_x3.py [--prec 2] [--variants 0,1,2,3,4,5,6] [--iters 30]"""
+"""Development tool (GPU box): times the split-bf16 (and bf16) nn.Linear kernels and the qkv projection of whichever library
+OCM_VIT_LIB names (default: the in-tree build) at the bench shapes (ViT-S/16, B=64: M = 12608). To compare two builds, run it
+once per library file.
+    python tools/microbench_x3.py [--prec 2] [--iters 30] [--only fc1,fc2,proj,qkv_as_linear,qkv]"""
 import argparse
 import ctypes as C
 import os
@@ -9,8 +10,6 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-# the knobs exist in the development build only (`make -C vit-ocm-wmsegmentation_amd/csrc dev`)
-os.environ.setdefault("OCM_VIT_LIB", os.path.join(ROOT, "exp_libs", "libocm_vit_dev.so"))
 import torch  # noqa: E402
 
 from vit_ocm_wmsegmentation_amd import _lib  # noqa: E402
@@ -41,7 +40,6 @@ def timeit(fn, iters):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--prec", type=int, default=2)
-    ap.add_argument("--variants", default="0,1,2,3,4,5,6")
     ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--rows", type=int, default=12608)
     ap.add_argument("--dim", type=int, default=384)
@@ -63,34 +61,16 @@ def main():
         act_out = epi in (2, 3)
         odt = torch.float32 if not act_out else {0: torch.bfloat16, 1: torch.float32, 2: torch.int32}[a.prec]
         resid = torch.randn((m, n), generator=g).to(dev)
-        ref = None
-        for v in map(int, a.variants.split(",")):
-            _lib.check(lib.ocm_debug_knob(0, v))
-            out = resid.clone() if epi == 1 else torch.zeros((m, n), dtype=odt, device=dev)
+        out = torch.empty((m, n), dtype=odt, device=dev)
 
-            def fn():
-                return lib.ocm_op_linear(a.prec, p(xa), p(wa), p(bias), p(out) if epi == 1 else None, p(out), m, n, k,
-                                         3 if epi == 1 else epi, s())  # timing: no in-place accumulation drift
-            if epi == 1:
-                rc = lib.ocm_op_linear(a.prec, p(xa), p(wa), p(bias), p(out), p(out), m, n, k, 1, s())
-            else:
-                rc = fn()
-            assert rc == 0, lib.ocm_last_error()
-            torch.cuda.synchronize()
-            got = out.clone()
-            if ref is None:
-                ref = got
-            same = torch.equal(got.view(torch.int32) if got.dtype != torch.bfloat16 else got.view(torch.int16),
-                               ref.view(torch.int32) if ref.dtype != torch.bfloat16 else ref.view(torch.int16))
-            if epi == 1:  # time the fp32-out epilogue 0 instead of accumulating in place
-                o2 = torch.empty((m, n), dtype=torch.float32, device=dev)
-                us = timeit(lambda: lib.ocm_op_linear(a.prec, p(xa), p(wa), p(bias), p(resid), p(o2), m, n, k, 1, s()), a.iters)
-            else:
-                us = timeit(fn, a.iters)
-            fl = 2.0 * m * n * k
-            print(f"{name:14s} variant {v}: {us:8.2f} us  {fl / us / 1e6:7.1f} TFLOP/s (algorithmic)  bit-identical to v0: {same}")
-    _lib.check(lib.ocm_debug_knob(0, 0))
-    if not only or "qkv" in only:  # the real qkv projection (head-major q / k / V^T scatter epilogues), knob 3
+        def fn():  # (the residual epilogue reads resid and writes out: no in-place accumulation drift)
+            return lib.ocm_op_linear(a.prec, p(xa), p(wa), p(bias), p(resid) if epi == 1 else None, p(out), m, n, k, epi, s())
+        assert fn() == 0, lib.ocm_last_error()
+        torch.cuda.synchronize()
+        us = timeit(fn, a.iters)
+        fl = 2.0 * m * n * k
+        print(f"{name:14s}: {us:8.2f} us  {fl / us / 1e6:7.1f} TFLOP/s (algorithmic)")
+    if not only or "qkv" in only:  # the real qkv projection (head-major q / k / V^T scatter epilogues)
         B, N, H = M // 197, 197, D // 64
         x = torch.randn((B * N, D), generator=g).to(dev)
         w = (torch.randn((3 * D, D), generator=g) * 0.02).to(dev)
@@ -98,24 +78,16 @@ def main():
         xa, wa = to_operand(x, a.prec), to_operand(w, a.prec)
         npad = lib.ocm_n_pad_prec(a.prec, N)
         edt = {0: torch.bfloat16, 1: torch.float32, 2: torch.int32}[a.prec]
-        ref = None
-        for v in (-1, 0, 1, 2, 3):
-            _lib.check(lib.ocm_debug_knob(3, v))
-            q = torch.zeros((B * H, npad, 64), dtype=edt, device=dev)
-            k = torch.zeros_like(q)
-            vt = torch.zeros((B * H, 64, npad), dtype=edt, device=dev)
+        q = torch.zeros((B * H, npad, 64), dtype=edt, device=dev)
+        k = torch.zeros_like(q)
+        vt = torch.zeros((B * H, 64, npad), dtype=edt, device=dev)
 
-            def fn():
-                return lib.ocm_op_qkv_proj(a.prec, p(xa), p(wa), p(bias), p(q), p(k), p(vt), None, B, N, H, s())
-            assert fn() == 0, lib.ocm_last_error()
-            torch.cuda.synchronize()
-            got = torch.cat([q.flatten().view(torch.int16), k.flatten().view(torch.int16), vt.flatten().view(torch.int16)])
-            if ref is None:
-                ref = got
-            us = timeit(fn, a.iters)
-            print(f"qkv (B={B})     knob3 {v:2d}: {us:8.2f} us  {2.0 * B * N * D * 3 * D / us / 1e6:7.1f} TFLOP/s (algorithmic)  "
-                  f"bit-identical to the register-staged kernel: {torch.equal(got, ref)}")
-        _lib.check(lib.ocm_debug_knob(3, 0))
+        def fn():
+            return lib.ocm_op_qkv_proj(a.prec, p(xa), p(wa), p(bias), p(q), p(k), p(vt), None, B, N, H, s())
+        assert fn() == 0, lib.ocm_last_error()
+        torch.cuda.synchronize()
+        us = timeit(fn, a.iters)
+        print(f"qkv (B={B})    : {us:8.2f} us  {2.0 * B * N * D * 3 * D / us / 1e6:7.1f} TFLOP/s (algorithmic)")
 
 
 if __name__ == "__main__":

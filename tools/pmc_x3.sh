@@ -1,4 +1,4 @@
-# SQ counters of the split-bf16 GEMM variants (two --pmc passes over tools/microbench_x3.py). Usage on the GPU box:
+# SQ counters of the split-bf16 GEMMs (three --pmc passes over tools/microbench_x3.py). Usage on the GPU box:
 #   bash tools/pmc_x3.sh "<microbench args>" <tag>
 R=$GRAFT_REPO_ROOT
 ARGS="$1"; TAG="$2"

@@ -333,17 +333,6 @@ def load():
         fn.argtypes = args
     if lib.ocm_abi_version() != OCM_ABI_VERSION:
         raise OcmError(f"libocm_vit ABI {lib.ocm_abi_version()} != binding ABI {OCM_ABI_VERSION}")
-    # development build only (include/ocm_vit_dev.h, loaded through OCM_VIT_LIB): the kernel-variant knobs; OCM_KNOBS="0=4,3=-1"
-    # presets them for A/B runs. The product library exports neither.
-    if hasattr(lib, "ocm_debug_knob"):
-        lib.ocm_debug_knob.restype, lib.ocm_debug_knob.argtypes = C.c_int, [_i32, _i32]
-        for item in filter(None, os.environ.get("OCM_KNOBS", "").split(",")):
-            which, value = item.split("=")
-            if lib.ocm_debug_knob(int(which), int(value)) != OCM_OK:
-                raise OcmError(f"OCM_KNOBS: bad entry {item!r}")
-    elif os.environ.get("OCM_KNOBS"):
-        raise OcmError("OCM_KNOBS is set but the loaded library is the product build (no ocm_debug_knob): "
-                       "`make -C csrc dev` and point OCM_VIT_LIB at exp_libs/libocm_vit_dev.so")
     _lib = lib
     return lib
 

@@ -1,9 +1,8 @@
 // attn_plan.h — which flash-attention kernel launch_attention (kernels_attn.hip) runs for a shape, on what grid and with how much
 // dynamic LDS, as a pure host function of integers. Plain C++17: no HIP, no element types. The launcher computes an AttnPlan and
 // executes it with one switch from plan to template instantiation; ocm_attention_plan (include/ocm_vit.h) reports the same answer
-// to tests and tools, so a threshold is written — and asserted — in exactly one place (tests/test_attn_plan_host.py).
-//
-// The development knobs 6 and 7 (dev_knobs.h) enter as plain parameters: product builds pass the constant 0.
+// to tests and tools through the very same call, so a threshold is written — and asserted — in exactly one place
+// (tests/test_attn_plan_host.py). A plan is a function of the shape and the workspace on offer alone.
 #pragma once
 #include <cstddef>
 
@@ -59,8 +58,8 @@ constexpr size_t attn_plan_workspace_bytes(int prec, int batch, int n_tokens, in
 }
 
 // prec: 0 bf16, 1 fp32, 2 split-bf16 pairs; head_dim 64 or 128 (the caller checks); workspace_bytes: what the caller offers for
-// key slices (0: none). knob6 / knob7: dev_knobs.h [6] and [7].
-inline AttnPlan attn_plan(int prec, int batch, int n_tokens, int heads, int head_dim, size_t workspace_bytes, int knob6, int knob7) {
+// key slices (0: none).
+inline AttnPlan attn_plan(int prec, int batch, int n_tokens, int heads, int head_dim, size_t workspace_bytes) {
     const int qtiles = attn_qtiles(n_tokens);
     const unsigned bh = (unsigned)(batch * heads), gx4 = (unsigned)((qtiles + 3) / 4);
     if (prec == 0) {
@@ -71,10 +70,9 @@ inline AttnPlan attn_plan(int prec, int batch, int n_tokens, int heads, int head
     if (prec == 1) return AttnPlan{ATTN_F32_STREAM, 4, 2, 1, gx4, bh, 1, ATTN_F32_LDS_PER_CHANNEL * head_dim, 0};
     // 128-wide heads (model.py:93-103): four wavefronts, two stages
     if (head_dim == 128) return AttnPlan{ATTN_X3_DMA, 4, 2, 1, gx4, bh, 1, 0, 0};
-    const bool wide = (n_tokens > ATTN_X3_WIDE_MIN_N && knob7 != 1) || knob7 == 2;
-    if (wide) {
+    if (n_tokens > ATTN_X3_WIDE_MIN_N) {
         const unsigned gx8 = (unsigned)((qtiles + 7) / 8);
-        if (workspace_bytes && knob7 == 0) {
+        if (workspace_bytes) {
             const long wgs = (long)gx8 * bh;
             const int want = wgs <= ATTN_KSPLIT_WGS_4 ? 4 : wgs <= ATTN_KSPLIT_WGS_3 ? 3 : wgs <= ATTN_KSPLIT_WGS_2 ? 2 : 1;
             const int per = (qtiles + want - 1) / want, nslice = (qtiles + per - 1) / per;  // every slice owns >= 1 tile
@@ -84,7 +82,7 @@ inline AttnPlan attn_plan(int prec, int batch, int n_tokens, int heads, int head
         return AttnPlan{ATTN_X3_DMA, 8, 3, 1, gx8, bh, 1, 0, 0};
     }
     // a handful of workgroups (one tile per call): the keys of a 32-query tile split over the four waves of a workgroup;
-    // otherwise the software-pipelined kernel (knob 6 = 4: everywhere)
-    if ((long)gx4 * bh < ATTN_X3_WS_MAX_WGS && knob6 != 4) return AttnPlan{ATTN_X3_WS, 4, 2, 1, (unsigned)qtiles, bh, 1, ATTN_WS_LDS, 0};
+    // otherwise the software-pipelined kernel
+    if ((long)gx4 * bh < ATTN_X3_WS_MAX_WGS) return AttnPlan{ATTN_X3_WS, 4, 2, 1, (unsigned)qtiles, bh, 1, ATTN_WS_LDS, 0};
     return AttnPlan{ATTN_X3_PP, 4, 3, 1, gx4, bh, 1, 0, 0};
 }

@@ -12,7 +12,6 @@
 
 #include "host_common.h"
 #include "launch.h"
-#include "dev_knobs.h"
 #include "attn_plan.h"
 #include "otsu.h"
 
@@ -74,14 +73,6 @@ extern "C" int ocm_prof_end(double *ms_per_class, int64_t *launches_per_class) {
     g_prof.used = 0;
     return rc;
 }
-
-#ifdef OCM_DEV  // development build only: include/ocm_vit_dev.h
-extern "C" int ocm_debug_knob(int32_t which, int32_t value) {
-    if (which < 0 || which >= 8) return fail(OCM_EINVAL, "knob %d out of range", which);
-    g_ocm_knobs[which] = value;
-    return OCM_OK;
-}
-#endif
 
 extern "C" int ocm_abi_version(void) { return OCM_ABI_VERSION; }
 extern "C" const char *ocm_last_error(void) { return g_err.c_str(); }
@@ -873,7 +864,7 @@ extern "C" int ocm_attention_plan(int32_t precision, int32_t batch, int32_t n_to
     if (rc) return rc;
     if (!plan) return fail(OCM_EINVAL, "null argument");
     if ((rc = attention_shape_ok(batch, n_tokens, heads, head_dim))) return rc;
-    const AttnPlan p = attn_plan(pc, batch, n_tokens, heads, head_dim, workspace_bytes, 0, 0);
+    const AttnPlan p = attn_plan(pc, batch, n_tokens, heads, head_dim, workspace_bytes);
     *plan = ocm_attention_plan_info{(int32_t)p.kernel, p.waves, p.stages, p.kslices, (int32_t)p.grid_x, (int32_t)p.grid_y,
                                     (int32_t)p.grid_z, p.lds_bytes, (uint64_t)p.workspace_need};
     return OCM_OK;

@@ -23,26 +23,6 @@
 #include <type_traits>
 #include "common.h"
 
-// Development instrumentation (make stamps -> exp_libs/stamps.so, tools/stamps.py): thread 0 of every workgroup
-// records the shader clock at the phase boundaries of gemm_kernel. Compiled out unless -DOCM_GEMM_STAMPS.
-#ifdef OCM_GEMM_STAMPS
-// per-wave timeline of ONE K step (the middle one) of the LDS-DMA loop: [workgroup][wave][point]
-__device__ unsigned long long g_wstamps[512 * 16 * 8];
-#define WSTAMP(k)                                                                                       \
-    do {                                                                                                \
-        if (t == nsteps / 2 && (threadIdx.x & 63) == 0 && blockIdx.x < 512)                              \
-            g_wstamps[(blockIdx.x * 16 + (threadIdx.x >> 6 & 15)) * 8 + (k)] = __builtin_readcyclecounter(); \
-    } while (0)
-__device__ unsigned long long g_stamps[8192 * 8];
-#define STAMP(i)                                                                                        \
-    do {                                                                                                \
-        if (threadIdx.x == 0 && blockIdx.x < 8192) g_stamps[blockIdx.x * 8 + (i)] = __builtin_readcyclecounter(); \
-    } while (0)
-#else
-#define STAMP(i) ((void)0)
-#define WSTAMP(k) ((void)0)
-#endif
-
 // MF16_: split-bf16 products on v_mfma_f32_16x16x32_bf16 (four 16 x 16 accumulators per 32 x 32 tile) instead of 32x32x16 — the
 // same LDS bytes and the same matrix cycles per product; the chip holds a higher clock on it (MI355X_MICROARCH.md, DVFS
 // give-back item 7). Pays where the matrix pipe is the busier resource: the 128 x 128 tiles with two workgroups per CU
@@ -75,11 +55,6 @@ template <int PBM, int PBN, int NT_>
 struct PassCfg {
     static constexpr int BM = PBM, BN = PBN, NT = NT_;
 };
-
-// 1: 8-wave register-staged split-bf16 main loops run their two half-workgroups in opposite phases (0: A/B builds)
-#ifndef OCM_PINGPONG
-#define OCM_PINGPONG 1
-#endif
 
 // operand element traits: an LDS row (one K step, 128 bytes) holds KROW elements; an epilogue lane writes EPW
 // consecutive elements of an activation row. MODE: 0 = bf16, 1 = fp32, 2 = split-bf16 pairs (common.h: sp32).
@@ -118,9 +93,6 @@ struct RowLoader {
     __device__ __forceinline__ Handle row(int m) const { return (const char *)A + (int64_t)m * lda * (int)sizeof(E); }
     // chunk c of K step t
     __device__ __forceinline__ Raw load(Handle h, int t, int c) const {
-#if defined(OCM_ABL) && (OCM_ABL == 8 || OCM_ABL == 10)  // ablation 8 (10: both operands): the A operand re-reads its first K step (cache hits)
-        t = 0;
-#endif
         return *(const Raw *)(h + t * 128 + c * 16);
     }
     __device__ __forceinline__ static Raw finish(const Raw &r, int) { return r; }
@@ -295,9 +267,6 @@ __device__ __forceinline__ void gemm_mainloop(const ALoad &al, const E *__restri
 #pragma unroll
         for (int i = 0; i < A_CH; ++i) sl.a[i] = al.load(a_h[i], t, cc);
 #pragma unroll
-#if defined(OCM_ABL) && (OCM_ABL == 9 || OCM_ABL == 10)  // ablation 9 (10: both operands): the W operand re-reads its first K step (cache hits)
-        for (int i = 0; i < B_CH; ++i) sl.b[i] = *(const Chunk *)(b_h[i]);
-#else
         for (int i = 0; i < B_CH; ++i) {
             if constexpr (aload_w_tail<ALoad>::v) {
                 sl.b[i] = Chunk{};
@@ -306,7 +275,6 @@ __device__ __forceinline__ void gemm_mainloop(const ALoad &al, const E *__restri
                 sl.b[i] = *(const Chunk *)(b_h[i] + t * 128);
             }
         }
-#endif
     };
     auto commit = [&](int buf, const Slot &sl) {
 #pragma unroll
@@ -337,21 +305,14 @@ __device__ __forceinline__ void gemm_mainloop(const ALoad &al, const E *__restri
         // in step t-2 (L2 latency under load is ~1 us, more than one step). The stream is unconditional (indices
         // past the end re-read the last tile into a dead slot) and the loop is fully unrolled with a constant
         // trip count, so hipcc counts its own `s_waitcnt vmcnt(N)` instead of draining to 0.
-#if defined(OCM_ABL) && OCM_ABL == 11  // ablation 11: no global loads after the prologue (slots keep their first tiles)
-        auto issue2 = [&](Slot &sl, int t) { if (t < 3) issue(sl, min(t, KSTEPS - 1)); };
-#else
         auto issue2 = [&](Slot &sl, int t) { issue(sl, min(t, KSTEPS - 1)); };
-#endif
         Slot s0, s1;
         issue2(s0, 0);
         issue2(s1, 1);
         commit(0, s0);
         issue2(s0, 2);
         lds_barrier();
-#ifdef OCM_GEMM_STAMPS
-        STAMP(6);  // first tile in LDS
-#endif
-        if constexpr (KSTEPS % 2 == 0 && Elem<E>::MODE == 2 && NT == 512 && OCM_PINGPONG) {
+        if constexpr (KSTEPS % 2 == 0 && Elem<E>::MODE == 2 && NT == 512) {
             // Eight waves = two per SIMD (waves w and w + 4 share SIMD w): run the two halves of the workgroup in
             // OPPOSITE phases instead of in lock step. Per K step two intervals, a barrier after each:
             //   interval 1: waves 0-3 multiply step t            | waves 4-7 commit their share of step t+1, issue t+3
@@ -576,50 +537,18 @@ __device__ __forceinline__ void gemm_mainloop_dma(const E *__restrict__ A, int64
 #pragma unroll
             for (int e = 0; e < 16; ++e) acc[i][j][e] = bv[j][SWAP ? e : (ACCL ? ((e >> 2) & 1) : 0)];
     int bc = 0, bi = D % NSTAGE;  // stage computed next / stage filled next
-#ifdef OCM_GEMM_STAMPS
-    unsigned long long stamp_wait = 0;
-#endif
     for (int t = 0; t < nsteps; ++t) {
         // own DMAs of step t have landed once at most the (younger) steps t+1 .. t+D-1 are pending
         const int younger = min(D - 1, nsteps - 1 - t);
-#ifdef OCM_GEMM_STAMPS
-        const unsigned long long tw0 = __builtin_readcyclecounter();
-#endif
-        WSTAMP(0);  // step entered
         wait_vm_steps<LPS, NSTAGE - 2>(younger);
-        WSTAMP(1);  // own DMAs landed
-#ifdef OCM_GEMM_STAMPS
-        const unsigned long long tw1 = __builtin_readcyclecounter();
-#endif
         raw_barrier();
-#ifdef OCM_GEMM_STAMPS
-        if (t == 0) STAMP(6);  // first tile landed
-        if (t > 0) {  // slot 7: cycles this wave spent waiting for its own DMAs (low 32 bits) and at the barrier (high 32 bits), steps 1..
-            const unsigned long long tw2 = __builtin_readcyclecounter();
-            stamp_wait += ((tw2 - tw1) << 32) | ((tw1 - tw0) & 0xFFFFFFFFull);
-        }
-#endif
-        WSTAMP(2);  // barrier passed
-#if !defined(OCM_ABL) || OCM_ABL != 2  // ablation 2: no DMA after the prologue
         if (t + D < nsteps) OCM_DMA_ISSUE(t + D, bi);
-#endif
         __builtin_amdgcn_sched_barrier(0);
-        WSTAMP(3);  // DMA issued
         compute(bc);
-#ifdef OCM_GEMM_STAMPS
-        if (t == nsteps / 2) {  // wait for the last MFMA's result, then stamp
-            __builtin_amdgcn_sched_barrier(0);
-            asm volatile("v_mov_b32 %0, %0\n\ts_nop 0" : "+v"(acc[TM - 1][TN - 1][15]));
-            WSTAMP(4);
-        }
-#endif
         bc = bc + 1 == NSTAGE ? 0 : bc + 1;
         bi = bi + 1 == NSTAGE ? 0 : bi + 1;
     }
     raw_barrier();  // every wave is done reading: the epilogue may reuse the LDS
-#ifdef OCM_GEMM_STAMPS
-    if (threadIdx.x == 0 && blockIdx.x < 8192) g_stamps[blockIdx.x * 8 + 7] = stamp_wait;
-#endif
 #undef OCM_DMA_ISSUE
 }
 
@@ -652,21 +581,17 @@ __device__ __forceinline__ auto epi_prefetch(const Epi &epi, int m0, int n0, int
 // LDS_AVAIL: bytes of LDS the kernel owns (the register-staged kernels: Cfg::LDS_BYTES; the LDS-DMA kernels: their ring)
 template <class Cfg, bool SWAP, class Epi, int LDS_AVAIL = Cfg::LDS_BYTES, class Pre = EpiNoPre, int ACCL = 0>
 __device__ __forceinline__ void run_epilogue(const f32x16 (&acc)[Cfg::TM][Cfg::TN], char *smem, const Epi &epi, int m0,
-                                             int n0, bool active = true, const Pre *pre = nullptr) {
+                                             int n0, const Pre *pre = nullptr) {
     f32x2 *rowtab = (f32x2 *)(smem + LDS_AVAIL), *coltab = rowtab + Cfg::BM;
     if constexpr (Epi::ROWTAB) {
         if (threadIdx.x < Cfg::BM) rowtab[threadIdx.x] = epi.row_final(pre->raw);
         if (threadIdx.x < Cfg::BN) coltab[threadIdx.x] = pre->cd;
     }
-    // `active` false (workgroup-uniform per wave): a wave that holds no accumulators (the loader waves of the
-    // wave-specialised kernel) only keeps the barrier count of the passes
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int wm = wave / Cfg::WAVES_N, wn = wave % Cfg::WAVES_N;
-    const int r = lane & 31, h = lane >> 5;
     if constexpr (Cfg::BM * Cfg::BN * 4 <= LDS_AVAIL) {
         constexpr int COLS = SWAP ? Cfg::BM : Cfg::BN;
         float *C = (float *)smem;
-        if (active)
 #pragma unroll
         for (int i = 0; i < Cfg::TM; ++i)
 #pragma unroll
@@ -679,10 +604,8 @@ __device__ __forceinline__ void run_epilogue(const f32x16 (&acc)[Cfg::TM][Cfg::T
                 for (int e = 0; e < (half ? 8 : 16); ++e)
                     C[(row0 + acc_rpos<ACCL>(e, lane)) * COLS + col0 + acc_cpos<ACCL>(e, lane)] = acc[i][j][e];
             }
-        STAMP(2);
         lds_barrier();
-        STAMP(3);
-        if (active) epi.template run<PassCfg<Cfg::BM, Cfg::BN, Cfg::NT>>((const float *)C, m0, n0, rowtab, coltab);
+        epi.template run<PassCfg<Cfg::BM, Cfg::BN, Cfg::NT>>((const float *)C, m0, n0, rowtab, coltab);
     } else if constexpr (!SWAP) {
         constexpr int PASS = Cfg::RB * Cfg::BN * 4;  // one band of RB rows
         static_assert(PASS <= LDS_AVAIL, "a row band must fit the operand LDS");
@@ -692,7 +615,6 @@ __device__ __forceinline__ void run_epilogue(const f32x16 (&acc)[Cfg::TM][Cfg::T
             if (NBUF == 1 && i) lds_barrier();  // the band's readers are done
             float *C = (float *)(smem + (i % NBUF) * PASS);
             const bool half = Cfg::HALF && i == Cfg::TM - 1;  // the bottom band of 16-row half tiles: RB / 2 rows
-            if (active)
 #pragma unroll
             for (int j = 0; j < Cfg::TN; ++j) {
                 const int col0 = (j * Cfg::WAVES_N + wn) * 32;
@@ -701,12 +623,10 @@ __device__ __forceinline__ void run_epilogue(const f32x16 (&acc)[Cfg::TM][Cfg::T
                     C[(wm * (half ? 16 : 32) + acc_rpos<ACCL>(e, lane)) * Cfg::BN + col0 + acc_cpos<ACCL>(e, lane)] = acc[i][j][e];
             }
             lds_barrier();  // also orders pass i-2's reads of this buffer before pass i's writes (see above)
-            if (active) {
-                if (half)
-                    epi.template run<PassCfg<Cfg::RB / 2, Cfg::BN, Cfg::NT>>((const float *)C, m0 + i * Cfg::RB, n0, rowtab + i * Cfg::RB, coltab);
-                else
-                    epi.template run<PassCfg<Cfg::RB, Cfg::BN, Cfg::NT>>((const float *)C, m0 + i * Cfg::RB, n0, rowtab + i * Cfg::RB, coltab);
-            }
+            if (half)
+                epi.template run<PassCfg<Cfg::RB / 2, Cfg::BN, Cfg::NT>>((const float *)C, m0 + i * Cfg::RB, n0, rowtab + i * Cfg::RB, coltab);
+            else
+                epi.template run<PassCfg<Cfg::RB, Cfg::BN, Cfg::NT>>((const float *)C, m0 + i * Cfg::RB, n0, rowtab + i * Cfg::RB, coltab);
         }
     } else {
         static_assert(!Cfg::HALF, "half tiles: normal orientation only");
@@ -717,7 +637,6 @@ __device__ __forceinline__ void run_epilogue(const f32x16 (&acc)[Cfg::TM][Cfg::T
         for (int j = 0; j < Cfg::TN; ++j) {
             if (NBUF == 1 && j) lds_barrier();
             float *C = (float *)(smem + (j % NBUF) * PASS);
-            if (active)
 #pragma unroll
             for (int i = 0; i < Cfg::TM; ++i) {
                 const int col0 = (i * Cfg::WAVES_M + wm) * 32;
@@ -726,7 +645,7 @@ __device__ __forceinline__ void run_epilogue(const f32x16 (&acc)[Cfg::TM][Cfg::T
                     C[(wn * 32 + acc_rpos<ACCL>(e, lane)) * Cfg::BM + col0 + acc_cpos<ACCL>(e, lane)] = acc[i][j][e];
             }
             lds_barrier();
-            if (active) epi.template run<PassCfg<Cfg::BM, Cfg::CB, Cfg::NT>>((const float *)C, m0, n0 + j * Cfg::CB, rowtab, coltab + j * Cfg::CB);
+            epi.template run<PassCfg<Cfg::BM, Cfg::CB, Cfg::NT>>((const float *)C, m0, n0 + j * Cfg::CB, rowtab, coltab + j * Cfg::CB);
         }
     }
 }
@@ -742,31 +661,8 @@ __global__ __launch_bounds__(Cfg::NT) void gemm_dma_kernel(const E *__restrict__
     const int m0 = tm * Cfg::BM, n0 = tn * Cfg::BN;
     f32x16 acc[Cfg::TM][Cfg::TN];
     const auto pre = epi_prefetch<Cfg>(epi, m0, n0, M, N);
-    STAMP(0);
-#if defined(OCM_ABL) && OCM_ABL == 4  // ablation 4: epilogue only
-#pragma unroll
-    for (int i = 0; i < Cfg::TM; ++i)
-#pragma unroll
-        for (int j = 0; j < Cfg::TN; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[i][j][e] = (float)(threadIdx.x + e);
-#else
     gemm_mainloop_dma<Cfg, E, SWAP, KSTEPS, NSTAGE, A_AUX>(A, lda, W, ldw, m0, n0, M, N, K, smem, acc, epi.bias);
-#endif
-    STAMP(1);
-#if defined(OCM_ABL) && OCM_ABL == 3  // ablation 3: no epilogue (accumulators kept live)
-#pragma unroll
-    for (int i = 0; i < Cfg::TM; ++i)
-#pragma unroll
-        for (int j = 0; j < Cfg::TN; ++j) asm volatile("" ::"v"(acc[i][j]));
-#else
-    run_epilogue<Cfg, SWAP, Epi, NSTAGE * (Cfg::BM + Cfg::BN) * 128, decltype(pre), accl_of<Cfg, E>()>(acc, smem, epi, m0, n0, true, &pre);
-#endif
-    STAMP(4);
-#ifdef OCM_GEMM_STAMPS
-    __builtin_amdgcn_s_waitcnt(0);
-    STAMP(5);
-#endif
+    run_epilogue<Cfg, SWAP, Epi, NSTAGE * (Cfg::BM + Cfg::BN) * 128, decltype(pre), accl_of<Cfg, E>()>(acc, smem, epi, m0, n0, &pre);
 }
 
 // Generic kernel: grid = tiles_m * tiles_n workgroups (linear, XCD-remapped so the
@@ -781,13 +677,6 @@ __global__ __launch_bounds__(Cfg::NT) void gemm_kernel(ALoad al, const E *__rest
     const int m0 = tm * Cfg::BM, n0 = tn * Cfg::BN;
     f32x16 acc[Cfg::TM][Cfg::TN];
     const auto pre = epi_prefetch<Cfg>(epi, m0, n0, M, N);
-    STAMP(0);
     gemm_mainloop<Cfg, E, SWAP, KSTEPS>(al, W, ldw, m0, n0, M, N, K, smem, acc, epi.bias);
-    STAMP(1);  // prologue + K loop done
-    run_epilogue<Cfg, SWAP, Epi, Cfg::LDS_BYTES, decltype(pre), accl_of<Cfg, E>()>(acc, smem, epi, m0, n0, true, &pre);  // STAMP 2: accumulators staged, 3: barrier passed
-    STAMP(4);  // epilogue body issued
-#ifdef OCM_GEMM_STAMPS
-    __builtin_amdgcn_s_waitcnt(0);
-    STAMP(5);  // stores acknowledged
-#endif
+    run_epilogue<Cfg, SWAP, Epi, Cfg::LDS_BYTES, decltype(pre), accl_of<Cfg, E>()>(acc, smem, epi, m0, n0, &pre);
 }

@@ -13,9 +13,6 @@
 #include "gemm_core.h"
 #include "launch.h"
 #include "gemm_plan.h"
-#include "dev_knobs.h"
-
-int ocm_wt_mask();  // kernels_gemm.hip
 
 // The tiles (gemm_plan.h: GEMM_TILES names each shape once; the plan functions there choose among them)
 template <GemmTile T>
@@ -26,7 +23,6 @@ typedef CfgOf<T128x128> Cfg128x128;
 typedef CfgOf<T128x128q> Cfg128x128q;
 // ... and on v_mfma_f32_16x16x32_bf16 for the split-bf16 LDS-DMA launches of that tile (gemm_core.h: GemmCfg::MF16)
 typedef CfgOf<T128x128q16> Cfg128x128q16;
-typedef CfgOf<T128x128m16> Cfg128x128m16;  // development A/B (four waves: the tile of forwards of 32 k rows and more)
 // 160 rows: two full 32-row tiles and a 16-row half tile per wave row (gemm_core.h: GemmCfg::HALF). At 12 608 rows (ViT-S/16, B = 64)
 // mlp.fc1 is 79 x 12 = 948 of these = 1.85 rounds of the 512 two-per-CU slots instead of 1 188 tiles of 128 x 128 = 2.32; mlp.fc2
 // with the statistics epilogue is 79 x 3 = 237 of them, one per CU on a three-stage ring, instead of 198 tiles of 128 x 192
@@ -34,12 +30,11 @@ typedef CfgOf<T160x128q16> Cfg160x128q16;
 typedef CfgOf<T256x256m16> Cfg256x256m16;  // ViT-B sizes
 typedef CfgOf<T64x128> Cfg64x128;
 // the same tile on eight wavefronts (32 x 32 each) for the one-tile-per-call forwards: with ONE workgroup per CU a lone wave per
-// SIMD waits out every LDS read before its MFMAs (850 cycles per K step for 384 of MFMA, tools/stamps_b1.py); two waves per SIMD
-// take turns
+// SIMD waits out every LDS read before its MFMAs (850 cycles per K step for 384 of MFMA, read from in-kernel cycle stamps: DESIGN
+// 3.11); two waves per SIMD take turns
 typedef CfgOf<T64x128w> Cfg64x128w;
 typedef CfgOf<T64x64> Cfg64x64;
 typedef CfgOf<T256x256> Cfg256x256;  // 8 waves, one workgroup per CU (gemm_plan.h: big_tiles_pay)
-typedef CfgOf<T256x128> Cfg256x128;
 // N = 384 outputs (attn.proj, mlp.fc2) at ~12 k rows: 198 tiles, one 8-wave workgroup per CU, wave tile 32 x 96. Per K step
 // 40 KiB of operands for 1152 cycles of MFMA per SIMD, against 56 KiB for the 64 x 384 full-row tile
 typedef CfgOf<T128x192> Cfg128x192;
@@ -372,12 +367,8 @@ static hipError_t launch_gemm_dma_ks(const E *a, int64_t lda, const E *w, int64_
     const int tiles = ((M + Cfg::BM - 1) / Cfg::BM) * ((N + Cfg::BN - 1) / Cfg::BN);
     auto kern = gemm_dma_kernel<Cfg, E, false, KSTEPS, NSTAGE, Epi>;
     static OptinMask optin;
-    int lds = LDS;
-#ifdef OCM_DEV  // knob 0 = 26: the two-stage 160-row mlp.fc2 asks for more than half a CU's LDS, so that workgroups cannot pair up
-    if (OCM_KNOB(0) == 26 && Cfg::HALF && NSTAGE == 2 && !Epi::ROWTAB) lds = 84 * 1024;
-#endif
-    if (hipError_t e = lds_optin((const void *)kern, lds, optin); e != hipSuccess) return e;
-    kern<<<dim3(tiles), dim3(Cfg::NT), lds, s>>>(a, lda, w, ldw, M, N, K, epi);
+    if (hipError_t e = lds_optin((const void *)kern, LDS, optin); e != hipSuccess) return e;
+    kern<<<dim3(tiles), dim3(Cfg::NT), LDS, s>>>(a, lda, w, ldw, M, N, K, epi);
     return hipGetLastError();
 }
 
@@ -401,13 +392,12 @@ struct epi_bn_mult<Epi, std::void_t<decltype(Epi::BN_MULT)>> {
 // nn.Linear on the tile, loop and depth gemm_plan_linear chooses. Each case names a kernel family that is instantiated for this
 // element type and epilogue: LDS-DMA tiles for split-bf16 operands only, the 160-row tile for the activation-output epilogues (two
 // stages) and the statistics epilogue (OCM_TALL_N384_STAGES), 128 x 96 where the epilogue serves that width; a plan outside them is
-// refused. The product switch, the guarded keys after it and the development switch must keep disjoint keys: a key moves from one
-// to another, it is never listed twice.
+// refused. The switch and the guarded keys after it keep disjoint keys.
 template <int MODE, class E, class Epi>
 static hipError_t launch_linear_epi(const E *a, const E *w, const Epi &epi, int M, int N, int K, hipStream_t s) {
     if (K % Elem<E>::KROW) return hipErrorInvalidValue;
     // (the statistics epilogue, to the plan, is the one that cannot take 128 x 96: the same condition as the guard of that case below)
-    const GemmPlan p = gemm_plan_linear(Elem<E>::MODE, MODE, M, N, K, Cfg128x96::BN % epi_bn_mult<Epi>::v != 0, false, OCM_KNOB(0));
+    const GemmPlan p = gemm_plan_linear(Elem<E>::MODE, MODE, M, N, K, Cfg128x96::BN % epi_bn_mult<Epi>::v != 0, false);
     const int ks = p.ksteps;
     if (p.loop == GEMM_LOOP_DMA) {
         const int key = gemm_dma_key(p.tile, p.stages);
@@ -418,7 +408,6 @@ static hipError_t launch_linear_epi(const E *a, const E *w, const Epi &epi, int 
                 case gemm_dma_key(T128x192, 3): return launch_gemm_dma<Cfg128x192, E, 3>(a, K, w, K, M, N, K, epi, s, ks);
                 case gemm_dma_key(T128x128q16, 2): return launch_gemm_dma<Cfg128x128q16, E, 2>(a, K, w, K, M, N, K, epi, s, ks);
                 case gemm_dma_key(T256x256m16, 2): return launch_gemm_dma<Cfg256x256m16, E, 2>(a, K, w, K, M, N, K, epi, s, ks);
-                case gemm_dma_key(T128x128, 2): return launch_gemm_dma<Cfg128x128, E, 2>(a, K, w, K, M, N, K, epi, s, ks);  // (knob 0 = 4 / 21; in every build)
                 default: break;
             }
             if constexpr (MODE == 2 || MODE == 3)
@@ -428,31 +417,8 @@ static hipError_t launch_linear_epi(const E *a, const E *w, const Epi &epi, int 
             if constexpr (MODE == 1 && epi_bn_mult<Epi>::v == 64) {  // (the statistics epilogue: mlp.fc2 on one 160-row workgroup per CU)
                 if (key == gemm_dma_key(T160x128q16, OCM_TALL_N384_STAGES))
                     return launch_gemm_dma<Cfg160x128q16, E, OCM_TALL_N384_STAGES>(a, K, w, K, M, N, K, epi, s, ks);
-#ifdef OCM_DEV  // (knob 0 = 27: the four-stage ring, which did not ship)
-                static_assert(OCM_TALL_N384_STAGES == 3, "the development key below is the depth that does not ship");
-                if (key == gemm_dma_key(T160x128q16, 4)) return launch_gemm_dma<Cfg160x128q16, E, 4>(a, K, w, K, M, N, K, epi, s, ks);
-#endif
             }
-#ifdef OCM_DEV  // the tiles only a forcing knob names
-            switch (key) {
-                case gemm_dma_key(T256x256, 2): return launch_gemm_dma<Cfg256x256, E, 2>(a, K, w, K, M, N, K, epi, s, ks);
-                case gemm_dma_key(T256x128, 2): return launch_gemm_dma<Cfg256x128, E, 2>(a, K, w, K, M, N, K, epi, s, ks);
-                case gemm_dma_key(T64x128, 2): return launch_gemm_dma<Cfg64x128, E, 2>(a, K, w, K, M, N, K, epi, s, ks);
-                case gemm_dma_key(T64x128, 3): return launch_gemm_dma<Cfg64x128, E, 3>(a, K, w, K, M, N, K, epi, s, ks);
-                case gemm_dma_key(T64x128, 4): return launch_gemm_dma<Cfg64x128, E, 4>(a, K, w, K, M, N, K, epi, s, ks);
-                case gemm_dma_key(T128x128q, 2): return launch_gemm_dma<Cfg128x128q, E, 2>(a, K, w, K, M, N, K, epi, s, ks);
-                case gemm_dma_key(T128x128m16, 2): return launch_gemm_dma<Cfg128x128m16, E, 2>(a, K, w, K, M, N, K, epi, s, ks);
-                case gemm_dma_key(T160x128q16, 2): return launch_gemm_dma<Cfg160x128q16, E, 2>(a, K, w, K, M, N, K, epi, s, ks);  // (knob 0 = 23: any epilogue; MODE 2 / 3 returned above)
-                default: break;
-            }
-#endif
         }
-#ifdef OCM_DEV
-        if constexpr (Elem<E>::MODE == 0) {  // development A/B: the LDS-DMA loop on single-bf16 operands (knob 0 = 4 / 7)
-            if (key == gemm_dma_key(T128x128, 2)) return launch_gemm_dma<Cfg128x128, E, 2>(a, K, w, K, M, N, K, epi, s, ks);
-            if (key == gemm_dma_key(T64x128, 2)) return launch_gemm_dma<Cfg64x128, E, 2>(a, K, w, K, M, N, K, epi, s, ks);
-        }
-#endif
         return hipErrorInvalidValue;
     }
     RowLoader<E> al{a, K};
@@ -474,12 +440,10 @@ template <int MODE, class E>
 hipError_t launch_linear_mode(const E *a, const E *w, const float *bias, const float *resid, void *out, int M,
                               int N, int K, hipStream_t s, const LnFold &ln = LnFold()) {
     EpiLinear<MODE, E> epi{bias, resid, out, M, N, N};
-    epi.wt = ocm_wt_mask() & 1;
+    epi.wt = OCM_WT_MASK & 1;
     if (ln.stats) {  // folded LayerNorm: the bias travels in ln.d, the accumulator starts at zero
         epi.ln = ln;
         epi.bias = nullptr;
-        if (OCM_KNOB(6) == 1) epi.ln.stats = nullptr;  // development timing probe (wrong results): fold arithmetic off
-        if (OCM_KNOB(6) == 2) epi.ln.nslot = 1;         // development timing probe (wrong results): one slot load per row
     }
     return launch_linear_epi<MODE, E>(a, w, epi, M, N, K, s);
 }
@@ -508,8 +472,7 @@ __global__ __launch_bounds__(Cfg::NT) void gemm_dma_splitk_kernel(const E *__res
     const auto pre = epi_prefetch<Cfg>(epi, m0, n0, M, N);
     gemm_mainloop_dma<Cfg, E, false, KSTEPS, NSTAGE>(A + (size_t)slice * Kslice, lda, W + (size_t)slice * Kslice, ldw, m0, n0, M,
                                                      N, Kslice, smem, acc, (const float *)nullptr);
-    run_epilogue<Cfg, false, EpiLinear<0, E>, NSTAGE * (Cfg::BM + Cfg::BN) * 128, decltype(pre), accl_of<Cfg, E>()>(acc, smem, epi, m0, n0, true,
-                                                                                                  &pre);
+    run_epilogue<Cfg, false, EpiLinear<0, E>, NSTAGE * (Cfg::BM + Cfg::BN) * 128, decltype(pre), accl_of<Cfg, E>()>(acc, smem, epi, m0, n0, &pre);
 }
 
 template <class E>
@@ -536,15 +499,15 @@ hipError_t launch_linear_e(const E *a, const E *w, const float *bias, const floa
         case 1:
             if constexpr (Elem<E>::MODE == 2)
                 if (so.part && resid && (!so.stats || so.xs) && K % Elem<E>::KROW == 0) {  // a split-K workspace is on offer
-                    const GemmPlan p = gemm_plan_linear(2, 1, M, N, K, so.stats != nullptr, true, OCM_KNOB(0));
+                    const GemmPlan p = gemm_plan_linear(2, 1, M, N, K, so.stats != nullptr, true);
                     if (p.splitk > 1) return launch_linear_splitk<E>(a, w, bias, resid, (float *)out, M, N, K, s, so);
                 }
             if (so.stats) {
                 if (N % 64) return hipErrorInvalidValue;
                 EpiResidStats<E> epi{bias, resid, (float *)out, so.xs, so.stats, M, N};
                 epi.shift = so.shift, epi.prev_stats = so.prev_stats, epi.prev_shift = so.prev_shift;
-                epi.wt = OCM_KNOB(5) ? OCM_KNOB(5) - 1 : 0;  // development knob 5: 1 + write-through mask. Plain stores ship: x written
-                // through costs the producers 3 us per launch and buys the consumers nothing (in-forward A/B)
+                epi.wt = 0;  // plain stores: x written through costs the producers 3 us per launch and buys the consumers nothing
+                // (in-forward A/B)
                 return launch_linear_epi<1, E>(a, w, epi, M, N, K, s);
             }
             return launch_linear_mode<1, E>(a, w, bias, resid, out, M, N, K, s);
@@ -676,7 +639,7 @@ struct EpiResidLN {
 };
 
 // One full-row GEMM + residual + LayerNorm launch, as gemm_plan_resid_ln says: one 8-wave workgroup per CU on the register-staged
-// loop, or the same tile on the two-stage LDS-DMA ring (the development A/B of knob 4 = 2; compiled into every build).
+// loop.
 template <class E, int D_>
 static hipError_t launch_resid_ln_d(const E *a, const E *w, const float *bias, const float *resid, float *x,
                                     const float *gamma, const float *beta, void *xn, int M, int K, float eps,
@@ -684,12 +647,11 @@ static hipError_t launch_resid_ln_d(const E *a, const E *w, const float *bias, c
     typedef GemmCfg<64, D_, 2, 4> Cfg8;  // 8 waves, wave tile 32 x D/4
     if (K % Elem<E>::KROW) return hipErrorInvalidValue;
     EpiResidLN<E, D_> epi{bias, resid, x, gamma, beta, xn, M, eps};
-    epi.wt = ((ocm_wt_mask() >> 2) & 1) | ((ocm_wt_mask() >> 4) & 2);  // mask 4: xn, mask 32: x
-    const GemmPlan p = gemm_plan_resid_ln(Elem<E>::MODE, D_, K, OCM_KNOB(4));
+    epi.wt = ((OCM_WT_MASK >> 2) & 1) | ((OCM_WT_MASK >> 4) & 2);  // mask 4: xn, mask 32: x
+    const GemmPlan p = gemm_plan_resid_ln(Elem<E>::MODE, D_, K);
     if (GEMM_TILES[p.tile].bm != Cfg8::BM || GEMM_TILES[p.tile].bn != D_) return hipErrorInvalidValue;
-    if (p.loop == GEMM_LOOP_REG) return launch_gemm<Cfg8, E, false>(RowLoader<E>{a, K}, w, K, M, D_, K, epi, s, p.ksteps);
-    if (p.stages == 2) return launch_gemm_dma<Cfg8, E, 2, KsResidLnDma>(a, K, w, K, M, D_, K, epi, s, p.ksteps);
-    return hipErrorInvalidValue;
+    if (p.loop != GEMM_LOOP_REG) return hipErrorInvalidValue;
+    return launch_gemm<Cfg8, E, false>(RowLoader<E>{a, K}, w, K, M, D_, K, epi, s, p.ksteps);
 }
 
 template <class E>
@@ -935,10 +897,10 @@ __global__ __launch_bounds__(Cfg::NT) void qkv_kernel(RowLoader<E> al, const E *
     const auto pre = epi_prefetch<Cfg>(eqk, m0, n0, M, N);
     if (n0 < 2 * D) {  // workgroup-uniform
         gemm_mainloop<Cfg, E, false, KSTEPS>(al, W, K, m0, n0, M, N, K, smem, acc, eqk.bias);
-        run_epilogue<Cfg, false, EpiQK<E>, Cfg::LDS_BYTES, decltype(pre), accl_of<Cfg, E>()>(acc, smem, eqk, m0, n0, true, &pre);
+        run_epilogue<Cfg, false, EpiQK<E>, Cfg::LDS_BYTES, decltype(pre), accl_of<Cfg, E>()>(acc, smem, eqk, m0, n0, &pre);
     } else {
         gemm_mainloop<Cfg, E, true, KSTEPS>(al, W, K, m0, n0, M, N, K, smem, acc, ev.bias);
-        run_epilogue<Cfg, true, EpiVt<E>, Cfg::LDS_BYTES, decltype(pre), accl_of<Cfg, E>()>(acc, smem, ev, m0, n0, true, &pre);
+        run_epilogue<Cfg, true, EpiVt<E>, Cfg::LDS_BYTES, decltype(pre), accl_of<Cfg, E>()>(acc, smem, ev, m0, n0, &pre);
     }
 }
 
@@ -957,10 +919,10 @@ __global__ __launch_bounds__(Cfg::NT) void qkv_dma_kernel(const E *__restrict__ 
     constexpr int RING = NSTAGE * (Cfg::BM + Cfg::BN) * 128;
     if (n0 < 2 * D) {  // workgroup-uniform
         gemm_mainloop_dma<Cfg, E, false, KSTEPS, NSTAGE>(A, K, W, K, m0, n0, M, N, K, smem, acc, eqk.bias);
-        run_epilogue<Cfg, false, EpiQK<E>, RING, decltype(pre), accl_of<Cfg, E>()>(acc, smem, eqk, m0, n0, true, &pre);
+        run_epilogue<Cfg, false, EpiQK<E>, RING, decltype(pre), accl_of<Cfg, E>()>(acc, smem, eqk, m0, n0, &pre);
     } else {
         gemm_mainloop_dma<Cfg, E, true, KSTEPS, NSTAGE>(A, K, W, K, m0, n0, M, N, K, smem, acc, ev.bias);
-        run_epilogue<Cfg, true, EpiVt<E>, RING, decltype(pre), accl_of<Cfg, E>()>(acc, smem, ev, m0, n0, true, &pre);
+        run_epilogue<Cfg, true, EpiVt<E>, RING, decltype(pre), accl_of<Cfg, E>()>(acc, smem, ev, m0, n0, &pre);
     }
 }
 
@@ -1015,15 +977,13 @@ hipError_t launch_qkv_e(const E *a, const E *w, const float *bias, E *q, E *k, E
     if (D % 64) return hipErrorInvalidValue;  // the kernels' column tiles (BN >= 64) must cover q | k | v exactly
     RowLoader<E> al{a, D};
     EpiQK<E> eqk{bias, q, k, qkv_f32, M, n_tokens, n_pad, heads, D, batch, head_dim};
-    eqk.wt = (ocm_wt_mask() >> 1) & 1;
+    eqk.wt = (OCM_WT_MASK >> 1) & 1;
     EpiVt<E> ev{bias, vt, qkv_f32, M, n_tokens, n_pad, heads, D, batch, head_dim, want_v};
     if (ln.stats) {  // folded norm1: the bias travels in ln.d, the accumulators start at zero
         eqk.ln = ev.ln = ln;
         eqk.bias = ev.bias = nullptr;
-        if (OCM_KNOB(6) == 1) eqk.ln.stats = ev.ln.stats = nullptr;  // development timing probe (wrong results)
-        if (OCM_KNOB(6) == 2) eqk.ln.nslot = ev.ln.nslot = 1;
     }
-    const GemmPlan p = gemm_plan_qkv(Elem<E>::MODE, M, D, OCM_KNOB(3));
+    const GemmPlan p = gemm_plan_qkv(Elem<E>::MODE, M, D);
     const int ks = p.ksteps;
     if (p.loop == GEMM_LOOP_DMA) {
         if constexpr (Elem<E>::MODE == 2) {
@@ -1031,12 +991,6 @@ hipError_t launch_qkv_e(const E *a, const E *w, const float *bias, E *q, E *k, E
                 case gemm_dma_key(T64x128w, OCM_SMALLM_STAGES): return launch_qkv_dma<Cfg64x128w, E, OCM_SMALLM_STAGES>(a, w, M, D, eqk, ev, s, ks);
                 case gemm_dma_key(T256x256m16, 2): return launch_qkv_dma<Cfg256x256m16, E, 2>(a, w, M, D, eqk, ev, s, ks);
                 case gemm_dma_key(T128x128q16, 2): return launch_qkv_dma<Cfg128x128q16, E, 2>(a, w, M, D, eqk, ev, s, ks);
-#ifdef OCM_DEV  // the tiles only a forcing knob names
-                case gemm_dma_key(T128x128, 2): return launch_qkv_dma<Cfg128x128, E, 2>(a, w, M, D, eqk, ev, s, ks);
-                case gemm_dma_key(T128x128q, 2): return launch_qkv_dma<Cfg128x128q, E, 2>(a, w, M, D, eqk, ev, s, ks);
-                case gemm_dma_key(T64x128, 2): return launch_qkv_dma<Cfg64x128, E, 2>(a, w, M, D, eqk, ev, s, ks);
-                case gemm_dma_key(T256x256, 2): return launch_qkv_dma<Cfg256x256, E, 2>(a, w, M, D, eqk, ev, s, ks);
-#endif
                 default: break;
             }
         }

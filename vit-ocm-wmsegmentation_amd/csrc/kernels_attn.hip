@@ -29,8 +29,6 @@
 #include "launch.h"
 
 #define LOG2E 1.4426950408889634f
-int ocm_wt_mask();  // kernels_gemm.hip
-#include "dev_knobs.h"
 #include "attn_plan.h"
 #define OCM_VMCNT_ATTN(n) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(n) : "memory")
 
@@ -633,31 +631,6 @@ __global__ __launch_bounds__(256) void attn_probs_f32_kernel(const float *__rest
 }
 
 // ------------------------------------------------------------------------------------------
-#ifdef OCM_GEMM_STAMPS
-// development only (make stamps, tools/attn_stamps.py): per-wave timeline of attn_fwd_x3_dma_kernel,
-// [workgroup (blockIdx.y * gridDim.x + blockIdx.x) < 1024][wave < 8][point < 16]
-__device__ unsigned long long g_astamps[1024 * 8 * 16];
-extern "C" int ocm_debug_stamps_attn(unsigned long long *host, int n) {
-    return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(g_astamps), (size_t)n * 8);
-}
-#define ASTAMP(k)                                                                                                    \
-    do {                                                                                                             \
-        const unsigned wg_ = blockIdx.y * gridDim.x + blockIdx.x;                                                    \
-        if ((threadIdx.x & 63) == 0 && wg_ < 1024 && (k) < 16)                                                       \
-            g_astamps[(wg_ * 8 + (threadIdx.x >> 6 & 7)) * 16 + (k)] = __builtin_readcyclecounter();                 \
-    } while (0)
-// the constant 100 MHz counter (the same on every XCD), for the entry spread and the span of the grid
-#define ASTAMP_RT(k)                                                                                                 \
-    do {                                                                                                             \
-        const unsigned wg_ = blockIdx.y * gridDim.x + blockIdx.x;                                                    \
-        if ((threadIdx.x & 63) == 0 && wg_ < 1024)                                                                   \
-            g_astamps[(wg_ * 8 + (threadIdx.x >> 6 & 7)) * 16 + (k)] = wall_clock64();                               \
-    } while (0)
-#else
-#define ASTAMP(k) ((void)0)
-#define ASTAMP_RT(k) ((void)0)
-#endif
-
 // OCM_PREC_BF16X3: the flash kernel on split-bf16 pairs (common.h: sp32). q / k rows are 256 bytes
 // [hi d 0..31 | lo d 0..31 | hi d 32..63 | lo d 32..63]; V^T rows are key-contiguous in the same 128-byte groups of
 // 32 keys. Every product runs as three bf16 MFMAs (hi*hi + hi*lo + lo*hi), P is split in registers. LDS tiles carry the
@@ -804,8 +777,6 @@ __global__ __launch_bounds__(NW * 64, WPS) void attn_fwd_x3_dma_kernel(const cha
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = lane & 31, h = lane >> 5;
-    ASTAMP(0);  // entered
-    ASTAMP_RT(12);
     int qblk, bh;
     xcd_remap2(qblk, bh);
     const int q0 = (qblk * NW + wave) * 32;
@@ -847,7 +818,6 @@ __global__ __launch_bounds__(NW * 64, WPS) void attn_fwd_x3_dma_kernel(const cha
     // see that the Q registers are complete, or it re-waits for them inside the loop with a count that also covers the
     // tile in flight). 0x0F70 = vmcnt(0), expcnt / lgkmcnt untouched.
     __builtin_amdgcn_s_waitcnt(0x0F70);
-    ASTAMP(1);  // Q and the first two tiles landed
 
     f32x16 O[ND];
 #pragma unroll
@@ -871,20 +841,13 @@ __global__ __launch_bounds__(NW * 64, WPS) void attn_fwd_x3_dma_kernel(const cha
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
-        ASTAMP(2 + kt);  // barrier of tile kt passed
-#if !defined(OCM_ABL) || OCM_ABL != 5  // ablation 5: no staging after the prologue
         if (kt + NSTAGE - 1 < nt) OCM_ATTN_DMA(tb + kt + NSTAGE - 1, si);  // into the stage of tile kt-1: everybody is past it
-#endif
         char *Kt = smem + sc * STAGE, *Vtile = Kt + KB;
         if (WANT_O && last_of_seq && first_pad < 32) {  // zero the V^T columns of the padding keys (wave-uniform)
             if (tid < 256) x3_zero_pad_keys<HD, 64>(Vtile, tid >> 2, tid & 3, first_pad);
             lds_barrier();
         }
-#if defined(OCM_ABL) && OCM_ABL == 6  // ablation 6: staging only, no arithmetic
-        if (false) {
-#else
         if (active) {
-#endif
             // own copy of the score step (see the steps above)
             f32x16 S;
 #pragma unroll
@@ -919,7 +882,6 @@ __global__ __launch_bounds__(NW * 64, WPS) void attn_fwd_x3_dma_kernel(const cha
         si = si == NSTAGE - 1 ? 0 : si + 1;
     }
 #undef OCM_ATTN_DMA
-    ASTAMP(14);  // key loop done
 
     if (!active) return;
     const float lt = l + __shfl_xor(l, 32, 64);
@@ -969,8 +931,6 @@ __global__ __launch_bounds__(NW * 64, WPS) void attn_fwd_x3_dma_kernel(const cha
                 }
         }
     }
-    ASTAMP(15);  // context stores issued
-    ASTAMP_RT(13);
 }
 
 
@@ -1704,7 +1664,7 @@ hipError_t launch_attention(int prec, const void *q, const void *k, const void *
                             size_t ksplit_bytes) {
     if (head_dim != 64 && head_dim != 128) return hipErrorInvalidValue;
     if (prec == 2 && n_pad % 32) return hipErrorInvalidValue;
-    const AttnPlan p = attn_plan(prec, batch, n_tokens, heads, head_dim, ksplit_ws ? ksplit_bytes : 0, OCM_KNOB(6), OCM_KNOB(7));
+    const AttnPlan p = attn_plan(prec, batch, n_tokens, heads, head_dim, ksplit_ws ? ksplit_bytes : 0);
     const dim3 grid(p.grid_x, p.grid_y, p.grid_z), block(p.waves * 64);
     const float scale2 = scale * LOG2E;
     const char *Q = (const char *)q, *K = (const char *)k, *V = (const char *)vt;  // split pairs
@@ -1751,7 +1711,7 @@ hipError_t launch_attention(int prec, const void *q, const void *k, const void *
                 kern<<<grid, block, 0, s>>>(Q, K, V, (char *)ctx, lse2, n_tokens, n_pad, heads, scale2, 0, nullptr);
             } else {  // eight wavefronts, three stages
                 auto kern = ctx ? attn_fwd_x3_dma_kernel<true, 8, 2> : attn_fwd_x3_dma_kernel<false, 8, 2>;
-                kern<<<grid, block, 0, s>>>(Q, K, V, (char *)ctx, lse2, n_tokens, n_pad, heads, scale2, (ocm_wt_mask() >> 4) & 1,
+                kern<<<grid, block, 0, s>>>(Q, K, V, (char *)ctx, lse2, n_tokens, n_pad, heads, scale2, (OCM_WT_MASK >> 4) & 1,
                                             nullptr);
             }
             break;
@@ -1794,8 +1754,7 @@ hipError_t launch_attention_probs(int prec, const void *q, const void *k, const 
     const dim3 grid((qtiles + 3) / 4, batch * heads);
     // split-bf16 kernels: key chunks in grid.z until there are ~512 workgroups (a one-tile call is 12 .. 114 otherwise)
     const int wgs = (int)(grid.x * grid.y), ktiles = qtiles;
-    int nz = wgs >= 256 ? 1 : min(ktiles, min(16, (512 + wgs - 1) / wgs));
-    if (OCM_KNOB(2) > 0) nz = min(ktiles, OCM_KNOB(2));  // development A/B
+    const int nz = wgs >= 256 ? 1 : min(ktiles, min(16, (512 + wgs - 1) / wgs));
     const dim3 gridz(grid.x, grid.y, nz);
     if (n_rows <= 0) rows = nullptr;
     bool folded = false;

@@ -1,9 +1,7 @@
 // kernels_gemm.hip — precision dispatch of the GEMM-shaped stages (launch.h) onto the per-element-type launchers of
-// gemm_kernels.h, whose instantiations are compiled in kernels_gemm_inst.hip. Holds the process-wide bits: the
-// write-through store mask and, in development builds only, the kernel-variant knobs.
+// gemm_kernels.h, whose instantiations are compiled in kernels_gemm_inst.hip, and ocm_gemm_plan.
 #include "launch.h"
 #include "host_common.h"
-#include "dev_knobs.h"
 
 // entry templates of gemm_kernels.h (defined and explicitly instantiated in kernels_gemm_inst.hip)
 template <class E>
@@ -21,17 +19,6 @@ hipError_t launch_qkv_e(const E *a, const E *w, const float *bias, E *q, E *k, E
 template <class E>
 hipError_t launch_patch_e(const PatchArgs &pa, const E *w, const float *bias, const float *pos, float *x, int dim,
                           hipStream_t s, const StatsOut &so);
-
-#ifdef OCM_DEV  // development build only (dev_knobs.h)
-int g_ocm_knobs[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#endif
-// Write-through (sc1) stores of streaming activation outputs, as a bit mask: 1 = nn.Linear activation outputs (fc1's
-// hidden tensor), 2 = q / k of the qkv projection, 4 = xn of the fused LayerNorm, 16 = attention context, 32 = x of the fused GEMM + LayerNorm; non-temporal loads of
-// the A rows of the full-row tiles (flat) and the nt policy on fc1's A-operand DMA (53.5 -> 63.4 us: the 12-fold reuse
-// of an A panel suffers) were tried too. Shipped: 1 | 2 | 32
-// (fc1 57.0 -> 54.2 us and +2.2 % end to end in alternating runs; qkv -0.7 us; x +0.6 % end to end; xn flat; the 8-byte
-// context stores get slower, 32 -> 39 us). Development knob 1: 0 = shipped mask, -1 = none, any other value = that mask.
-int ocm_wt_mask() { return OCM_KNOB(1) == 0 ? 35 : OCM_KNOB(1) < 0 ? 0 : OCM_KNOB(1); }
 
 hipError_t launch_linear_ld(int prec, const void *a, int64_t lda, const void *w, const float *bias, const float *resid,
                             void *out, int64_t ldo, int M, int N, int K, int epilogue, hipStream_t s) {
@@ -83,7 +70,8 @@ hipError_t launch_patch_embed(int prec, const PatchArgs &pa, const void *w, cons
     return launch_patch_e<bf16>(pa, (const bf16 *)w, bias, pos, x, dim, s, so);
 }
 
-// ocm_gemm_plan (include/ocm_vit.h): the plan functions of gemm_plan.h behind the operators' own argument checks, knobs at 0
+// ocm_gemm_plan (include/ocm_vit.h): the plan functions of gemm_plan.h behind the operators' own argument checks: the very calls
+// the launchers make
 extern "C" int ocm_gemm_plan(int32_t family, int32_t precision, int32_t epilogue, int32_t M, int32_t N, int32_t K,
                              uint32_t flags, ocm_gemm_plan_info *plan) {
     if (!plan) return ocm_fail(OCM_EINVAL, "null argument");
@@ -99,11 +87,11 @@ extern "C" int ocm_gemm_plan(int32_t family, int32_t precision, int32_t epilogue
             if ((flags & OCM_PLAN_STATS_EPILOGUE) && epilogue != OCM_EPI_BIAS_RESID_F32)
                 return ocm_fail(OCM_EINVAL, "the statistics epilogue is the residual one (epilogue %d)", epilogue);
             p = gemm_plan_linear(precision, epilogue, M, N, K, (flags & OCM_PLAN_STATS_EPILOGUE) != 0,
-                                 (flags & OCM_PLAN_SPLITK_OFFERED) != 0, 0);
+                                 (flags & OCM_PLAN_SPLITK_OFFERED) != 0);
             break;
         case OCM_GEMM_QKV:
             if (K % 64 || N != 3 * K) return ocm_fail(OCM_EINVAL, "qkv projection: N=%d K=%d (N = 3 K, K %% 64)", N, K);
-            p = gemm_plan_qkv(precision, M, K, 0);
+            p = gemm_plan_qkv(precision, M, K);
             break;
         case OCM_GEMM_LINEAR_LD:
             if (precision == OCM_PREC_BF16X3) return ocm_fail(OCM_EINVAL, "the strided launcher serves bf16 and fp32");
@@ -117,7 +105,7 @@ extern "C" int ocm_gemm_plan(int32_t family, int32_t precision, int32_t epilogue
         case OCM_GEMM_RESID_LN:
             if (!linear_resid_ln_supported(N)) return ocm_fail(OCM_EINVAL, "row width %d not in {128, 256, 384}", N);
             if (K % 64) return ocm_fail(OCM_EINVAL, "bad shape K=%d (K%%64)", K);
-            p = gemm_plan_resid_ln(precision, N, K, 0);
+            p = gemm_plan_resid_ln(precision, N, K);
             break;
         default: return ocm_fail(OCM_EINVAL, "bad family %d", family);
     }

@@ -20,6 +20,14 @@ static inline hipError_t lds_optin(const void *kern, int bytes, OptinMask &done)
     return e;
 }
 
+// Write-through (sc1) stores of streaming activation outputs, as a bit mask: 1 = nn.Linear activation outputs (fc1's
+// hidden tensor), 2 = q / k of the qkv projection, 4 = xn of the fused LayerNorm, 16 = attention context, 32 = x of the fused
+// GEMM + LayerNorm; non-temporal loads of the A rows of the full-row tiles (flat) and the nt policy on fc1's A-operand DMA
+// (53.5 -> 63.4 us: the 12-fold reuse of an A panel suffers) were tried too. Shipped: 1 | 2 | 32
+// (fc1 57.0 -> 54.2 us and +2.2 % end to end in alternating runs; qkv -0.7 us; x +0.6 % end to end; xn flat; the 8-byte
+// context stores get slower, 32 -> 39 us). The launchers feed the bits to their epilogues' run-time `wt` fields.
+constexpr int OCM_WT_MASK = 35;
+
 // ---- kernels_misc.hip
 // out_kind: 0 fp32, 1 bf16, 2 split-bf16 pairs
 hipError_t launch_layernorm(const float *x, const float *gamma, const float *beta, void *y, int out_kind,

@@ -1,5 +1,5 @@
 /*
- * ocm_swin.h — C ABI of the Swin-T forward (BASELINE.json config 5), part of libocm_vit.so.
+ * ocm_swin.h — C ABI of the Swin forward (BASELINE.json config 5), part of libocm_vit.so.
  *
  * Replaces, for inference, what Allen_data_Backbone/train.py:70-85 of linum-uqam/ViT-OCM-WMSegmentation
  * builds: transformers' SwinForImageClassification(SwinConfig(num_labels=5)) — patch embedding, four stages
@@ -26,7 +26,7 @@ typedef struct ocm_swin_config {
     int32_t num_stages;   /* 1..4                                                                     */
     int32_t depths[4];    /* (2, 2, 6, 2)                                                             */
     int32_t num_heads[4]; /* (3, 6, 12, 24): channels / heads must be 32                              */
-    int32_t window_size;  /* 7                                                                        */
+    int32_t window_size;  /* 7; 2 .. 12 in inference (12: the window12-384 checkpoints), 2 .. 7 in training */
     int32_t num_labels;   /* classifier outputs (5 in the reference), positive unless a backbone      */
     float mlp_ratio;      /* 4.0                                                                      */
     float ln_eps;         /* 1e-5                                                                     */
@@ -129,7 +129,7 @@ int ocm_op_swin_mlp(int32_t precision, float *x, const float *gamma, const float
  * as split pairs (ocm_op_cast_split); rel_table: (2*ws-1)^2 x heads fp32 device table; scratch: heads * 4096 floats of device
  * memory, plus batch * height * width * C floats with 4 or 6 heads. Built for OCM_PREC_BF16X3 and 3 heads (C = 96, stage 0 of
  * Swin-T: one kernel), 4 heads (C = 128) or 6 heads (C = 192, stage 1 of Swin-T): one kernel up to the context + the o_proj GEMM;
- * anything else returns OCM_EINVAL. */
+ * anything else — windows above 7 included — returns OCM_EINVAL. */
 int ocm_op_swin_attn_block(int32_t precision, float *x, const float *gamma, const float *beta, const void *wqkv,
                            const float *bqkv, const void *wo, const float *bo, const float *rel_table, float *scratch,
                            int32_t batch, int32_t height, int32_t width, int32_t window, int32_t shift, int32_t heads, float eps,
@@ -138,10 +138,22 @@ int ocm_op_swin_attn_block(int32_t precision, float *x, const float *gamma, cons
 /* Stand-alone (shifted-)window attention of one SwinLayer (modeling_swin.py:529-563 without the projections):
  * qkv (B*H*W, ld) holds q | k | v (heads*32 channels each) per token in E = bf16 / fp32 / split-bf16 pairs (`precision`; pairs: ld and ldc multiples of 32);
  * ctx (B*H*W, ldc) receives softmax(q k^T / sqrt(32) + bias + shift mask) v at the token's own row.
- * rel_table: (2*ws-1)^2 x heads fp32 device table; scratch: heads*(4096 + ws^4) floats of device memory. */
+ * rel_table: (2*ws-1)^2 x heads fp32 device table; scratch: ocm_swin_window_scratch_floats(window, heads) floats of device
+ * memory. Windows of 2 to 7 run one wavefront per (window, head) (two 32-query tiles, two 32-key halves); windows of 8 to 12
+ * (64 .. 144 positions) one workgroup of ceil(ws^2 / 32) wavefronts per (window, head): K and V of the window staged in LDS once,
+ * each wavefront 32 queries against every 32-key sub-tile, scores in registers, exact two-pass softmax, the head's bias table
+ * in LDS; bf16 and pairs on the bf16 MFMA, fp32 on the exact-fp32 MFMA. Above 7, ld and ldc are whole 16-byte pieces (8 bf16 /
+ * 4 fp32 elements / groups of 32 pairs) with ld >= 3 * 32 * heads and ldc >= 32 * heads; anything else returns OCM_EINVAL. */
 int ocm_op_swin_window_attention(int32_t precision, const void *qkv, int32_t ld, void *ctx, int32_t ldc,
                                  const float *rel_table, float *scratch, int32_t batch, int32_t height, int32_t width,
                                  int32_t window, int32_t shift, int32_t heads, void *stream);
+
+/* Scratch floats of ocm_op_swin_window_attention / ocm_op_swin_window_probs (a host function; 0 for a window outside [2, 12] or
+ * heads <= 0). window <= 7: heads * (4096 + ws^4) — the bias permuted into the kernels' register order, heads * 4096 floats,
+ * then the dense [head][ws^2][ws^2] table. window 8 .. 12: heads * 544 — [head][bin] = rel_table[bin][head] * log2(e) for the
+ * (2*ws-1)^2 <= 529 bins, bin = (dy + ws - 1) * (2*ws - 1) + (dx + ws - 1) with (dy, dx) = query - key position, zeros behind.
+ * The operators fill the scratch themselves on every call. */
+size_t ocm_swin_window_scratch_floats(int32_t window, int32_t heads);
 
 /* The probabilities of those windows as an output (transformers' per-layer `attentions`): the arguments and argument domain of
  * ocm_op_swin_window_attention (qkv rows with ld >= 3 * 32 * heads in whole 16-byte pieces, rel_table, the same scratch, all
@@ -149,8 +161,9 @@ int ocm_op_swin_window_attention(int32_t precision, const void *qkv, int32_t ld,
  * mask), windows of the grid rolled by -shift in window_partition order, tokens row-major inside a window. Scores are computed
  * from the element format as the attention kernel of that precision computes them (bf16 and pairs on MFMA, three instructions
  * per product for pairs; fp32 by FMAs), the softmax is fp32; the -100 mask is additive as in transformers (masked entries are
- * ~4e-44 or 0). One workgroup per (window, head) stages its block in LDS and writes it linearly; no atomics and a fixed
- * summation order: reruns give the same bits. */
+ * ~4e-44 or 0). One workgroup per (window, head) stages its block in LDS and writes it linearly (windows of 8 to 12: each of
+ * its wavefronts the 32 x ws^2 rows of its query tile, with the score path of the wide attention kernel); no atomics and a
+ * fixed summation order: reruns give the same bits. */
 int ocm_op_swin_window_probs(int32_t precision, const void *qkv, int32_t ld, float *probs, const float *rel_table,
                              float *scratch, int32_t batch, int32_t height, int32_t width, int32_t window, int32_t shift,
                              int32_t heads, void *stream);

@@ -11,6 +11,8 @@
 //                          of the window staged in LDS, both contractions on MFMA   (SwinLayer.forward :529-574)
 //   swin_wattn_f32_kernel  the same in plain fp32 FMAs (OCM_PREC_FP32)
 //   swin_wprobs_kernel     the softmax of those windows as an output (transformers' `attentions`)
+//   swin_wide_kernel       both for windows of 8 to 12 (64 .. 144 positions): one workgroup of ceil(ws^2 / 32) wavefronts per
+//                          (window, head), K and V staged once, the head's bias table in LDS; all three precisions
 //   swin_tokens_to_nchw_kernel  (B, L, C) -> (B, C, H, W) through an LDS tile (reshaped_hidden_states)
 //   swin_pool_head_kernel  final LayerNorm + mean over tokens + classifier       (SwinModel :887-892, :1052)
 #include "launch.h"
@@ -320,6 +322,7 @@ hipError_t launch_swin_crop_add(float *x, const float *yp, int batch, int H, int
 //   i >= ws*ws 0.
 // `dense` (optional) receives the plain [head][ws*ws][ws*ws] table (natural-log domain) for the fp32 kernel.
 // ------------------------------------------------------------------------------------------
+static hipError_t launch_swin_bias_wide(const float *table, float *out, int heads, int ws, hipStream_t s);
 __global__ __launch_bounds__(256) void swin_bias_perm_kernel(const float *__restrict__ table, float *__restrict__ perm,
                                                              float *__restrict__ dense, int heads, int ws) {
     const int A = ws * ws;
@@ -345,7 +348,9 @@ __global__ __launch_bounds__(256) void swin_bias_perm_kernel(const float *__rest
     }
 }
 
+// ws > 7: the wide layout, perm = heads x SWIN_WIDE_BINS (swin_bias_wide_kernel below), `dense` is not written
 hipError_t launch_swin_bias_perm(const float *table, float *perm, float *dense, int heads, int ws, hipStream_t s) {
+    if (ws > 7) return launch_swin_bias_wide(table, perm, heads, ws, s);
     swin_bias_perm_kernel<<<dim3(64), dim3(256), 0, s>>>(table, perm, dense, heads, ws);
     return hipGetLastError();
 }
@@ -818,9 +823,14 @@ __global__ __launch_bounds__(256) void swin_wattn_f32_kernel(const float *__rest
     for (int d = 0; d < 32; d += 4) *(f32x4 *)(dst + d) = f32x4{o[d] * inv, o[d + 1] * inv, o[d + 2] * inv, o[d + 3] * inv};
 }
 
+static hipError_t launch_swin_wide(int prec, const void *qkv, int ld, void *ctx, int ldc, float *probs, const float *bias_tab,
+                                   int batch, int H, int W, int ws, int shift, int heads, hipStream_t s);
+
+// windows above 7: the wide kernels further down, bias_perm in their layout (launch_swin_bias_perm), bias_dense unused
 hipError_t launch_swin_window_attention(int prec, const void *qkv, int ld, void *ctx, int ldc, const float *bias_perm,
                                         const float *bias_dense, int batch, int H, int W, int ws, int shift, int heads,
                                         hipStream_t s) {
+    if (ws > 7) return launch_swin_wide(prec, qkv, ld, ctx, ldc, nullptr, bias_perm, batch, H, W, ws, shift, heads, s);
     if (ws * ws > 49 + 15 || H % ws || W % ws) return hipErrorInvalidValue;
     WinGeom g{H, W, ws, shift, W / ws, (H / ws) * (W / ws), heads};
     const long total = (long)batch * g.nW * heads;
@@ -1045,8 +1055,318 @@ __global__ __launch_bounds__(64) void swin_wprobs_f32_kernel(const float *__rest
     swin_wprobs_store(Ps, probs, (size_t)id * (A * A), A * A, lane);
 }
 
+// ------------------------------------------------------------------------------------------
+// wide windows, 8 <= ws <= 12 (A = ws^2 = 64 .. 144 positions: the window12-384 checkpoints). A window no longer fits the
+// two 32-query tiles / two 32-key halves of one wavefront, so ONE WORKGROUP owns a (window, head) pair with NT = ceil(A / 32)
+// wavefronts (2, 3, 4, 4, 5 — the block is sized from ws, no wavefront idles):
+//   * all waves stage the window's K rows (pi order is applied on the read side, chunk swizzle as in the ws <= 7 kernels) and
+//     V rows into LDS once, padding keys as exact zeros, then one __syncthreads() — no wavefront leaves before it. K and V
+//     of a window are read from HBM once per (window, head);
+//   * wave w owns queries 32 w .. 32 w + 31 in the lane layout of swin_wattn_kernel: S^T = K.Q^T for all NT key sub-tiles
+//     stays in registers (NT x 16 accumulators), the exact two-pass softmax runs on them (in-register reductions plus one
+//     lane <-> lane + 32 exchange), and P feeds O^T += V^T.P^T directly (tr_read8);
+//   * relative-position bias: the head's (2 ws - 1)^2 <= 529 table entries, times log2(e), sit in LDS (2.1 KiB) and are
+//     indexed bin(query) - off(key); off(key), the key's mask region and the padding flag share one int per key (Kinfo),
+//     read as one 16-byte piece per four accumulator registers;
+//   * keys j >= A get -1e30, the shift mask is transformers' additive -100 on the region comparison, skipped wave-uniformly
+//     in interior windows (win_masked).
+// PREC 0 (bf16) and 2 (split pairs) run both products on the bf16 MFMA; PREC 1 (fp32) runs the same scheme on the exact-fp32
+// MFMA (v_mfma_f32_32x32x2_f32, correctness-grade: 32 instructions per 32 x 32 x 32 product), K rows padded to 33 floats.
+// PROBS: the same score and softmax steps; each wave stages its 32 x A probabilities in LDS — the rows of a query tile are one
+// contiguous piece of the (A x A) block — and writes them with swin_wprobs_store. V is not read.
+// ------------------------------------------------------------------------------------------
+constexpr int SWIN_WIDE_BINS = OCM_SWIN_WIDE_BINS;  // floats per head of the wide bias table (launch.h)
+
+__global__ __launch_bounds__(256) void swin_bias_wide_kernel(const float *__restrict__ table, float *__restrict__ out, int heads,
+                                                             int ws) {
+    const int nb = (2 * ws - 1) * (2 * ws - 1), total = heads * SWIN_WIDE_BINS;
+    for (int idx = blockIdx.x * 256 + threadIdx.x; idx < total; idx += gridDim.x * 256) {
+        const int head = idx / SWIN_WIDE_BINS, bin = idx - head * SWIN_WIDE_BINS;
+        out[idx] = bin < nb ? table[bin * heads + head] * 1.4426950408889634f : 0.f;
+    }
+}
+
+static hipError_t launch_swin_bias_wide(const float *table, float *out, int heads, int ws, hipStream_t s) {
+    if (ws < 8 || ws > 12 || heads <= 0) return hipErrorInvalidValue;
+    swin_bias_wide_kernel<<<dim3((heads * SWIN_WIDE_BINS + 255) / 256), dim3(256), 0, s>>>(table, out, heads, ws);
+    return hipGetLastError();
+}
+
+// O / l as bf16 into the head's 64-byte group `dst` of the lane's token: lane (r, h) holds dims {8 g + 4 h + e}; the two lanes
+// of a query trade half of their dims so that each writes 32 contiguous bytes (the store step of swin_wattn_kernel)
+__device__ __forceinline__ void swin_store_ctx_bf16(const f32x16 &O, float l, bf16 *dst, int h, bool live) {
+    const float inv = 1.0f / l;
+    uint32_t pk[8];
+#pragma unroll
+    for (int gq = 0; gq < 4; ++gq)
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            bf16x2 t;
+            t[0] = (bf16)(O[4 * gq + 2 * e] * inv);
+            t[1] = (bf16)(O[4 * gq + 2 * e + 1] * inv);
+            pk[2 * gq + e] = __builtin_bit_cast(uint32_t, t);
+        }
+    uint32_t out[8];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const uint32_t send = h ? pk[k] : pk[4 + k];
+        const uint32_t recv = (uint32_t)__shfl_xor((int)send, 32, 64);
+        const uint32_t keep = h ? pk[4 + k] : pk[k];
+        const int gsel = k >> 1, w = k & 1;
+        out[4 * gsel + (h ? 2 : 0) + w] = keep;
+        out[4 * gsel + (h ? 0 : 2) + w] = recv;
+    }
+    if (live) {
+        *(uint4 *)(dst + 16 * h) = uint4{out[0], out[1], out[2], out[3]};
+        *(uint4 *)(dst + 16 * h + 8) = uint4{out[4], out[5], out[6], out[7]};
+    }
+}
+
+// bytes per K row in LDS, bytes of V per key, dynamic LDS of a launch
+constexpr int swin_wide_krow(int prec) { return prec == 0 ? 64 : prec == 1 ? 33 * 4 : 128; }
+constexpr int swin_wide_vrow(int prec) { return prec == 0 ? 64 : 128; }
+static inline int swin_wide_lds(int prec, int nt, int A, bool probs) {
+    const int kp = nt * 32;
+    return kp * 4 + SWIN_WIDE_BINS * 4 + kp * swin_wide_krow(prec) + (probs ? nt * 32 * A * 4 : kp * swin_wide_vrow(prec));
+}
+
+template <int PREC, int NT, bool PROBS>
+__global__ __launch_bounds__(NT * 64) void swin_wide_kernel(const char *__restrict__ qkv, int ld, char *__restrict__ ctx, int ldc,
+                                                            float *__restrict__ probs, const float *__restrict__ bias_tab,
+                                                            WinGeom g, float scale2) {
+    constexpr int KP = NT * 32, NTHR = NT * 64;     // padded keys, threads
+    constexpr int ESZ = PREC == 0 ? 2 : 4;          // bytes per element (pairs: 4)
+    constexpr int NCH = PREC == 0 ? 4 : 8;          // 16-byte chunks of a head's row
+    constexpr int KROW = swin_wide_krow(PREC);
+    extern __shared__ __attribute__((aligned(16))) char wide_smem[];
+    int *Kinfo = (int *)wide_smem;                  // per key: off(key) | region << 16, negative for a padding key
+    float *Tb = (float *)(wide_smem + KP * 4);      // the head's bias table, log2 domain
+    char *Ks = wide_smem + KP * 4 + SWIN_WIDE_BINS * 4;
+    char *Vh = Ks + KP * KROW;                      // bf16: [KP][32] row-major; pairs: hi image, lo image; fp32: [KP][32] floats
+    char *Vl = Vh + KP * 64;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int r = lane & 31, h = lane >> 5;
+    const int id = blockIdx.x;
+    const auto [head, b, wy, wx] = win_decode(g, id, g.heads);
+    const int ws = g.ws, A = ws * ws, C = g.heads * 32, nb1 = 2 * ws - 1;
+    const size_t ldb = (size_t)ld * ESZ;
+    const char *base = qkv + (size_t)head * 32 * ESZ;
+    const bool masked = win_masked(g, ws, wy, wx);
+
+    // K (and V) rows of the window -> LDS, every thread of the workgroup KP * NCH / NTHR = NCH / 2 pieces of 16 bytes
+#pragma unroll
+    for (int i = 0; i < NCH / 2; ++i) {
+        const int idx = tid + NTHR * i, key = idx / NCH, ch = idx % NCH;
+        uint4 kv = uint4{0u, 0u, 0u, 0u}, vv = kv;
+        if (key < A) {
+            const char *row = base + win_token(g, ws, b, wy, wx, key) * ldb + ch * 16;
+            kv = *(const uint4 *)(row + (size_t)C * ESZ);
+            if (!PROBS) vv = *(const uint4 *)(row + (size_t)2 * C * ESZ);
+        }
+        if constexpr (PREC == 0) {
+            *(uint4 *)(Ks + key * 64 + ((ch ^ ((key >> 2) & 3)) << 4)) = kv;
+            if (!PROBS) *(uint4 *)(Vh + key * 64 + ch * 16) = vv;
+        } else if constexpr (PREC == 2) {
+            *(uint4 *)(Ks + lds_off(key, ch)) = kv;
+            if (!PROBS) *(uint4 *)((ch < 4 ? Vh : Vl) + key * 64 + (ch & 3) * 16) = vv;
+        } else {
+            uint32_t *kr = (uint32_t *)Ks + key * 33 + ch * 4;  // 33-float rows: the column reads below hit 32 banks
+            kr[0] = kv.x; kr[1] = kv.y; kr[2] = kv.z; kr[3] = kv.w;
+            if (!PROBS) *(uint4 *)(Vh + key * 128 + ch * 16) = vv;
+        }
+    }
+    for (int j = tid; j < KP; j += NTHR) {
+        int info = (int)0x80000000;
+        if (j < A) {
+            const int py = j / ws, px = j - py * ws;
+            info = (py * nb1 + px) | (masked ? win_region(g, ws, wy, wx, j) << 16 : 0);
+        }
+        Kinfo[j] = info;
+    }
+    for (int i = tid; i < SWIN_WIDE_BINS; i += NTHR) Tb[i] = bias_tab[(size_t)head * SWIN_WIDE_BINS + i];
+
+    // the wave's 32 queries (the last tile's rows past A repeat row A - 1 and are not stored)
+    const int qi = wave * 32 + r, qc = min(qi, A - 1);
+    const size_t qtok = win_token(g, ws, b, wy, wx, qc);
+    const char *qrow = base + qtok * ldb;
+    bf16x8 qh[2], ql[2];
+    float qf[PREC == 1 ? 16 : 1];
+    if constexpr (PREC == 1) {
+#pragma unroll
+        for (int kk = 0; kk < 16; ++kk) qf[kk] = ((const float *)qrow)[2 * kk + h];
+    } else {
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            qh[s] = *(const bf16x8 *)(qrow + (16 * s + 8 * h) * 2);
+            if constexpr (PREC == 2) ql[s] = *(const bf16x8 *)(qrow + (16 * s + 8 * h) * 2 + 64);
+        }
+    }
+    __syncthreads();
+
+    const int pr = pi_row(r);
+    f32x16 S[NT];
+#pragma unroll
+    for (int sub = 0; sub < NT; ++sub) {
+#pragma unroll
+        for (int e = 0; e < 16; ++e) S[sub][e] = 0.f;
+        if constexpr (PREC == 1) {
+            const float *kr = (const float *)Ks + (sub * 32 + pr) * 33 + h;
+#pragma unroll
+            for (int kk = 0; kk < 16; ++kk) S[sub] = mfma32f(kr[2 * kk], qf[kk], S[sub]);
+        } else {
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                if constexpr (PREC == 0) {
+                    const bf16x8 a = *(const bf16x8 *)(Ks + (sub * 32 + pr) * 64 + (((2 * s + h) ^ ((pr >> 2) & 3)) << 4));
+                    S[sub] = mfma32(a, qh[s], S[sub]);
+                } else {
+                    const bf16x8 kh = *(const bf16x8 *)(Ks + lds_off(sub * 32 + pr, 2 * s + h));
+                    const bf16x8 kl = *(const bf16x8 *)(Ks + lds_off(sub * 32 + pr, 4 + 2 * s + h));
+                    S[sub] = mfma32x3(kh, kl, qh[s], ql[s], S[sub]);
+                }
+            }
+        }
+    }
+    // scale + bias + mask in the log2 domain, exact two-pass softmax over the NT sub-tiles
+    const int qy = qc / ws, qx = qc - qy * ws;
+    const int qoff = (qy + ws - 1) * nb1 + qx + ws - 1;
+    const int myreg = (Kinfo[qc] >> 16) & 0xff;
+    float mx = -INFINITY;
+#pragma unroll
+    for (int sub = 0; sub < NT; ++sub)
+#pragma unroll
+        for (int e4 = 0; e4 < 4; ++e4) {
+            const int4 ki = *(const int4 *)(Kinfo + sub * 32 + key_of_reg(e4 * 4, h));  // four consecutive keys
+            const int kk[4] = {ki.x, ki.y, ki.z, ki.w};
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                float v = fmaf(S[sub][e4 * 4 + e], scale2, Tb[qoff - (kk[e] & 0xffff)]);
+                if (masked && ((kk[e] >> 16) & 0xff) != myreg) v += -100.0f * 1.4426950408889634f;
+                if (kk[e] < 0) v = -1e30f;
+                S[sub][e4 * 4 + e] = v;
+                mx = fmaxf(mx, v);
+            }
+        }
+    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+    float l = 0.f;
+#pragma unroll
+    for (int sub = 0; sub < NT; ++sub)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+            const float p = fast_exp2(S[sub][e] - mx);
+            S[sub][e] = p;
+            l += p;
+        }
+    l += __shfl_xor(l, 32, 64);
+
+    if constexpr (PROBS) {
+        float *Pw = (float *)Vh + (size_t)wave * 32 * A;  // this wave's rows: no other wave touches them
+        const float inv = 1.0f / l;
+        if (qi < A) {
+            float *prow = Pw + r * A;
+#pragma unroll
+            for (int sub = 0; sub < NT; ++sub)
+#pragma unroll
+                for (int e = 0; e < 16; ++e) {
+                    const int j = sub * 32 + key_of_reg(e, h);
+                    if (j < A) prow[j] = S[sub][e] * inv;
+                }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
+        const int nq = min(32, A - wave * 32);
+        swin_wprobs_store(Pw, probs, (size_t)id * (A * A) + (size_t)wave * 32 * A, nq * A, lane);
+    } else {
+        f32x16 O;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) O[e] = 0.f;
+#pragma unroll
+        for (int sub = 0; sub < NT; ++sub) {
+            if constexpr (PREC == 1) {
+#pragma unroll
+                for (int e = 0; e < 16; ++e)  // keys key_of_reg(e, 0) and key_of_reg(e, 1): one k step of two
+                    O = mfma32f(((const float *)Vh)[(sub * 32 + key_of_reg(e, h)) * 32 + r], S[sub][e], O);
+            } else {
+#pragma unroll
+                for (int s2 = 0; s2 < 2; ++s2) {
+                    const int voff = (sub * 32 + 16 * s2 + 8 * h + ((lane >> 2) & 3)) * 64 + (16 * ((lane >> 4) & 1) + 4 * (lane & 3)) * 2;
+                    if constexpr (PREC == 0) {
+                        bf16x8 pb;
+#pragma unroll
+                        for (int e = 0; e < 8; ++e) pb[e] = (bf16)S[sub][8 * s2 + e];
+                        O = mfma32(tr_read8(Vh + voff), pb, O);
+                    } else {
+                        bf16x8 ph, pl;
+                        x3_split_p(S[sub], s2, ph, pl);
+                        const bf16x8 vh = tr_read8(Vh + voff), vl = tr_read8(Vl + voff);
+                        O = mfma32x3(vh, vl, ph, pl, O);
+                    }
+                }
+            }
+        }
+        if constexpr (PREC == 0) {
+            swin_store_ctx_bf16(O, l, (bf16 *)ctx + qtok * (size_t)ldc + head * 32, h, qi < A);
+        } else if constexpr (PREC == 2) {
+            if (qi < A) swin_store_ctx_pairs(O, l, ctx + qtok * (size_t)ldc * 4 + head * 128, h);
+        } else if (qi < A) {
+            const float inv = 1.0f / l;
+            float *dst = (float *)ctx + qtok * (size_t)ldc + head * 32 + 4 * h;
+#pragma unroll
+            for (int gq = 0; gq < 4; ++gq)
+                *(f32x4 *)(dst + 8 * gq) = f32x4{O[4 * gq] * inv, O[4 * gq + 1] * inv, O[4 * gq + 2] * inv, O[4 * gq + 3] * inv};
+        }
+    }
+}
+
+template <int PREC, int NT, bool PROBS>
+static hipError_t launch_swin_wide_nt(const void *qkv, int ld, void *ctx, int ldc, float *probs, const float *bias_tab,
+                                      const WinGeom &g, unsigned total, float scale2, hipStream_t s) {
+    static OptinMask optin;
+    constexpr int AMAX = NT == 2 ? 64 : NT == 3 ? 81 : NT == 4 ? 121 : 144;  // the largest window this block size serves
+    auto kern = swin_wide_kernel<PREC, NT, PROBS>;
+    if (hipError_t e = lds_optin((const void *)kern, swin_wide_lds(PREC, NT, AMAX, PROBS), optin); e != hipSuccess) return e;
+    kern<<<dim3(total), dim3(NT * 64), swin_wide_lds(PREC, NT, g.ws * g.ws, PROBS), s>>>((const char *)qkv, ld, (char *)ctx, ldc,
+                                                                                      probs, bias_tab, g, scale2);
+    return hipGetLastError();
+}
+
+// ctx (attention) or probs (probabilities) of windows of 8 to 12; bias_tab: heads x SWIN_WIDE_BINS (launch_swin_bias_perm)
+static hipError_t launch_swin_wide(int prec, const void *qkv, int ld, void *ctx, int ldc, float *probs, const float *bias_tab,
+                                   int batch, int H, int W, int ws, int shift, int heads, hipStream_t s) {
+    if (ws < 8 || ws > 12 || H <= 0 || W <= 0 || H % ws || W % ws || shift < 0 || shift >= ws || heads <= 0 ||
+        ld < 3 * heads * 32)
+        return hipErrorInvalidValue;
+    if (prec == 2 ? ld % 32 : prec == 0 ? ld % 8 : ld % 4) return hipErrorInvalidValue;  // 16-byte loads of q, k and v
+    if (probs) {
+        if ((uintptr_t)probs & 15) return hipErrorInvalidValue;
+    } else if (ldc < heads * 32 || (prec == 2 ? ldc % 32 : prec == 0 ? ldc % 8 : ldc % 4)) {
+        return hipErrorInvalidValue;
+    }
+    WinGeom g{H, W, ws, shift, W / ws, (H / ws) * (W / ws), heads};
+    const long total = (long)batch * g.nW * heads;
+    if (total <= 0 || total > 0x7fffffffL) return hipErrorInvalidValue;
+    const float scale2 = 0.17677669529663687f * 1.4426950408889634f;  // 32^-0.5 in the log2 domain
+    const int nt = (ws * ws + 31) / 32;
+#define OCM_WIDE_NT(P, NT)                                                                                              \
+    return probs ? launch_swin_wide_nt<P, NT, true>(qkv, ld, ctx, ldc, probs, bias_tab, g, (unsigned)total, scale2, s) \
+                 : launch_swin_wide_nt<P, NT, false>(qkv, ld, ctx, ldc, probs, bias_tab, g, (unsigned)total, scale2, s)
+#define OCM_WIDE(P)                                                                                                     \
+    switch (nt) {                                                                                                       \
+        case 2: OCM_WIDE_NT(P, 2);                                                                                      \
+        case 3: OCM_WIDE_NT(P, 3);                                                                                      \
+        case 4: OCM_WIDE_NT(P, 4);                                                                                      \
+        default: OCM_WIDE_NT(P, 5);                                                                                     \
+    }
+    if (prec == 0) OCM_WIDE(0)
+    if (prec == 1) OCM_WIDE(1)
+    OCM_WIDE(2)
+#undef OCM_WIDE
+#undef OCM_WIDE_NT
+}
+
 hipError_t launch_swin_window_probs(int prec, const void *qkv, int ld, float *probs, const float *bias_perm,
                                     const float *bias_dense, int batch, int H, int W, int ws, int shift, int heads, hipStream_t s) {
+    if (ws > 7) return launch_swin_wide(prec, qkv, ld, nullptr, 0, probs, bias_perm, batch, H, W, ws, shift, heads, s);
     if (ws < 2 || ws > 7 || H % ws || W % ws || ld < 3 * heads * 32 || ((uintptr_t)probs & 15)) return hipErrorInvalidValue;
     if (prec == 2 ? ld % 32 : prec == 0 ? ld % 8 : ld % 4) return hipErrorInvalidValue;  // 16-byte loads of q and k
     WinGeom g{H, W, ws, shift, W / ws, (H / ws) * (W / ws), heads};
@@ -1708,7 +2028,7 @@ __global__ __launch_bounds__(NW * 64, 2) void swin_attn_block_x3_kernel(float *_
 
 // proj_fused: the whole half in one kernel (C = 96); otherwise (C = 192) the kernel stops at the context pairs
 bool swin_attn_block_fused_supported(int prec, int C, int heads, int ws) {
-    return prec == 2 && (C == 96 || C == 128 || C == 192) && heads * 32 == C && ws >= 2 && ws * ws <= 64;
+    return prec == 2 && (C == 96 || C == 128 || C == 192) && heads * 32 == C && ws >= 2 && ws <= 7;
 }
 bool swin_attn_block_proj_fused(int C) { return C == 96; }
 

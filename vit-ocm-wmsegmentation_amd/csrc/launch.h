@@ -184,6 +184,13 @@ hipError_t launch_swin_ln(int prec, const float *x, const float *g, const float 
 hipError_t launch_swin_pad_rows(const void *src, void *dst, int batch, int H, int W, int Hp, int Wp, size_t row_bytes,
                                 hipStream_t s);
 hipError_t launch_swin_crop_add(float *x, const float *yp, int batch, int H, int W, int Hp, int Wp, int C, hipStream_t s);
+// Windows of 8 to 12 (the wide kernels) keep the bias as the head's own table: perm = heads x OCM_SWIN_WIDE_BINS floats,
+// [head][bin] = table[bin][head] * log2(e) for the (2 ws - 1)^2 <= 529 bins, zeros behind; dense is not used.
+constexpr int OCM_SWIN_WIDE_BINS = 544;
+// floats of bias storage of one layer: perm | dense (ws <= 7: heads * 4096 | heads * ws^4)
+static inline size_t swin_bias_floats(int ws, int heads) {
+    return ws > 7 ? (size_t)heads * OCM_SWIN_WIDE_BINS : (size_t)heads * (4096 + (size_t)ws * ws * ws * ws);
+}
 hipError_t launch_swin_bias_perm(const float *table, float *perm, float *dense, int heads, int ws, hipStream_t s);
 hipError_t launch_swin_window_attention(int prec, const void *qkv, int ld, void *ctx, int ldc, const float *bias_perm,
                                         const float *bias_dense, int batch, int H, int W, int ws, int shift, int heads,

@@ -92,8 +92,8 @@ struct ocm_swin {
 static int swin_check_config(const ocm_swin_config *cfg) {
     if (cfg->patch_size != 4) return fail(OCM_EINVAL, "patch_size %d: only 4 is built", cfg->patch_size);
     if (cfg->num_channels != 1 && cfg->num_channels != 3) return fail(OCM_EINVAL, "num_channels must be 1 or 3");
-    if (cfg->window_size < 2 || cfg->window_size > 7)
-        return fail(OCM_EINVAL, "window_size %d must be in [2,7] (one 64-position tile per window)", cfg->window_size);
+    if (cfg->window_size < 2 || cfg->window_size > 12)
+        return fail(OCM_EINVAL, "window_size %d must be in [2,12] (up to five 32-position tiles per window)", cfg->window_size);
     if (cfg->num_stages < 1 || cfg->num_stages > 4) return fail(OCM_EINVAL, "num_stages %d must be in [1,4]", cfg->num_stages);
     if (cfg->embed_dim <= 0 || cfg->embed_dim % 32 || cfg->embed_dim > 128)
         return fail(OCM_EINVAL, "embed_dim %d must be a multiple of 32, <= 128", cfg->embed_dim);
@@ -154,8 +154,9 @@ extern "C" int ocm_swin_create(const ocm_swin_config *cfg, ocm_swin_t **out) {
             lp.wo = h->reserve((size_t)C * Kc * h->esz);
             h->add(pre + "attention.o_proj.weight", S_MAT, (size_t)C * C, lp.wo, C, C, Kc);
             lp.bo = h->add_f32(pre + "attention.o_proj.bias", C);
-            lp.bias_perm = h->reserve((size_t)heads * 2 * 64 * 32 * 4);
-            lp.bias_dense = h->reserve((size_t)heads * A * A * 4);
+            // ws <= 7: the permuted image | the dense table; wider windows: the head's own table (launch_swin_bias_perm)
+            lp.bias_perm = h->reserve(ws > 7 ? swin_bias_floats(ws, heads) * 4 : (size_t)heads * 2 * 64 * 32 * 4);
+            lp.bias_dense = ws > 7 ? lp.bias_perm : h->reserve((size_t)heads * A * A * 4);
             h->add(pre + "attention.relative_position_bias.relative_position_bias_table", S_TABLE,
                    (size_t)(2 * ws - 1) * (2 * ws - 1) * heads, lp.bias_perm, 0, 0, 0, 0, heads, lp.bias_dense);
             const size_t g1 = h->add_f32(pre + "layernorm_before.weight", C), b1 = h->add_f32(pre + "layernorm_before.bias", C);
@@ -627,7 +628,7 @@ extern "C" int ocm_op_swin_window_probs(int32_t precision, const void *qkv, int3
     if (!qkv || !probs || !rel_table || !scratch) return fail(OCM_EINVAL, "null argument");
     if (precision != OCM_PREC_BF16 && precision != OCM_PREC_FP32 && precision != OCM_PREC_BF16X3)
         return fail(OCM_EINVAL, "bad precision");
-    if (window < 2 || window > 7 || height <= 0 || width <= 0 || height % window || width % window || batch <= 0 || heads <= 0 ||
+    if (window < 2 || window > 12 || height <= 0 || width <= 0 || height % window || width % window || batch <= 0 || heads <= 0 ||
         shift < 0 || shift >= window)
         return fail(OCM_EINVAL, "bad window geometry");
     if (ld < 3 * 32 * heads || ld % (precision == OCM_PREC_BF16X3 ? 32 : precision == OCM_PREC_BF16 ? 8 : 4))
@@ -637,11 +638,17 @@ extern "C" int ocm_op_swin_window_probs(int32_t precision, const void *qkv, int3
     if ((int64_t)batch * (height / window) * (width / window) * heads > 0x7fffffffLL || (int64_t)batch * height * width > 0x7fffffffLL)
         return fail(OCM_EINVAL, "too many windows");
     hipStream_t s = (hipStream_t)stream;
-    float *perm = scratch, *dense = scratch + (size_t)heads * 4096;  // the layout ocm_op_swin_window_attention leaves
+    // the layout ocm_op_swin_window_attention leaves (ocm_swin_window_scratch_floats: no dense table for windows above 7)
+    float *perm = scratch, *dense = window > 7 ? scratch : scratch + (size_t)heads * 4096;
     HIP_TRY(launch_swin_bias_perm(rel_table, perm, dense, heads, window, s));
     HIP_TRY(launch_swin_window_probs(prec_index(precision), qkv, ld, probs, perm, dense, batch, height, width, window, shift,
                                      heads, s));
     return OCM_OK;
+}
+
+extern "C" size_t ocm_swin_window_scratch_floats(int32_t window, int32_t heads) {
+    if (window < 2 || window > 12 || heads <= 0) return 0;
+    return swin_bias_floats(window, heads);
 }
 
 extern "C" int ocm_op_swin_tokens_to_nchw(const float *x, float *out, int32_t batch, int32_t tokens, int32_t channels,
@@ -661,11 +668,19 @@ extern "C" int ocm_op_swin_window_attention(int32_t precision, const void *qkv, 
         return fail(OCM_EINVAL, "bad precision");
     if (precision == OCM_PREC_BF16X3 && (ld % 32 || ldc % 32))
         return fail(OCM_EINVAL, "split-bf16 rows are whole groups of 32 elements: ld %d, ldc %d", ld, ldc);
-    if (window < 2 || window > 7 || height % window || width % window || batch <= 0 || heads <= 0 || shift < 0 ||
-        shift >= window)
+    if (window < 2 || window > 12 || height <= 0 || width <= 0 || height % window || width % window || batch <= 0 || heads <= 0 ||
+        shift < 0 || shift >= window)
         return fail(OCM_EINVAL, "bad window geometry");
+    if (window > 7) {  // the wide kernels load and store whole 16-byte pieces
+        const int piece = precision == OCM_PREC_BF16X3 ? 32 : precision == OCM_PREC_BF16 ? 8 : 4;
+        if (ld < 3 * 32 * heads || ld % piece || ldc < 32 * heads || ldc % piece)
+            return fail(OCM_EINVAL, "ld %d, ldc %d: rows hold q | k | v (ctx: the context) of %d heads in whole 16-byte pieces", ld,
+                        ldc, heads);
+        if ((int64_t)batch * (height / window) * (width / window) * heads > 0x7fffffffLL || (int64_t)batch * height * width > 0x7fffffffLL)
+            return fail(OCM_EINVAL, "too many windows");
+    }
     hipStream_t s = (hipStream_t)stream;
-    float *perm = scratch, *dense = scratch + (size_t)heads * 4096;
+    float *perm = scratch, *dense = window > 7 ? scratch : scratch + (size_t)heads * 4096;
     HIP_TRY(launch_swin_bias_perm(rel_table, perm, dense, heads, window, s));
     HIP_TRY(launch_swin_window_attention(prec_index(precision), qkv, ld, ctx, ldc, perm, dense, batch, height, width, window,
                                          shift, heads, s));

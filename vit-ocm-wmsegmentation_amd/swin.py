@@ -9,7 +9,9 @@ feature maps), `output_attentions=True` the window-softmax of every layer (`atte
 `attentions[cumsum(depths) - 1]` for those). `SwinModel` is the model without the classifier, and
 `SwinForImageClassification.swin` the same view over a (fine-tuned) classifier's own parameters and engine.
 
-Inference runs the engine (ocm_swin_forward). Training — train.py's Trainer loop — runs when the module is in training mode,
+Inference runs the engine (ocm_swin_forward) with windows of 2 to 12 — 12 is the geometry of the window12-384 checkpoints
+(`SwinConfig(image_size=384, embed_dim=128, depths=(2, 2, 18, 2), num_heads=(4, 8, 16, 32), window_size=12)`), whose windows
+tile a 384^2 tile's grids without padding; training keeps windows of 2 to 7. Training — train.py's Trainer loop — runs when the module is in training mode,
 grad mode is on and a parameter requires grad (the parameters are created with requires_grad=False: opt in with
 `model.requires_grad_(True)`): the stand-alone operators under one autograd Function (_SwinTrain) whose backward is HIP
 (kernels_swin_train.hip plus the ViT training operators).

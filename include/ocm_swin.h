@@ -198,6 +198,20 @@ int ocm_op_swin_window_attention_backward(const float *qkv, const float *dctx, c
                                           int32_t batch, int32_t height, int32_t width, int32_t window, int32_t shift,
                                           int32_t heads, void *workspace, size_t workspace_bytes, void *stream);
 
+/* The same backward for windows of 8 to 12 (ws^2 = 64 .. 144 positions; the window12-384 checkpoints): the arguments, outputs and
+ * recomputation of ocm_op_swin_window_attention_backward, qkv / dctx / dqkv 16-byte aligned. One workgroup of ceil(ws^2 / 32)
+ * wavefronts owns a (window, head) pair; all five products (S = q k^T, dP = dO v^T, dQ = dS k, dK = dS^T q, dV = P^T dO) run on
+ * the exact-fp32 MFMA in every precision mode, padding key slots contribute exact zeros, no atomics, reruns give the same bits.
+ * Workspace: (nwin + ceil(nwin / 64)) * (2*ws-1)^2 * heads * 4 bytes with nwin = batch * (height / ws) * (width / ws) — the
+ * per-window bin partials and the first level of their fixed-order column sum; 0 for a window outside 8 .. 12 or a non-positive
+ * size. OCM_EINVAL: a window outside 8 .. 12, a grid that is not a multiple of the window, shift >= window, null pointers, a
+ * short workspace, more than 2^31 (window, head) pairs. */
+size_t ocm_swin_window_attention_backward_wide_workspace_bytes(int32_t batch, int32_t height, int32_t width, int32_t window,
+                                                               int32_t heads);
+int ocm_op_swin_window_attention_backward_wide(const float *qkv, const float *dctx, const float *rel_table, float *dqkv,
+                                               float *dtable, int32_t batch, int32_t height, int32_t width, int32_t window,
+                                               int32_t shift, int32_t heads, void *workspace, size_t workspace_bytes, void *stream);
+
 /* SwinPatchMerging's 2 x 2 gather (modeling_swin.py:309-326) as fp32 rows, even height and width only:
  * y (batch * height/2 * width/2, 4 * channels) = x0 | x1 | x2 | x3 of x (batch, height, width, channels) fp32 — the merging
  * LayerNorm's input; and its inverse in gather form, dx (batch, height, width, channels) from dy of y's shape (bit exact). */

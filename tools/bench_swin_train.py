@@ -4,9 +4,13 @@ prints the padded / real token counts per stage), 5 labels, AdamW (lr 5e-5), dro
 `step` is their sum) and, as a yardstick, an fp32 eager twin on the same GPU: the oracle's functions (oracle/swin_oracle.py)
 under torch autograd with the same weights, timed in alternation with the HIP step in one process. Also reports the activations
 the training forward keeps per image. The split by kernel class comes from a kernel trace of this tool
-(rocprofv3 --kernel-trace --stats).
+(rocprofv3 --kernel-trace --stats). --arch swin_b_w12 times Swin-B / window 12 (embed_dim 128, depths 2/2/18/2, heads 4/8/16/32:
+the window12-384 checkpoints' geometry, --image-size 384 tiles every stage without padding) with enable_wide_window_training on;
+--embed-dim / --depths / --num-heads / --window-size override single fields of either architecture.
 
   python tools/bench_swin_train.py [--batch 8] [--precision bf16] [--reps 5] [--optimizer hip] [--image-size 384] [--no-twin]
+                                   [--arch swin_b_w12] [--embed-dim 128] [--depths 2,2,18,2] [--num-heads 4,8,16,32]
+                                   [--window-size 12]
 """
 import argparse
 import json
@@ -24,6 +28,9 @@ from oracle import swin_oracle as SO  # noqa: E402
 from vit_ocm_wmsegmentation_amd import _lib, synth  # noqa: E402
 from vit_ocm_wmsegmentation_amd import optimizer as OPT  # noqa: E402
 from vit_ocm_wmsegmentation_amd import swin as SW  # noqa: E402
+
+
+ARCHS = {"swin_t": {}, "swin_b_w12": dict(embed_dim=128, depths=(2, 2, 18, 2), num_heads=(4, 8, 16, 32), window_size=12)}
 
 
 def _timed(fn):
@@ -44,11 +51,20 @@ def main():
                     help="the HIP step's optimizer: torch.optim (default) or optimizer.py's multi-tensor kernels")
     ap.add_argument("--image-size", type=int, default=224, help="square input side, a multiple of the patch size 4")
     ap.add_argument("--no-twin", action="store_true", help="skip the fp32 eager twin (for a kernel trace of the HIP step alone)")
+    ints = lambda v: tuple(int(t) for t in v.split(","))  # noqa: E731
+    ap.add_argument("--arch", default="swin_t", choices=sorted(ARCHS), help="swin_t, or swin_b_w12 (Swin-B with windows of 12)")
+    ap.add_argument("--embed-dim", type=int, help="channels of stage 0 (32-wide heads: 32 * num_heads[0])")
+    ap.add_argument("--depths", type=ints, help="layers per stage, comma separated")
+    ap.add_argument("--num-heads", type=ints, help="heads per stage, comma separated")
+    ap.add_argument("--window-size", type=int, help="2 to 12; above 7 the tool turns enable_wide_window_training on")
     args = ap.parse_args()
     dev, B, S = torch.device("cuda:0"), args.batch, args.image_size
-    cfg = dict(synth.SWIN_TINY, image_size=S)
+    cfg = dict(synth.SWIN_TINY, **ARCHS[args.arch], image_size=S, num_labels=5)
+    for k in ("embed_dim", "depths", "num_heads", "window_size"):
+        if getattr(args, k) is not None:
+            cfg[k] = getattr(args, k)
     sd = synth.synth_swin_state_dict(cfg, seed=3)
-    m = SW.SwinForImageClassification(SW.SwinConfig(image_size=S, num_labels=5))
+    m = SW.SwinForImageClassification(SW.SwinConfig(**{k: v for k, v in cfg.items() if k != "patch_size"}))
     m.load_state_dict(sd)
     m = m.to(dev).set_precision(args.precision).train().requires_grad_(True)
     tokens, side, ws = [], S // cfg["patch_size"], cfg["window_size"]
@@ -60,6 +76,8 @@ def main():
     needs_padding = any(t["padded"] != t["real"] or t["odd_merge"] for t in tokens)
     if needs_padding:
         m.enable_padded_training()
+    if ws > 7:
+        m.enable_wide_window_training()
     for t in tokens:
         print(f"stage {t['stage']}: grid {t['grid']}^2 = {t['real']} tokens, padded {t['padded_grid']}^2 = {t['padded']} "
               f"({t['ratio']:.2f}x){', odd merge' if t['odd_merge'] else ''}")
@@ -100,7 +118,9 @@ def main():
         rows["step"].append(tf + tb + to)
         rows["twin"].append(twin_step())
     med = {k: sorted(v)[len(v) // 2] for k, v in rows.items()}
-    res = dict(box=socket.gethostname(), gpu=torch.cuda.get_device_name(0), batch=B, precision=args.precision, image_size=S,
+    res = dict(box=socket.gethostname(), gpu=torch.cuda.get_device_name(0), arch=args.arch, embed_dim=cfg["embed_dim"],
+               depths=list(cfg["depths"]), num_heads=list(cfg["num_heads"]), window_size=ws, wide_window_training=ws > 7,
+               batch=B, precision=args.precision, image_size=S,
                padded_training=needs_padding, padded_over_real_tokens=[t["ratio"] for t in tokens],
                ms={k: round(v, 2) for k, v in med.items()}, speedup_vs_eager=round(med["twin"] / med["step"], 2),
                kept_mib_per_image=round(m.__dict__["_train_kept_bytes"] / B / 2 ** 20, 1), reps=args.reps)

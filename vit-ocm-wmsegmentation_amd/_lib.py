@@ -210,6 +210,9 @@ SIGNATURES = {
     "ocm_op_swin_merge_ln": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                        C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "ocm_swin_window_attention_backward_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32, _i32]),
+    "ocm_swin_window_attention_backward_wide_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32, _i32]),
+    "ocm_op_swin_window_attention_backward_wide": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp,
+                                                             _sz, _vp]),
     "ocm_op_swin_window_attention_backward": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _sz,
                                                         _vp]),
     "ocm_op_swin_merge_gather": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp]),

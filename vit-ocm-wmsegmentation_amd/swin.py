@@ -11,7 +11,8 @@ feature maps), `output_attentions=True` the window-softmax of every layer (`atte
 
 Inference runs the engine (ocm_swin_forward) with windows of 2 to 12 — 12 is the geometry of the window12-384 checkpoints
 (`SwinConfig(image_size=384, embed_dim=128, depths=(2, 2, 18, 2), num_heads=(4, 8, 16, 32), window_size=12)`), whose windows
-tile a 384^2 tile's grids without padding; training keeps windows of 2 to 7. Training — train.py's Trainer loop — runs when the module is in training mode,
+tile a 384^2 tile's grids without padding; training takes windows of 2 to 7, and 8 to 12 after
+enable_wide_window_training(). Training — train.py's Trainer loop — runs when the module is in training mode,
 grad mode is on and a parameter requires grad (the parameters are created with requires_grad=False: opt in with
 `model.requires_grad_(True)`): the stand-alone operators under one autograd Function (_SwinTrain) whose backward is HIP
 (kernels_swin_train.hip plus the ViT training operators).
@@ -322,9 +323,18 @@ class SwinForImageClassification(_SwinBase):
         self.__dict__["_padded_training"] = bool(on)
         return self
 
+    def enable_wide_window_training(self, on=True):
+        """Opt in to training with windows of 8 to 12 (the window12-384 checkpoints: grids 96 / 48 / 24 / 12 on a 384^2 tile,
+        no padding in any stage): their window-attention backward is ocm_op_swin_window_attention_backward_wide. A per-module
+        setting, not part of the state_dict; windows of 2 to 7 launch what they launch without it. Composes with
+        enable_padded_training (image 80 with windows of 8 pads 20 -> 24 and 10 -> 16). Returns self."""
+        self.__dict__["_wide_window_training"] = bool(on)
+        return self
+
     def _check_trainable(self, x, labels):
         """What the training path refuses, before anything is launched."""
         c = self.config
+        wide = self.__dict__.get("_wide_window_training", False)
         if x.requires_grad:
             raise NotImplementedError("the training path does not produce the gradient of the input image; pass pixel_values "
                                       "that do not require grad")
@@ -332,8 +342,10 @@ class SwinForImageClassification(_SwinBase):
             raise NotImplementedError(f"training is built without dropout (hidden_dropout_prob = {c.hidden_dropout_prob}, "
                                       f"attention_probs_dropout_prob = {c.attention_probs_dropout_prob}); set both to 0. "
                                       "Stochastic depth (drop_path_rate) is supported")
-        if c.patch_size != 4 or not 2 <= c.window_size <= 7:
-            raise NotImplementedError("training is built for patch_size 4 and windows of 2 to 7")
+        if c.patch_size != 4 or not 2 <= c.window_size <= (12 if wide else 7):
+            raise NotImplementedError("training is built for patch_size 4 and windows of 2 to 12" if wide else
+                                      "training is built for patch_size 4 and windows of 2 to 7; "
+                                      "model.enable_wide_window_training() trains windows of 8 to 12")
         side = c.image_size // c.patch_size
         padded = self.__dict__.get("_padded_training", False)
         hint = "; model.enable_padded_training() trains through transformers' padding paths"
@@ -572,7 +584,7 @@ class _SwinTrain(torch.autograd.Function):
                               torch.cat([P[a + n + "_proj.bias"] for n in "qkv"]), None, Tp, 3 * C, Kc)
                 del xo
                 cx = torch.zeros((Tp, Kc), dtype=adt, device=dev)
-                scratch = torch.empty(heads * (4096 + ws ** 4), **f32)
+                scratch = torch.empty(lib.ocm_swin_window_scratch_floats(ws, heads), **f32)
                 table = P[a + "relative_position_bias.relative_position_bias_table"]
                 _lib.check(lib.ocm_op_swin_window_attention(prec, _p(to_operand(qkv, prec)), 3 * C, _p(cx), Kc, _p(table),
                                                             _p(scratch), B, Hp, Hp, ws, shift, heads, _stream()))
@@ -770,10 +782,11 @@ class _SwinTrain(torch.autograd.Function):
                 tkey = a + "relative_position_bias.relative_position_bias_table"
                 dqkv = torch.empty((Tp, 3 * C), **f32)
                 dtab = torch.empty(P[tkey].shape, **f32)
-                nbytes = lib.ocm_swin_window_attention_backward_workspace_bytes(B, Hp, Hp, ws, heads)
+                wide = "_wide" if ws > 7 else ""  # windows of 8 to 12: the MFMA backward (enable_wide_window_training)
+                nbytes = getattr(lib, f"ocm_swin_window_attention_backward{wide}_workspace_bytes")(B, Hp, Hp, ws, heads)
                 wsb = _ws(nbytes, dev)
-                _lib.check(lib.ocm_op_swin_window_attention_backward(_p(qkv), _p(dctx), _p(P[tkey]), _p(dqkv), _p(dtab), B,
-                                                                     Hp, Hp, ws, shift, heads, _p(wsb), nbytes, _stream()))
+                _lib.check(getattr(lib, "ocm_op_swin_window_attention_backward" + wide)(
+                    _p(qkv), _p(dctx), _p(P[tkey]), _p(dqkv), _p(dtab), B, Hp, Hp, ws, shift, heads, _p(wsb), nbytes, _stream()))
                 if need[tkey]:
                     grads[tkey] = dtab
                 del dctx, wsb

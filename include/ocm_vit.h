@@ -925,6 +925,63 @@ int ocm_op_grad_norm(const OcmOptimTensor *tensors, int32_t n, double max_norm, 
 /* grad = grad * *coef for every gradient of the table, the coefficient read from device memory by the kernel. */
 int ocm_op_grad_scale(const OcmOptimTensor *tensors, int32_t n, const float *coef, void *stream);
 
+/* param = param * m + grad * (1 - m) for every tensor of the table: the teacher's exponential moving average of DINO
+ * (dino/utils.py ema_update; param = the teacher's tensor, grad = the student's), torch's p.mul_(m).add_((1 - m) * q): 1 - m is
+ * formed in double and rounded to float once, then three separately rounded operations, no FMA. The launcher and limits of the
+ * optimizer step: 16-byte accesses for a tensor whose two pointers are 16-byte aligned, element accesses otherwise, count == 0
+ * legal. Refused with OCM_EINVAL: as ocm_op_optim_step (param and grad are looked at), a non-finite momentum. */
+int ocm_op_ema_update(const OcmOptimTensor *tensors, int32_t n, double momentum, void *stream);
+
+/* ---- DINO self-distillation (dino/vision_transformer.py DINOHead, dino/utils.py DINOLoss; kernels_dino.hip) ----
+ * Row kernels over fp32 data: one workgroup per row (or per slice of 4096 columns of the loss), 16-byte loads and stores for a row
+ * whose address is 16-byte aligned, element accesses otherwise and for the tail of any length. Every reduction runs in float64 in
+ * an order fixed by the shapes alone (no atomics): equal inputs give equal bits. Every output element is written exactly once,
+ * nothing synchronises with the host, and bad arguments (null or misaligned pointers, shapes outside the stated ranges) are
+ * refused with OCM_EINVAL before any launch. */
+
+/* F.normalize(x, p = 2, dim = -1) over `rows` rows of `dim` floats: norm[r] = max(|x[r]|_2, 1e-12), y = x / norm. rows >= 1,
+ * dim >= 1. */
+int ocm_op_l2_normalize(const float *x, float *y, float *norm, int64_t rows, int32_t dim, void *stream);
+/* dx = (dy - y (y . dy)) / norm from the forward's y and norm; a row whose norm is the clamp (<= 1e-12) gets dx = dy / norm, the
+ * gradient torch's graph gives through clamp_min. dx may alias dy. */
+int ocm_op_l2_normalize_backward(const float *dy, const float *y, const float *norm, float *dx, int64_t rows, int32_t dim,
+                                 void *stream);
+
+/* nn.utils.weight_norm (dim = 0) of a Linear: w[n][:] = g[n] v[n][:] / |v[n]|_2 for v [N][K], g [N]; norm[n] = |v[n]|_2. */
+int ocm_op_weight_norm(const float *v, const float *g, float *w, float *norm, int32_t N, int32_t K, void *stream);
+/* From dw [N][K]: dg[n] = (dw[n] . v[n]) / norm[n], dv[n] = g[n] / norm[n] (dw[n] - v[n] (dw[n] . v[n]) / norm[n]^2). Either of
+ * dg, dv may be NULL (not both). dv may alias dw. */
+int ocm_op_weight_norm_backward(const float *dw, const float *v, const float *g, const float *norm, float *dg, float *dv, int32_t N,
+                                int32_t K, void *stream);
+
+/* The DINO loss. student [V*B][K] crop-major (crop v owns rows v*B .. v*B + B - 1), teacher [2*B][K], center [K];
+ *   q[i,b,:] = softmax((teacher[i,b,:] - center) / teacher_temp), l[v,b,:] = log_softmax(student[v,b,:] / student_temp),
+ *   loss = 1 / (2 (V - 1)) sum_i sum_{v != i} (1 / B) sum_b sum_k -q[i,b,k] l[v,b,k],
+ * every softmax with its row maximum subtracted. Two passes over the logits: the row statistics (row_stats[(V + 2) * B][2]
+ * float64: the maximum and the sum of exp(z - max) of every student row, then of every teacher row), then the 2 x V table of
+ * q_i . S_v per image through the workspace, from which sum_k q l = (q . S_v) / student_temp - lse_v. loss_out[1] is device
+ * memory. V >= 2, B >= 1, K >= 1, temperatures finite and > 0; K <= 65535 * 4096. row_stats 8-byte aligned. */
+size_t ocm_dino_loss_workspace_bytes(int32_t B, int32_t V, int32_t K);
+int ocm_op_dino_loss(const float *student, const float *teacher, const float *center, float student_temp, float teacher_temp,
+                     int32_t B, int32_t V, int32_t K, float *loss_out, double *row_stats, void *workspace, size_t workspace_bytes,
+                     void *stream);
+/* One pass: dstudent[v,b,k] = grad_loss[0] / (2 (V - 1) B student_temp) (c_v p[v,b,k] - sum_{i != v} q[i,b,k]), p =
+ * softmax(student / student_temp), c_v = 1 for v < 2 and 2 otherwise; grad_loss[1] is read from device memory, row_stats is
+ * the forward's. No workspace. */
+int ocm_op_dino_loss_backward(const float *grad_loss, const float *student, const float *teacher, const float *center,
+                              float student_temp, float teacher_temp, int32_t B, int32_t V, int32_t K, const double *row_stats,
+                              float *dstudent, void *stream);
+
+/* The centre of the DINO loss, in two calls because a distributed run all-reduces batch_sum in between:
+ *   OCM_DINO_CENTER_SUM     batch_sum[k] = ((teacher[0][k] + teacher[1][k]) + teacher[2][k]) + ... over `rows` rows, in fp32
+ *                           (center, count, momentum unused)
+ *   OCM_DINO_CENTER_UPDATE  center = center * m + (batch_sum / count) * (1 - m), count = rows * world size rounded to float,
+ *                           1 - m formed in double and rounded once, each operation rounded on its own (teacher, rows unused) */
+#define OCM_DINO_CENTER_SUM 0
+#define OCM_DINO_CENTER_UPDATE 1
+int ocm_op_dino_center(int32_t mode, const float *teacher, int64_t rows, int32_t K, float *batch_sum, float *center, double count,
+                       double momentum, void *stream);
+
 /* ---- sliding-window index math (host, integer; sw_processing.py:151-163) ---- */
 /* Number of windows per axis: len(range(0, size - 2*stride, stride)). */
 int32_t ocm_sw_count(int32_t size, int32_t stride);

@@ -132,6 +132,7 @@ class OcmOptimHyper(C.Structure):  # ocm_op_optim_step: the values of one step, 
 
 
 OCM_OPTIM_ADAMW, OCM_OPTIM_ADAM, OCM_OPTIM_SGD = 0, 1, 2
+OCM_DINO_CENTER_SUM, OCM_DINO_CENTER_UPDATE = 0, 1  # ocm_op_dino_center modes
 
 (OCM_ATTN_BF16_WHOLE, OCM_ATTN_BF16_STREAM, OCM_ATTN_FP32_STREAM, OCM_ATTN_X3_WAVE_SPLIT, OCM_ATTN_X3_PIPELINED, OCM_ATTN_X3_DMA,
  OCM_ATTN_X3_DMA_KSPLIT) = range(7)
@@ -305,6 +306,15 @@ SIGNATURES = {
     "ocm_grad_norm_workspace_bytes": (_sz, [_vp, _i32]),
     "ocm_op_grad_norm": (C.c_int, [_vp, _i32, C.c_double, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ocm_op_grad_scale": (C.c_int, [_vp, _i32, _vp, _vp]),
+    "ocm_op_ema_update": (C.c_int, [_vp, _i32, C.c_double, _vp]),
+    "ocm_op_l2_normalize": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _vp]),
+    "ocm_op_l2_normalize_backward": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _vp]),
+    "ocm_op_weight_norm": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _vp]),
+    "ocm_op_weight_norm_backward": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp]),
+    "ocm_dino_loss_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "ocm_op_dino_loss": (C.c_int, [_vp, _vp, _vp, _f32, _f32, _i32, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "ocm_op_dino_loss_backward": (C.c_int, [_vp, _vp, _vp, _vp, _f32, _f32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "ocm_op_dino_center": (C.c_int, [_i32, _vp, _i64, _i32, _vp, _vp, C.c_double, C.c_double, _vp]),
     "ocm_sw_count": (_i32, [_i32, _i32]),
     "ocm_sw_origins": (_i32, [_i32, _i32, _i32, C.POINTER(_i32), _i32]),
     "ocm_sw_shard": (_i32, [_i32, _i32, _i32, C.POINTER(_i32), C.POINTER(_i32)]),

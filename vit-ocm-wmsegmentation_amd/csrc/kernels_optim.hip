@@ -11,6 +11,7 @@
 //   sumsq_kernel             one workgroup writes the float64 sum of squares of one chunk of a gradient to partial[global chunk].
 //   norm_finish_kernel       one workgroup adds the partials and writes the sum (float64), the norm and the clip coefficient.
 //   grad_scale_kernel        one workgroup multiplies one chunk of a gradient by the coefficient it reads from device memory.
+//   ema_kernel               one workgroup moves one chunk of a teacher tensor towards its student's (DINO's momentum encoder).
 // A thread owns quads of four consecutive elements (quad i of a chunk: thread i % 256, in rising i) and the chunk's tail of
 // count % 4 elements goes one element per thread: 16-byte loads and stores when every pointer of the tensor is 16-byte aligned
 // (OP_CHUNK is a multiple of 4, so a chunk is aligned as its tensor is), element accesses otherwise (a parameter that is a view
@@ -216,6 +217,35 @@ __global__ __launch_bounds__(OP_THREADS) void grad_scale_kernel(const OptimTable
     if (i < n) g[i] = g[i] * c;
 }
 
+// p = p * m + g * w (torch's p.mul_(m).add_(w * q)), one chunk per workgroup
+__global__ __launch_bounds__(OP_THREADS) void ema_kernel(const OptimTable tab, float m, float w) {
+    const uint32_t e = tab.map[blockIdx.x];
+    const int t = (int)(e >> 24);
+    const int64_t off = (int64_t)(e & 0xffffffu) * OP_CHUNK;
+    const int n = (int)std::min<int64_t>(OP_CHUNK, tab.count[t] - off);
+    float *p = tab.p[t] + off;
+    const float *g = tab.g[t] + off;
+    const bool vec = (((uintptr_t)p | (uintptr_t)g) & 15) == 0;
+    const int nq = n / 4;
+    for (int i = threadIdx.x; i < nq; i += OP_THREADS) {
+        f32x4 pv = load4(p + 4 * i, vec);
+        const f32x4 gv = load4(g + 4 * i, vec);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float keep = pv[k] * m;
+            const float add = gv[k] * w;
+            pv[k] = keep + add;
+        }
+        store4(p + 4 * i, pv, vec);
+    }
+    const int i = 4 * nq + (int)threadIdx.x;
+    if (i < n) {
+        const float keep = p[i] * m;
+        const float add = g[i] * w;
+        p[i] = keep + add;
+    }
+}
+
 int64_t chunks_of(int64_t count) { return (count + OP_CHUNK - 1) / OP_CHUNK; }
 
 // which of a descriptor's pointers an operator dereferences
@@ -331,6 +361,19 @@ extern "C" int ocm_op_optim_step(const OcmOptimTensor *tensors, int32_t n, const
             optim_step_kernel<RULE_ADAM><<<dim3(blocks), dim3(OP_THREADS), 0, st>>>(tab, s);
         else
             optim_step_kernel<RULE_SGD><<<dim3(blocks), dim3(OP_THREADS), 0, st>>>(tab, s);
+        HIP_TRY(hipGetLastError());
+        return OCM_OK;
+    });
+}
+
+extern "C" int ocm_op_ema_update(const OcmOptimTensor *tensors, int32_t n, double momentum, void *stream) {
+    if (!std::isfinite(momentum)) return fail(OCM_EINVAL, "ema_update: momentum = %g (finite)", momentum);
+    const int rc = check_table("ema_update", tensors, n, Needs{true, true, false, false});
+    if (rc != OCM_OK) return rc;
+    const float m = (float)momentum, w = (float)(1.0 - momentum);
+    const hipStream_t st = (hipStream_t)stream;
+    return for_each_launch(tensors, n, [&](const OptimTable &tab, int blocks, int64_t) -> int {
+        ema_kernel<<<dim3(blocks), dim3(OP_THREADS), 0, st>>>(tab, m, w);
         HIP_TRY(hipGetLastError());
         return OCM_OK;
     });

@@ -8,6 +8,9 @@ method signatures / return conventions of `VisionTransformer`
 (reference dino/vision_transformer.py:135-256), so eval.py:60-77,136, sw_processing.py:181-239,
 analyse_attention.py:55-116 and the subclasses in model.py:11-53,110-139 bind unchanged.
 
+`DINOHead` (:282-316) keeps its module tree and keys too and trains through a HIP backward; a plain `VisionTransformer` trains
+after `enable_training()` (DINO's student backbone).
+
 What is different: the nn.Linear / nn.Conv2d / nn.LayerNorm children are parameter containers.
 No forward below calls their ATen kernels; every method packs device pointers and calls the C ABI
 (include/ocm_vit.h). Inputs must be on a HIP device — there is deliberately no CPU fallback
@@ -399,6 +402,7 @@ class VisionTransformer(nn.Module):
     AUTO_GRAPH_TOKENS = 1024
     AUTO_GRAPH_ENTRIES = 8
     auto_graph = True
+    training_backward = False  # enable_training(): a plain attribute, not a parameter, not a buffer, not in the state_dict
 
     def _run(self, x, **kw):
         x = self._check_input(x)
@@ -500,7 +504,20 @@ class VisionTransformer(nn.Module):
             return attn
         return (xo, attn, qkv) if return_qkv else xo
 
+    def enable_training(self, flag=True):
+        """Opt this encoder in to (or out of) the HIP backward: in training mode with grad mode on and a trainable parameter,
+        forward() then returns the CLS row of model.py's _EncoderTrain path, with a graph into the encoder's parameters (DINO's
+        student backbone). The position table is the one of the input's own size at every call, so crops of several sizes go
+        through one model. A plain attribute, like VisionTransformerForFinetune.enable_finetune; without it nothing changes."""
+        self.training_backward = bool(flag)
+        return self
+
     def forward(self, x):
+        if self.training_backward and self.training and torch.is_grad_enabled():
+            from .. import model as _model  # (model.py imports this module)
+            if _model._differentiable(self):
+                _model._check_trainable(self, x, masked=False)
+                return _model._encode_train(self, x, None, own_size=True)[:, 0]
         return self._run(x, flags=_lib.OCM_OUT_FEAT)["feat"][0][:, 0]
 
     def forward_feats(self, x):
@@ -601,6 +618,223 @@ class GraphedCall:
         xs.copy_(x)
         graph.replay()
         return _tree_map(torch.clone, out) if clone else out
+
+
+def _linear_f32(lib, prec, a_op, w_op, bias, M, N, K):
+    out = torch.empty((M, N), dtype=torch.float32, device=bias.device)
+    _lib.check(lib.ocm_op_linear(prec, _p(a_op), _p(w_op), _p(bias), None, _p(out), M, N, K, _lib.OCM_EPI_BIAS_F32, _stream()))
+    return out
+
+
+def _head_zeros(head, n, dev):
+    return head._w.get(("zeros", n), (), lambda: torch.zeros(n, device=dev, dtype=torch.float32), dev)
+
+
+def _head_last_layer(head, prec, dev):
+    """(W fp32 (out, bottleneck), |v| per row, W as an operand) of the weight-normed last layer, rebuilt when weight_v or
+    weight_g changes."""
+    v, g = head.last_layer.weight_v, head.last_layer.weight_g
+
+    def make():
+        v32, g32 = _f32c(v), _f32c(g)
+        w, norm = torch.empty_like(v32), torch.empty(v32.shape[0], dtype=torch.float32, device=dev)
+        _lib.check(_lib.load().ocm_op_weight_norm(_p(v32), _p(g32), _p(w), _p(norm), v32.shape[0], v32.shape[1], _stream()))
+        return w, norm, to_operand(w, prec)
+
+    return head._w.get("last_layer", (v, g), make, (dev, prec))
+
+
+def _head_run(head, x32, prec):
+    """The head over fp32 rows x32 (rows, in_dim) -> (logits, [fp32 pre-activations of the hidden layers], normalised bottleneck
+    y, its row norms): ocm_op_linear + ocm_op_gelu per MLP layer, ocm_op_l2_normalize, the weight-normed last layer."""
+    lib, dev, rows = _lib.load(), x32.device, x32.shape[0]
+    a, pre, layers = to_operand(x32, prec), [], head._linears()
+    for j, (name, lin) in enumerate(layers):
+        w = lin.weight
+        w_op = head._w.get(name, (w,), lambda: to_operand(_f32c(w), prec), (dev, prec))
+        h = _linear_f32(lib, prec, a, w_op, _bias_or_zeros(lin), rows, lin.out_features, lin.in_features)
+        if j + 1 < len(layers):
+            a = torch.empty((rows, lin.out_features), dtype=OPERAND_DTYPE[prec], device=dev)
+            _lib.check(lib.ocm_op_gelu(prec, _p(h), _p(a), None, h.numel(), _stream()))
+            pre.append(h)
+    y, norm = torch.empty_like(h), torch.empty(rows, dtype=torch.float32, device=dev)
+    _lib.check(lib.ocm_op_l2_normalize(_p(h), _p(y), _p(norm), rows, h.shape[1], _stream()))
+    _, _, w_op = _head_last_layer(head, prec, dev)
+    out_dim = head.last_layer.out_features
+    logits = _linear_f32(lib, prec, to_operand(y, prec), w_op, _head_zeros(head, out_dim, dev), rows, out_dim, h.shape[1])
+    return logits, pre, y, norm
+
+
+class _DINOHeadTrain(torch.autograd.Function):
+    """DINOHead in training mode: forward(head, prec, x (rows, in_dim), *params) -> logits; backward -> the gradient of the input
+    rows and of every parameter, all through HIP: data gradients as ocm_op_linear on transposed operand copies, weight and bias
+    gradients through ocm_op_weight_grad, ocm_op_gelu_backward, ocm_op_l2_normalize_backward, ocm_op_weight_norm_backward. Kept:
+    the input rows, the fp32 pre-activation of every hidden layer, the normalised bottleneck and its norms."""
+
+    @staticmethod
+    def forward(ctx, head, prec, x, *params):
+        x32 = _f32c(x)
+        with torch.cuda.device(x32.device):
+            logits, pre, y, norm = _head_run(head, x32, prec)
+        ctx.head, ctx.prec, ctx.nhidden = head, prec, len(pre)
+        # through save_for_backward: freed after the backward, a second backward over the same graph is refused, and so is a
+        # parameter modified in place in between
+        ctx.save_for_backward(x32, y, norm, *pre, *params)
+        return logits
+
+    @staticmethod
+    def backward(ctx, gout):
+        from ..model import _weight_grad  # (model.py imports this module)
+        head, prec, nh = ctx.head, ctx.prec, ctx.nhidden
+        st = ctx.saved_tensors
+        x32, y, norm, pre, params = st[0], st[1], st[2], st[3:3 + nh], st[3 + nh:]
+        names = head._param_names()
+        P = dict(zip(names, params))
+        need = dict(zip(names, ctx.needs_input_grad[3:]))
+        lib, dev, rows = _lib.load(), x32.device, x32.shape[0]
+        grads = {}
+        with torch.cuda.device(dev):
+            g = _f32c(gout)
+            out_dim, bott = g.shape[1], y.shape[1]
+            w32, vnorm, _ = _head_last_layer(head, prec, dev)
+            if need.get("last_layer.weight_v") or need.get("last_layer.weight_g"):
+                dw, _ = _weight_grad(prec, g, y, False)
+                dg = torch.empty(out_dim, dtype=torch.float32, device=dev) if need.get("last_layer.weight_g") else None
+                dv = torch.empty_like(dw) if need.get("last_layer.weight_v") else None
+                _lib.check(lib.ocm_op_weight_norm_backward(_p(dw), _p(_f32c(P["last_layer.weight_v"])),
+                                                           _p(_f32c(P["last_layer.weight_g"])), _p(vnorm), _p(dg), _p(dv), out_dim,
+                                                           bott, _stream()))
+                grads["last_layer.weight_g"], grads["last_layer.weight_v"] = dg, dv
+            layers = head._linears()
+            if not (ctx.needs_input_grad[2] or any(need.get(n) for n in names if not n.startswith("last_layer."))):
+                return (None, None, None, *[_grad_like(grads.get(n), P[n]) for n in names])
+            # d logits -> d y: K = out_dim, padded with zero columns to the GEMM's K step where single bf16 needs a multiple of 64
+            kpad = -(-out_dim // 64) * 64 if prec == _lib.OCM_PREC_BF16 else out_dim
+            v_src = (head.last_layer.weight_v, head.last_layer.weight_g)
+
+            def w_t():
+                wt = torch.zeros((bott, kpad), dtype=torch.float32, device=dev)
+                wt[:, :out_dim] = w32.t()
+                return to_operand(wt, prec)
+
+            if kpad != out_dim:
+                gp = torch.zeros((rows, kpad), dtype=torch.float32, device=dev)
+                gp[:, :out_dim] = g
+            else:
+                gp = g
+            d = _linear_f32(lib, prec, to_operand(gp, prec), head._w.get("last_layer.T", v_src, w_t, (dev, prec)),
+                            _head_zeros(head, bott, dev), rows, bott, kpad)
+            _lib.check(lib.ocm_op_l2_normalize_backward(_p(d), _p(y), _p(norm), _p(d), rows, bott, _stream()))
+            dx = None
+            for j in reversed(range(len(layers))):
+                name, lin = layers[j]
+                w = P[name + ".weight"]
+                want_w, want_b = bool(need.get(name + ".weight")), bool(need.get(name + ".bias"))
+                if j == 0 and not ctx.needs_input_grad[2]:
+                    a32, dh = x32, None
+                else:
+                    w_op = head._w.get(name + ".T", (lin.weight,), lambda: to_operand(_f32c(w).t().contiguous(), prec), (dev, prec))
+                    dh = _linear_f32(lib, prec, to_operand(d, prec), w_op, _head_zeros(head, lin.in_features, dev), rows,
+                                     lin.in_features, lin.out_features)
+                    if j == 0:
+                        a32 = x32
+                    else:
+                        a32 = torch.empty_like(dh)
+                        _lib.check(lib.ocm_op_gelu_backward(_p(dh), _p(pre[j - 1]), _p(dh), _p(a32), dh.numel(), _stream()))
+                if want_w or want_b:
+                    dw, db = _weight_grad(prec, d, a32, want_b)
+                    grads[name + ".weight"], grads[name + ".bias"] = (dw if want_w else None), db
+                if j == 0:
+                    dx = dh
+                d = dh
+        return (None, None, dx, *[_grad_like(grads.get(n), P[n]) for n in names])
+
+
+def _grad_like(t, like):
+    return None if t is None else t.reshape(like.shape).to(device=like.device, dtype=like.dtype)
+
+
+class DINOHead(nn.Module):
+    """The projection head of DINO — reference DINOHead (:282-316): an MLP of `nlayers` Linear layers (GELU between them,
+    BatchNorm1d after every hidden Linear with use_bn) down to bottleneck_dim, L2 normalisation, and a weight-normed bias-free
+    Linear to out_dim whose magnitudes weight_g start at 1 and stay frozen with norm_last_layer. Same module tree, initialisation
+    and state_dict keys (mlp.{0,2,4}.weight/bias or mlp.weight/bias, last_layer.weight_g / weight_v).
+
+    The modules hold the parameters; the arithmetic runs through ocm_op_linear, ocm_op_gelu, ocm_op_l2_normalize and
+    ocm_op_weight_norm in this module's `precision` ("bf16x3" by default; "bf16" / "fp32"). In eval mode or without grad: a plain
+    forward. In training mode with grad mode on and a trainable parameter: _DINOHeadTrain, whose backward is HIP and returns the
+    gradient of the input rows for the backbone. A use_bn head can be built and loaded but not run."""
+
+    def __init__(self, in_dim, out_dim, use_bn=False, norm_last_layer=True, nlayers=3, hidden_dim=2048, bottleneck_dim=256):
+        super().__init__()
+        depth = max(nlayers, 1)
+        if depth == 1:
+            self.mlp = nn.Linear(in_dim, bottleneck_dim)
+        else:
+            mods, width = [], in_dim
+            for _ in range(depth - 1):
+                mods.append(nn.Linear(width, hidden_dim))
+                if use_bn:
+                    mods.append(nn.BatchNorm1d(hidden_dim))
+                mods.append(nn.GELU())
+                width = hidden_dim
+            mods.append(nn.Linear(width, bottleneck_dim))
+            self.mlp = nn.Sequential(*mods)
+        self.apply(self._init_weights)  # (before the last layer exists: it keeps nn.Linear's own initialisation)
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")  # the weight_g / weight_v parametrisation is the one the checkpoints hold
+            self.last_layer = nn.utils.weight_norm(nn.Linear(bottleneck_dim, out_dim, bias=False))
+        self.last_layer.weight_g.data.fill_(1)
+        if norm_last_layer:
+            self.last_layer.weight_g.requires_grad = False
+        self.precision = _lib.DEFAULT_PRECISION
+        self._w = SourceCache()
+
+    def _init_weights(self, m):
+        if isinstance(m, nn.Linear):
+            trunc_normal_(m.weight, std=.02)
+            if m.bias is not None:
+                nn.init.constant_(m.bias, 0)
+
+    def _linears(self):
+        """[(state-dict prefix, nn.Linear)] of the MLP, in order."""
+        if isinstance(self.mlp, nn.Linear):
+            return [("mlp", self.mlp)]
+        return [(f"mlp.{i}", m) for i, m in enumerate(self.mlp) if isinstance(m, nn.Linear)]
+
+    def _param_names(self):
+        """The parameters _DINOHeadTrain differentiates, in the order it takes them."""
+        names = [f"{n}.{k}" for n, lin in self._linears() for k in ("weight", "bias") if lin._parameters.get(k) is not None]
+        return names + ["last_layer.weight_g", "last_layer.weight_v"]
+
+    def _check(self, x):
+        if any(isinstance(m, nn.modules.batchnorm._BatchNorm) for m in self.modules()):
+            raise NotImplementedError("DINOHead(use_bn=True) is not implemented on the HIP path: the head can be built and loaded, "
+                                      "not run")
+        layers = self._linears()
+        widths = [layers[0][1].in_features] + [lin.out_features for _, lin in layers]
+        out_dim = self.last_layer.out_features
+        if any(w % 64 for w in widths) or out_dim % 32:
+            raise ValueError(f"DINOHead widths {widths} -> {out_dim}: the HIP GEMMs need in_dim, hidden_dim and bottleneck_dim that "
+                             "are multiples of 64 and an out_dim that is a multiple of 32")
+        _require_hip(x, "DINOHead input")
+        if x.shape[-1] != widths[0] or x.numel() == 0:
+            raise ValueError(f"DINOHead input {tuple(x.shape)}: expected rows of {widths[0]} features")
+        for p in self.parameters():
+            if p.device != x.device:
+                raise RuntimeError(f"parameters are on {p.device} but the input is on {x.device}; call head.to(device)")
+
+    def forward(self, x):
+        self._check(x)
+        prec = _module_prec(self)
+        rows = x.reshape(-1, x.shape[-1])
+        if self.training and torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            named = dict(self.named_parameters())
+            out = _DINOHeadTrain.apply(self, prec, rows, *[named[n] for n in self._param_names()])
+        else:
+            with torch.cuda.device(x.device):
+                out = _head_run(self, _f32c(rows), prec)[0]
+        return out.reshape(*x.shape[:-1], out.shape[-1])
 
 
 def vit_tiny(patch_size=16, **kwargs):

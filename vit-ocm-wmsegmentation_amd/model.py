@@ -572,17 +572,24 @@ def _first_block_to_train(enc, named):
     return min(trainable) if trainable else len(enc.blocks)
 
 
-def _encode_train(enc, x, mask):
-    """Differentiable token path of VisionTransformerForSimMIM (with its mask) and of VisionTransformerForFinetune (mask None:
-    no blend): (B, N, D) normed tokens with a graph into the encoder's parameters."""
+def _encode_train(enc, x, mask, own_size=False):
+    """Differentiable token path of VisionTransformerForSimMIM (with its mask), of VisionTransformerForFinetune (mask None: no
+    blend) and, with own_size, of a plain VisionTransformer that has opted in (enable_training): (B, N, D) normed tokens with a
+    graph into the encoder's parameters. The position table is the one of the configured size for the two map encoders
+    (_FmapEncoder._positions) and the one of the input's own (w, h) with own_size, as prepare_tokens takes it at every call."""
     x = enc._check_input(x).contiguous()
     if mask is not None or "mask_token" in enc._parameters:
         _check_mask(enc, x, mask)
     eng = enc._engine(x.device)
     npatch = (x.shape[-2] // eng.p) * (x.shape[-1] // eng.p)
     named = _encoder_params(enc)
-    meta = {"enc": enc, "eng": eng, "names": [n for n, _ in named], "pos": enc._positions(npatch, x.device),
-            "side": enc.img_size[0], "npatch": npatch,
+    wh = (x.shape[-2], x.shape[-1]) if own_size else (enc.img_size[0], enc.img_size[0])
+    if own_size:  # one cached table per crop size: a step alternates between the global and the local crops' sizes
+        pos = enc._pos_cache.get(("pos", wh), (enc.pos_embed,), lambda: enc._interpolated_pos(npatch, *wh)[0].to(
+            device=x.device, dtype=torch.float32).contiguous(), (npatch, x.device))
+    else:
+        pos = enc._positions(npatch, x.device)
+    meta = {"enc": enc, "eng": eng, "names": [n for n, _ in named], "pos": pos, "wh": wh, "npatch": npatch,
             "first": _first_block_to_train(enc, named),
             "mask": mask.reshape(x.shape[0], -1).to(torch.float32).contiguous() if mask is not None else None}
     with torch.cuda.device(x.device):
@@ -793,7 +800,7 @@ class _EncoderTrain(torch.autograd.Function):
                 # back through the host-side bicubic resampling of _interpolated_pos, with torch autograd on the small table
                 pe = params["pos_embed"].detach().float().cpu().requires_grad_(True)
                 with torch.enable_grad():
-                    full = enc._interpolated_pos(meta["npatch"], meta["side"], meta["side"], pos=pe)
+                    full = enc._interpolated_pos(meta["npatch"], *meta["wh"], pos=pe)
                     (gpe,) = torch.autograd.grad(full, pe, dpos.cpu().reshape(full.shape))
                 grads["pos_embed"] = gpe
         return (None, None, *[put(n) for n in names])

@@ -872,6 +872,62 @@ int ocm_op_resample_u8(const uint8_t *src, int64_t stride_b, int64_t stride_y, i
                        const int32_t *ycoeffs, int32_t yksize, int32_t per_image, int32_t out_h, int32_t out_w, uint8_t *out_u8,
                        float *out_f32, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- DINO's augmentations per pixel: ColorJitter, RandomGrayscale, GaussianBlur, Solarization, ToTensor + Normalize
+ * (dino/utils.py:36-68 and upstream main_dino.py's DataAugmentationDINO; kernels_augment.hip) ----
+ * Restated from Pillow's libImaging (BoxBlur.c, Blend.c, Convert.c) and ImageEnhance / ImageOps, pinned on the live library by
+ * tests/test_augment_host.py. Images are dense uint8 (batch, h, w, 3), 1..65535 images of up to 2^26 pixels; every per-image
+ * choice is a table on the device, so one call serves a batch in which each image has its own parameters. Stream-ordered,
+ * nothing synchronises with the host; float arithmetic is C's statements one by one (no fused multiply-add).
+ *
+ * ocm_op_color_u8: the point operations of one view, in that view's own order. out may be src. Per image:
+ *   ops[4], factors[4]  four slots run in order, each OCM_COLOR_NONE or
+ *     BRIGHTNESS / CONTRAST / SATURATION  ImageEnhance = Image.blend(degenerate, image, f): per byte in float32
+ *       t = d + f * (x - d), truncated when 0 <= f <= 1, else clipped to 0..255 and truncated. d = 0 for brightness; the pixel's
+ *       L = (19595 r + 38470 g + 7471 b + 0x8000) >> 16 for saturation; int(mean(L) + 0.5) for contrast, the mean a double
+ *       quotient of the exact integer sum of L over the image as it stands when that slot runs
+ *     HUE  convert('HSV'), H += (int)factor modulo 256, convert('RGB') (Convert.c's float / double statements; round() puts
+ *       halves away from zero); the factor holds the byte shift, torchvision's uint8(hue_factor * 255)
+ *   flags[3]  grey != 0: L to all three channels (convert('L')); solarize != 0 with threshold: x < threshold ? x : 255 - x
+ *             (ImageOps.solarize), after grey
+ * The workspace (8-byte aligned, ocm_color_u8_workspace_bytes: 0 for a batch the operator refuses) holds one 64-bit sum per
+ * image and slot; the operator zeroes it in stream order and the images add to it in integer atomics (exact in any order).
+ * Factors are finite. Five launches: one per slot for the images whose slot is a contrast (the others leave at once), one to apply.
+ * Refused before any launch with OCM_EINVAL (a short or null workspace: OCM_ENOMEM): null pointers, batch outside 1..65535, h or
+ * w < 1, more than 2^26 pixels, a workspace that is not 8-byte aligned. */
+#define OCM_COLOR_NONE 0
+#define OCM_COLOR_BRIGHTNESS 1
+#define OCM_COLOR_CONTRAST 2
+#define OCM_COLOR_SATURATION 3
+#define OCM_COLOR_HUE 4
+size_t ocm_color_u8_workspace_bytes(int32_t batch);
+int ocm_op_color_u8(const uint8_t *src, uint8_t *out, int32_t batch, int32_t h, int32_t w, const int32_t *ops,
+                    const float *factors, const int32_t *flags, void *workspace, size_t workspace_bytes, void *stream);
+/* Image.filter(ImageFilter.GaussianBlur(radius)): three box-blur passes along the rows, then three along the columns, in 8.24
+ * fixed point with the rounding to bytes after every pass.
+ * ocm_gaussian_blur_table (host, no device) gives table[3] = r, ww, fw of one radius as BoxBlur.c forms them, in float variables:
+ *   s2 = radius * radius / 3; L = sqrt(12.0 * s2 + 1.0); l = floor((L - 1.0) / 2.0);
+ *   a = (2 l + 1)(l (l + 1) - 3 s2) / (6 (s2 - (l + 1)^2)); fr = l + a;
+ *   r = (int)fr; ww = (uint32)(2^24 / (2 fr + 1)); fw = (2^24 - (2 r + 1) ww) / 2
+ * Radius 0 gives (0, 2^24, 0), the identity: "not blurred this time" shares the launch. Refused with OCM_EINVAL: a null table, a
+ * radius that is NaN, negative or above 4096.
+ * One pass of a line: out[x] = (ww * sum_{i=-r..r} in[clamp(x+i)] + fw * (in[clamp(x-r-1)] + in[clamp(x+r+1)]) + 2^23) >> 24 in
+ * uint32, the clamp to the line's ends on that pass's own input; r may exceed the line.
+ * ocm_op_gaussian_blur_u8: table is device memory, [batch][3]. Two launches, one per axis: a workgroup holds whole lines in LDS
+ * through the three passes, so an axis holds at most ocm_gaussian_blur_max_axis() = 1024 pixels. solarize (device, [batch], or
+ * null) is a threshold per image applied after the blur, x < threshold ? x : 255 - x; 256 leaves the image as it is (upstream's
+ * second global view solarizes after its blur). Outputs, either or both: out_u8 (batch, h, w, 3) and out_f32 (batch, 3, h, w) =
+ * ((float)u8 / 255.0f - mean[c]) / std[c] as separate float32 operations (ToTensor, then Normalize's sub_().div_()); mean and std
+ * are host arrays of three floats read during the call, both null for plain ToTensor. The workspace (ocm_gaussian_blur_u8_
+ * workspace_bytes: 0 for arguments the operator refuses) needs no initialisation; out_u8 may be src.
+ * Refused before any launch with OCM_EINVAL (a short or null workspace: OCM_ENOMEM): null src or table, both outputs null, one of
+ * mean / std without the other, batch outside 1..65535, h or w outside 1..1024. */
+int ocm_gaussian_blur_table(float radius, uint32_t *table);
+int32_t ocm_gaussian_blur_max_axis(void);
+size_t ocm_gaussian_blur_u8_workspace_bytes(int32_t batch, int32_t h, int32_t w);
+int ocm_op_gaussian_blur_u8(const uint8_t *src, int32_t batch, int32_t h, int32_t w, const uint32_t *table,
+                            const int32_t *solarize, uint8_t *out_u8, float *out_f32, const float *mean, const float *std,
+                            void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- the optimizer step, the gradient norm and its clipping (optimizer.py, utils.py:363 get_grad_norm, mim.py's and train.py's
  * clip_grad_norm_; kernels_optim.hip) ----
  * fp32 tensors, many per call: the host array `tensors` describes them, the operator cuts it into launches whose table of

@@ -133,6 +133,7 @@ class OcmOptimHyper(C.Structure):  # ocm_op_optim_step: the values of one step, 
 
 OCM_OPTIM_ADAMW, OCM_OPTIM_ADAM, OCM_OPTIM_SGD = 0, 1, 2
 OCM_DINO_CENTER_SUM, OCM_DINO_CENTER_UPDATE = 0, 1  # ocm_op_dino_center modes
+OCM_COLOR_NONE, OCM_COLOR_BRIGHTNESS, OCM_COLOR_CONTRAST, OCM_COLOR_SATURATION, OCM_COLOR_HUE = range(5)  # ocm_op_color_u8 slots
 
 (OCM_ATTN_BF16_WHOLE, OCM_ATTN_BF16_STREAM, OCM_ATTN_FP32_STREAM, OCM_ATTN_X3_WAVE_SPLIT, OCM_ATTN_X3_PIPELINED, OCM_ATTN_X3_DMA,
  OCM_ATTN_X3_DMA_KSPLIT) = range(7)
@@ -301,6 +302,12 @@ SIGNATURES = {
     "ocm_resample_u8_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32]),
     "ocm_op_resample_u8": (C.c_int, [_vp, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _i32,
                                      _i32, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "ocm_color_u8_workspace_bytes": (_sz, [_i32]),
+    "ocm_op_color_u8": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "ocm_gaussian_blur_table": (C.c_int, [_f32, _vp]),
+    "ocm_gaussian_blur_max_axis": (_i32, []),
+    "ocm_gaussian_blur_u8_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "ocm_op_gaussian_blur_u8": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ocm_optim_limits": (None, [C.POINTER(_i32), C.POINTER(_i32)]),
     "ocm_op_optim_step": (C.c_int, [_vp, _i32, C.POINTER(OcmOptimHyper), _vp]),
     "ocm_grad_norm_workspace_bytes": (_sz, [_vp, _i32]),

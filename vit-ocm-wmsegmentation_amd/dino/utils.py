@@ -7,6 +7,11 @@
                                 cross-entropy between the centred, sharpened teacher softmax of the two global crops and the
                                 student's log-softmax of every other crop; the centre is a momentum average of the teacher logits
   ema_update                    the teacher's exponential moving average of main_dino.py's training loop
+  GaussianBlur, Solarization    dino/utils.py:36-68 for a uint8 (B, H, W, 3) batch on the device, every image with its own draw
+  DataAugmentationDINO, dino_augment_params
+                                upstream main_dino.py's multi-crop transform for a batch of decoded tiles: every random choice drawn
+                                on the host into per-image tables, then 2 + n resamples (utils.pil_resize) and, per crop size,
+                                one colour and one blur call (kernels_augment.hip), byte for byte what the Pillow chain gives
 
 The loss, its gradient, the centre and the EMA are kernels_dino.hip / kernels_optim.hip (include/ocm_vit.h); clip_gradients runs the
 gradient-norm table operators of the optimizer, one tensor per table. fp32 tensors on one HIP device; there is no CPU or eager
@@ -14,17 +19,19 @@ fall-back. Raw-pointer writes (centre, teacher parameters, clipped gradients) ra
 does, so operand caches and engines see them.
 """
 import math
+import random
 
 import numpy as np
 import torch
 import torch.nn as nn
 
-from .. import _lib
+from .. import _lib, data, utils
 from ..engine import _p, _require_hip, _stream, _ws
 from ..optimizer import get_params_groups  # DINO's two parameter groups: one statement, shared with optimizer.py
 
 __all__ = ["trunc_normal_", "MultiCropWrapper", "DINOLoss", "ema_update", "get_params_groups", "has_batchnorms",
-           "cosine_scheduler", "clip_gradients", "cancel_gradients_last_layer"]
+           "cosine_scheduler", "clip_gradients", "cancel_gradients_last_layer", "GaussianBlur", "Solarization",
+           "DataAugmentationDINO", "dino_augment_params"]
 
 
 def trunc_normal_(tensor, mean=0., std=1., a=-2., b=2.):
@@ -238,3 +245,138 @@ class DINOLoss(nn.Module):
             _lib.check(lib.ocm_op_dino_center(_lib.OCM_DINO_CENTER_UPDATE, None, 0, K, _p(batch_sum), _p(self.center),
                                               float(rows * world), float(self.center_momentum), _stream()))
         torch.autograd.graph.increment_version(self.center)
+
+
+# ---- the multi-crop augmentation (dino/utils.py:36-68; upstream main_dino.py DataAugmentationDINO; kernels_augment.hip) ----------
+IMAGENET_MEAN, IMAGENET_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
+SOLARIZE_THRESHOLD, SOLARIZE_OFF = 128, 256  # ImageOps.solarize's default; a threshold no byte reaches
+
+
+class GaussianBlur:
+    """dino/utils.py:36-54 for a batch: per image `random() <= p`, then `uniform(radius_min, radius_max)`, from `rng` (a
+    random.Random; the module's global stream when None), and Pillow's ImageFilter.GaussianBlur of that radius on the device. An
+    image that is not blurred has radius 0, which copies it: one call serves the batch."""
+
+    def __init__(self, p=0.5, radius_min=0.1, radius_max=2., rng=None):
+        self.prob = p
+        self.radius_min = radius_min
+        self.radius_max = radius_max
+        self.rng = rng
+
+    def draw(self):
+        """The radius of one image: 0.0 when it is not blurred."""
+        rng = self.rng or random
+        if not rng.random() <= self.prob:
+            return 0.0
+        return rng.uniform(self.radius_min, self.radius_max)
+
+    def __call__(self, images_u8):
+        return utils.pil_gaussian_blur(images_u8, np.array([self.draw() for _ in range(images_u8.shape[0])], np.float32))
+
+
+class Solarization:
+    """dino/utils.py:57-68 for a batch: per image `random() < p` from `rng`, then ImageOps.solarize on the device."""
+
+    def __init__(self, p, rng=None):
+        self.p = p
+        self.rng = rng
+
+    def draw(self):
+        return (self.rng or random).random() < self.p
+
+    def __call__(self, images_u8):
+        on = np.array([self.draw() for _ in range(images_u8.shape[0])], bool)
+        return utils.pil_color(images_u8, utils.COLOR_NONE, 0.0, solarize=on, threshold=SOLARIZE_THRESHOLD)
+
+
+def _color_jitter_params(generator, brightness=0.4, contrast=0.4, saturation=0.2, hue=0.1):
+    """torchvision's ColorJitter.get_params on a torch.Generator: randperm(4), then one uniform_ each for brightness, contrast,
+    saturation and hue. Returns the four slots in the order they run as (op, factor): the enhancement factor as the float32 Pillow
+    receives, for the hue the byte shift int(hue_factor * 255) modulo 256 (the uint8 cast of torchvision's adjust_hue on x86)."""
+    order = torch.randperm(4, generator=generator).tolist()
+    ranges = ((max(0.0, 1.0 - brightness), 1.0 + brightness), (max(0.0, 1.0 - contrast), 1.0 + contrast),
+              (max(0.0, 1.0 - saturation), 1.0 + saturation), (-hue, hue))
+    values = [float(torch.empty(1).uniform_(lo, hi, generator=generator)) for lo, hi in ranges]
+    values[3] = float(int(values[3] * 255) % 256)
+    return [(fn + 1, values[fn]) for fn in order]  # utils.COLOR_BRIGHTNESS .. COLOR_HUE are torchvision's fn_id + 1
+
+
+def dino_augment_params(batch, height, width, global_crops_scale=(0.4, 1.), local_crops_scale=(0.05, 0.4), local_crops_number=8,
+                        generator=None, rng=None):
+    """Every random choice of upstream's DataAugmentationDINO for `batch` images of height x width, drawn on the host: image after
+    image and, within an image, view after view (global 1, global 2, the local views), each in its Compose's order:
+      RandomResizedCrop.get_params (data.random_resized_crop_params), rand(1) < 0.5 for the flip, rand(1) for RandomApply (the
+      jitter runs unless 0.8 < it) and only then ColorJitter.get_params (randperm(4) and four uniform_), rand(1) < 0.2 for grey,
+      all from `generator` (a torch.Generator; torch's global stream when None); then GaussianBlur's draws (p = 1.0, 0.1, 0.5
+      for global 1, global 2, local) and, for global 2, Solarization's (p = 0.2) from `rng` (a random.Random, or the module's).
+    Returns one table per view, 2 + local_crops_number dicts of numpy arrays over the images: crops (B,4) int64 (x0, y0, x1, y1),
+    hflip (B,) bool, ops (B,4) int32 and factors (B,4) float32 (utils.pil_color's slots; all COLOR_NONE when RandomApply
+    skipped the jitter), grey (B,) bool, radius (B,) float32 (0: not blurred), solarize (B,) bool.
+    torchvision is not installed here, so the parity of the torch stream with a live torchvision is unpinned, as for
+    data.random_resized_crop_params; what the tables do to the pixels is pinned on live Pillow (tests/test_augment_host.py)."""
+    B, V = int(batch), 2 + int(local_crops_number)
+    blurs = [GaussianBlur(1.0, rng=rng), GaussianBlur(0.1, rng=rng)] + [GaussianBlur(0.5, rng=rng)] * (V - 2)
+    solarization = Solarization(0.2, rng=rng)
+    views = [dict(crops=np.zeros((B, 4), np.int64), hflip=np.zeros(B, bool), ops=np.zeros((B, 4), np.int32),
+                  factors=np.zeros((B, 4), np.float32), grey=np.zeros(B, bool), radius=np.zeros(B, np.float32),
+                  solarize=np.zeros(B, bool)) for _ in range(V)]
+    for b in range(B):
+        for v, view in enumerate(views):
+            i, j, h, w = data.random_resized_crop_params(height, width, global_crops_scale if v < 2 else local_crops_scale,
+                                                         generator=generator)
+            view["crops"][b] = (j, i, j + w, i + h)
+            view["hflip"][b] = bool(torch.rand(1, generator=generator).item() < 0.5)
+            if not 0.8 < torch.rand(1, generator=generator).item():
+                slots = _color_jitter_params(generator)
+                view["ops"][b] = [op for op, _ in slots]
+                view["factors"][b] = [f for _, f in slots]
+            view["grey"][b] = bool(torch.rand(1, generator=generator).item() < 0.2)
+            view["radius"][b] = blurs[v].draw()
+            if v == 1:
+                view["solarize"][b] = solarization.draw()
+    return views
+
+
+class DataAugmentationDINO:
+    """Upstream main_dino.py's DataAugmentationDINO for a batch of decoded tiles on the device. __call__ takes uint8 (B, H, W, 3)
+    and returns the list MultiCropWrapper takes: 2 + local_crops_number float32 tensors (B, 3, S, S), element v holding view v of
+    every image (S = global_size for the first two, local_size after them). The transforms are upstream's: RandomResizedCrop
+    (BICUBIC), a flip (0.5), RandomApply(ColorJitter(0.4, 0.4, 0.2, 0.1), 0.8), RandomGrayscale(0.2), GaussianBlur (p = 1.0 / 0.1
+    / 0.5), Solarization(0.2) on the second global view, ToTensor and Normalize with ImageNet's mean and std.
+    A step is 2 + n resample calls (one per view, every image with its own rectangle and flip) and, per crop size, one colour call
+    and one blur call on that size's views concatenated; the blur's column launch solarizes, converts and normalises as it stores."""
+
+    def __init__(self, global_crops_scale=(0.4, 1.), local_crops_scale=(0.05, 0.4), local_crops_number=8, global_size=224,
+                 local_size=96, generator=None, rng=None):
+        self.global_crops_scale, self.local_crops_scale = tuple(global_crops_scale), tuple(local_crops_scale)
+        self.local_crops_number = int(local_crops_number)
+        self.global_size, self.local_size = int(global_size), int(local_size)
+        self.generator, self.rng = generator, rng
+        self.mean, self.std = IMAGENET_MEAN, IMAGENET_STD
+
+    def params(self, batch, height, width):
+        return dino_augment_params(batch, height, width, self.global_crops_scale, self.local_crops_scale, self.local_crops_number,
+                                   self.generator, self.rng)
+
+    def __call__(self, images_u8, params=None):
+        if not isinstance(images_u8, torch.Tensor) or images_u8.dtype != torch.uint8 or images_u8.dim() != 4 or images_u8.shape[3] != 3:
+            raise ValueError(f"expected a uint8 (B, H, W, 3) batch of decoded tiles, got {getattr(images_u8, 'dtype', type(images_u8))} "
+                             f"{tuple(getattr(images_u8, 'shape', ()))}")
+        _require_hip(images_u8, "images")
+        B, H, W, _ = images_u8.shape
+        views = self.params(B, H, W) if params is None else list(params)
+        if len(views) != 2 + self.local_crops_number:
+            raise ValueError(f"{len(views)} view tables for 2 + {self.local_crops_number} views")
+        out = []
+        for group, size in ((views[:2], self.global_size), (views[2:], self.local_size)):
+            if not group:
+                continue
+            crops = torch.cat([utils.pil_resize(images_u8, (size, size), utils.BICUBIC, crop=v["crops"], hflip=v["hflip"],
+                                                to_tensor=False) for v in group])
+            table = {k: np.concatenate([np.asarray(v[k]) for v in group]) for k in ("ops", "factors", "grey", "radius", "solarize")}
+            utils.pil_color(crops, table["ops"], table["factors"], grey=table["grey"], out=crops)
+            done = utils.pil_gaussian_blur(crops, table["radius"],
+                                           solarize=np.where(table["solarize"], SOLARIZE_THRESHOLD, SOLARIZE_OFF), to_tensor=True,
+                                           mean=self.mean, std=self.std)
+            out.extend(done[i * B:(i + 1) * B] for i in range(len(group)))
+        return out

@@ -27,6 +27,10 @@ region-query index of analyse_attention.py, on device.
                       PIL.Image.resize / Image.crop(...).resize / ToTensor of uint8 images (sw_processing.py:217-231,
                       analyse_attention.py:102-120, data.py's transforms), byte for byte, for a batch in one call on device
                       (kernels_resample.hip); the transforms themselves are in data.py
+  pil_color, pil_gaussian_blur, gaussian_blur_table
+                      ImageEnhance.{Brightness, Contrast, Color}, the convert('HSV') round trip of adjust_hue, convert('L'),
+                      ImageOps.solarize, ImageFilter.GaussianBlur and ToTensor + Normalize of uint8 RGB batches, byte for byte,
+                      every image with its own parameters (kernels_augment.hip); DINO's transform itself is in dino/utils.py
   clip_grad_norm_, grad_norm, get_grad_norm
                       torch.nn.utils.clip_grad_norm_ (mim.py, train.py) and reference utils.py:363-373, the 2-norm of every
                       gradient in one multi-tensor pass with float64 sums and the scaling by a coefficient that never leaves
@@ -848,6 +852,103 @@ def pil_resize(images_u8, size, resample=BICUBIC, box=None, crop=None, hflip=Non
     if to_tensor not in (False, True, "both"):
         raise ValueError(f"to_tensor = {to_tensor!r} (False, True or 'both')")
     return ResamplePlan(images_u8, size, resample, box, crop, hflip, vflip, layout).run(images_u8, to_tensor)
+
+
+# ---- Pillow's point operations and Gaussian blur for a batch (ImageEnhance, convert('HSV' / 'L'), ImageOps.solarize,
+# ImageFilter.GaussianBlur, ToTensor + Normalize; kernels_augment.hip) -------------------------------------------------------------
+COLOR_NONE, COLOR_BRIGHTNESS, COLOR_CONTRAST, COLOR_SATURATION, COLOR_HUE = range(5)  # the slots of pil_color
+
+
+def gaussian_blur_table(radius):
+    """(r, ww, fw) of every radius as Pillow's box blur forms them (ocm_gaussian_blur_table, host): uint32 (n, 3)."""
+    radii = np.atleast_1d(np.asarray(radius, dtype=np.float32))
+    table = np.empty((radii.size, 3), np.uint32)
+    lib = _lib.load()
+    for i, r in enumerate(radii.reshape(-1)):
+        _lib.check(lib.ocm_gaussian_blur_table(float(r), table[i].ctypes.data_as(C.c_void_p)))
+    return table
+
+
+def _u8_batch_rgb(images_u8, what):
+    if not isinstance(images_u8, torch.Tensor) or images_u8.dtype != torch.uint8 or images_u8.dim() != 4 or images_u8.shape[-1] != 3:
+        raise ValueError(f"{what}: expected a uint8 (B,H,W,3) batch, got {getattr(images_u8, 'dtype', type(images_u8))} "
+                         f"{tuple(getattr(images_u8, 'shape', ()))}")
+    _require_hip(images_u8, what)
+    return images_u8.contiguous()
+
+
+def _per_image_table(value, shape, dtype, what):
+    """One value for the whole batch, or one per image -> a contiguous array of `shape`."""
+    if isinstance(value, torch.Tensor):
+        value = value.cpu().numpy()
+    try:
+        return np.ascontiguousarray(np.broadcast_to(np.asarray(value, dtype=dtype), shape))
+    except ValueError:
+        raise ValueError(f"{what}: shape {np.shape(value)} for {shape}") from None
+
+
+def pil_color(images_u8, ops, factors, grey=False, solarize=False, threshold=128, out=None):
+    """The point operations of torchvision's ColorJitter / RandomGrayscale on PIL images and ImageOps.solarize for a uint8
+    (B,H,W,3) HIP batch in one ocm_op_color_u8 call, byte for byte what Pillow gives (tests/test_augment_host.py), every image
+    with its own parameters. ops (B,4): COLOR_* slots run in order; factors (B,4) float32: the enhancement factor of
+    ImageEnhance.{Brightness, Contrast, Color}, or for COLOR_HUE the byte shift uint8(hue_factor * 255). grey / solarize: a flag
+    or one per image (grey, then solarize with `threshold`, after the slots). out: the batch itself for an in-place call."""
+    x = _u8_batch_rgb(images_u8, "images")
+    B, H, W, _ = x.shape
+    ops = _per_image_table(ops, (B, 4), np.int32, "ops")
+    if ((ops < COLOR_NONE) | (ops > COLOR_HUE)).any():
+        raise ValueError("ops: slots are COLOR_NONE .. COLOR_HUE (0..4)")
+    fac = _per_image_table(factors, (B, 4), np.float32, "factors")
+    if not np.isfinite(fac).all():
+        raise ValueError("factors must be finite")
+    flags = np.stack([_per_image_table(grey, (B,), np.int32, "grey"), _per_image_table(solarize, (B,), np.int32, "solarize"),
+                      _per_image_table(threshold, (B,), np.int32, "threshold")], 1)
+    if out is None:
+        out = torch.empty_like(x)
+    elif out.dtype != torch.uint8 or out.shape != x.shape or out.device != x.device or not out.is_contiguous():
+        raise ValueError("out: a contiguous uint8 tensor of the batch's shape on its device")
+    dev, lib = x.device, _lib.load()
+    tables = torch.from_numpy(np.concatenate([ops.reshape(-1), fac.view(np.int32).reshape(-1), flags.reshape(-1)])).to(dev)
+    base = tables.data_ptr()
+    nbytes = lib.ocm_color_u8_workspace_bytes(B)
+    ws = _ws(nbytes, dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.ocm_op_color_u8(_p(x), _p(out), B, H, W, C.c_void_p(base), C.c_void_p(base + 16 * B), C.c_void_p(base + 32 * B),
+                                       _p(ws), nbytes, _stream()))
+    return out
+
+
+def pil_gaussian_blur(images_u8, radius, solarize=None, to_tensor=False, mean=None, std=None):
+    """Image.filter(ImageFilter.GaussianBlur(radius)) of every image of a uint8 (B,H,W,3) HIP batch in one
+    ocm_op_gaussian_blur_u8 call (two launches), byte for byte. radius: one value or one per image; 0 copies the image.
+    solarize: None, or per image a threshold applied after the blur (256: not solarized). Returns uint8 (B,H,W,3); with
+    to_tensor=True float32 (B,3,H,W) = ToTensor, then Normalize(mean, std) when the two are given; with "both" the pair."""
+    if to_tensor not in (False, True, "both"):
+        raise ValueError(f"to_tensor = {to_tensor!r} (False, True or 'both')")
+    if (mean is None) != (std is None):
+        raise ValueError("mean and std come together")
+    x = _u8_batch_rgb(images_u8, "images")
+    B, H, W, _ = x.shape
+    dev, lib = x.device, _lib.load()
+    cap = lib.ocm_gaussian_blur_max_axis()
+    if H > cap or W > cap:
+        raise ValueError(f"a {H} x {W} image: the blur holds an axis of up to {cap} pixels")
+    parts = [gaussian_blur_table(_per_image_table(radius, (B,), np.float32, "radius")).view(np.int32).reshape(-1)]
+    if solarize is not None:
+        parts.append(_per_image_table(solarize, (B,), np.int32, "solarize"))
+    tables = torch.from_numpy(np.concatenate(parts)).to(dev)
+    want_u8, want_f32 = to_tensor in (False, "both"), to_tensor in (True, "both")
+    out_u8 = torch.empty_like(x) if want_u8 else None
+    out_f32 = torch.empty((B, 3, H, W), dtype=torch.float32, device=dev) if want_f32 else None
+    norm = [None, None] if mean is None else [(C.c_float * 3)(*(float(v) for v in m)) for m in (mean, std)]
+    nbytes = lib.ocm_gaussian_blur_u8_workspace_bytes(B, H, W)
+    ws = _ws(nbytes, dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.ocm_op_gaussian_blur_u8(_p(x), B, H, W, C.c_void_p(tables.data_ptr()),
+                                               None if solarize is None else C.c_void_p(tables.data_ptr() + 12 * B), _p(out_u8),
+                                               _p(out_f32), *(None if m is None else C.cast(m, C.c_void_p) for m in norm), _p(ws),
+                                               nbytes, _stream()))
+    return (out_u8, out_f32) if to_tensor == "both" else out_f32 if to_tensor else out_u8
 
 
 # ---- the gradient norm and its clipping (torch.nn.utils.clip_grad_norm_, reference utils.py:363-373; kernels_optim.hip) -----------

@@ -596,6 +596,23 @@ int ocm_op_layernorm_backward(const float *dy, const float *x, const float *gamm
                               float *dbeta, int64_t rows, int32_t dim, float eps, void *workspace, size_t workspace_bytes,
                               void *stream);
 
+/* Stochastic depth (DropPath, dino/vision_transformer.py:25-44) behind a branch whose GEMM ran with OCM_EPI_BIAS_F32 into
+ * `branch`; scale [batch] fp32 holds 0 or 1 / keep per image, the image of a row is row / tokens (kernels_drop_path.hip).
+ *   x_out[b][t][:] = x[b][t][:] + branch[b][t][:] * scale[b]   (fp32: the product rounded, then the sum; x_out may alias x or
+ *   branch)
+ *   y              = LayerNorm(x_out; gamma, beta, eps) in out_kind (OCM_LN_F32 / OCM_LN_BF16 / OCM_LN_SPLIT), bit for bit
+ *   what ocm_op_layernorm makes of x_out.
+ * Every dim ocm_op_layernorm accepts. Null pointers, batch or tokens <= 0, a bad dim or out_kind return OCM_EINVAL before any
+ * launch. */
+int ocm_op_drop_path_layernorm(const float *x, const float *branch, const float *scale, const float *gamma, const float *beta,
+                               float *x_out, void *y, int32_t out_kind, int32_t batch, int32_t tokens, int32_t dim, float eps,
+                               void *stream);
+/* dbranch_f32 = dout * scale[image] (it may alias dout); dbranch_op (NULL for OCM_PREC_FP32) = the same values in the operand
+ * type of `precision` (bf16, or split pairs with dim % 32 == 0), as ocm_op_cast_bf16 / ocm_op_cast_split would write them from
+ * dbranch_f32. One pass; dim % 8 == 0. Refusals as above. */
+int ocm_op_drop_path_backward(int32_t precision, const float *dout, const float *scale, float *dbranch_f32, void *dbranch_op,
+                              int32_t batch, int32_t tokens, int32_t dim, void *stream);
+
 /* erf GELU (nn.GELU()) of `count` fp32 values: out in the operand type E of `precision` (count % 32 == 0 for split pairs, rows
  * whose length is a multiple of 32), out_f32 (optional) in fp32. */
 int ocm_op_gelu(int32_t precision, const float *h, void *out, float *out_f32, size_t count, void *stream);

@@ -263,6 +263,8 @@ SIGNATURES = {
     "ocm_op_attention_backward_delta": (C.c_int, [_i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "ocm_layernorm_backward_workspace_bytes": (_sz, [_i64, _i32]),
     "ocm_op_layernorm_backward": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _f32, _vp, _sz, _vp]),
+    "ocm_op_drop_path_layernorm": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _vp]),
+    "ocm_op_drop_path_backward": (C.c_int, [_i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     "ocm_op_gelu": (C.c_int, [_i32, _vp, _vp, _vp, _sz, _vp]),
     "ocm_op_gelu_backward": (C.c_int, [_vp, _vp, _vp, _vp, _sz, _vp]),
     "ocm_op_patch_unfold": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),

@@ -9,7 +9,8 @@ method signatures / return conventions of `VisionTransformer`
 analyse_attention.py:55-116 and the subclasses in model.py:11-53,110-139 bind unchanged.
 
 `DINOHead` (:282-316) keeps its module tree and keys too and trains through a HIP backward; a plain `VisionTransformer` trains
-after `enable_training()` (DINO's student backbone).
+after `enable_training()` (DINO's student backbone; DESIGN §3.37). `drop_path` / `DropPath` (:25-44) sit where the reference has them;
+on the training path the draws are `draw_drop_path_scales` and the arithmetic is HIP. Dropout proper stays refused.
 
 What is different: the nn.Linear / nn.Conv2d / nn.LayerNorm children are parameter containers.
 No forward below calls their ATen kernels; every method packs device pointers and calls the C ABI
@@ -48,6 +49,50 @@ def _bias_or_zeros(linear):
     if linear.bias is not None:
         return _f32c(linear.bias)
     return torch.zeros(linear.out_features, dtype=torch.float32, device=linear.weight.device)
+
+
+def drop_path(x, drop_prob: float = 0., training: bool = False):
+    """Stochastic depth per sample — reference drop_path (:25-33): in training mode every sample's branch is kept with
+    probability 1 - drop_prob and scaled by 1 / (1 - drop_prob), else zeroed. Identity in eval mode and at drop_prob 0."""
+    if drop_prob == 0. or not training:
+        return x
+    keep_prob = 1 - drop_prob
+    shape = (x.shape[0],) + (1,) * (x.ndim - 1)  # one draw per sample, whatever the tensor's rank
+    random_tensor = keep_prob + torch.rand(shape, dtype=x.dtype, device=x.device)
+    random_tensor.floor_()
+    return x.div(keep_prob) * random_tensor
+
+
+class DropPath(nn.Module):
+    """Drop paths (stochastic depth) per sample in the main path of a residual block — reference DropPath (:36-44). No
+    parameters. Inside a VisionTransformer the module marks the place and holds the rate: the training path draws the scales
+    (draw_drop_path_scales) and applies them in ocm_op_drop_path_layernorm; called directly it is the torch formula above."""
+
+    def __init__(self, drop_prob=None):
+        super().__init__()
+        self.drop_prob = drop_prob
+
+    def forward(self, x):
+        return drop_path(x, self.drop_prob, self.training)
+
+
+def draw_drop_path_scales(model, batch, device):
+    """The DropPath draws of one training forward over `batch` images, in execution order: 2 * depth entries, block 0's attention
+    branch, block 0's MLP branch, block 1's, ... An entry is None at rate 0 (the reference builds an Identity there and draws
+    nothing), else the fp32 (batch,) table floor(keep + rand) / keep with ONE torch.rand((batch, 1, 1)) call, as DropPath.forward
+    draws it: a seeded run consumes the device generator in the order the reference's forward would, and a kept image's scale is
+    1 / keep, a dropped one's 0. The training path looks this function up at every call."""
+    out = []
+    for blk in model.blocks:
+        rate = float(getattr(blk.drop_path, "drop_prob", None) or 0.)
+        for _ in range(2):
+            if rate == 0.:
+                out.append(None)
+                continue
+            keep = 1 - rate
+            rnd = torch.rand((batch, 1, 1), dtype=torch.float32, device=device)
+            out.append(torch.floor(keep + rnd).reshape(batch) / keep)
+    return out
 
 
 class LayerNorm(nn.LayerNorm):
@@ -160,7 +205,7 @@ class Block(nn.Module):
         self.norm1 = _make_norm(norm_layer, dim)
         self.attn = Attention(dim, num_heads=num_heads, qkv_bias=qkv_bias, qk_scale=qk_scale, attn_drop=attn_drop,
                               proj_drop=drop)
-        self.drop_path = nn.Identity()
+        self.drop_path = DropPath(drop_path) if drop_path > 0. else nn.Identity()
         self._drop_rates = (drop, attn_drop, drop_path)
         self.norm2 = _make_norm(norm_layer, dim)
         self.mlp = Mlp(in_features=dim, hidden_features=int(dim * mlp_ratio), act_layer=act_layer, drop=drop)
@@ -173,8 +218,8 @@ class Block(nn.Module):
         y, attn, qkv = self.attn(self.norm1(x))
         if return_attention:
             return attn
-        x = _f32c(x) + y
-        x = x + self.mlp(self.norm2(x))
+        x = _f32c(x) + self.drop_path(y)
+        x = x + self.drop_path(self.mlp(self.norm2(x)))
         return (x, attn, qkv) if return_qkv else x
 
 
@@ -234,7 +279,7 @@ class VisionTransformer(nn.Module):
         self._hyper = dict(patch_size=patch_size, in_chans=in_chans, embed_dim=embed_dim, depth=depth,
                            num_heads=num_heads, mlp_hidden=int(embed_dim * mlp_ratio), ln_eps=float(self.norm.eps),
                            qk_scale=float(qk_scale or (embed_dim // num_heads) ** -0.5))
-        self._drop_any = max(drop_rate, attn_drop_rate, drop_path_rate) > 0
+        self._dropout_any, self._drop_path_any = max(drop_rate, attn_drop_rate) > 0, drop_path_rate > 0
         self.__dict__["_engines"] = SourceCache()  # device -> Engine, made from _named_engine_params()
         self.__dict__["_pos_cache"] = SourceCache()  # "pos" -> the table of the latest (shape, device), made from pos_embed
         self.__dict__["_gray_fold"] = False
@@ -319,9 +364,15 @@ class VisionTransformer(nn.Module):
             return [p for mod, key, _ in cached[0] if (p := mod._parameters.get(key)) is not None]
         return [(n, p) for mod, key, n in cached[0] if (p := mod._parameters.get(key)) is not None]
 
-    def _engine(self, device):
-        if self.training and self._drop_any:
-            raise NotImplementedError("dropout / drop-path > 0 in training mode is outside the inference hot path")
+    def _engine(self, device, training_path=False):
+        """The engine of `device`. training_path: the caller is model.py's _encode_train, which applies drop-path itself."""
+        if self.training and self._dropout_any:
+            raise NotImplementedError("dropout (drop_rate / attn_drop_rate > 0) in training mode is not implemented on the HIP "
+                                      "path")
+        if self.training and self._drop_path_any and not training_path:
+            raise NotImplementedError("drop-path > 0 in training mode runs on the training path only: call .eval() for "
+                                      "inference, or train with grad mode on, a trainable parameter and the opt-in where the "
+                                      "class has one (enable_training(), enable_finetune())")
         params = self._named_engine_params(names=False)
         sig = signature(params)
         eng = self._engines.hit(device, sig)

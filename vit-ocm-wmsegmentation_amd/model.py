@@ -34,6 +34,7 @@ import torch.nn as nn
 
 from . import _lib
 from .dino.utils import trunc_normal_
+from .dino import vision_transformer as _vt
 from .dino.vision_transformer import VisionTransformer
 from .engine import OPERAND_DTYPE as _OPERAND_DTYPE, SourceCache, _p, _require_hip, _stream, _ws, to_operand
 
@@ -580,7 +581,7 @@ def _encode_train(enc, x, mask, own_size=False):
     x = enc._check_input(x).contiguous()
     if mask is not None or "mask_token" in enc._parameters:
         _check_mask(enc, x, mask)
-    eng = enc._engine(x.device)
+    eng = enc._engine(x.device, training_path=True)
     npatch = (x.shape[-2] // eng.p) * (x.shape[-1] // eng.p)
     named = _encoder_params(enc)
     wh = (x.shape[-2], x.shape[-1]) if own_size else (enc.img_size[0], enc.img_size[0])
@@ -590,10 +591,25 @@ def _encode_train(enc, x, mask, own_size=False):
     else:
         pos = enc._positions(npatch, x.device)
     meta = {"enc": enc, "eng": eng, "names": [n for n, _ in named], "pos": pos, "wh": wh, "npatch": npatch,
-            "first": _first_block_to_train(enc, named),
+            "first": _first_block_to_train(enc, named), "scales": _drop_path_scales(enc, x.shape[0], x.device),
             "mask": mask.reshape(x.shape[0], -1).to(torch.float32).contiguous() if mask is not None else None}
     with torch.cuda.device(x.device):
         return _EncoderTrain.apply(meta, x, *[p for _, p in named])
+
+
+def _drop_path_scales(enc, batch, dev):
+    """The per-image DropPath scale tables of one training forward (vision_transformer.draw_drop_path_scales, looked up at call
+    time): 2 * depth entries, None or a contiguous fp32 (batch,) tensor on `dev`. One call per _encode_train call, so DINO's
+    MultiCropWrapper draws per resolution group, as upstream's does."""
+    scales = list(_vt.draw_drop_path_scales(enc, batch, dev))
+    if len(scales) != 2 * len(enc.blocks):
+        raise ValueError(f"draw_drop_path_scales returned {len(scales)} entries for {len(enc.blocks)} blocks")
+    for j, sc in enumerate(scales):
+        if sc is not None:
+            if sc.numel() != batch:
+                raise ValueError(f"drop-path scale table {j} has {sc.numel()} entries for a batch of {batch}")
+            scales[j] = sc.detach().to(device=dev, dtype=torch.float32).reshape(batch).contiguous()
+    return scales
 
 
 def _vec(t, n, dev):
@@ -604,6 +620,26 @@ def _ln(lib, x, w, b, kind, rows, dim, eps, dtype):
     y = torch.empty((rows, dim), dtype=dtype, device=x.device)
     _lib.check(lib.ocm_op_layernorm(_p(x), _p(w), _p(b), _p(y), kind, rows, dim, eps, _stream()))
     return y
+
+
+def _drop_path_ln(lib, x, branch, scale, w, b, kind, B, N, dim, eps, dtype):
+    """(x + branch * scale[image], its LayerNorm in `kind`) from one kernel; the sum is written over `branch`."""
+    y = torch.empty((B * N, dim), dtype=dtype, device=x.device)
+    _lib.check(lib.ocm_op_drop_path_layernorm(_p(x), _p(branch), _p(scale), _p(w), _p(b), _p(branch), _p(y), kind, B, N, dim, eps,
+                                              _stream()))
+    return branch, y
+
+
+def _drop_path_backward(lib, prec, dout, scale, B, N, dim):
+    """(dout * scale[image] in fp32, the same as the operand of the data-gradient GEMM) from one kernel."""
+    d32 = torch.empty_like(dout)
+    if prec == _lib.OCM_PREC_FP32:
+        d_op = d32
+    else:
+        d_op = torch.empty((B * N, dim), dtype=_OPERAND_DTYPE[prec], device=dout.device)
+    _lib.check(lib.ocm_op_drop_path_backward(prec, _p(dout), _p(scale), _p(d32), None if d_op is d32 else _p(d_op), B, N, dim,
+                                             _stream()))
+    return d32, d_op
 
 
 def _ln_backward(lib, dy, x, w, dres, rows, dim, eps):
@@ -627,7 +663,12 @@ class _EncoderTrain(torch.autograd.Function):
     """The SimMIM / fine-tuning encoder in training mode: forward(meta, x, *params) -> normed tokens (B, N, D); backward ->
     parameter gradients. Per block from meta["first"] on (_first_block_to_train) it keeps the block input (norm1's input), qkv_f32, lse2, the context in the operand type, norm2's input
     and the fp32 fc1 pre-activation: (5 + mlp_ratio) * N * D * 4 bytes per image plus the context (2 or 4 bytes per element)
-    — 35 MB per block per image at 384^2, D = 384. The LayerNorm outputs are recomputed in fp32."""
+    — 35 MB per block per image at 384^2, D = 384. The LayerNorm outputs are recomputed in fp32.
+    Stochastic depth (meta["scales"]: per branch None or a per-image scale table, _drop_path_scales): a branch with a table runs its
+    attn.proj / mlp.fc2 GEMM with the plain bias epilogue into a temporary and ocm_op_drop_path_layernorm writes the new residual
+    stream and the NEXT LayerNorm's output (norm2, the next block's norm1, or the final norm), so a site's LayerNorm output may
+    arrive from the preceding branch; its backward starts with ocm_op_drop_path_backward while the residual gradient passes on
+    unscaled. A branch without a table runs the launches it always ran. The tables are kept with the saved tensors."""
 
     @staticmethod
     def forward(ctx, meta, x, *params):
@@ -655,9 +696,17 @@ class _EncoderTrain(torch.autograd.Function):
         _lib.check(lib.ocm_vit_prepare_tokens(eng._h, C.byref(io), _p(t)))
         npad = lib.ocm_n_pad_prec(prec, N)
         saved = []
+        scales = meta["scales"]
+        xn = out = None  # a LayerNorm output that arrived with the preceding scaled branch (ocm_op_drop_path_layernorm)
+
+        def norm_args(name):
+            return P[name + ".weight"], _vec(P.get(name + ".bias"), D, dev)
+
         for i, blk in enumerate(enc.blocks):
             pre = f"blocks.{i}."
-            xn = _ln(lib, t, P[pre + "norm1.weight"], _vec(P.get(pre + "norm1.bias"), D, dev), kind, T, D, eps, adt)
+            s_attn, s_mlp = scales[2 * i], scales[2 * i + 1]
+            if xn is None:
+                xn = _ln(lib, t, *norm_args(pre + "norm1"), kind, T, D, eps, adt)
             q = torch.empty((B * H, npad, hd), dtype=adt, device=dev)
             k = torch.empty_like(q)
             vt = torch.zeros((B * H, hd, npad), dtype=adt, device=dev)
@@ -670,26 +719,42 @@ class _EncoderTrain(torch.autograd.Function):
             _lib.check(lib.ocm_op_attention_hd(prec, _p(q), _p(k), _p(vt), _p(cx), _p(lse), B, N, H, hd,
                                                float(blk.attn.scale), _stream()))
             del q, k, vt, xn
-            x1 = _linear(lib, prec, cx, op(pre + "attn.proj.weight"), _vec(P.get(pre + "attn.proj.bias"), D, dev), t, T, D, D,
-                         _lib.OCM_EPI_BIAS_RESID_F32)
-            xn2 = _ln(lib, x1, P[pre + "norm2.weight"], _vec(P.get(pre + "norm2.bias"), D, dev), kind, T, D, eps, adt)
+            if s_attn is None:
+                x1 = _linear(lib, prec, cx, op(pre + "attn.proj.weight"), _vec(P.get(pre + "attn.proj.bias"), D, dev), t, T, D, D,
+                             _lib.OCM_EPI_BIAS_RESID_F32)
+                xn2 = _ln(lib, x1, *norm_args(pre + "norm2"), kind, T, D, eps, adt)
+            else:  # the plain GEMM into a temporary, then residual + scaled branch and norm2 in one kernel
+                br = _linear(lib, prec, cx, op(pre + "attn.proj.weight"), _vec(P.get(pre + "attn.proj.bias"), D, dev), None, T,
+                             D, D)
+                x1, xn2 = _drop_path_ln(lib, t, br, s_attn, *norm_args(pre + "norm2"), kind, B, N, D, eps, adt)
             hpre = _linear(lib, prec, xn2, op(pre + "mlp.fc1.weight"), _vec(P.get(pre + "mlp.fc1.bias"), Mh, dev), None,
                            T, Mh, D)
             del xn2
             g = torch.empty((T, Mh), dtype=adt, device=dev)
             _lib.check(lib.ocm_op_gelu(prec, _p(hpre), _p(g), None, T * Mh, _stream()))
-            x2 = _linear(lib, prec, g, op(pre + "mlp.fc2.weight"), _vec(P.get(pre + "mlp.fc2.bias"), D, dev), x1, T, D, Mh,
-                         _lib.OCM_EPI_BIAS_RESID_F32)
+            xn = None
+            if s_mlp is None:
+                x2 = _linear(lib, prec, g, op(pre + "mlp.fc2.weight"), _vec(P.get(pre + "mlp.fc2.bias"), D, dev), x1, T, D, Mh,
+                             _lib.OCM_EPI_BIAS_RESID_F32)
+            else:  # the next LayerNorm is norm1 of the next block, or the final norm (fp32) behind the last block
+                br = _linear(lib, prec, g, op(pre + "mlp.fc2.weight"), _vec(P.get(pre + "mlp.fc2.bias"), D, dev), None, T, D, Mh)
+                if i + 1 < L:
+                    x2, xn = _drop_path_ln(lib, x1, br, s_mlp, *norm_args(f"blocks.{i + 1}.norm1"), kind, B, N, D, eps, adt)
+                else:
+                    x2, out = _drop_path_ln(lib, x1, br, s_mlp, *norm_args("norm"), _lib.OCM_LN_F32, B, N, D, eps,
+                                            torch.float32)
             del g
             if i >= meta["first"]:
                 saved.append((t, qkv, lse, cx, x1, hpre))
             t = x2
-        out = _ln(lib, t, P["norm.weight"], _vec(P.get("norm.bias"), D, dev), _lib.OCM_LN_F32, T, D, eps, torch.float32)
+        if out is None:
+            out = _ln(lib, t, *norm_args("norm"), _lib.OCM_LN_F32, T, D, eps, torch.float32)
         # through save_for_backward: autograd frees them after the backward, refuses a second backward over the same graph
         # and raises if a parameter is modified in place between this forward and the backward
         ctx.meta, ctx.nblocks = meta, len(saved)
         ctx.dims = (B, N, D, H, hd, T, Mh, eps, prec)
-        ctx.save_for_backward(x, t, *[a for blk in saved for a in blk], *params)
+        ctx.scaled = [j for j in range(2 * meta["first"], 2 * L) if scales[j] is not None]
+        ctx.save_for_backward(x, t, *[a for blk in saved for a in blk], *params, *[scales[j] for j in ctx.scaled])
         return out.reshape(B, N, D)
 
     @staticmethod
@@ -702,6 +767,7 @@ class _EncoderTrain(torch.autograd.Function):
         x, xL, nb, first = st[0], st[1], ctx.nblocks, meta["first"]
         blocks = {first + i: st[2 + 6 * i:8 + 6 * i] for i in range(nb)}
         params = dict(zip(names, st[2 + 6 * nb:]))
+        scales = dict(zip(ctx.scaled, st[2 + 6 * nb + len(names):]))  # branch 2 i: attention of block i, 2 i + 1: its MLP
         lib, dev = _lib.load(), gout.device
         f32 = dict(device=dev, dtype=torch.float32)
         cache = enc.__dict__.setdefault("_train_cache", SourceCache())
@@ -721,6 +787,13 @@ class _EncoderTrain(torch.autograd.Function):
                 if need.get(bname):
                     grads[bname] = db
 
+        def branch_grad(dres, j):
+            """(fp32, operand) gradient of branch j from the gradient of the residual stream behind it: that gradient itself, or
+            scaled per image where the forward dropped paths (the stream's own gradient passes on unscaled)."""
+            if j in scales:
+                return _drop_path_backward(lib, prec, dres, scales[j], B, N, D)
+            return dres, to_operand(dres, prec)
+
         def put(n):
             return _put(grads.get(n), params[n])
 
@@ -739,11 +812,12 @@ class _EncoderTrain(torch.autograd.Function):
                 blk = enc.blocks[i]
                 xin, qkv, lse, cx, x1, hpre = blocks[i]
                 # mlp: x2 = x1 + fc2(gelu(fc1(norm2(x1))))
-                dh = _linear(lib, prec, to_operand(dx, prec), op_t(pre + "mlp.fc2.weight"), zero(Mh), None, T, Mh, D)
+                db2, db2_op = branch_grad(dx, 2 * i + 1)
+                dh = _linear(lib, prec, db2_op, op_t(pre + "mlp.fc2.weight"), zero(Mh), None, T, Mh, D)
                 g32 = torch.empty((T, Mh), **f32)
                 _lib.check(lib.ocm_op_gelu_backward(_p(dh), _p(hpre), _p(dh), _p(g32), T * Mh, _stream()))
-                wgrad(dx, g32, pre + "mlp.fc2.weight", pre + "mlp.fc2.bias")
-                del g32
+                wgrad(db2, g32, pre + "mlp.fc2.weight", pre + "mlp.fc2.bias")
+                del g32, db2, db2_op
                 g2w, g2b = params[pre + "norm2.weight"], _vec(params.get(pre + "norm2.bias"), D, dev)
                 if need.get(pre + "mlp.fc1.weight") or need.get(pre + "mlp.fc1.bias"):
                     xn2 = _ln(lib, x1, g2w, g2b, _lib.OCM_LN_F32, T, D, eps, torch.float32)
@@ -755,13 +829,14 @@ class _EncoderTrain(torch.autograd.Function):
                 lngrads(pre + "norm2", dg, db)
                 del dxn2, dx
                 # attention: x1 = xin + proj(attn(norm1(xin)))
-                dctx = _linear(lib, prec, to_operand(dx1, prec), op_t(pre + "attn.proj.weight"), zero(D), None, T, D, D)
+                db1, db1_op = branch_grad(dx1, 2 * i)
+                dctx = _linear(lib, prec, db1_op, op_t(pre + "attn.proj.weight"), zero(D), None, T, D, D)
                 delta = torch.empty((B * H, N), **f32)
                 c32 = torch.empty((T, D), **f32)
                 _lib.check(lib.ocm_op_attention_backward_delta(prec, _p(cx), _p(dctx), _p(delta), _p(c32), B, N, H, hd,
                                                                _stream()))
-                wgrad(dx1, c32, pre + "attn.proj.weight", pre + "attn.proj.bias")
-                del c32
+                wgrad(db1, c32, pre + "attn.proj.weight", pre + "attn.proj.bias")
+                del c32, db1, db1_op
                 dqkv = torch.empty((T, 3 * D), **f32)
                 _lib.check(lib.ocm_op_attention_backward(_p(qkv), _p(lse), _p(dctx), _p(delta), _p(dqkv), B, N, H, hd,
                                                          float(blk.attn.scale), _stream()))

@@ -52,7 +52,9 @@ void ocm_swin_destroy(ocm_swin_t *h);
  *   swin.encoder.layers.{s}.blocks.{b}.mlp.{fc1,fc2}.{weight,bias},
  *   swin.encoder.layers.{s}.downsample.{reduction.weight,norm.weight,norm.bias},
  *   swin.layernorm.{weight,bias}, classifier.{weight,bias}
- * from a contiguous fp32 device buffer in the reference layout; the engine keeps its own packed copy. */
+ * from a contiguous fp32 device buffer in the reference layout; the engine keeps its own packed copy.
+ * swin.embeddings.mask_token (embed_dim floats: transformers' SwinForMaskedImageModeling) is optional:
+ * ocm_swin_params_ready does not wait for it, and only ocm_swin_forward_masked with a mask reads it. */
 int ocm_swin_set_param(ocm_swin_t *h, const char *name, const float *dev_src, size_t count, void *stream);
 int ocm_swin_params_ready(const ocm_swin_t *h);
 
@@ -92,6 +94,14 @@ typedef struct ocm_swin_outputs {
 int ocm_swin_forward_ex(ocm_swin_t *h, const float *pixel_values, int32_t batch, float *logits, float *pooled,
                         float *last_hidden, const ocm_swin_outputs *outputs, void *workspace, size_t workspace_bytes,
                         void *stream);
+
+/* ocm_swin_forward_ex with SwinEmbeddings' bool_masked_pos: patch_mask (B, L_0) uint8 on the device, one byte per token of the
+ * patch grid, or null. A token whose byte is nonzero is replaced by swin.embeddings.mask_token (ocm_op_swin_mask_tokens, a row
+ * select, bit exact) after embeddings.norm and before hidden[0] is emitted; everything behind it is ocm_swin_forward_ex.
+ * A null mask is ocm_swin_forward_ex bit for bit (which is this call with null); a mask without the parameter is OCM_EINVAL. */
+int ocm_swin_forward_masked(ocm_swin_t *h, const float *pixel_values, const uint8_t *patch_mask, int32_t batch, float *logits,
+                            float *pooled, float *last_hidden, const ocm_swin_outputs *outputs, void *workspace,
+                            size_t workspace_bytes, void *stream);
 
 /* Shape of an output of ocm_swin_forward_ex for a configuration and batch: a host function, no device is touched (the
  * configuration is checked as ocm_swin_create checks it). kind OCM_SWIN_OUT_HIDDEN: index in [0, num_stages] -> dims

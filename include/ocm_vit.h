@@ -535,6 +535,39 @@ int ocm_op_bn_relu_backward(const float *dz, const float *y, const float *mean, 
 int ocm_op_pixel_shuffle_backward(const float *grad_out, float *grad_lin, int32_t batch, int32_t hp, int32_t wp,
                                   int32_t c_out, int32_t s, void *stream);
 
+/* ---- masked image modelling on the decoder GEMM's rows (transformers' SwinForMaskedImageModeling; kernels_mim.hip) ----
+ * SimMIM's masked L1 reconstruction loss straight from the 1x1 convolution evaluated token-major:
+ *   lin  (batch*hp*wp, c*s*s) fp32, the layout ocm_op_pixel_shuffle reads;  x (batch, c, S, S) fp32 with S = hp*s = wp*s;
+ *   mask (batch, S/p, S/p) uint8, nonzero = masked; p divides S (p < s, p = s and p > s are all served).
+ * Outputs, each optional (null skips it):
+ *   rec  (batch, c, S, S): rec[b][ch][y*s+i][xx*s+j] = lin[b*hp*wp + y*wp + xx][ch*s*s + i*s + j], the bits of ocm_op_pixel_shuffle;
+ *   dlin (lin's shape): sign(rec - x) * m * scale with m the pixel's mask bit, sign(0) = 0 (torch's abs backward) and
+ *        scale = (float)(1.0 / ((count + 1e-5) * c)) formed in double, count = p*p * (nonzero mask bytes) the masked pixels of
+ *        one channel: every element is exactly +scale, -scale or 0 — the gradient of `loss` with respect to lin;
+ *   loss (one float): (float)(sum |x - rec| * m / (count + 1e-5) / c), each |x - rec| exact in float64, summed as float64
+ *        per-workgroup partials combined in a fixed order. count = 0 gives loss = 0 and dlin = 0.
+ * Three stream-ordered launches (mask count, main pass, finalise; only the main pass when rec alone is asked for), no atomics,
+ * nothing synchronises, reruns give the same bits. The workspace (ocm_mim_l1_loss_workspace_bytes, 8-byte aligned) needs no
+ * initialisation; it is required even when no output needs it. With s % 4 == 0 the float pointers are 16-byte aligned.
+ * OCM_EINVAL: null lin / x / mask, a non-positive size, p not dividing S, hp*s != wp*s, a misaligned pointer;
+ * OCM_ENOMEM: a null or short workspace. */
+size_t ocm_mim_l1_loss_workspace_bytes(int32_t batch, int32_t hp, int32_t wp, int32_t c, int32_t s);
+int ocm_op_mim_l1_loss(const float *lin, const float *x, const uint8_t *mask, int32_t batch, int32_t hp, int32_t wp, int32_t c,
+                       int32_t s, int32_t p, float *rec, float *dlin, float *loss, void *workspace, size_t workspace_bytes,
+                       void *stream);
+
+/* The mask-token step of SwinEmbeddings.forward, embeddings * (1 - w) + mask_token * w with a 0 / 1 w, as a row select:
+ * rows (tokens, channels) fp32 in place — a row whose mask byte is nonzero becomes mask_token (channels floats) bit for bit,
+ * the other rows are not touched. channels a multiple of 4, rows and mask_token 16-byte aligned.
+ * Backward: d_rows (may alias d; optional) = d at the unmasked rows and zero at the masked ones; d_mask_token (channels floats;
+ * optional) = the sum of d over the masked rows, float64 partials per 256 rows combined in row order and rounded once. Its
+ * workspace (ocm_swin_mask_tokens_backward_workspace_bytes, 8-byte aligned) needs no initialisation; null or short: OCM_ENOMEM. */
+int ocm_op_swin_mask_tokens(float *rows, const uint8_t *mask, const float *mask_token, int64_t tokens, int32_t channels,
+                            void *stream);
+size_t ocm_swin_mask_tokens_backward_workspace_bytes(int64_t tokens, int32_t channels);
+int ocm_op_swin_mask_tokens_backward(const float *d, const uint8_t *mask, float *d_rows, float *d_mask_token, int64_t tokens,
+                                     int32_t channels, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- training of build_unet (model.py:227-320; PGT.py's and unet.py's step; kernels_conv_train.hip) ----
  * The forward runs every convolution without its ReLU (ocm_op_conv3x3 with relu = 0, or ocm_op_im2col3x3 + ocm_op_linear),
  * ocm_op_batch_stats and ocm_op_bn_relu; the backward runs ocm_op_bn_relu_backward, ocm_op_weight_grad on an im2col operand,

@@ -193,6 +193,8 @@ SIGNATURES = {
                                    C.c_size_t, C.c_void_p]),
     "ocm_swin_forward_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.POINTER(OcmSwinOutputs), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "ocm_swin_forward_masked": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.POINTER(OcmSwinOutputs), C.c_void_p, C.c_size_t, C.c_void_p]),
     "ocm_swin_output_shape": (C.c_int, [C.POINTER(OcmSwinConfig), C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
     "ocm_swin_set_option": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
     "ocm_op_swin_window_probs": (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
@@ -228,6 +230,11 @@ SIGNATURES = {
     "ocm_op_swin_drop_path": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     "ocm_op_swin_drop_path_backward": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     "ocm_op_pixel_shuffle": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "ocm_mim_l1_loss_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32, _i32]),
+    "ocm_op_mim_l1_loss": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "ocm_op_swin_mask_tokens": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _vp]),
+    "ocm_swin_mask_tokens_backward_workspace_bytes": (_sz, [_i64, _i32]),
+    "ocm_op_swin_mask_tokens_backward": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _sz, _vp]),
     "ocm_op_stitch_image_u8": (C.c_int, [_vp, _i64, _i64, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp]),
     "ocm_op_weighted_u8": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ocm_op_histogram_u8": (C.c_int, [_vp, _i64, _vp, _vp]),

@@ -221,4 +221,7 @@ hipError_t launch_swin_attn_block(int prec, float *x, const float *g, const floa
 hipError_t launch_swin_pool_head(const float *x, const float *g, const float *be, const float *cw, const float *cb,
                                  float *logits, float *pooled, float *hidden, int batch, int L, int C, int labels,
                                  float eps, hipStream_t s);
+// SwinEmbeddings' mask-token blend as a row select (kernels_mim.hip): rows (tokens, channels) fp32 in place, channels % 4 == 0
+hipError_t launch_swin_mask_tokens(float *rows, const uint8_t *mask, const float *token, size_t tokens, int channels,
+                                   hipStream_t s);
 hipError_t launch_cast_pad(int prec, const float *src, void *dst, size_t rows, int K, int Kp, hipStream_t s);

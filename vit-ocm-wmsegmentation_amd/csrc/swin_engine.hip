@@ -36,6 +36,7 @@ struct Slot {
     int heads;           // S_TABLE
     size_t dense_offset; // S_TABLE: dense [heads][A][A] table (fp32 kernel)
     bool set;
+    bool optional;       // ocm_swin_params_ready does not wait for it (swin.embeddings.mask_token)
 };
 
 struct LayerP {
@@ -60,6 +61,8 @@ struct ocm_swin {
     std::vector<Slot> slots;
     std::vector<StageP> stages;
     size_t emb_w, emb_b, emb_g, emb_be, fin_g, fin_b, cls_w, cls_b;
+    size_t mask_tok = 0;  // swin.embeddings.mask_token (optional: ocm_swin_forward_masked)
+    int mask_slot = -1;
     char *arena = nullptr;
     size_t arena_bytes = 0;
     bool fuse_mlp = true;  // ocm_swin_set_option(OCM_SWIN_OPT_FUSE_MLP)
@@ -72,7 +75,7 @@ struct ocm_swin {
     }
     int add(const std::string &name, SlotKind kind, size_t count, size_t offset, int rows = 0, int K = 0, int Kp = 0,
             size_t row_offset = 0, int heads = 0, size_t dense_offset = 0) {
-        slots.push_back(Slot{name, kind, count, offset, rows, K, Kp, row_offset, heads, dense_offset, false});
+        slots.push_back(Slot{name, kind, count, offset, rows, K, Kp, row_offset, heads, dense_offset, false, false});
         return (int)slots.size() - 1;
     }
     size_t add_f32(const std::string &name, size_t count) {
@@ -191,6 +194,10 @@ extern "C" int ocm_swin_create(const ocm_swin_config *cfg, ocm_swin_t **out) {
         h->cls_w = h->add_f32("classifier.weight", (size_t)cfg->num_labels * Cl);
         h->cls_b = h->add_f32("classifier.bias", cfg->num_labels);
     }
+    // the optional mask token goes behind everything else: the other parameters keep the offsets they have without it
+    h->mask_tok = h->add_f32(e + "mask_token", C0);
+    h->mask_slot = (int)h->slots.size() - 1;
+    h->slots[h->mask_slot].optional = true;
     if (h->arena_bytes > ((size_t)1 << 31)) {
         delete h;
         return fail(OCM_EINVAL, "parameter arena too large");
@@ -241,7 +248,7 @@ extern "C" int ocm_swin_set_param(ocm_swin_t *h, const char *name, const float *
 extern "C" int ocm_swin_params_ready(const ocm_swin_t *h) {
     if (!h) return fail(OCM_EINVAL, "null handle");
     for (const Slot &sl : h->slots)
-        if (!sl.set) return fail(OCM_ESTATE, "parameter '%s' has not been set", sl.name.c_str());
+        if (!sl.set && !sl.optional) return fail(OCM_ESTATE, "parameter '%s' has not been set", sl.name.c_str());
     return OCM_OK;
 }
 
@@ -334,7 +341,16 @@ extern "C" int ocm_swin_forward(ocm_swin_t *h, const float *pixel_values, int32_
 extern "C" int ocm_swin_forward_ex(ocm_swin_t *h, const float *pixel_values, int32_t batch, float *logits, float *pooled,
                                    float *last_hidden, const ocm_swin_outputs *outs, void *workspace, size_t workspace_bytes,
                                    void *stream) {
+    return ocm_swin_forward_masked(h, pixel_values, nullptr, batch, logits, pooled, last_hidden, outs, workspace, workspace_bytes,
+                                   stream);
+}
+
+extern "C" int ocm_swin_forward_masked(ocm_swin_t *h, const float *pixel_values, const uint8_t *patch_mask, int32_t batch,
+                                       float *logits, float *pooled, float *last_hidden, const ocm_swin_outputs *outs,
+                                       void *workspace, size_t workspace_bytes, void *stream) {
     if (!h || !pixel_values || (!logits && h->labels > 0)) return fail(OCM_EINVAL, "null argument");
+    if (patch_mask && !h->slots[h->mask_slot].set)
+        return fail(OCM_EINVAL, "a patch mask needs the parameter 'swin.embeddings.mask_token', which has not been set");
     if (batch <= 0) return fail(OCM_EINVAL, "batch %d must be positive", batch);
     int rc = ocm_swin_params_ready(h);
     if (rc) return rc;
@@ -353,6 +369,8 @@ extern "C" int ocm_swin_forward_ex(ocm_swin_t *h, const float *pixel_values, int
                                   h->ptr<float>(h->emb_be), w.x, batch, c.num_channels, c.image_size, c.embed_dim, 1e-5f, s));
     }
     float *x = w.x, *xo = w.x2;
+    if (patch_mask)  // SwinEmbeddings: masked tokens become the mask token, after embeddings.norm
+        HIP_TRY(launch_swin_mask_tokens(x, patch_mask, h->ptr<float>(h->mask_tok), (size_t)batch * H * H, c.embed_dim, s));
     if (int rc2 = swin_emit_hidden(outs, 0, x, batch, H * H, c.embed_dim, s)) return rc2;
     int layer = 0;  // global layer index: the slot of outs->attentions
     // A requested attention map needs the q | k | v rows, so that layer's attention half runs unfused — and so does every

@@ -37,7 +37,7 @@ class SwinConfig:
     def __init__(self, image_size=224, patch_size=4, num_channels=3, embed_dim=96, depths=(2, 2, 6, 2),
                  num_heads=(3, 6, 12, 24), window_size=7, mlp_ratio=4.0, qkv_bias=True, hidden_act="gelu",
                  layer_norm_eps=1e-5, num_labels=2, label2id=None, id2label=None, drop_path_rate=0.1,
-                 hidden_dropout_prob=0.0, attention_probs_dropout_prob=0.0, **unused):
+                 hidden_dropout_prob=0.0, attention_probs_dropout_prob=0.0, encoder_stride=32, **unused):
         if hidden_act != "gelu" or not qkv_bias:
             raise ValueError("only hidden_act='gelu' with qkv_bias=True (the Swin-T defaults) is built")
         self.image_size, self.patch_size, self.num_channels, self.embed_dim = image_size, patch_size, num_channels, embed_dim
@@ -50,6 +50,7 @@ class SwinConfig:
         self.hidden_size = int(embed_dim * 2 ** (self.num_layers - 1))
         self.drop_path_rate = drop_path_rate
         self.hidden_dropout_prob, self.attention_probs_dropout_prob = hidden_dropout_prob, attention_probs_dropout_prob
+        self.encoder_stride = encoder_stride  # SwinForMaskedImageModeling's decoder: Conv2d + PixelShuffle(encoder_stride)
 
 
 class SwinOutput(types.SimpleNamespace):
@@ -73,6 +74,20 @@ class SwinModelOutput(types.SimpleNamespace):
     def to_tuple(self):
         return tuple(v for v in (self.last_hidden_state, self.pooler_output, self.hidden_states,
                                  self.reshaped_hidden_states, self.attentions) if v is not None)
+
+    def __getitem__(self, key):
+        if isinstance(key, str):
+            return getattr(self, key)
+        return self.to_tuple()[key]
+
+
+class SwinMaskedImageModelingOutput(types.SimpleNamespace):
+    """What SwinForMaskedImageModeling.forward returns: loss (None without a mask), reconstruction, hidden_states, attentions,
+    reshaped_hidden_states; out["name"] and out[i] over the non-None of them in that order."""
+
+    def to_tuple(self):
+        return tuple(v for v in (self.loss, self.reconstruction, self.hidden_states, self.attentions,
+                                 self.reshaped_hidden_states) if v is not None)
 
     def __getitem__(self, key):
         if isinstance(key, str):
@@ -123,9 +138,33 @@ def _layer_list(config, output_attentions):
     return layers
 
 
-def _engine_run(eng, config, pixel_values, want_last, want_hidden, layers):
-    """One inference forward through an engine entry (ocm_swin_forward_ex) -> dict(logits, pooled, last_hidden, hidden_states,
-    reshaped_hidden_states, attentions). Shapes come from ocm_swin_output_shape."""
+class MaskTokenMissing(ValueError, NotImplementedError):
+    """bool_masked_pos on a model that has no mask token. A ValueError, as the other mask refusals are, and still the
+    NotImplementedError that SwinModel raised for any bool_masked_pos before the mask token was built."""
+
+
+def _patch_mask(config, pixel_values, bool_masked_pos, has_token):
+    """bool_masked_pos (B, L_0) torch.bool -> the uint8 bytes the kernels read, or None. transformers blends
+    embeddings * (1 - w) + mask_token * w with w = the mask cast to the embeddings' dtype; this path selects rows, so anything
+    but a 0 / 1 mask is refused."""
+    if bool_masked_pos is None:
+        return None
+    if not has_token:
+        raise MaskTokenMissing("bool_masked_pos needs the mask token, which this model does not have: it is built in "
+                               "SwinForMaskedImageModeling and its `.swin` view")
+    if not isinstance(bool_masked_pos, torch.Tensor) or bool_masked_pos.dtype != torch.bool:
+        raise ValueError("bool_masked_pos must be a torch.bool tensor (this path selects rows; transformers would blend a "
+                         f"fractional mask softly), got {getattr(bool_masked_pos, 'dtype', type(bool_masked_pos))}")
+    L0 = (config.image_size // config.patch_size) ** 2
+    if tuple(bool_masked_pos.shape) != (pixel_values.shape[0], L0):
+        raise ValueError(f"expected a ({pixel_values.shape[0]}, {L0}) bool_masked_pos, got {tuple(bool_masked_pos.shape)}")
+    return bool_masked_pos.to(pixel_values.device).to(torch.uint8).contiguous()
+
+
+def _engine_run(eng, config, pixel_values, want_last, want_hidden, layers, patch_mask=None):
+    """One inference forward through an engine entry (ocm_swin_forward_ex; ocm_swin_forward_masked with a patch mask, the
+    uint8 bytes of _patch_mask) -> dict(logits, pooled, last_hidden, hidden_states, reshaped_hidden_states, attentions).
+    Shapes come from ocm_swin_output_shape."""
     lib = _lib.load()
     x = pixel_values.detach().to(torch.float32).contiguous()
     dev, B = x.device, x.shape[0]
@@ -164,9 +203,14 @@ def _engine_run(eng, config, pixel_values, want_last, want_hidden, layers):
         eng["ws"] = {B: ws}
     off = (-ws.data_ptr()) % 256
     with torch.cuda.device(dev):
-        _lib.check(lib.ocm_swin_forward_ex(eng["h"], _p(x), B, _p(logits), _p(pooled), _p(hidden),
-                                           C.byref(outs) if outs is not None else None,
-                                           C.c_void_p(ws.data_ptr() + off), ws.numel() - off, _stream()))
+        if patch_mask is None:
+            _lib.check(lib.ocm_swin_forward_ex(eng["h"], _p(x), B, _p(logits), _p(pooled), _p(hidden),
+                                               C.byref(outs) if outs is not None else None,
+                                               C.c_void_p(ws.data_ptr() + off), ws.numel() - off, _stream()))
+        else:
+            _lib.check(lib.ocm_swin_forward_masked(eng["h"], _p(x), _p(patch_mask), B, _p(logits), _p(pooled), _p(hidden),
+                                                   C.byref(outs) if outs is not None else None,
+                                                   C.c_void_p(ws.data_ptr() + off), ws.numel() - off, _stream()))
     return dict(logits=logits, pooled=pooled, last_hidden=hidden, hidden_states=hs, reshaped_hidden_states=rs, attentions=at)
 
 
@@ -234,8 +278,13 @@ class _SwinBase(nn.Module):
         except Exception:
             pass
 
+    def _engine_params(self):
+        """(flat name, parameter) of what the engine holds: every parameter, unless a subclass has some of its own."""
+        return list(self.named_parameters())
+
     def _get_engine(self, device):
-        params = list(self.parameters())
+        named = self._engine_params()
+        params = [p for _, p in named]
         sig = signature(params)
         eng = self._engine_cache.hit("engine", sig, device)
         if eng is not None:
@@ -253,7 +302,7 @@ class _SwinBase(nn.Module):
         h = C.c_void_p(0)
         with torch.cuda.device(device):
             _lib.check(lib.ocm_swin_create(C.byref(cfg), C.byref(h)))
-            for flat, p in self.named_parameters():
+            for flat, p in named:
                 if p.device != device:
                     lib.ocm_swin_destroy(h)
                     raise RuntimeError(f"parameters are on {p.device} but the input is on {device}; call model.to(device)")
@@ -269,6 +318,41 @@ class _SwinBase(nn.Module):
         if pixel_values.dim() != 4 or tuple(pixel_values.shape[1:]) != (c.num_channels, c.image_size, c.image_size):
             raise ValueError(f"expected (B, {c.num_channels}, {c.image_size}, {c.image_size}) pixel_values, got "
                              f"{tuple(pixel_values.shape)}")
+
+
+def _check_swin_trainable(c, x, padded=False, wide=False):
+    """What the Swin training path refuses, before anything is launched (SwinForImageClassification and
+    SwinForMaskedImageModeling; `padded` / `wide`: the classifier's enable_padded_training / enable_wide_window_training)."""
+    if x.requires_grad:
+        raise NotImplementedError("the training path does not produce the gradient of the input image; pass pixel_values "
+                                  "that do not require grad")
+    if c.hidden_dropout_prob or c.attention_probs_dropout_prob:
+        raise NotImplementedError(f"training is built without dropout (hidden_dropout_prob = {c.hidden_dropout_prob}, "
+                                  f"attention_probs_dropout_prob = {c.attention_probs_dropout_prob}); set both to 0. "
+                                  "Stochastic depth (drop_path_rate) is supported")
+    if c.patch_size != 4 or not 2 <= c.window_size <= (12 if wide else 7):
+        raise NotImplementedError("training is built for patch_size 4 and windows of 2 to 12" if wide else
+                                  "training is built for patch_size 4 and windows of 2 to 7; "
+                                  "model.enable_wide_window_training() trains windows of 8 to 12")
+    side = c.image_size // c.patch_size
+    hint = "; model.enable_padded_training() trains through transformers' padding paths"
+    for s in range(c.num_layers):
+        if c.embed_dim * 2 ** s != 32 * c.num_heads[s] or c.embed_dim % 32 or c.embed_dim > 128:
+            raise NotImplementedError(f"stage {s}: training is built for 32-wide heads and embed_dim a multiple of 32 "
+                                      "up to 128")
+        if padded and side < c.window_size:
+            raise NotImplementedError(f"stage {s}: its {side} x {side} grid is smaller than window_size {c.window_size}; "
+                                      "neither training nor inference is built for that")
+        if not padded and (side < c.window_size or side % c.window_size):
+            raise NotImplementedError(f"stage {s}: its {side} x {side} grid is not a multiple of window_size "
+                                      f"{c.window_size}; training is built for geometries without transformers' padding "
+                                      "paths (every stage grid a multiple of the window, even before each merge)" + hint)
+        if s + 1 < c.num_layers:
+            if side % 2 and not padded:
+                raise NotImplementedError(f"stage {s}: the odd {side} x {side} grid would be padded before the patch "
+                                          "merging; training is built for geometries without transformers' padding paths"
+                                          + hint)
+            side = (side + 1) // 2
 
 
 class SwinForImageClassification(_SwinBase):
@@ -334,38 +418,8 @@ class SwinForImageClassification(_SwinBase):
     def _check_trainable(self, x, labels):
         """What the training path refuses, before anything is launched."""
         c = self.config
-        wide = self.__dict__.get("_wide_window_training", False)
-        if x.requires_grad:
-            raise NotImplementedError("the training path does not produce the gradient of the input image; pass pixel_values "
-                                      "that do not require grad")
-        if c.hidden_dropout_prob or c.attention_probs_dropout_prob:
-            raise NotImplementedError(f"training is built without dropout (hidden_dropout_prob = {c.hidden_dropout_prob}, "
-                                      f"attention_probs_dropout_prob = {c.attention_probs_dropout_prob}); set both to 0. "
-                                      "Stochastic depth (drop_path_rate) is supported")
-        if c.patch_size != 4 or not 2 <= c.window_size <= (12 if wide else 7):
-            raise NotImplementedError("training is built for patch_size 4 and windows of 2 to 12" if wide else
-                                      "training is built for patch_size 4 and windows of 2 to 7; "
-                                      "model.enable_wide_window_training() trains windows of 8 to 12")
-        side = c.image_size // c.patch_size
-        padded = self.__dict__.get("_padded_training", False)
-        hint = "; model.enable_padded_training() trains through transformers' padding paths"
-        for s in range(c.num_layers):
-            if c.embed_dim * 2 ** s != 32 * c.num_heads[s] or c.embed_dim % 32 or c.embed_dim > 128:
-                raise NotImplementedError(f"stage {s}: training is built for 32-wide heads and embed_dim a multiple of 32 "
-                                          "up to 128")
-            if padded and side < c.window_size:
-                raise NotImplementedError(f"stage {s}: its {side} x {side} grid is smaller than window_size {c.window_size}; "
-                                          "neither training nor inference is built for that")
-            if not padded and (side < c.window_size or side % c.window_size):
-                raise NotImplementedError(f"stage {s}: its {side} x {side} grid is not a multiple of window_size "
-                                          f"{c.window_size}; training is built for geometries without transformers' padding "
-                                          "paths (every stage grid a multiple of the window, even before each merge)" + hint)
-            if s + 1 < c.num_layers:
-                if side % 2 and not padded:
-                    raise NotImplementedError(f"stage {s}: the odd {side} x {side} grid would be padded before the patch "
-                                              "merging; training is built for geometries without transformers' padding paths"
-                                              + hint)
-                side = (side + 1) // 2
+        _check_swin_trainable(c, x, self.__dict__.get("_padded_training", False),
+                              self.__dict__.get("_wide_window_training", False))
         if labels is not None:
             if c.num_labels < 2:
                 raise ValueError(f"training with labels is built for single-label classification with num_labels >= 2 (got "
@@ -412,8 +466,12 @@ class SwinModel(_SwinBase):
 
     forward(pixel_values, output_hidden_states=False, output_attentions=False) -> SwinModelOutput(last_hidden_state,
     pooler_output (None when add_pooling_layer=False), hidden_states, reshaped_hidden_states, attentions), the three
-    tuples as SwinForImageClassification.forward describes them. Not built (NotImplementedError): use_mask_token=True, a
-    bool_masked_pos, interpolate_pos_encoding=True, and training (training mode with a parameter that requires grad)."""
+    tuples as SwinForImageClassification.forward describes them. The `.swin` view of a SwinForMaskedImageModeling holds its
+    `embeddings.mask_token`; its forward(bool_masked_pos=...) takes a torch.bool (B, L_0) tensor and replaces the masked tokens
+    of the embeddings output by the token (ocm_swin_forward_masked; any other dtype raises ValueError). Not built
+    (NotImplementedError): use_mask_token=True on a stand-alone SwinModel, a bool_masked_pos on a model without the token
+    (MaskTokenMissing, refused before anything else as it always was), interpolate_pos_encoding=True, and training (training
+    mode with a parameter that requires grad)."""
 
     _engine_prefix = "swin."
     _engine_labels = 0
@@ -421,18 +479,20 @@ class SwinModel(_SwinBase):
     def __init__(self, config, add_pooling_layer=True, use_mask_token=False):
         super().__init__()
         if use_mask_token:
-            raise NotImplementedError("use_mask_token=True (SwinForMaskedImageModeling's mask token) is not built")
+            raise NotImplementedError("use_mask_token=True is not built for a stand-alone SwinModel: the mask token lives in "
+                                      "SwinForMaskedImageModeling, whose `.swin` is the backbone with it")
         self.config = config
         self.add_pooling_layer = add_pooling_layer
         self.__dict__["_owner"] = None
         self._register(shapes={k[len("swin."):]: v for k, v in _param_shapes(config).items() if k.startswith("swin.")})
 
     @classmethod
-    def _view_of(cls, owner):
-        """A SwinModel over the `swin.*` Parameter objects of a SwinForImageClassification, running through its engine."""
+    def _view_of(cls, owner, add_pooling_layer=True):
+        """A SwinModel over the `swin.*` Parameter objects of a SwinForImageClassification or SwinForMaskedImageModeling,
+        running through its engine."""
         self = cls.__new__(cls)
         nn.Module.__init__(self)
-        self.config, self.add_pooling_layer = owner.config, True
+        self.config, self.add_pooling_layer = owner.config, add_pooling_layer
         self.__dict__["_owner"] = owner
         self._register(params={owner._names[flat][len("swin."):]: p for flat, p in owner.named_parameters()
                                if owner._names[flat].startswith("swin.")})
@@ -449,8 +509,9 @@ class SwinModel(_SwinBase):
 
     def forward(self, pixel_values=None, bool_masked_pos=None, output_hidden_states=False, output_attentions=False,
                 interpolate_pos_encoding=False, **unused):
-        if bool_masked_pos is not None:
-            raise NotImplementedError("bool_masked_pos (masked image modelling) is not built")
+        has_token = "embeddings.mask_token" in self._names.values()
+        if bool_masked_pos is not None and not has_token:
+            _patch_mask(self.config, pixel_values, bool_masked_pos, False)  # raises MaskTokenMissing, before anything else
         if interpolate_pos_encoding:
             raise NotImplementedError("interpolate_pos_encoding=True is not built: pixel_values must be config.image_size wide")
         self._check_pixels(pixel_values)
@@ -458,12 +519,104 @@ class SwinModel(_SwinBase):
             raise NotImplementedError("SwinModel is inference only: call .eval(), run under torch.no_grad(), or train "
                                       "through SwinForImageClassification")
         layers = _layer_list(self.config, output_attentions)
+        mask = _patch_mask(self.config, pixel_values, bool_masked_pos, has_token)
         with torch.no_grad():
             eng = (self._owner if self._owner is not None else self)._get_engine(pixel_values.device)
-            r = _engine_run(eng, self.config, pixel_values, True, output_hidden_states, layers)
+            r = _engine_run(eng, self.config, pixel_values, True, output_hidden_states, layers, mask)
         return SwinModelOutput(last_hidden_state=r["last_hidden"], pooler_output=r["pooled"] if self.add_pooling_layer else None,
                                hidden_states=r["hidden_states"], reshaped_hidden_states=r["reshaped_hidden_states"],
                                attentions=r["attentions"])
+
+
+class SwinForMaskedImageModeling(_SwinBase):
+    """transformers' SwinForMaskedImageModeling (SimMIM pre-training; the checkpoint microsoft/swin-base-simmim-window6-192
+    loads with load_state_dict): the backbone with a mask token and without a pooler (`.swin`), and the decoder
+    Conv2d(hidden_size, encoder_stride^2 * num_channels, 1) + PixelShuffle(encoder_stride) under the keys decoder.0.weight /
+    decoder.0.bias.
+
+    forward(pixel_values, bool_masked_pos=None, output_hidden_states=False, output_attentions=False) ->
+    SwinMaskedImageModelingOutput(loss, reconstruction, hidden_states, attentions, reshaped_hidden_states). bool_masked_pos is a
+    torch.bool (B, L_0) tensor over the patch grid (data.MaskGenerator's layout, flattened); the loss is SimMIM's masked L1,
+    sum |x - rec| * m / (sum m + 1e-5) / num_channels with m the mask repeated over each patch's pixels, and None without a mask.
+      * inference (eval mode, no_grad, or nothing trainable): the engine's masked forward, the decoder GEMM on
+        last_hidden_state in the module's precision, then ocm_op_mim_l1_loss for the reconstruction and the loss.
+      * training (module.train(), grad mode on, a parameter requiring grad): _SwinTrain with the sequence ending and the mask
+        select in its embeddings unit, then _MimHead (one GEMM + ocm_op_mim_l1_loss, which leaves the loss gradient in the
+        GEMM's row layout). Stochastic depth as in the classifier; hidden_states and attentions are inference only.
+    The geometries of the classifier's training path without its opt-ins (patch 4, 32-wide heads, windows of 2 to 7 on grids
+    that are multiples of the window), no dropout."""
+
+    _engine_labels = 0
+
+    def __init__(self, config):
+        super().__init__()
+        if config.encoder_stride != config.patch_size * 2 ** (config.num_layers - 1):
+            raise ValueError(f"encoder_stride {config.encoder_stride} must be patch_size * 2^(num_layers - 1) = "
+                             f"{config.patch_size * 2 ** (config.num_layers - 1)}: the decoder's PixelShuffle has to give the "
+                             "image back")
+        self.config = config
+        shapes = {k: v for k, v in _param_shapes(config).items() if k.startswith("swin.")}
+        shapes["swin.embeddings.mask_token"] = (1, 1, config.embed_dim)
+        shapes["decoder.0.weight"] = (config.encoder_stride ** 2 * config.num_channels, config.hidden_size, 1, 1)
+        shapes["decoder.0.bias"] = (config.encoder_stride ** 2 * config.num_channels,)
+        self._register(shapes=shapes)
+
+    def _engine_params(self):  # the decoder is not the engine's
+        return [(flat, p) for flat, p in self.named_parameters() if self._names[flat].startswith("swin.")]
+
+    @property
+    def swin(self):
+        """The backbone as a SwinModel (with the mask token, no pooling layer) over this module's own Parameter objects and
+        engine; built on access, not a submodule."""
+        return SwinModel._view_of(self, add_pooling_layer=False)
+
+    def forward(self, pixel_values=None, bool_masked_pos=None, output_hidden_states=False, output_attentions=False,
+                interpolate_pos_encoding=False, **unused):
+        if interpolate_pos_encoding:
+            raise NotImplementedError("interpolate_pos_encoding=True is not built: pixel_values must be config.image_size wide")
+        self._check_pixels(pixel_values)
+        mask = _patch_mask(self.config, pixel_values, bool_masked_pos, True)
+        layers = _layer_list(self.config, output_attentions)
+        if _differentiable(self):
+            if layers or output_hidden_states:
+                raise NotImplementedError("hidden_states and attentions are built in inference only: call model.eval() (or "
+                                          "run under torch.no_grad())")
+            return self._train_forward(pixel_values, mask)
+        with torch.no_grad():
+            return self._infer(pixel_values, mask, output_hidden_states, layers)
+
+    def _named(self, dev):
+        named = [(self._names[n], p) for n, p in self.named_parameters()]
+        for key, p in named:
+            if p.device != dev:
+                raise RuntimeError(f"parameters are on {p.device} but the input is on {dev}; call model.to(device)")
+        return named
+
+    def _train_forward(self, pixel_values, mask):
+        _check_swin_trainable(self.config, pixel_values)
+        x = pixel_values.detach().to(torch.float32).contiguous()
+        dev = x.device
+        named = self._named(dev)
+        trunk = [(k, p) for k, p in named if k.startswith("swin.")]
+        P = dict(named)
+        meta = {"model": self, "keys": [k for k, _ in trunk], "ending": "sequence", "patch_mask": mask,
+                "masks": draw_drop_path_masks(self.config, x.shape[0], dev)}
+        with torch.cuda.device(dev):
+            seq = _SwinTrain.apply(meta, x, *[p for _, p in trunk])
+            loss, rec = _MimHead.apply({"model": self}, seq, P["decoder.0.weight"], P["decoder.0.bias"], x, mask)
+        self.__dict__["_train_kept_bytes"] = meta["kept_bytes"]
+        return SwinMaskedImageModelingOutput(loss=loss if mask is not None else None, reconstruction=rec, hidden_states=None,
+                                             attentions=None, reshaped_hidden_states=None)
+
+    def _infer(self, pixel_values, mask, output_hidden_states, layers=()):
+        dev = pixel_values.device
+        r = _engine_run(self._get_engine(dev), self.config, pixel_values, True, output_hidden_states, list(layers), mask)
+        P = dict(self._named(dev))
+        x = pixel_values.detach().to(torch.float32).contiguous()
+        with torch.cuda.device(dev):
+            _, rec, loss = _mim_head_forward(self, P, r["last_hidden"], x, mask, False)
+        return SwinMaskedImageModelingOutput(loss=loss, reconstruction=rec, hidden_states=r["hidden_states"],
+                                             attentions=r["attentions"], reshaped_hidden_states=r["reshaped_hidden_states"])
 
 
 # ---- training: SwinForImageClassification as stand-alone operators under one autograd Function. Token-major rows
@@ -563,6 +716,10 @@ class _SwinTrain(torch.autograd.Function):
                       P[e + "patch_embeddings.projection.bias"], None, T, C, _kpad(Cin * 16, prec))
         del cols
         t = _ln(lib, tok, P[e + "norm.weight"], P[e + "norm.bias"], F32, T, C, 1e-5, torch.float32)
+        pmask = meta.get("patch_mask")  # uint8 (B, L_0) or None: SwinEmbeddings' mask-token select, after embeddings.norm
+        if pmask is not None:
+            _lib.check(lib.ocm_op_swin_mask_tokens(_p(t), _p(pmask), _p(P[e + "mask_token"].detach().contiguous()), T, C,
+                                                   _stream()))
         keep = [tok]  # tensors for the backward, in this order: tok, per layer 6, per merge 1, final input, pooled
         masks, li = meta["masks"], 0
         for s in range(c.num_layers):
@@ -634,6 +791,12 @@ class _SwinTrain(torch.autograd.Function):
         L, nl = H * H, c.num_labels
         NLp = -(-nl // 32) * 32
         seq = _ln(lib, t, P["swin.layernorm.weight"], P["swin.layernorm.bias"], F32, B * L, C, eps, torch.float32)
+        if meta.get("ending") == "sequence":  # SwinForMaskedImageModeling: the sequence output, no pool and no classifier
+            keep += [t, None]
+            meta["kept_bytes"] = sum(k.numel() * k.element_size() for k in keep if k is not None)
+            ctx.meta, ctx.prec = meta, prec
+            ctx.save_for_backward(x, *keep, *params)
+            return seq.view(B, L, C)
         pooled = torch.empty((B, C), **f32)
         _lib.check(lib.ocm_op_swin_pool(_p(seq), _p(pooled), B, L, C, _stream()))
         meta["hidden"] = seq.view(B, L, C)
@@ -648,8 +811,10 @@ class _SwinTrain(torch.autograd.Function):
         return logits[:, :nl].contiguous(), pooled
 
     @staticmethod
-    def backward(ctx, dlogits, dpooled):
+    def backward(ctx, *douts):
         meta, prec = ctx.meta, ctx.prec
+        sequence = meta.get("ending") == "sequence"
+        dlogits, dpooled = (None, None) if sequence else douts
         model, keys = meta["model"], meta["keys"]
         c = model.config
         lib = _lib.load()
@@ -673,6 +838,8 @@ class _SwinTrain(torch.autograd.Function):
         units.append(("head", None))
         heads_keys = ("swin.layernorm.weight", "swin.layernorm.bias", "classifier.weight", "classifier.bias")
         wanted = [any(need[k] for k in keys if (k.startswith(pre) if pre else k in heads_keys)) for _, pre in units]
+        if True not in wanted:  # the sequence ending with a frozen trunk behind a graph of the caller's: nothing to walk
+            return (None, None, *[None] * len(keys))
         stop = wanted.index(True)
 
         def wgrad(dy, xin, wkey, bkey, rows=None):
@@ -700,21 +867,28 @@ class _SwinTrain(torch.autograd.Function):
         NLp = -(-nl // 32) * 32
         tL, pooled = keep[-2], keep[-1]
         with torch.cuda.device(dev):
-            # head: logits = pooled W^T + b (rows padded to NLp), pooled = mean_l LayerNorm(tL)
-            dl = torch.zeros((B, NLp), **f32)
-            if dlogits is not None:
-                dl[:, :nl] = dlogits
-            wgrad(dl, pooled, "classifier.weight", "classifier.bias", rows=nl)
             dx = None
-            if stop < len(units) - 1 or need["swin.layernorm.weight"] or need["swin.layernorm.bias"]:
-                dp = _linear(lib, prec, _operand(dl, prec), W.wt("classifier.weight", rows=NLp), torch.zeros(C, **f32), None,
-                             B, C, _kpad(NLp, prec))
-                if dpooled is not None:
-                    dp = dp + dpooled
-                dseq = torch.empty((B * L, C), **f32)
-                _lib.check(lib.ocm_op_swin_pool_backward(_p(dp), _p(dseq), B, L, C, _stream()))
+            if sequence:  # the backward starts from d_seq: the final LayerNorm, then the units
+                if douts[0] is None:
+                    return (None, None, *[None] * len(keys))
+                dseq = douts[0].detach().to(torch.float32).contiguous().view(B * L, C)
                 dx, dg, db = _ln_backward(lib, dseq, tL, P["swin.layernorm.weight"], None, B * L, C, eps)
                 lngrads("swin.layernorm.", dg, db)
+            else:
+                # head: logits = pooled W^T + b (rows padded to NLp), pooled = mean_l LayerNorm(tL)
+                dl = torch.zeros((B, NLp), **f32)
+                if dlogits is not None:
+                    dl[:, :nl] = dlogits
+                wgrad(dl, pooled, "classifier.weight", "classifier.bias", rows=nl)
+                if stop < len(units) - 1 or need["swin.layernorm.weight"] or need["swin.layernorm.bias"]:
+                    dp = _linear(lib, prec, _operand(dl, prec), W.wt("classifier.weight", rows=NLp), torch.zeros(C, **f32), None,
+                                 B, C, _kpad(NLp, prec))
+                    if dpooled is not None:
+                        dp = dp + dpooled
+                    dseq = torch.empty((B * L, C), **f32)
+                    _lib.check(lib.ocm_op_swin_pool_backward(_p(dp), _p(dseq), B, L, C, _stream()))
+                    dx, dg, db = _ln_backward(lib, dseq, tL, P["swin.layernorm.weight"], None, B * L, C, eps)
+                    lngrads("swin.layernorm.", dg, db)
             ki = len(keep) - 2
             for u in reversed(range(1, len(units) - 1)):
                 if u < stop:
@@ -815,6 +989,16 @@ class _SwinTrain(torch.autograd.Function):
                 e = "swin.embeddings."
                 C, H = c.embed_dim, c.image_size // c.patch_size
                 T, Cin = B * H * H, c.num_channels
+                pmask = meta.get("patch_mask")
+                if pmask is not None:  # the select's backward: masked rows pass nothing down, their sum is the token's gradient
+                    mk = e + "mask_token"
+                    dtk = torch.empty(C, **f32) if need[mk] else None
+                    nbytes = lib.ocm_swin_mask_tokens_backward_workspace_bytes(T, C)
+                    wsb = _ws(nbytes, dev)
+                    _lib.check(lib.ocm_op_swin_mask_tokens_backward(_p(dx), _p(pmask), _p(dx), _p(dtk), T, C, _p(wsb), nbytes,
+                                                                    _stream()))
+                    if need[mk]:
+                        grads[mk] = dtk
                 dtok, dg, db = _ln_backward(lib, dx, keep[0], P[e + "norm.weight"], None, T, C, 1e-5)
                 lngrads(e + "norm.", dg, db)
                 wk = e + "patch_embeddings.projection."
@@ -834,3 +1018,84 @@ class _SwinTrain(torch.autograd.Function):
             p = P[k]
             out.append(None if g is None else g.contiguous().reshape(p.shape).to(dtype=p.dtype))
         return (None, None, *out)
+
+
+# ---- SwinForMaskedImageModeling's head: Conv2d(C_last, s^2 * channels, 1) on the token rows, PixelShuffle(s), masked L1 ----
+def _mim_head_forward(model, P, seq, x, mask, want_dlin):
+    """seq (B, L, C) fp32 -> (dlin, reconstruction, loss): one GEMM over the token rows in the module's precision (the weight
+    operand cached in the module's SourceCache, _Weights), then ocm_op_mim_l1_loss reading the GEMM's rows once — or, without
+    a mask (uint8 (B, L_0), _patch_mask), ocm_op_pixel_shuffle alone and no loss. dlin (the loss gradient in the GEMM's row
+    layout) only where asked for."""
+    c = model.config
+    lib, dev = _lib.load(), seq.device
+    prec = _lib.PRECISIONS[model._precision]
+    B, L, C = seq.shape
+    hp = int(L ** 0.5)
+    s, ch = c.encoder_stride, c.num_channels
+    O = s * s * ch
+    f32 = dict(device=dev, dtype=torch.float32)
+    lin = _linear(lib, prec, _operand(seq.detach().reshape(B * L, C), prec), _Weights(model, P, prec).w("decoder.0.weight"),
+                  P["decoder.0.bias"].detach().float().contiguous(), None, B * L, O, _kpad(C, prec))
+    rec = torch.empty((B, ch, hp * s, hp * s), **f32)
+    if mask is None:
+        _lib.check(lib.ocm_op_pixel_shuffle(_p(lin), _p(rec), B, hp, hp, ch, s, _stream()))
+        return None, rec, None
+    loss = torch.empty((), **f32)
+    dlin = torch.empty_like(lin) if want_dlin else None
+    nbytes = lib.ocm_mim_l1_loss_workspace_bytes(B, hp, hp, ch, s)
+    wsb = _ws(nbytes, dev)
+    _lib.check(lib.ocm_op_mim_l1_loss(_p(lin), _p(x), _p(mask), B, hp, hp, ch, s, c.patch_size, _p(rec), _p(dlin), _p(loss),
+                                      _p(wsb), nbytes, _stream()))
+    return dlin, rec, loss
+
+
+class _MimHead(torch.autograd.Function):
+    """SwinForMaskedImageModeling's decoder and loss in training mode: forward(meta, seq, weight, bias, x, mask) -> (loss,
+    reconstruction) as _mim_head_forward computes them (without a mask the loss is a zero that carries no graph). Kept: seq
+    and dlin = d loss / d lin, which ocm_op_mim_l1_loss wrote in the forward (every element +scale, -scale or 0). backward:
+    d_lin = d_loss * dlin with the device scalar (no host read), plus ocm_op_pixel_shuffle_backward(d_reconstruction) when that
+    gradient arrives; the weight and bias gradients from _weight_grad, d_seq from the transposed-weight GEMM only when the trunk
+    carries a graph."""
+
+    @staticmethod
+    def forward(ctx, meta, seq, weight, bias, x, mask):
+        model = meta["model"]
+        ctx.set_materialize_grads(False)
+        dlin, rec, loss = _mim_head_forward(model, {"decoder.0.weight": weight, "decoder.0.bias": bias}, seq, x, mask, True)
+        ctx.meta, ctx.prec, ctx.bias = meta, _lib.PRECISIONS[model._precision], bias
+        ctx.save_for_backward(seq, weight, dlin)
+        if loss is None:
+            loss = torch.zeros((), dtype=torch.float32, device=seq.device)
+            ctx.mark_non_differentiable(loss)
+        return loss, rec
+
+    @staticmethod
+    def backward(ctx, dloss, drec):
+        model, prec = ctx.meta["model"], ctx.prec
+        seq, weight, dlin = ctx.saved_tensors
+        _, need_x, need_w, need_b = ctx.needs_input_grad[:4]
+        c = model.config
+        lib, dev = _lib.load(), seq.device
+        B, L, C = seq.shape
+        hp, s, M = int(L ** 0.5), c.encoder_stride, B * L
+        O = weight.shape[0]
+        dx = dw = db = None
+        with torch.cuda.device(dev):
+            d = None
+            if dloss is not None and dlin is not None:
+                d = dlin * dloss.to(torch.float32)
+            if drec is not None:
+                g = drec.detach().to(torch.float32).contiguous()
+                dsh = torch.empty((M, O), dtype=torch.float32, device=dev)
+                _lib.check(lib.ocm_op_pixel_shuffle_backward(_p(g), _p(dsh), B, hp, hp, c.num_channels, s, _stream()))
+                d = dsh if d is None else d + dsh
+            if d is None:
+                return None, None, None, None, None, None
+            if need_w or need_b:
+                dw, db = _weight_grad(prec, d, seq.reshape(M, C), need_b)
+            if need_x:
+                P = {"decoder.0.weight": weight}
+                dx = _linear(lib, prec, _operand(d, prec), _Weights(model, P, prec).wt("decoder.0.weight"),
+                             torch.zeros(C, dtype=torch.float32, device=dev), None, M, C, _kpad(O, prec)).view(B, L, C)
+        return (None, dx, dw.reshape(weight.shape).to(weight.dtype) if need_w else None,
+                db.reshape(ctx.bias.shape).to(ctx.bias.dtype) if need_b else None, None, None)

@@ -646,6 +646,46 @@ int ocm_op_drop_path_layernorm(const float *x, const float *branch, const float 
 int ocm_op_drop_path_backward(int32_t precision, const float *dout, const float *scale, float *dbranch_f32, void *dbranch_op,
                               int32_t batch, int32_t tokens, int32_t dim, void *stream);
 
+/* nn.Dropout of the ViT training path without a stored mask (kernels_dropout.hip, csrc/philox.h). The mask of one site over a
+ * tensor in row-major order of its unpadded shape, flat index f: Philox4x32-10 with key (seed & 0xffffffff, seed >> 32), seed
+ * the site's non-negative int64, and counter (g & 0xffffffff, g >> 32, 0, 0), g = f >> 2; element f reads output word f & 3 and
+ * is kept iff word >= thresh. A kept element's factor is inv_keep, a dropped one's 0.0f; every operator applies it as one
+ * rounded fp32 multiplication.
+ * The three functions below run on the host and need no device. */
+void ocm_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
+/* thresh = (uint32) floor(p * 2^32 + 0.5) in double, inv_keep = (float)(1.0 / (1.0 - p)); OCM_EINVAL outside 0 < p < 1. */
+int ocm_dropout_threshold(double p, uint32_t *thresh, float *inv_keep);
+/* keep[i] = 1 where element first + i is kept, else 0, for i < count. */
+int ocm_dropout_keep_host(int64_t seed, uint64_t first, uint64_t count, uint32_t thresh, uint8_t *keep);
+/* The device operators read the seed as seeds[site] from DEVICE memory, so nothing is synchronised. fp32 pointers are 16-byte
+ * aligned. Null pointers, a negative site, non-positive sizes, a bad dim, out_kind or precision return OCM_EINVAL before any
+ * launch.
+ * keep[i] = 1 / 0 for i < count: the mask itself, as the device generator forms it. */
+int ocm_op_dropout_mask(const int64_t *seeds, int32_t site, size_t count, uint32_t thresh, uint8_t *keep, void *stream);
+/* y = x * factor, fp32; y may alias x; count % 4 == 0. Its own backward. */
+int ocm_op_dropout(const float *x, const int64_t *seeds, int32_t site, uint32_t thresh, float inv_keep, float *y, size_t count,
+                   void *stream);
+/* The sibling of ocm_op_drop_path_layernorm behind a dropped branch: d = branch * factor; with scale ([batch], or NULL)
+ * d = d * scale[image]; x_out = x + d (each step rounded); y = LayerNorm(x_out) in out_kind, bit for bit what ocm_op_layernorm
+ * makes of x_out. The flat index of the mask is row * dim + column. Same aliasing and widths as ocm_op_drop_path_layernorm. */
+int ocm_op_dropout_layernorm(const float *x, const float *branch, const int64_t *seeds, int32_t site, uint32_t thresh,
+                             float inv_keep, const float *scale, const float *gamma, const float *beta, float *x_out, void *y,
+                             int32_t out_kind, int32_t batch, int32_t tokens, int32_t dim, float eps, void *stream);
+/* The sibling of ocm_op_drop_path_backward: dbranch_f32 = (dout * factor) * scale[image] (scale may be NULL; dbranch_f32 may
+ * alias dout), dbranch_op (NULL for OCM_PREC_FP32) the same values as ocm_op_cast_bf16 / ocm_op_cast_split would write them.
+ * One pass; dim % 8 == 0. */
+int ocm_op_dropout_backward(int32_t precision, const float *dout, const int64_t *seeds, int32_t site, uint32_t thresh,
+                            float inv_keep, const float *scale, float *dbranch_f32, void *dbranch_op, int32_t batch,
+                            int32_t tokens, int32_t dim, void *stream);
+/* gelu(h) as ocm_op_gelu forms it in fp32, times the factor, then the operand cast of `precision` into out; out_f32 (optional)
+ * the masked fp32 values. ocm_op_gelu's conditions on count. */
+int ocm_op_gelu_dropout(int32_t precision, const float *h, const int64_t *seeds, int32_t site, uint32_t thresh, float inv_keep,
+                        void *out, float *out_f32, size_t count, void *stream);
+/* dh = (dg * factor) * gelu'(h), as ocm_op_gelu_backward forms it from the masked dg (dh may alias dg); g_f32 (optional) =
+ * gelu(h) * factor, the masked activation of the forward. */
+int ocm_op_gelu_dropout_backward(const float *dg, const float *h, const int64_t *seeds, int32_t site, uint32_t thresh,
+                                 float inv_keep, float *dh, float *g_f32, size_t count, void *stream);
+
 /* erf GELU (nn.GELU()) of `count` fp32 values: out in the operand type E of `precision` (count % 32 == 0 for split pairs, rows
  * whose length is a multiple of 32), out_f32 (optional) in fp32. */
 int ocm_op_gelu(int32_t precision, const float *h, void *out, float *out_f32, size_t count, void *stream);

@@ -272,6 +272,16 @@ SIGNATURES = {
     "ocm_op_layernorm_backward": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _f32, _vp, _sz, _vp]),
     "ocm_op_drop_path_layernorm": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _vp]),
     "ocm_op_drop_path_backward": (C.c_int, [_i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
+    "ocm_philox4x32_10": (None, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "ocm_dropout_threshold": (C.c_int, [C.c_double, C.POINTER(C.c_uint32), C.POINTER(_f32)]),
+    "ocm_dropout_keep_host": (C.c_int, [_i64, C.c_uint64, C.c_uint64, C.c_uint32, _vp]),
+    "ocm_op_dropout_mask": (C.c_int, [_vp, _i32, _sz, C.c_uint32, _vp, _vp]),
+    "ocm_op_dropout": (C.c_int, [_vp, _vp, _i32, C.c_uint32, _f32, _vp, _sz, _vp]),
+    "ocm_op_dropout_layernorm": (C.c_int, [_vp, _vp, _vp, _i32, C.c_uint32, _f32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32,
+                                           _f32, _vp]),
+    "ocm_op_dropout_backward": (C.c_int, [_i32, _vp, _vp, _i32, C.c_uint32, _f32, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
+    "ocm_op_gelu_dropout": (C.c_int, [_i32, _vp, _vp, _i32, C.c_uint32, _f32, _vp, _vp, _sz, _vp]),
+    "ocm_op_gelu_dropout_backward": (C.c_int, [_vp, _vp, _vp, _i32, C.c_uint32, _f32, _vp, _vp, _sz, _vp]),
     "ocm_op_gelu": (C.c_int, [_i32, _vp, _vp, _vp, _sz, _vp]),
     "ocm_op_gelu_backward": (C.c_int, [_vp, _vp, _vp, _vp, _sz, _vp]),
     "ocm_op_patch_unfold": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),

@@ -10,7 +10,9 @@ analyse_attention.py:55-116 and the subclasses in model.py:11-53,110-139 bind un
 
 `DINOHead` (:282-316) keeps its module tree and keys too and trains through a HIP backward; a plain `VisionTransformer` trains
 after `enable_training()` (DINO's student backbone; DESIGN §3.37). `drop_path` / `DropPath` (:25-44) sit where the reference has them;
-on the training path the draws are `draw_drop_path_scales` and the arithmetic is HIP. Dropout proper stays refused.
+on the training path the draws are `draw_drop_path_scales` and the arithmetic is HIP. `drop_rate` trains after
+`enable_dropout()`: one seed per site from `draw_dropout_seeds`, the masks recomputed from Philox in the forward and the backward
+(DESIGN §3.41); `attn_drop_rate` stays refused.
 
 What is different: the nn.Linear / nn.Conv2d / nn.LayerNorm children are parameter containers.
 No forward below calls their ATen kernels; every method packs device pointers and calls the C ABI
@@ -93,6 +95,35 @@ def draw_drop_path_scales(model, batch, device):
             rnd = torch.rand((batch, 1, 1), dtype=torch.float32, device=device)
             out.append(torch.floor(keep + rnd).reshape(batch) / keep)
     return out
+
+
+def dropout_site_rates(model):
+    """The dropout rate of every site of `model` in execution order, read from the modules that hold them: 1 + 3 * depth entries,
+    site 0 pos_drop, sites 1 + 3 i, 2 + 3 i, 3 + 3 i block i's attn.proj_drop, mlp.drop after GELU and mlp.drop after fc2.
+    Attention dropout is not built (NotImplementedError); a rate outside [0, 1) is a ValueError (the mask threshold is defined
+    for p < 1)."""
+    rates = [float(model.pos_drop.p)]
+    for i, blk in enumerate(model.blocks):
+        if float(blk.attn.attn_drop.p) > 0:
+            raise NotImplementedError(f"blocks.{i}.attn.attn_drop.p = {blk.attn.attn_drop.p}: attention dropout (attn_drop_rate) is "
+                                      "not built on the HIP path, the mask would sit inside the attention kernels; set it to 0")
+        rates += [float(blk.attn.proj_drop.p), float(blk.mlp.drop.p), float(blk.mlp.drop.p)]
+    for r in rates:
+        if not 0.0 <= r < 1.0:
+            raise ValueError(f"dropout rate {r} is outside [0, 1)")
+    return rates
+
+
+def draw_dropout_seeds(model, device):
+    """The dropout draw of one training forward: None when every site's rate is 0 (nothing is drawn), else ONE
+    torch.randint(0, 2**62, (1 + 3 * depth,)) of int64 on `device`, entry j the seed of site j (dropout_site_rates' order). A
+    site's mask is a function of its seed and the element index (Philox4x32-10, csrc/philox.h), so a seeded run is reproducible
+    and the mask does not depend on set_precision; torch's own mask stream is not matched. The training path looks this function
+    up at every call and calls it before draw_drop_path_scales."""
+    rates = dropout_site_rates(model)
+    if not any(r > 0 for r in rates):
+        return None
+    return torch.randint(0, 2 ** 62, (len(rates),), dtype=torch.int64, device=device)
 
 
 class LayerNorm(nn.LayerNorm):
@@ -366,9 +397,13 @@ class VisionTransformer(nn.Module):
 
     def _engine(self, device, training_path=False):
         """The engine of `device`. training_path: the caller is model.py's _encode_train, which applies drop-path itself."""
-        if self.training and self._dropout_any:
+        if self.training and self._dropout_any and not self.dropout_enabled:
             raise NotImplementedError("dropout (drop_rate / attn_drop_rate > 0) in training mode is not implemented on the HIP "
-                                      "path")
+                                      "path unless the model opts in: drop_rate trains after enable_dropout()")
+        if self.training and self.dropout_enabled and any(r > 0 for r in dropout_site_rates(self)) and not training_path:
+            raise NotImplementedError("dropout > 0 in training mode runs on the training path only: call .eval() for "
+                                      "inference, or train with grad mode on, a trainable parameter and the opt-in where the "
+                                      "class has one (enable_training(), enable_finetune())")
         if self.training and self._drop_path_any and not training_path:
             raise NotImplementedError("drop-path > 0 in training mode runs on the training path only: call .eval() for "
                                       "inference, or train with grad mode on, a trainable parameter and the opt-in where the "
@@ -454,6 +489,7 @@ class VisionTransformer(nn.Module):
     AUTO_GRAPH_ENTRIES = 8
     auto_graph = True
     training_backward = False  # enable_training(): a plain attribute, not a parameter, not a buffer, not in the state_dict
+    dropout_enabled = False  # enable_dropout(): likewise
 
     def _run(self, x, **kw):
         x = self._check_input(x)
@@ -561,6 +597,14 @@ class VisionTransformer(nn.Module):
         student backbone). The position table is the one of the input's own size at every call, so crops of several sizes go
         through one model. A plain attribute, like VisionTransformerForFinetune.enable_finetune; without it nothing changes."""
         self.training_backward = bool(flag)
+        return self
+
+    def enable_dropout(self, flag=True):
+        """Opt this encoder in to (or out of) dropout on the training path: pos_drop, every block's attn.proj_drop and mlp.drop
+        (after GELU and after fc2) then apply their rates `p`, read at every call, with masks recomputed from one seed per site
+        (draw_dropout_seeds). Attention dropout stays refused. Eval mode is untouched. A plain attribute; without
+        it a model with drop_rate > 0 refuses training mode as before."""
+        self.dropout_enabled = bool(flag)
         return self
 
     def forward(self, x):

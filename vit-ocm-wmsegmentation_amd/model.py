@@ -590,7 +590,8 @@ def _encode_train(enc, x, mask, own_size=False):
             device=x.device, dtype=torch.float32).contiguous(), (npatch, x.device))
     else:
         pos = enc._positions(npatch, x.device)
-    meta = {"enc": enc, "eng": eng, "names": [n for n, _ in named], "pos": pos, "wh": wh, "npatch": npatch,
+    dropout = _dropout_sites(enc, x.device)  # drawn before the drop-path tables: a seeded run is reproducible
+    meta = {"enc": enc, "eng": eng, "names": [n for n, _ in named], "pos": pos, "wh": wh, "npatch": npatch, "dropout": dropout,
             "first": _first_block_to_train(enc, named), "scales": _drop_path_scales(enc, x.shape[0], x.device),
             "mask": mask.reshape(x.shape[0], -1).to(torch.float32).contiguous() if mask is not None else None}
     with torch.cuda.device(x.device):
@@ -612,6 +613,30 @@ def _drop_path_scales(enc, batch, dev):
     return scales
 
 
+def _dropout_sites(enc, dev):
+    """Dropout of one training forward of an encoder that has opted in (enable_dropout): None when no site has a rate above 0,
+    else (seeds, sites): the int64 device tensor of vision_transformer.draw_dropout_seeds (looked up at call time; one draw per
+    _encode_train call) and per site None or (thresh, inv_keep) as ocm_dropout_threshold forms them. Site order:
+    vision_transformer.dropout_site_rates."""
+    if not getattr(enc, "dropout_enabled", False):
+        return None
+    rates = _vt.dropout_site_rates(enc)
+    seeds = _vt.draw_dropout_seeds(enc, dev)
+    if seeds is None:
+        return None
+    if seeds.numel() != len(rates) or seeds.dtype != torch.int64:
+        raise ValueError(f"draw_dropout_seeds returned {seeds.numel()} {seeds.dtype} entries for {len(rates)} sites")
+    lib, sites = _lib.load(), []
+    for r in rates:
+        if r > 0:
+            th, ik = C.c_uint32(), C.c_float()
+            _lib.check(lib.ocm_dropout_threshold(r, C.byref(th), C.byref(ik)))
+            sites.append((th.value, ik.value))
+        else:
+            sites.append(None)
+    return seeds.detach().to(device=dev).contiguous(), sites
+
+
 def _vec(t, n, dev):
     return t.detach().to(device=dev, dtype=torch.float32).contiguous() if t is not None else torch.zeros(n, device=dev)
 
@@ -628,6 +653,31 @@ def _drop_path_ln(lib, x, branch, scale, w, b, kind, B, N, dim, eps, dtype):
     _lib.check(lib.ocm_op_drop_path_layernorm(_p(x), _p(branch), _p(scale), _p(w), _p(b), _p(branch), _p(y), kind, B, N, dim, eps,
                                               _stream()))
     return branch, y
+
+
+def _dropout_ln(lib, x, branch, seeds, site, drop, scale, w, b, kind, B, N, dim, eps, dtype):
+    """(x + branch * factor [* scale[image]], its LayerNorm in `kind`) from one kernel; the sum is written over `branch`."""
+    y = torch.empty((B * N, dim), dtype=dtype, device=x.device)
+    _lib.check(lib.ocm_op_dropout_layernorm(_p(x), _p(branch), _p(seeds), site, drop[0], drop[1], _p(scale), _p(w), _p(b),
+                                            _p(branch), _p(y), kind, B, N, dim, eps, _stream()))
+    return branch, y
+
+
+def _dropout_backward(lib, prec, dout, seeds, site, drop, scale, B, N, dim):
+    """(dout * factor [* scale[image]] in fp32, the same as the operand of the data-gradient GEMM) from one kernel."""
+    d32 = torch.empty_like(dout)
+    if prec == _lib.OCM_PREC_FP32 and scale is None:
+        # nothing to fuse: no scale, no operand copy. ocm_op_dropout writes the same bits and measured 0.8 us faster than the
+        # eight-element kernel at 12 608 x 384 (DESIGN.md 3.41), so this one site runs the composition
+        _lib.check(lib.ocm_op_dropout(_p(dout), _p(seeds), site, drop[0], drop[1], _p(d32), dout.numel(), _stream()))
+        return d32, d32
+    if prec == _lib.OCM_PREC_FP32:
+        d_op = d32
+    else:
+        d_op = torch.empty((B * N, dim), dtype=_OPERAND_DTYPE[prec], device=dout.device)
+    _lib.check(lib.ocm_op_dropout_backward(prec, _p(dout), _p(seeds), site, drop[0], drop[1], _p(scale), _p(d32),
+                                           None if d_op is d32 else _p(d_op), B, N, dim, _stream()))
+    return d32, d_op
 
 
 def _drop_path_backward(lib, prec, dout, scale, B, N, dim):
@@ -668,7 +718,13 @@ class _EncoderTrain(torch.autograd.Function):
     attn.proj / mlp.fc2 GEMM with the plain bias epilogue into a temporary and ocm_op_drop_path_layernorm writes the new residual
     stream and the NEXT LayerNorm's output (norm2, the next block's norm1, or the final norm), so a site's LayerNorm output may
     arrive from the preceding branch; its backward starts with ocm_op_drop_path_backward while the residual gradient passes on
-    unscaled. A branch without a table runs the launches it always ran. The tables are kept with the saved tensors."""
+    unscaled. A branch without a table runs the launches it always ran. The tables are kept with the saved tensors.
+    Dropout (meta["dropout"]: None or (seeds, sites), _dropout_sites): pos_drop is ocm_op_dropout in place on the prepared tokens;
+    a branch whose proj_drop / second mlp.drop has a rate takes the same hand-off as a scaled one through
+    ocm_op_dropout_layernorm (with the branch's scale table, if it has one) and starts its backward with
+    ocm_op_dropout_backward; the first mlp.drop is ocm_op_gelu_dropout / ocm_op_gelu_dropout_backward in place of the GELU
+    operators. A site at rate 0 runs the launches it always ran. Only the seeds are kept: every mask is recomputed (DESIGN.md
+    3.41)."""
 
     @staticmethod
     def forward(ctx, meta, x, *params):
@@ -697,6 +753,9 @@ class _EncoderTrain(torch.autograd.Function):
         npad = lib.ocm_n_pad_prec(prec, N)
         saved = []
         scales = meta["scales"]
+        seeds, sites = meta["dropout"] or (None, [None] * (1 + 3 * L))
+        if sites[0] is not None:  # pos_drop
+            _lib.check(lib.ocm_op_dropout(_p(t), _p(seeds), 0, *sites[0], _p(t), T * D, _stream()))
         xn = out = None  # a LayerNorm output that arrived with the preceding scaled branch (ocm_op_drop_path_layernorm)
 
         def norm_args(name):
@@ -705,6 +764,7 @@ class _EncoderTrain(torch.autograd.Function):
         for i, blk in enumerate(enc.blocks):
             pre = f"blocks.{i}."
             s_attn, s_mlp = scales[2 * i], scales[2 * i + 1]
+            d_proj, d_act, d_fc2 = sites[1 + 3 * i], sites[2 + 3 * i], sites[3 + 3 * i]
             if xn is None:
                 xn = _ln(lib, t, *norm_args(pre + "norm1"), kind, T, D, eps, adt)
             q = torch.empty((B * H, npad, hd), dtype=adt, device=dev)
@@ -719,30 +779,42 @@ class _EncoderTrain(torch.autograd.Function):
             _lib.check(lib.ocm_op_attention_hd(prec, _p(q), _p(k), _p(vt), _p(cx), _p(lse), B, N, H, hd,
                                                float(blk.attn.scale), _stream()))
             del q, k, vt, xn
-            if s_attn is None:
+            if s_attn is None and d_proj is None:
                 x1 = _linear(lib, prec, cx, op(pre + "attn.proj.weight"), _vec(P.get(pre + "attn.proj.bias"), D, dev), t, T, D, D,
                              _lib.OCM_EPI_BIAS_RESID_F32)
                 xn2 = _ln(lib, x1, *norm_args(pre + "norm2"), kind, T, D, eps, adt)
             else:  # the plain GEMM into a temporary, then residual + scaled branch and norm2 in one kernel
                 br = _linear(lib, prec, cx, op(pre + "attn.proj.weight"), _vec(P.get(pre + "attn.proj.bias"), D, dev), None, T,
                              D, D)
-                x1, xn2 = _drop_path_ln(lib, t, br, s_attn, *norm_args(pre + "norm2"), kind, B, N, D, eps, adt)
+                if d_proj is None:
+                    x1, xn2 = _drop_path_ln(lib, t, br, s_attn, *norm_args(pre + "norm2"), kind, B, N, D, eps, adt)
+                else:
+                    x1, xn2 = _dropout_ln(lib, t, br, seeds, 1 + 3 * i, d_proj, s_attn, *norm_args(pre + "norm2"), kind, B, N, D,
+                                          eps, adt)
             hpre = _linear(lib, prec, xn2, op(pre + "mlp.fc1.weight"), _vec(P.get(pre + "mlp.fc1.bias"), Mh, dev), None,
                            T, Mh, D)
             del xn2
             g = torch.empty((T, Mh), dtype=adt, device=dev)
-            _lib.check(lib.ocm_op_gelu(prec, _p(hpre), _p(g), None, T * Mh, _stream()))
+            if d_act is None:
+                _lib.check(lib.ocm_op_gelu(prec, _p(hpre), _p(g), None, T * Mh, _stream()))
+            else:
+                _lib.check(lib.ocm_op_gelu_dropout(prec, _p(hpre), _p(seeds), 2 + 3 * i, *d_act, _p(g), None, T * Mh, _stream()))
             xn = None
-            if s_mlp is None:
+            if s_mlp is None and d_fc2 is None:
                 x2 = _linear(lib, prec, g, op(pre + "mlp.fc2.weight"), _vec(P.get(pre + "mlp.fc2.bias"), D, dev), x1, T, D, Mh,
                              _lib.OCM_EPI_BIAS_RESID_F32)
             else:  # the next LayerNorm is norm1 of the next block, or the final norm (fp32) behind the last block
                 br = _linear(lib, prec, g, op(pre + "mlp.fc2.weight"), _vec(P.get(pre + "mlp.fc2.bias"), D, dev), None, T, D, Mh)
-                if i + 1 < L:
-                    x2, xn = _drop_path_ln(lib, x1, br, s_mlp, *norm_args(f"blocks.{i + 1}.norm1"), kind, B, N, D, eps, adt)
+                nxt = (*norm_args(f"blocks.{i + 1}.norm1"), kind, B, N, D, eps, adt) if i + 1 < L else (
+                    *norm_args("norm"), _lib.OCM_LN_F32, B, N, D, eps, torch.float32)
+                if d_fc2 is None:
+                    x2, y = _drop_path_ln(lib, x1, br, s_mlp, *nxt)
                 else:
-                    x2, out = _drop_path_ln(lib, x1, br, s_mlp, *norm_args("norm"), _lib.OCM_LN_F32, B, N, D, eps,
-                                            torch.float32)
+                    x2, y = _dropout_ln(lib, x1, br, seeds, 3 + 3 * i, d_fc2, s_mlp, *nxt)
+                if i + 1 < L:
+                    xn = y
+                else:
+                    out = y
             del g
             if i >= meta["first"]:
                 saved.append((t, qkv, lse, cx, x1, hpre))
@@ -754,7 +826,9 @@ class _EncoderTrain(torch.autograd.Function):
         ctx.meta, ctx.nblocks = meta, len(saved)
         ctx.dims = (B, N, D, H, hd, T, Mh, eps, prec)
         ctx.scaled = [j for j in range(2 * meta["first"], 2 * L) if scales[j] is not None]
-        ctx.save_for_backward(x, t, *[a for blk in saved for a in blk], *params, *[scales[j] for j in ctx.scaled])
+        ctx.sites = sites
+        ctx.save_for_backward(x, t, *[a for blk in saved for a in blk], *params, *[scales[j] for j in ctx.scaled],
+                              *([] if seeds is None else [seeds]))
         return out.reshape(B, N, D)
 
     @staticmethod
@@ -768,6 +842,8 @@ class _EncoderTrain(torch.autograd.Function):
         blocks = {first + i: st[2 + 6 * i:8 + 6 * i] for i in range(nb)}
         params = dict(zip(names, st[2 + 6 * nb:]))
         scales = dict(zip(ctx.scaled, st[2 + 6 * nb + len(names):]))  # branch 2 i: attention of block i, 2 i + 1: its MLP
+        sites = ctx.sites  # dropout: site 0 pos_drop, 1 + 3 i / 2 + 3 i / 3 + 3 i block i's proj_drop, mlp.drop twice
+        seeds = st[-1] if any(d is not None for d in sites) else None
         lib, dev = _lib.load(), gout.device
         f32 = dict(device=dev, dtype=torch.float32)
         cache = enc.__dict__.setdefault("_train_cache", SourceCache())
@@ -790,6 +866,9 @@ class _EncoderTrain(torch.autograd.Function):
         def branch_grad(dres, j):
             """(fp32, operand) gradient of branch j from the gradient of the residual stream behind it: that gradient itself, or
             scaled per image where the forward dropped paths (the stream's own gradient passes on unscaled)."""
+            site = 1 + 3 * (j // 2) + 2 * (j % 2)
+            if sites[site] is not None:
+                return _dropout_backward(lib, prec, dres, seeds, site, sites[site], scales.get(j), B, N, D)
             if j in scales:
                 return _drop_path_backward(lib, prec, dres, scales[j], B, N, D)
             return dres, to_operand(dres, prec)
@@ -815,7 +894,11 @@ class _EncoderTrain(torch.autograd.Function):
                 db2, db2_op = branch_grad(dx, 2 * i + 1)
                 dh = _linear(lib, prec, db2_op, op_t(pre + "mlp.fc2.weight"), zero(Mh), None, T, Mh, D)
                 g32 = torch.empty((T, Mh), **f32)
-                _lib.check(lib.ocm_op_gelu_backward(_p(dh), _p(hpre), _p(dh), _p(g32), T * Mh, _stream()))
+                if sites[2 + 3 * i] is None:
+                    _lib.check(lib.ocm_op_gelu_backward(_p(dh), _p(hpre), _p(dh), _p(g32), T * Mh, _stream()))
+                else:  # the masked dg through gelu', and the masked activation for fc2's weight gradient
+                    _lib.check(lib.ocm_op_gelu_dropout_backward(_p(dh), _p(hpre), _p(seeds), 2 + 3 * i, *sites[2 + 3 * i], _p(dh),
+                                                                _p(g32), T * Mh, _stream()))
                 wgrad(db2, g32, pre + "mlp.fc2.weight", pre + "mlp.fc2.bias")
                 del g32, db2, db2_op
                 g2w, g2b = params[pre + "norm2.weight"], _vec(params.get(pre + "norm2.bias"), D, dev)
@@ -853,7 +936,9 @@ class _EncoderTrain(torch.autograd.Function):
                 del dxn1, dx1
             if first > 0 or not any(need.get(n) for n in names if not n.startswith(("blocks.", "norm."))):
                 return (None, None, *[put(n) for n in names])  # nothing below the blocks trains
-            # tokens t = cat(cls, patch * (1 - w) + mask_token * w) + pos
+            # tokens t = pos_drop(cat(cls, patch * (1 - w) + mask_token * w) + pos)
+            if sites[0] is not None:
+                _lib.check(lib.ocm_op_dropout(_p(dx), _p(seeds), 0, *sites[0], _p(dx), T * D, _stream()))
             mask = meta["mask"]
             P_ = N - 1
             dpatch, dmask, dpos = torch.empty((B * P_, D), **f32), torch.empty(D, **f32), torch.empty((N, D), **f32)
